@@ -19,12 +19,21 @@ torch.distributed.run --nproc-per-node N bench.py --gpus N ...`) this process IS
 relays rank 0's JSON line, and exits non-zero if a rank fails or the box has fewer than N devices.
 
 Timing protocol: untimed set-up ticks (code objects, RCCL channels, clocks), W warm-up ticks, then
-`--repeats` (3) timed regions of EXACTLY K ticks each, every one bracketed by a barrier + device synchronisation;
-per region the MAX over ranks, over regions the MEDIAN.  Prints ONE JSON line (rank 0) with `roofline`
-(dominant kernel, HIP-event timed on its own stream; + `issue` = the instruction-issue ceiling and `cache` = L2
-hit rate from the committed rocprofv3 counters), `cpu_baseline` (the oracle = CPU restatement of the reference,
-timed on this host's cores), `value_with_snapshots` (the reference driver's read-backs inside the timed region)
-and `exact` (the rounding-faithful arithmetic policy timed the same way).
+`--repeats` timed regions of EXACTLY K ticks each, every one bracketed by a barrier + device synchronisation;
+per region the MAX over ranks, over regions the MEDIAN.  A plain run times ONE region (K timed ticks in all) and
+prints ONE JSON line (rank 0): the headline (`metric`, `value`, `unit`, `ms_per_step`, ...) and nothing that needs
+runs of its own.
+
+--full (off by default) adds everything else, as 3 timed regions by default: `roofline` (dominant kernel,
+HIP-event timed on its own stream; + `issue` = the instruction-issue ceiling and `cache` = L2 hit rate from the
+committed rocprofv3 counters), `cpu_baseline` (the oracle = CPU restatement of the reference, timed on this
+host's cores), `value_with_snapshots` (the reference driver's read-backs inside the timed region), `exact` (the
+rounding-faithful arithmetic policy timed the same way), `configs` (BASELINE's other single-GPU configurations)
+and, at N > 1, the side legs (parity against one device, the 512x512 and rows1 legs, the one-device run of the
+same grid).  The --no-* switches narrow a --full run.
+
+--dump-outputs DIR writes the state arrays the last timed tick left (what `_State[name].eval()` hands a caller) as
+DIR/<name>.npy, float32; above 64 MB in all every array is cut to the same fixed, seeded sample of its cells.
 """
 import argparse
 import json
@@ -52,6 +61,34 @@ CYC_VALU, CYC_TRANS = 2.0, 8.0   # issue cycles of a wave64 VALU / transcendenta
 # writes 4 (100 B); the every-10th tick also assigns the other 17 (168 B); mean 106.8.
 ALGO_BYTES = {'fenton': 32, 'br': 64, 'court': 106.8}
 COURT_FAST_BYTES, COURT_SLOW_BYTES = 100.0, 168.0
+# a single timed region (a plain run) is preceded by an untimed one of the same ticks, at most this many: the first region
+# after the warm-up is the slowest of a series (20-tick regions: 0.258 ms, then 0.242, 0.242) — the median of 3 dropped it
+REHEARSAL_TICKS = 2000
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs: at most this much in all
+DUMP_SEED = 20240601             # --dump-outputs: the sample of cells kept from a larger output
+
+
+def dump_outputs(path, arrays):
+    """[(name, array)] -> path/<name>.npy as float32.  If the arrays hold more than DUMP_BYTES together, each is cut to
+    the same fixed, seeded sample of its cells (a flat, sorted index set that depends only on the array's size)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = [(n, np.ascontiguousarray(a, dtype=np.float32)) for n, a in arrays]
+    room = DUMP_BYTES - 256 * len(arrays)                       # (each .npy file has a header of 128 bytes)
+    if sum(a.nbytes for _, a in arrays) > room:
+        per = room // (4 * len(arrays))
+        picks = {}
+        for i, (n, a) in enumerate(arrays):
+            if a.size > per:
+                if a.size not in picks:
+                    picks[a.size] = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, per, replace=False))
+                arrays[i] = (n, a.ravel()[picks[a.size]])
+    for n, a in arrays:
+        np.save(os.path.join(path, n + '.npy'), a)
+
+
+def state_arrays(m):
+    """what a caller of the model receives: every state array, by name (a collective on a sharded model)"""
+    return [(n, np.array(m._State[n].eval(), np.float32)) for n in m.VAR_NAMES]
 
 
 def make_model(args, height=None, device=0, exact=None):
@@ -286,8 +323,9 @@ def kernel_key(args, exact, H, W, fused, shard=False, ticks=1):
                                    ticks if ticks > 1 else fused, '/shard' if shard else '')
 
 
-def measure_single(args, exact, with_extras, snapshots=None, height=None, device=0):
-    """one model on one device: (value, ms_per_tick, roofline dict, walls, snapshots value, model)"""
+def measure_single(args, exact, with_extras, snapshots=None, height=None, device=0, kernel_timing=True, dump=None):
+    """one model on one device: (value, ms_per_tick, roofline dict, walls, snapshots value, model).
+    kernel_timing=False: nothing after the timed regions (roofline None); dump: --dump-outputs' directory"""
     snapshots = with_extras if snapshots is None else snapshots
     m, (loc, amp, s2_ms) = make_model(args, height=height, device=device, exact=exact)
     m.define()
@@ -309,6 +347,8 @@ def measure_single(args, exact, with_extras, snapshots=None, height=None, device
     gc.freeze()
     advance(args.setup)                               # set-up: clocks and caches in their steady state
     advance(args.warmup)
+    if args.repeats == 1:                             # set-up: see REHEARSAL_TICKS
+        timed_regions(advance, st.sync, min(args.steps, REHEARSAL_TICKS), 1)
     def nlaunch():
         return st.launch_stats()['launches']
     nlaunch.log = []
@@ -317,6 +357,10 @@ def measure_single(args, exact, with_extras, snapshots=None, height=None, device
     m._launches_per_region = nlaunch.log
     cells = m.height * m.width
     value = cells * args.steps * spt / wall / 1e6
+    if dump:
+        dump_outputs(dump, state_arrays(m))
+    if not kernel_timing:
+        return value, wall * 1000.0 / args.steps, None, walls, None, m
 
     # dominant kernel: HIP events on the kernel's own stream, back-to-back launches.  Courtemanche: around the SAME tick
     # mix as above (every 10th tick's fused fast+slow launch included).  Multi-tick launches (Fenton / Beeler-Reuter on a
@@ -385,6 +429,12 @@ def measure_single(args, exact, with_extras, snapshots=None, height=None, device
     return value, wall * 1000.0 / args.steps, roof, walls, snaps, m
 
 
+def timing_text(repeats, steps):
+    if repeats == 1:
+        return 'one region of %d ticks' % steps
+    return 'median of %d regions of %d ticks' % (repeats, steps)
+
+
 def plan_text(st):
     fused, per_tick = st.launch_plan()
     t = st.plan_tile()
@@ -425,7 +475,9 @@ def config_legs(args):
 
 
 def bench_single(args):
-    value, ms_tick, roof, walls, snaps, m = measure_single(args, args.exact, True)
+    full = args.full
+    value, ms_tick, roof, walls, snaps, m = measure_single(args, args.exact, full, snapshots=full, kernel_timing=full,
+                                                           dump=args.dump_outputs)
     st = m._stepper
     fused, per_tick = st.launch_plan()
     spt = m.dt_per_step
@@ -443,17 +495,23 @@ def bench_single(args):
                    'tile': '%dx%d cells, %s (chosen by measurement on the first tick)' % (
                        (lambda t: (t[0], t[1], ('%d rows per wave' % t[2]) if t[2] > 0 else ('%d threads' % -t[2])))(st.plan_tile())),
                    'arithmetic': 'exact (one rounding per reference op)' if args.exact else 'fast_math (default policy)',
-                   'parallelism': 'single device', 'setup_ticks': args.setup + 1,
-                   'timing': 'median of %d regions of %d ticks' % (args.repeats, args.steps)},
+                   'parallelism': 'single device',
+                   'setup_ticks': args.setup + 1 + (min(args.steps, REHEARSAL_TICKS) if args.repeats == 1 else 0),
+                   'timing': timing_text(args.repeats, args.steps)},
         'repeats': args.repeats, 'wall_ms_per_region': [round(w * 1e3, 4) for w in walls],
         'launches_per_region': getattr(m, '_launches_per_region', None),
+    }
+    if not full:
+        out['extras'] = 'roofline, value_with_snapshots, exact, configs and cpu_baseline: bench.py --full'
+        return out
+    out.update({
         'roofline': roof,
         'value_with_snapshots': None if snaps is None else round(snaps, 1),
         'snapshots_regions': getattr(m, '_snap_regions', None),
         'snapshots_note': 'median of %d regions of the same %d ticks with the reference driver\'s read-backs inside the timed '
                           'region: image() (the potential, into page-locked memory) every 10 ms of simulated time '
                           '(fenton.py:184-185)' % (args.repeats, args.steps),
-    }
+    })
     try:                                              # achievable-bandwidth yardstick, measured in this very run
         from fib_tf_amd import _lib
         out['roofline']['copy_bandwidth_measured'] = round(_lib.copy_bandwidth(1 << 30, 5, m.device), 1)   # (from the stock library)
@@ -671,6 +729,9 @@ def sharded_run(a, H, local, steps, repeats, setup, warmup):
         st.sync()
         torch.cuda.synchronize()
 
+    rehearsal = min(steps, REHEARSAL_TICKS) if repeats == 1 else 0
+    if rehearsal:                                       # set-up: see REHEARSAL_TICKS
+        timed_regions(advance, sync, rehearsal, 1, barrier=dist.barrier)
     comm0 = getattr(st, 'comm_s', 0.0)
     walls = timed_regions(advance, sync, steps, repeats, barrier=dist.barrier)
     wt = torch.tensor(walls, dtype=torch.float64, device='cuda')
@@ -681,7 +742,7 @@ def sharded_run(a, H, local, steps, repeats, setup, warmup):
     wall = statistics.median(walls)
     return {'m': m, 'st': st, 'advance': advance, 'sync': sync, 'walls': walls, 'wall': wall, 'halo_wait': float(comm.item()),
             'value': H * m.width * steps * m.dt_per_step / wall / 1e6, 'halo_ticks': halo_ticks,
-            'setup_ticks': 2 * halo_ticks + setup // halo_ticks * halo_ticks}
+            'setup_ticks': 2 * halo_ticks + setup // halo_ticks * halo_ticks + rehearsal}
 
 
 def side_leg(a, H, local, rank, world, steps, repeats, setup, label):
@@ -725,6 +786,11 @@ def bench_ranks(args):
     H = args.size if strong else args.rows_per_gpu * world
     r = sharded_run(args, H, local, args.steps, args.repeats, args.setup, args.warmup)
     m, st, walls, wall = r['m'], r['st'], r['walls'], r['wall']
+    if args.dump_outputs:
+        arrays = state_arrays(m)                                    # (every rank: the arrays are gathered)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
+        del arrays
     spt = m.dt_per_step
     halo_ticks, ghost, halo_n = r['halo_ticks'], getattr(st, 'g', 0), getattr(st, 'halo_n', 0)
     nranks = torch.tensor([1], dtype=torch.int32, device='cuda')
@@ -732,9 +798,9 @@ def bench_ranks(args):
     fused, per_tick = st.launch_plan()
     backend = dist.get_backend()
 
-    # per-GPU kernel figure (rank 0): the same row block as a stand-alone handle, HIP-event timed
+    # per-GPU kernel figure (rank 0, --full): the same row block as a stand-alone handle, HIP-event timed
     kern = None
-    if rank == 0 and hasattr(st, 'lh'):
+    if args.full and rank == 0 and hasattr(st, 'lh'):
         kern = block_kernels(m, st, H, local, spt, halo_ticks)
 
     out = None
@@ -787,7 +853,7 @@ def bench_ranks(args):
                        'halo_transport': getattr(st, 'halo_path', 'none'), 'backend': backend,
                        'ranks_in_communicator': int(nranks.item()),
                        'halo_wait_s_max_rank': round(r['halo_wait'], 4), 'setup_ticks': r['setup_ticks'],
-                       'timing': 'median of %d regions of %d ticks; per region the max over ranks' % (args.repeats, args.steps)},
+                       'timing': '%s; per region the max over ranks' % timing_text(args.repeats, args.steps)},
             'repeats': args.repeats, 'wall_ms_per_region': [round(w * 1e3, 4) for w in walls],
             'roofline': roof,
             'predicted': predicted_figure(args.size, world, scheme, 'library' if getattr(st, 'rccl_direct', False) else 'torch')
@@ -822,7 +888,7 @@ def bench_ranks(args):
         sys.stderr.flush()
         os._exit(0)
 
-    side = world > 1 and not args.no_side_legs
+    side = world > 1 and args.full and not args.no_side_legs
     watchdog = None
     if side:
         emit_early()
@@ -921,7 +987,7 @@ def bench_ranks(args):
         watchdog.cancel()
     if out is not None:
         out.update(legs_done)
-    if out is not None and (not args.no_single_leg or parity):
+    if out is not None and ((args.full and not args.no_single_leg) or parity):
         # rank 0, after the group is gone (the other ranks have left): the SAME grid on this one device — (1) the ticks of the
         # parity leg repeated on one handle, compared bit for bit; (2) timed like the N = 1 line times its workload: the
         # denominator a scaling figure of this series needs (the N = 1 line of bench.py is BASELINE configs[1], another grid)
@@ -947,7 +1013,7 @@ def bench_ranks(args):
                 except Exception as e:
                     out['sharded_equals_single'] = {'error': '%s: %s' % (type(e).__name__, e)}
                 parity.clear()
-            if not args.no_single_leg:
+            if args.full and not args.no_single_leg:
                 v1, ms1, roof1, _, _, m1 = measure_single(a, args.exact, False, snapshots=False, height=H, device=local)
                 out['single_device_same_grid'] = {
                     'value': round(v1, 1), 'unit': 'Mcell-steps/s', 'ms_per_step': round(ms1, 6), 'steps': a.steps,
@@ -967,7 +1033,7 @@ def bench_ranks(args):
                             'multi-GPU run)'}
         except Exception as e:                          # never lose the result line over the side leg
             out['single_device_same_grid'] = {'error': '%s: %s' % (type(e).__name__, e)}
-    if out is not None and not args.no_cpu:             # rank 0, after the group is gone: the other ranks have left
+    if out is not None and args.full and not args.no_cpu:   # rank 0, after the group is gone: the other ranks have left
         out['cpu_baseline'] = cpu_baseline(args, height=H, seconds=8.0)
     return out
 
@@ -977,7 +1043,12 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5000, help='ticks timed per region (1 tick = dt_per_step sub-steps)')
     ap.add_argument('--warmup', type=int, default=100)
-    ap.add_argument('--repeats', type=int, default=3, help='timed regions of --steps ticks; the median is reported')
+    ap.add_argument('--repeats', type=int, default=None, help='timed regions of --steps ticks; the median is reported (default: '
+                    '1, so that a plain run times exactly --steps ticks; 3 with --full)')
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline: roofline, snapshots, exact and config legs, '
+                    'cpu_baseline; at N > 1 the side legs and the one-device run of the same grid')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the state arrays of the last timed tick as '
+                    'DIR/<name>.npy (float32; a fixed, seeded sample of every array above 64 MB in all)')
     ap.add_argument('--setup', type=int, default=4000, help='untimed set-up ticks before the warm-up: 50 ms at 512x512, the time the '
                     'shader clock takes to settle after idling (400 ticks left a tick 3-4 %% slower: 12.3 vs 11.95 us)')
     ap.add_argument('--model', default='fenton', choices=['fenton', 'br', 'court'])
@@ -1018,6 +1089,10 @@ def main():
               file=sys.stderr)
         sys.exit(2)
     multi = world > 1 or args.force_dist
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.repeats < 1:
+        ap.error('--repeats must be at least 1')
     if args.scaling is None:
         args.scaling = 'strong'
     if not args.size:

@@ -142,11 +142,40 @@ def test_bench_rank_path_on_rccl_backend_single_rank(gpu_lib):
     """bench.py's rank path on the real backend with a one-rank group (--force-dist): process-group init with
     device_id, barriers, the MAX all-reduce of the timing, the result line (what two RCCL ranks would add is only the
     halo messages themselves, covered by the self-exchange test above)"""
-    r, line = _bench(['--gpus', '1', '--force-dist', '--steps', '100', '--warmup', '10', '--setup', '20', '--no-cpu'],
+    r, line = _bench(['--gpus', '1', '--force-dist', '--full', '--steps', '100', '--warmup', '10', '--setup', '20', '--no-cpu'],
                      {'RANK': '0', 'WORLD_SIZE': '1', 'LOCAL_RANK': '0'})
     assert r.returncode == 0, r.stderr[-2000:]
     assert line['n_gpus'] == 1 and line['value'] > 1000 and line['config']['backend'] == 'nccl'
     assert line['config']['ranks_in_communicator'] == 1 and len(line['wall_ms_per_region']) == 3
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu_lib, tmp_path):
+    """a plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline alone, ONE timed region of exactly K
+    ticks (after an untimed rehearsal of the same ticks), and the state arrays of the last timed tick — equal to the same ticks
+    driven through the public API here"""
+    import argparse
+    import bench
+    K, W, S = 50, 5, 200                                   # 1 + 200 + 5 + 50 ticks: past the S2 stimulus at tick 210
+    r, line = _bench(['--gpus', '1', '--steps', str(K), '--warmup', str(W), '--setup', str(S), '--dump-outputs',
+                      str(tmp_path)], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in line, key
+    assert line['steps'] == K and line['warmup'] == W and line['repeats'] == 1 and len(line['wall_ms_per_region']) == 1
+    assert abs(line['ms_per_step'] - line['wall_ms_per_region'][0] / K) < 1e-3 * line['ms_per_step'] + 1e-6
+    assert line['value'] > 1000 and 'roofline' not in line and 'cpu_baseline' not in line and 'exact' not in line
+    a = argparse.Namespace(model='fenton', size=512, exact=False, no_cheby=False, skip=False, halo_ticks=0, halo=None)
+    m, (loc, amp, s2_ms) = bench.make_model(a)
+    m.define()
+    m.add_pace_op('s2', loc, amp)
+    m._stepper.step(1)
+    bench.driver_loop(m, m._stepper, m.millisecond_to_step(s2_ms), False)(S + W + min(K, bench.REHEARSAL_TICKS) + K)
+    for name in m.VAR_NAMES:
+        got = np.load(str(tmp_path / (name + '.npy')))
+        want = m._State[name].eval()
+        assert got.dtype == np.float32 and got.shape == (512, 512), (name, got.dtype, got.shape)
+        assert np.array_equal(got, want), (name, float(np.abs(got - want).max()))
+    m._stepper.close()
 
 
 def test_bench_more_gpus_than_devices_fails_loudly(gpu_lib):
@@ -160,7 +189,7 @@ def test_bench_spawns_its_ranks(gpu_lib):
     """`python bench.py --gpus 2` without a launcher starts two child ranks and relays rank 0's line.  The box has one
     GPU, so the ranks share it and talk through gloo (FIBTF_ONE_DEVICE / FIBTF_DIST_BACKEND: rehearsal switches);
     spawning, rendezvous, the timed regions, the kernel probe and the teardown are the production code."""
-    r, line = _bench(['--gpus', '2', '--size', '512', '--steps', '40', '--warmup', '8', '--setup', '16', '--no-cpu'],
+    r, line = _bench(['--gpus', '2', '--full', '--size', '512', '--steps', '40', '--warmup', '8', '--setup', '16', '--no-cpu'],
                      {'FIBTF_ONE_DEVICE': '1', 'FIBTF_DIST_BACKEND': 'gloo'})
     assert r.returncode == 0, r.stderr[-3000:]
     assert line['n_gpus'] == 2 and line['scaling'] == 'strong' and line['config']['ranks_in_communicator'] == 2
@@ -179,10 +208,10 @@ def test_bench_spawns_its_ranks(gpu_lib):
 
 
 def test_bench_side_legs_on_the_headline_grid(gpu_lib):
-    """the driver's plain `bench.py --gpus N` (BASELINE configs[3]: 4096x4096) rehearsed with 2 ranks sharing the one GPU:
+    """`bench.py --gpus N --full` (BASELINE configs[3]: 4096x4096) rehearsed with 2 ranks sharing the one GPU:
     the line carries the on-hardware parity statement, north_star's 512x512 series on the same ranks and the rows1 leg,
     each with the figure predicted for it"""
-    r, line = _bench(['--gpus', '2', '--steps', '8', '--warmup', '4', '--setup', '8', '--no-cpu'],
+    r, line = _bench(['--gpus', '2', '--full', '--steps', '8', '--warmup', '4', '--setup', '8', '--no-cpu'],
                      {'FIBTF_ONE_DEVICE': '1', 'FIBTF_DIST_BACKEND': 'gloo'}, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     assert line['n_gpus'] == 2 and '4096x4096' in line['metric'] and 'configs[3]' in line['config']['workload']
@@ -201,8 +230,9 @@ def test_bench_side_legs_on_the_headline_grid(gpu_lib):
 
 def test_bench_under_the_drivers_launcher(gpu_lib):
     """the driver's own way of starting N ranks — `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
-    127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W` — rehearsed with 2 gloo ranks sharing the one GPU: one JSON
-    line on stdout (rank 0's), side legs included, exit code 0 (no rank leaves early, nothing for the elastic agent to flag)"""
+    127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W` (with --full: the side legs too) — rehearsed with 2 gloo
+    ranks sharing the one GPU: one JSON line on stdout (rank 0's), side legs included, exit code 0 (no rank leaves early,
+    nothing for the elastic agent to flag)"""
     import json
     import subprocess
     from test_sharded_cpu import free_port
@@ -211,7 +241,7 @@ def test_bench_under_the_drivers_launcher(gpu_lib):
     env.update(HSA_ENABLE_IPC_MODE_LEGACY='0', FIBTF_ONE_DEVICE='1', FIBTF_DIST_BACKEND='gloo')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '8', '--warmup', '4',
-           '--setup', '8', '--no-cpu']
+           '--setup', '8', '--no-cpu', '--full']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]

@@ -165,15 +165,39 @@ def test_bench_cli_contract():
             break
     else:
         pytest.fail('bench.py must emit a roofline object')
-    for flag in ('--gpus', '--steps', '--warmup'):
+    for flag in ('--gpus', '--steps', '--warmup', '--full', '--dump-outputs'):
         assert flag in src
     assert bench.ALGO_BYTES['fenton'] + 4 == 36 and bench.ALGO_BYTES['br'] + 4 == 68
 
 
+def test_bench_dump_outputs_bounded_and_seeded(tmp_path, monkeypatch):
+    """--dump-outputs: float32 <name>.npy files, whole arrays while they fit, above the bound the same fixed sample of cells
+    for every array and every run, the files together within the bound"""
+    import bench
+    rng = np.random.default_rng(3)
+    small = [('U', rng.random((8, 6))), ('V', rng.random((8, 6)).astype(np.float32))]
+    bench.dump_outputs(str(tmp_path / 'a'), small)
+    for n, a in small:
+        got = np.load(str(tmp_path / 'a' / (n + '.npy')))
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    big = [(n, (np.arange(60000, dtype=np.float32) + 100000 * k).reshape(300, 200)) for k, n in enumerate(('V', '_Na_i_', 'XI'))]
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 200000)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), big)
+    total, cells = 0, []
+    for k, (n, a) in enumerate(big):
+        b, c = (np.load(str(tmp_path / d / (n + '.npy'))) for d in ('b', 'c'))
+        total += os.path.getsize(str(tmp_path / 'b' / (n + '.npy')))
+        assert b.dtype == np.float32 and 1000 < b.size < a.size and np.array_equal(b, c)
+        cells.append(b - 100000 * k)                     # the flat index of every cell kept
+    assert total <= 200000
+    assert all(np.array_equal(cells[0], x) for x in cells) and (np.diff(cells[0]) > 0).all()
+
+
 def test_bench_multi_gpu_line_schema():
-    """the N > 1 line: what the first multi-GPU run must answer travels in the driver's plain invocation — the on-hardware
-    parity statement, north_star's 512x512 series, the rows1 leg, each next to its predicted figure (no GPU here: the keys are
-    pinned in the source, the prediction table is parsed for real)"""
+    """the N > 1 line of `bench.py --full`: what the first multi-GPU run must answer — the on-hardware parity statement,
+    north_star's 512x512 series, the rows1 leg, each next to its predicted figure (no GPU here: the keys are pinned in the
+    source, the prediction table is parsed for real)"""
     import bench
     src = open(os.path.join(ROOT, 'bench.py')).read()
     for key in ("'sharded_equals_single'", "'north_star_512'", "'rows1_leg'", "'scaling_efficiency'", "'single_device_same_grid'",

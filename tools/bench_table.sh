@@ -2,7 +2,7 @@
 # the DESIGN.md measurement table: bench.py on one MI355X for every model / size of the table (fast + exact)
 out=${1:-gpurun_out/bench_table.txt}
 : > $out
-run() { python3 bench.py --no-cpu --no-exact-leg --no-config-legs "$@" 2>/dev/null | python3 -c "
+run() { python3 bench.py --full --no-cpu --no-exact-leg --no-config-legs "$@" 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']

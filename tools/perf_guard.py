@@ -19,7 +19,7 @@ CASES = {
 
 
 def run(args):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu'] + args, capture_output=True, text=True)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu'] + args, capture_output=True, text=True)
     line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
     return json.loads(line)['value']
 

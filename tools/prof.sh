@@ -13,7 +13,7 @@ tag=$1; shift
 out=$PWD/gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-B="python3 bench.py --no-cpu --no-exact-leg --no-config-legs --repeats 1"
+B="python3 bench.py --full --no-cpu --no-exact-leg --no-config-legs --repeats 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- $B --steps 300 "$@" > $out/bench_trace.json 2> $out/trace.err
 pass() {   # name counters...
     local name=$1; shift
