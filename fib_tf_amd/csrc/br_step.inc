@@ -2,13 +2,10 @@
         const T C = s[1], M = s[2], H = s[3], J = s[4], D = s[5], F = s[6], XI = s[7];
         // n = number of dt the slow gates advance (br.py:98-107): 1, or with skip 5 / 0
         // (k.skip == 2: solve(state, 0) on its own — the slow gates are held, FIBHIP_HOLD)
-#ifdef FIB_BR_NOSKIP_EXPERIMENT            // (diagnostic builds of tools/ubench/br_mt_ab.hip only: what does the run-time `skip` cost?)
-        const bool slow = true;
-        const float mdtn = k.mdt;
-#else
+        // (`skip` as a compile-time constant: 82 v_mov, 15 branches and 24 scalar spills fewer, no time gained — 15.16 against
+        // 15.11 us per tick; profiles/r04_ab_boundary_and_br.txt)
         const bool slow = k.skip == 2 ? false : (k.skip ? (sub == 0) : true);
         const float mdtn = k.skip ? k.mdt_skip : k.mdt;
-#endif
         T M1, H1, J1 = J, D1 = D, F1 = F, XI1 = XI;
         if (MODE == MODE_CHEBY) {                                   // br.py:207-252
             constexpr float xmid = FC(0.5 * (30.0 + -90.0)), xhalf = FC(0.5 * (30.0 - -90.0));
@@ -55,10 +52,6 @@
             }
         }
         // currents from the OLD gates, br.py:150-165
-        T iK1, ix1;
-#if FIB_BR_FEWER
-        T iK1x;                                                     // iK1 / 0.35 (Fast)
-#endif
         if constexpr (same_type<P, Fast>::value) {
             // Fast: the five exponentials of iK1 and ix1 are all powers of ONE e = exp(0.04 V0) times constants
             // (exp(0.08 (V0+53)) = (e*E53)^2, exp(-0.04 (V0+23)) = 1 / (e*E23), ...): one v_exp and three v_rcp instead
@@ -70,60 +63,36 @@
             const T a = e * E53;
             const T t1 = vfma(e, 4.0f * E85, -4.0f) * P::rcp(vfma(a, a, a));          // 4 (e^{.04(V+85)} - 1) / (a^2 + a)
             const T t2 = (V0 + 23.0f) * P::rcp(vfma(re, FC(-1.0 / 2.5092903899362979), 1.0f));   // (V+23) / (1 - e^{-.04(V+23)})
-#if FIB_BR_FEWER
-            iK1x = vfma(t2, 0.2f, t1);
-            iK1 = iK1x;                                             // (unused in this build)
-#else
-            iK1 = 0.35f * vfma(t2, 0.2f, t1);
-#endif
-#if FIB_BR_FEWER >= 2
-            ix1 = XI * vfma(re, FC(-0.8 / 4.0551999668446745), FC(0.8 * 21.7584023961970 / 4.0551999668446745));   // 0.8 (e*E77 - 1) / (e*E35)
-#else
-            ix1 = (XI * 0.8f) * vfma(re, FC(-1.0 / 4.0551999668446745), E77 / E35);   // (e*E77 - 1) / (e*E35)
-#endif
+            const T iK1x = vfma(t2, 0.2f, t1);                         // iK1 / 0.35
+            const T ix1 = XI * vfma(re, FC(-0.8 / 4.0551999668446745), FC(0.8 * 21.7584023961970 / 4.0551999668446745));   // 0.8 (e*E77 - 1) / (e*E35)
             (void)E23; (void)E35; (void)E77; (void)E85;
-        } else {
-            iK1 = 0.35f * (P::div(4.0f * (P::exp(0.04f * (V0 + 85.0f)) - 1.0f),
-                                  P::exp(0.08f * (V0 + 53.0f)) + P::exp(0.04f * (V0 + 53.0f))) +
-                           0.2f * P::div(V0 + 23.0f, 1.0f - P::exp(-0.04f * (V0 + 23.0f))));
-            ix1 = P::div((XI * 0.8f) * (P::exp(0.04f * (V0 + 77.0f)) - 1.0f), P::exp(0.04f * (V0 + 35.0f)));
-        }
-#if FIB_BR_FEWER
-        if constexpr (same_type<P, Fast>::value) {
-            // Fast: the same currents with every a*b+c that the reference leaves as two operations written as ONE multiply-add, and
+            // ... and the same currents with every a*b+c that the reference leaves as two operations written as ONE multiply-add, and
             // log C as the bare v_log_f32 (C is a concentration of 1e-7 .. 1e-5: never subnormal, the library form's range
             // scaling is dead code) with ln 2 and E_Ca's factor folded into the multiply-add behind it: 11 instructions of 222 per
-            // cell fewer.  Rounding-level differences only (br.py:150-170).
-#if FIB_BR_FEWER >= 2
-            // ... the factor 4 of the sodium conductance moved into the driving force (a power of two: exact), the calcium
-            // conductance's 0.09 into E_Ca's multiply-add
+            // cell fewer.  Rounding-level differences only (br.py:150-170).  The factor 4 of the sodium conductance moved into the
+            // driving force (a power of two: exact), the calcium conductance's 0.09 into E_Ca's multiply-add.
             const T gNa = vfma(((M * M) * M) * H, J, T_of<T>(0.00125f));
             const T dNa = vfma(V0, 4.0f, -200.0f);
             const T l2C = vmap(C, [](float y) { return __builtin_amdgcn_logf(y); });
             const T dCa = vfma(l2C, FC(0.09 * 13.0278 * 0.69314718055994530942), vfma(V0, FC(0.09), FC(0.09 * 82.3)));   // 0.09 (V - E_Ca)
             const T iCa = (D * F) * dCa;
             const T I_sum = vfma(gNa, dNa, vfma(iK1x, 0.35f, ix1)) + iCa;
-#else
-            const T gNa = vfma((((4.0f * M) * M) * M) * H, J, T_of<T>(0.005f));
-            const T l2C = vmap(C, [](float y) { return __builtin_amdgcn_logf(y); });
-            const T ECa = vfma(l2C, FC(-13.0278 * 0.69314718055994530942), FC(0.0 - 82.3));
-            const T iCa = ((FC(1.0 * 0.09) * D) * F) * (V0 - ECa);
-            const T I_sum = vfma(gNa, V0 - 50.0f, vfma(iK1x, 0.35f, ix1)) + iCa;
-#endif
             const T V1 = clipf(P::mad(I_sum, -k.dt, P::mad(lap, k.ddt, V0)), -85.0f, 25.0f);   // :167-168
             s[0] = V1;
             s[1] = P::mad(vfma(iCa, -1.0e-7f, vfma(C, -0.07f, FC(0.07 * 1.0e-7))), k.dt, C);      // :170
-        } else
-#endif
-        {
-        const T iNa = (1.0f * (((((4.0f * M) * M) * M) * H) * J + 0.005f)) * (V0 - 50.0f);
-        const T ECa = FC(0.0 - 82.3) - 13.0278f * P::log(C);
-        const T iCa = ((FC(1.0 * 0.09) * D) * F) * (V0 - ECa);
-        const T I_sum = ((iK1 + ix1) + iNa) + iCa;
-        const T V1 = clipf(P::mad(I_sum, -k.dt, P::mad(lap, k.ddt, V0)), -85.0f, 25.0f);   // :167-168
-        const T dC = -1.0e-7f * iCa + 0.07f * (1.0e-7f - C);                                   // :170
-        s[0] = V1;
-        s[1] = P::mad(dC, k.dt, C);
+        } else {
+            const T iK1 = 0.35f * (P::div(4.0f * (P::exp(0.04f * (V0 + 85.0f)) - 1.0f),
+                                          P::exp(0.08f * (V0 + 53.0f)) + P::exp(0.04f * (V0 + 53.0f))) +
+                                   0.2f * P::div(V0 + 23.0f, 1.0f - P::exp(-0.04f * (V0 + 23.0f))));
+            const T ix1 = P::div((XI * 0.8f) * (P::exp(0.04f * (V0 + 77.0f)) - 1.0f), P::exp(0.04f * (V0 + 35.0f)));
+            const T iNa = (1.0f * (((((4.0f * M) * M) * M) * H) * J + 0.005f)) * (V0 - 50.0f);
+            const T ECa = FC(0.0 - 82.3) - 13.0278f * P::log(C);
+            const T iCa = ((FC(1.0 * 0.09) * D) * F) * (V0 - ECa);
+            const T I_sum = ((iK1 + ix1) + iNa) + iCa;
+            const T V1 = clipf(P::mad(I_sum, -k.dt, P::mad(lap, k.ddt, V0)), -85.0f, 25.0f);   // :167-168
+            const T dC = -1.0e-7f * iCa + 0.07f * (1.0e-7f - C);                                   // :170
+            s[0] = V1;
+            s[1] = P::mad(dC, k.dt, C);
         }
         s[2] = M1; s[3] = H1; s[4] = J1; s[5] = D1; s[6] = F1; s[7] = XI1;
     

@@ -16,39 +16,26 @@
             const T a = U - u_c;
             const T Huc = heav(a);                                           // :73-75
             const T b = U - u_so;
-#if FIB_FENTON_FEWER & 1
             const T Huso = heav(b);                                          // :77-79 (G = 1 - H exactly: the values are 0, 0.5, 1)
-#else
-            const T Huso = heav(b), Guso = heav_not(b);                      // :77-79
-#endif
             // I_fi = -V*H*(U-u_c)*(u_m-U)/tau_d = (V*H/tau_d) * (a*U - a)     (u_m = 1)                        :81
             const T t1 = (V * Huc) * FC(1.0 / 0.065);
             const T t2 = vfma(a, U, -a);
             // 1 + tanh((U-b_so)/c_so) = 2 - 2*q1,  q1 = 1/(2^(A*U - A*b_so) + 1)                               :83
             const T q1 = P::sigm_q2(vfma(U, FC(2.0 * 1.44269504088896340736 / 0.02), FC(-2.0 * 1.44269504088896340736 / 0.02 * 0.84)));
             T iso = vfma(q1, FC(-2.0 * 0.5 * (0.115 - 0.009)), FC(2.0 * 0.5 * (0.115 - 0.009)));
-#if FIB_FENTON_FEWER & 1
             // U*G = U - U*H in ONE multiply-add, exact (H is 0, 0.5 or 1): the second Heaviside — a form with a scalar operand, twice
             // the issue cost of a plain one — and its product are gone; bit-identical
             iso = vfma(vfma(-U, Huso, U), FC(1.0 / 31.8364), iso);           // (U - u_0) = U                  :84
-#else
-            iso = vfma(U * Guso, FC(1.0 / 31.8364), iso);                    // (U - u_0) = U                  :84
-#endif
             iso = vfma(Huso, tau_a, iso);
             // dU = -(I_fi + I_si + I_so),  I_si = -W*S/tau_si                                                 :82,:86
             const T dU = vfma(-t1, t2, vfma(W * S, FC(1.0 / 31.8364), -iso));
             const auto exc = vgt(U, u_c);
             const T r_s = vfma(Huc, rsp_m_rsn, r_sn);                                                        // :89
             // 0.5*(1 + tanh(k(U-u_csi))) = 1 - q2                                                            :90
-#if FIB_FENTON_FEWER & 2
             // ... = 1/(1 + 2^-x): the sigmoid itself instead of one minus its complement (one subtraction fewer, and no cancellation
             // where the complement is close to one)
             const T p2 = P::sigm_q2(vfma(U, FC(-2.0 * 1.44269504088896340736 * 3.0), FC(2.0 * 1.44269504088896340736 * 3.0 * 0.8)));
             const T dS = r_s * (p2 - S);
-#else
-            const T q2 = P::sigm_q2(vfma(U, FC(2.0 * 1.44269504088896340736 * 3.0), FC(-2.0 * 1.44269504088896340736 * 3.0 * 0.8)));
-            const T dS = r_s * ((1.0f - q2) - S);
-#endif
             dU_out = dU;                                                     // the potential's update: Fenton::post
             s[1] = vsel(exc, V * k.cvp, vfma(V, k.cvn, k.dvn));                                              // :87,:105
             s[2] = vsel(exc, W * k.cwp, vfma(W, k.cwn, k.dwn));              // tau_wn1 == tau_wn2           :88,:106
@@ -58,35 +45,20 @@
         const T U = s[0], V = s[1], W = s[2], S = s[3];         // raw U: fenton.py:101
 
         const T Huc = heav(U - u_c);                            // H(), :73-75
-        const T Huso = heav(U - u_so);
-#if !(FIB_FENTON_FEWER & 16)
-        const T Guso = heav_not(U - u_so);                      // G(), :77-79
-#endif
+        const T Huso = heav(U - u_so);                          // G() = 1 - H, :77-79: formed below
 
         const T I_fi = DC((((-V) * Huc) * (U - u_c)) * (u_m - U), 0.065);                       // :81
         const T I_si = DC((-W) * S, 31.8364);                                                    // :82
-        // (bit 4 of FIB_FENTON_FEWER: H * c is EXACT for H in {0, 0.5, 1}, so the reference's two roundings of H*c + x are the one
-        // rounding of a fused multiply-add — same bits, one instruction; likewise (U - u_0) G)
-#if FIB_FENTON_FEWER & 16
+        // (H * c is EXACT for H in {0, 0.5, 1}, so the reference's two roundings of H*c + x are the one rounding of a fused
+        // multiply-add — same bits, one instruction; likewise (U - u_0) G)
         const T I_so = vfma(Huso, tau_a, P::mad(P::one_plus_tanh(DC(U - b_so, 0.02)), half_aso,
-#else
-        const T I_so = P::mad(Huso, tau_a, P::mad(P::one_plus_tanh(DC(U - b_so, 0.02)), half_aso,
-#endif
-#if FIB_FENTON_FEWER & 16
                                                   // (U - u_0) G = U - U H in one multiply-add: exact (u_0 = 0; H is 0, 0.5 or 1), bit-identical
                                                   DC(vfma(-U, Huso, U), 31.8364)));                // :83-84
-#else
-                                                  DC((U - u_0) * Guso, 31.8364)));               // :83-84
-#endif
         const T dU = -((I_fi + I_si) + I_so);                                                    // :86
         const auto exc = vgt(U, u_c);
         const T dV = vsel(exc, DC(-V, 3.33), DC(1.0f - V, 19.2));                                // :87
         const T dW = vsel(exc, DC(-W, 160.0), vsel(vgt(U, u_w), DC(1.0f - W, 75.0), DC(1.0f - W, 75.0)));  // :88
-#if FIB_FENTON_FEWER & 16
         const T r_s = vfma(Huc, rsp_m_rsn, T_of<T>(r_sn));                                      // :89
-#else
-        const T r_s = P::mad(Huc, rsp_m_rsn, r_sn);                                              // :89
-#endif
         const T dS = r_s * P::half_one_plus_tanh_minus((U - u_csi) * k_, S);                     // :90
 
         dU_out = dU;                                                                             // :103 -> Fenton::post

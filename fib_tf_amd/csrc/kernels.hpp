@@ -461,17 +461,6 @@ struct MtArgs {
     int snap_var;         // low byte: which array the frame is; the other three: the bound on a tile's wait for its neighbours in
                           // milliseconds (0 = MT_WAIT_TICKS; packed, not an argument of its own: see ticks_id)
 };
-#define FIB_STR2(x) #x
-#define FIB_STR(x) FIB_STR2(x)
-#ifndef FIB_POLL_SLEEP
-#define FIB_POLL_SLEEP 1
-#endif
-#ifndef FIB_B_LASTWAVE
-#define FIB_B_LASTWAVE 0
-#endif
-#ifndef FIB_B_INBOX
-#define FIB_B_INBOX 0
-#endif
 constexpr int MT_SNAP_STRIDE = 16;                    // words between two tiles' words in snap_flag
 constexpr int MT_MAX_TILES = 1024;                    // epoch / snap words allocated per handle (only grids of <= ncu tiles use them)
 constexpr int MT_HOST_WORD_AT = MT_MAX_TILES * MT_SNAP_STRIDE;   // the host's word, in words from snap_flag
@@ -479,21 +468,14 @@ constexpr int MT_GIVEUP_WORD = 8;                     // ... and, this many word
 constexpr int MT_EPOCH_STRIDE = 64;                   // words (256 bytes)
 constexpr unsigned MT_CANCEL = 0xFFFFu;               // the host's word, low half: this launch is not wanted any more
 constexpr unsigned long long MT_WAIT_TICKS = 200000000ull;   // 2 s of the 100 MHz s_memrealtime clock
-constexpr int MT_WAIT_SHIFT = 17;                            // MtArgs::snap_var's upper three bytes count 2^17 such ticks (1.31 ms)
+constexpr int MT_POLL_SLEEP = 1;                             // s_sleep between two polls of the neighbours' words
 // The multi-tick kernels sit at their register limits (Fenton: 128 vector registers, and scalar registers spilled into vector
 // lanes): an edit ANYWHERE in them — one `& 0xFF` in the prologue — re-draws the register allocation and moves the kernel by 2-3 %
-// (round 4, tools/r04_h.sh -> profiles/r04_ab_kernel_variants.txt: round 3's text 12.28 us per tick, the same with the give-up
-// word set by compare-and-swap 12.60, by a plain store 12.29, the wait bound as a shift 12.60 or 12.24 depending on what else is
-// in, ...).  These switches keep the equivalent forms that were measured; the defaults are the combination that lost nothing
-// against round 3's kernel for Fenton (12.32 / 12.28) and is the fastest measured for the other two (rounding-faithful Fenton 18.8
-// against 21.5, Beeler-Reuter 15.36 against 15.75).
-#ifndef FIB_WAIT_FORM
-#define FIB_WAIT_FORM 0     // the wait bound: 0 = milliseconds in MtArgs::snap_var's upper bytes (0: MT_WAIT_TICKS), 1 = units of 2^17 ticks, 2 = MT_WAIT_TICKS
-#endif
-#ifndef FIB_GIVEUP_CAS
-#define FIB_GIVEUP_CAS 0    // the give-up word: a plain store of the launch's id (every tile of a launch writes the same id, and a launch
-                            // queued behind one that gave up finds the word before its own wait can run out) / compare-and-swap
-#endif
+// (round 4, profiles/r04_ab_kernel_variants.txt: round 3's text 12.28 us per tick, the same with the give-up word set by
+// compare-and-swap 12.60, by a plain store 12.29, the wait bound as a shift 12.60 or 12.24 depending on what else is in, ...).
+// The forms in the tree are the combination that lost nothing against round 3's kernel for Fenton (12.32 / 12.28) and is the
+// fastest measured for the other two (rounding-faithful Fenton 18.8 against 21.5, Beeler-Reuter 15.36 against 15.75).  Measure
+// any edit here against the kernel it replaces on one box (tools/ubench/mt_ab.hip, br_mt_ab.hip).
 
 typedef unsigned fib_v4u __attribute__((ext_vector_type(4)));
 typedef float fib_v4f __attribute__((ext_vector_type(4)));
@@ -553,16 +535,12 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
     constexpr int SPARE = PAIR ? R + 6 : R + 4;
     __shared__ __attribute__((aligned(16))) float lds[2][NL + SPARE * 64];   // (+ spare rows: see `wi`)
     __shared__ int mt_abort;
-    __shared__ unsigned mt_arrive[1];                               // (FIB_B_LASTWAVE, measured and not taken: waves whose stores have been acknowledged)
     __shared__ float snapl[MT ? NW * R * 64 : 1];                    // multi-tick launches: the frame's values, parked for one tick
 
     const int tile = xcd_tile(blockIdx.x, g.ntiles);
     if (tile >= g.ntiles) return;
     FIB_STAMP(0);
-    if (MT && threadIdx.x == 0) {
-        mt_abort = 0;                                               // (read after the first tick's barriers)
-        if (FIB_B_LASTWAVE) mt_arrive[0] = 0u;                         // (first added to after the first tick's barriers)
-    }
+    if (MT && threadIdx.x == 0) mt_abort = 0;                       // (read after the first tick's barriers)
     auto &&kk = pinned_for<M, (MT && SameType<P, Exact>::value)>(k);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -630,11 +608,7 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
             for (int r = 0; r < R; ++r) {
                 float x = s[r][0];
 #pragma unroll
-#if FIB_WAIT_FORM == 2
-                for (int v = 1; v < NV; ++v) x = mt.snap_var == v ? s[r][v] : x;
-#else
                 for (int v = 1; v < NV; ++v) x = (mt.snap_var & 0xFF) == v ? s[r][v] : x;
-#endif
                 snapl[(c0 + r) * 64 + lane] = x;                    // (read back by the same thread: no barrier needed)
             }
         }
@@ -701,11 +675,8 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
     FIB_STAMP(2);
 
     // two sub-steps per loop body: the loop-carried state then needs no register moves at the back edge (measured:
-    // -5 % under Exact, -7 % for R = 4 strips, nothing for Fast R = 3; tools/ubench/diag_strip.hip)
-#ifndef FIB_STEP_UNROLL
-#define FIB_STEP_UNROLL 2
-#endif
-    constexpr int STEP_UNROLL = FIB_STEP_UNROLL;
+    // -5 % under Exact, -7 % for R = 4 strips, nothing for Fast R = 3)
+    constexpr int STEP_UNROLL = 2;
     // A strip that stays whole for all K sub-steps — no row of it goes stale inside the tick, none is a border or a
     // ghost-source row of the grid (more than half of a tile's strips, and the ones that carry its own cells) — runs the
     // step loop without any of the row bookkeeping: ~35 scalar instructions and a dozen branches fewer per sub-step.
@@ -716,18 +687,12 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
     // (and only where the registers are there and the bookkeeping is a visible share of the sub-step: four-row strips spilled
     // with the second loop — at 16 waves per workgroup the budget is 128 registers — and Beeler-Reuter's eight arrays with ~270
     // instructions per cell ran 1.5-3 % slower with it; both keep one loop)
-#ifndef FIB_PRE_FIRST
-#define FIB_PRE_FIRST 0
-#endif
-#ifndef FIB_WHOLE_NVR
-#define FIB_WHOLE_NVR 12
-#endif
-    constexpr bool WHOLE_LOOP = MT && NV * R <= FIB_WHOLE_NVR;
+    constexpr int WHOLE_NVR = 12;                                   // state registers per lane (NV x R) up to which it pays
+    constexpr bool WHOLE_LOOP = MT && NV * R <= WHOLE_NVR;
     const bool whole = WHOLE_LOOP && ra_fix == 0 && rb_fix == R && (!top_open || c0 >= K - 1) && (!bot_open || c0 + R <= CY - (K - 1)) &&
                        pub == (1u << R) - 1u && top_r < 0 && bot_r < 0;
-#ifdef FIB_LOOP_ALIGN           // (experiment: does the placement of the tick loop in the instruction stream matter?)
-    asm volatile(".p2align " FIB_STR(FIB_LOOP_ALIGN));
-#endif
+    // (the tick loop aligned to 32-256 bytes in the instruction stream: 12.55 +- 0.03 us per tick for every alignment;
+    // profiles/r04_ab_kernel_variants.txt)
 #pragma unroll 1
     for (int tick = 0;; ++tick) {
     // the host's word is read over PCIe by ONE thread of the grid at the START of a tick and looked at at the tick's end: the
@@ -756,35 +721,8 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
         for (int st = 0; st < K; ++st) {
             float *B = lds[(st & 1) ^ 1];
             float lp[R], cc[R];
-#if FIB_PRE_FIRST
-            // (experiment) the part of the update that needs no neighbour — the whole reaction term — is ISSUED before anything
-            // waits for the window the barrier's other side has just requested from the LDS
-            float dU[R];
-            M::template stepN_pre<P, MODE, R>(s, dU, kk);
-#if FIB_PRE_FIRST >= 2
-            // two statements the compiler keeps in order: the first consumes everything the reaction term produced, the second
-            // "produces" the window — so the wait for the LDS sits between them
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                asm volatile("" ::"v"(dU[r]));
-#pragma unroll
-                for (int v = 1; v < NV; ++v) asm volatile("" ::"v"(s[r][v]));
-            }
-#pragma unroll
-            for (int r = 0; r < R + 2; ++r) asm volatile("" : "+v"(win[r][0]), "+v"(win[r][1]), "+v"(win[r][2]));
-#else
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                float l = lap9<P>(win[r][1], win[r + 2][1], win[r + 1][0], win[r + 1][2], win[r][0], win[r + 2][0],
-                                  win[r][2], win[r + 2][2], win[r + 1][1]);
-                if (PHASE) l = pc[r].add(l, win[r][1], win[r + 2][1], win[r + 1][0], win[r + 1][2]);
-                lp[r] = l;
-                cc[r] = win[r + 1][1];
-            }
-            M::template stepN_post<P, MODE, R>(s, dU, cc, lp, kk);
-#else
+            // (tried: the reaction term issued before the wait for the window, behind a sched_barrier or ordered asm statements:
+            // 12.24-12.84 against 12.14 us per tick, rounding-faithful 19.1-19.8 against 18.5; profiles/r04_ab_reaction_first.txt)
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 float l = lap9<P>(win[r][1], win[r + 2][1], win[r + 1][0], win[r + 1][2], win[r][0], win[r + 2][0],
@@ -799,22 +737,12 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
 #pragma unroll
                 for (int r = 0; r < R; ++r) M::template step<P, MODE>(s[r], cc[r], lp[r], kk, sub0 + st);
             }
-#endif
             if (st + 1 < K) {
 #pragma unroll
                 for (int r = 0; r < R; ++r) B[wi + ro(r)] = s[r][0];
                 FIB_WSTAMP(st);
-#ifndef FIB_DIAG_NO_BARRIER
                 __syncthreads();
-#endif
-#ifndef FIB_DIAG_NO_RELOAD
                 window(B, win);
-#endif
-#if FIB_PRE_FIRST == 3
-                // (the state as the reaction term sees it exists only on this side of the barrier and of the window's reads)
-#pragma unroll
-                for (int r = 0; r < R; ++r) asm volatile("" : "+v"(s[r][0]), "+v"(s[r][1]), "+v"(s[r][2]), "+v"(s[r][3])::"memory");
-#endif
             }
             FIB_STAMP(3 + st);
         }
@@ -880,12 +808,8 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
                 }
             }
             FIB_WSTAMP(st);
-#ifndef FIB_DIAG_NO_BARRIER                 // (diagnostic builds of tools/ubench/diag_strip.hip only)
             __syncthreads();
-#endif
-#ifndef FIB_DIAG_NO_RELOAD
             window(B, win);
-#endif
         }
         FIB_STAMP(3 + st);
     }
@@ -917,50 +841,20 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // EVERY storing wave, before the barrier / before it is counted
         FIB_BSTAMP(2);
         const unsigned want = mt.epoch0 + (unsigned)tick + 1u;
-#if FIB_B_LASTWAVE
-        // No workgroup barrier between the stores and the epoch word: every wave counts itself in LDS once its stores have
-        // been acknowledged, and the wave that comes LAST raises the word.  The strips that went stale early (the rim strips:
-        // nothing to store) pass at once — wave 0 among them, so its poll of the neighbours' words is already running when the
-        // tile's own word goes up — and nobody waits for the slowest strip twice.
-        {
-            unsigned old = 0;
-            if (lane == 0) old = __hip_atomic_fetch_add(&mt_arrive[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            old = __builtin_amdgcn_readfirstlane(old);
-            if (old + 1u == (unsigned)NW * ((unsigned)tick + 1u) && lane == 0) {
-                __hip_atomic_store(mt.epoch + (size_t)tile * MT_EPOCH_STRIDE, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                // (every wave's write-through stores to the host frame have been acknowledged before it was counted)
-                if (tick == snap_at)
-                    __hip_atomic_store(mt.snap_flag + (size_t)tile * MT_SNAP_STRIDE, mt.snap_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-        FIB_BSTAMP(3);
-#else
+        // (tried: no barrier here — every wave counts itself in LDS once its stores are acknowledged, the last raises the word:
+        // 12.67 against 12.15 us per tick, Beeler-Reuter 15.7 against 15.1; profiles/r04_ab_boundary_and_br.txt)
         __syncthreads();
         FIB_BSTAMP(3);
-#if FIB_B_INBOX
-        // PUSH instead of pull: the tile writes its tick count into a word of each neighbour's OWN line (slot = the direction it
-        // is seen from), so that a tile polls ONE 64-byte line — eight neighbours in one memory request — instead of eight lines
-        // on eight channels
-        if (wave == 0 && lane < 8) {
-            const int tiles_y = g.ntiles / g.tiles_x;
-            const int d = lane < 4 ? lane : lane + 1;
-            const int ny = by + d / 3 - 1, nx = bx + d % 3 - 1;
-            const int od = 8 - d, slot = od < 4 ? od : od - 1;     // the direction this tile lies in, seen from that neighbour
-            if (ny >= 0 && ny < tiles_y && nx >= 0 && nx < g.tiles_x)
-                __hip_atomic_store(mt.epoch + (size_t)(ny * g.tiles_x + nx) * MT_EPOCH_STRIDE + slot, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#endif
+        // (tried: the tick count pushed into a word of each neighbour's own line, so that a tile polls one line instead of eight:
+        // 12.37 against 12.38 us per tick, Beeler-Reuter 15.34 against 15.27; profiles/r04_ab_boundary_and_br.txt)
         if (threadIdx.x == 0) {
-#if !FIB_B_INBOX
             __hip_atomic_store(mt.epoch + (size_t)tile * MT_EPOCH_STRIDE, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
             // every wave's write-through stores to the host frame have been acknowledged (vmcnt(0) before the barrier above):
             // the word follows them
             if (tick == snap_at) {
                 __hip_atomic_store(mt.snap_flag + (size_t)tile * MT_SNAP_STRIDE, mt.snap_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
-#endif
         // ---- wait for the eight neighbours (bounded) ---------------------------------------------------------
         if (wave == 0) {
             const int tiles_y = g.ntiles / g.tiles_x;
@@ -981,22 +875,13 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
                 if ((hws >> 16) == (mt.ticks_id >> 16) && lane == 0)
                     __hip_atomic_store(mt.err + MT_EPOCH_STRIDE, hws, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-#if FIB_B_INBOX
-            const unsigned *f = lane == 8 ? mt.err : (lane == 9 ? mt.err + MT_EPOCH_STRIDE
-                                                                : mt.epoch + (size_t)tile * MT_EPOCH_STRIDE + (lane & 7));
-#else
             const unsigned *f = lane == 8 ? mt.err : (lane == 9 ? mt.err + MT_EPOCH_STRIDE
                                                                 : mt.epoch + (size_t)(need ? ny * g.tiles_x + nx : tile) * MT_EPOCH_STRIDE);
-#endif
             const unsigned done = (unsigned)tick + 1u;
-#if FIB_WAIT_FORM == 2
-            const unsigned long long t_end = __builtin_amdgcn_s_memrealtime() + MT_WAIT_TICKS;
-#elif FIB_WAIT_FORM == 1        // the bound in units of 2^17 ticks of 10 ns (1.31 ms), set by the host: a shift, no multiply, no default
-            const unsigned long long t_end = __builtin_amdgcn_s_memrealtime() + ((unsigned long long)((unsigned)mt.snap_var >> 8) << MT_WAIT_SHIFT);
-#else
+            // (tried: the bound as a constant, 12.29 us per tick, or as a shift, 12.24-12.60, against 12.32 in milliseconds;
+            // rounding-faithful Fenton 19.4 / 19.0 against 18.8; profiles/r04_ab_kernel_variants.txt)
             const unsigned wait_ms = (unsigned)mt.snap_var >> 8;
             const unsigned long long t_end = __builtin_amdgcn_s_memrealtime() + (wait_ms ? (unsigned long long)wait_ms * 100000ull : MT_WAIT_TICKS);
-#endif
             for (;;) {
                 const unsigned e = __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 // one ballot for everything that is not the ordinary case: a tile gave up (lane 8), or the host's word concerns
@@ -1021,19 +906,15 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
                     if (lane == 0) {
                         // the give-up word names the launch (its id is never 0): the host replays from the state THAT launch
                         // started from (fibhip.hip, `recover`); launches queued behind it find the word and leave at their first
-                        // boundary without writing anything
-#if FIB_GIVEUP_CAS
-                        unsigned expected = 0u;
-                        __hip_atomic_compare_exchange_strong(mt.err, &expected, mt.ticks_id >> 16, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_AGENT);
-#else
+                        // boundary without writing anything.  (A plain store: every tile of a launch writes the same id, and a launch
+                        // queued behind one that gave up finds the word before its own wait can run out.  Compare-and-swap: 12.60
+                        // against 12.29 us per tick, profiles/r04_ab_kernel_variants.txt.)
                         __hip_atomic_store(mt.err, mt.ticks_id >> 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
                         mt_abort = 1;
                     }
                     break;
                 }
-                __builtin_amdgcn_s_sleep(FIB_POLL_SLEEP);
+                __builtin_amdgcn_s_sleep(MT_POLL_SLEEP);
             }
         }
         FIB_BSTAMP(4);
@@ -1150,10 +1031,10 @@ template <class M, class P, int MODE, int K, int TX, int TY, int R, bool PHASE>
 __global__ void __launch_bounds__(64 * ((TY + 2 * (K - 1) + R - 1) / R))
 strip_mt_kernel(Geo g, PtrTab<M::NVAR> pt, PhaseTab ph, typename M::Consts k, int sub0, MtArgs mt)
 {
-#ifndef FIB_MT_FULL_GEO
     // The host launches this kernel on whole single-device grids only (fibhip.hip mt_eligible: planar slab, no ghost rows, one band
     // of rows): say so, and seven of Geo's twelve scalars are constants or copies instead of live scalar registers — the kernel
-    // spills scalar registers into vector lanes as it is, and sits at its 128 vector registers.
+    // spills scalar registers into vector lanes as it is, and sits at its 128 vector registers.  (Against the full Geo:
+    // profiles/r04_ab_kernel_variants.txt, block 3.)
     g.pitch = g.W;
     g.Hg = g.H;
     g.row_off = 0;
@@ -1161,7 +1042,6 @@ strip_mt_kernel(Geo g, PtrTab<M::NVAR> pt, PhaseTab ph, typename M::Consts k, in
     g.r1 = g.H;
     g.rb0 = g.rb1 = 0;
     g.ty_a = 0x7fffffff;
-#endif
     strip_body<M, P, MODE, K, TX, TY, R, PHASE, true>(g, pt, ph, k, sub0, mt);
 }
 

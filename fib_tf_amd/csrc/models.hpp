@@ -207,24 +207,18 @@ static FIB_DEV float one_plus_tanh_rf(float x)
     return __builtin_fmaf(-2.0f, r, 2.0f);
 }
 
-// Fenton, fewer instructions per cell (the kernels' sub-steps cost what their arithmetic costs).  Fast policy: bit 0 =
-// U*G(b) as U - U*H(b) (exact: one multiply-add for a Heaviside and a product), bit 1 = the second sigmoid itself instead of one minus
-// its complement (52 -> 50 per cell).  Rounding-faithful policy, bit 4: where one factor of a*b + c is 0, 0.5 or 1 (the Heavisides) or
-// exactly 0.5, the product is EXACT and the reference's two roundings are the one rounding of a fused multiply-add — the same bits in
-// one instruction: H*tau_a + x, H*(r_sp - r_sn) + r_sn, x*0.5 - S, and (U - u_0)*G as U - U*H (kernel 18.3 -> 17.3 us per tick).
-// 0 = the forms of rounds 2-3, kept for same-box A/B (tools/r04_l.sh, r04_q.sh).
-#ifndef FIB_FENTON_FEWER
-#define FIB_FENTON_FEWER 19
-#endif
-// Beeler-Reuter, fast policy (br_step.inc): 1 = every a*b+c of the currents that the reference leaves as two operations as ONE
-// multiply-add and log C as the bare v_log_f32 (C is never subnormal); 2 = constant factors folded into neighbouring multiply-adds.
-// 222 -> 202 instructions per cell; the error along the golden trajectories is the one of the old forms (tools/r04_p.sh).  0 = the
-// forms of rounds 1-3, kept for same-box A/B.  (Measured and NOT taken: the twelve sums by Horner's rule, x as one multiply-add —
+// Fenton, fewer instructions per cell (the kernels' sub-steps cost what their arithmetic costs; fenton_step.inc).  Fast
+// policy: U*G(b) as U - U*H(b) (exact: one multiply-add for a Heaviside and a product), and the second sigmoid itself instead of one
+// minus its complement (52 -> 50 per cell; kernel 12.2 -> 12.0 us per tick, profiles/r04_fewer_instructions.txt).  Rounding-faithful
+// policy: where one factor of a*b + c is 0, 0.5 or 1 (the Heavisides) or exactly 0.5, the product is EXACT and the reference's two
+// roundings are the one rounding of a fused multiply-add — the same bits in one instruction: H*tau_a + x, H*(r_sp - r_sn) + r_sn,
+// x*0.5 - S, and (U - u_0)*G as U - U*H (kernel 18.3 -> 17.3 us per tick, profiles/r04_ab_exact_contractions.txt).
+// Beeler-Reuter, fast policy (br_step.inc): every a*b+c of the currents that the reference leaves as two operations as ONE
+// multiply-add and log C as the bare v_log_f32 (C is never subnormal), and constant factors folded into neighbouring multiply-adds.
+// 222 -> 202 instructions per cell, kernel 15.1 -> 14.3 us per tick; the error along the golden trajectories is the one of the old
+// forms (profiles/r04_fewer_instructions.txt).  (Measured and NOT taken: the twelve sums by Horner's rule, x as one multiply-add —
 // 13 instructions fewer, but the ascending sums are what the reference computes and its rounding errors are what parity is
 // measured against: 4-10 x the distance from the golden trajectories)
-#ifndef FIB_BR_FEWER
-#define FIB_BR_FEWER 2
-#endif
 struct Exact {
     // a*b + c: the reference rounds the product and the sum separately
     template <class T, class B, class C>
@@ -239,23 +233,13 @@ struct Exact {
     }
     template <class T>
     static FIB_DEV T tanhv(const T &a) { return vmap(a, [](float x) { return tanh_rf(x); }); }
-    // 1 + tanh(a) and 0.5*(1 + tanh(a)) - s, as the reference writes them (fenton.py:83,90)
-#ifdef FIB_EXACT_TANH_SUM_VIA_TANH                 // (the form before round 4: the sum through the stand-alone tanh; A/B builds only)
-    template <class T>
-    static FIB_DEV T one_plus_tanh(const T &a) { return 1.0f + tanhv(a); }
-#else
+    // 1 + tanh(a) and 0.5*(1 + tanh(a)) - s, as the reference writes them (fenton.py:83,90).  (The sum through the stand-alone
+    // tanh, 1 + tanh_rf(a): 21.9 against 18.8 us per tick, profiles/r04_accuracy_one_plus_tanh.txt)
     template <class T>
     static FIB_DEV T one_plus_tanh(const T &a) { return vmap(a, [](float x) { return one_plus_tanh_rf(x); }); }
-#endif
+    // (halving is exact: the two roundings of x * 0.5 + (-s) are the one rounding of a fused multiply-add)
     template <class T>
-    static FIB_DEV T half_one_plus_tanh_minus(const T &a, const T &s)
-    {
-#if FIB_FENTON_FEWER & 16      // (halving is exact: the two roundings of x * 0.5 + (-s) are the one rounding of a fused multiply-add)
-        return vfma(one_plus_tanh(a), 0.5f, -s);
-#else
-        return one_plus_tanh(a) * 0.5f + (-s);
-#endif
-    }
+    static FIB_DEV T half_one_plus_tanh_minus(const T &a, const T &s) { return vfma(one_plus_tanh(a), 0.5f, -s); }
     template <class A, class T>
     static FIB_DEV T div(const A &a, const T &b) { return vzip(a, b, [](float x, float y) { return x / y; }); }
     template <class T> static FIB_DEV T rcp(const T &a) { return vmap(a, [](float x) { return 1.0f / x; }); }
@@ -299,20 +283,8 @@ struct Fast {
     template <class T>
     static FIB_DEV T sigm_q2(const T &x)
     {
-#ifdef FIB_DIAG_NOTRANS                     // (diagnostic builds only: what do the transcendental instructions cost?)
-        return x * 0.001f + 0.5f;
-#else
-#if defined(FIB_DIAG_NOEXP)                 // (diagnostic builds: the two transcendentals priced separately)
-        const T e = x * 0.001f;
-#else
         const T e = vmap(x, [](float y) { return __builtin_amdgcn_exp2f(y); });
-#endif
-#if defined(FIB_DIAG_NORCP)
-        return (e + 1.0f) * 0.37f;
-#else
         return vmap(e + 1.0f, [](float y) { return __builtin_amdgcn_rcpf(y); });
-#endif
-#endif
     }
     template <class T>
     static FIB_DEV T one_plus_tanh(const T &a) { return vfma(sigm_q(a), -2.0f, 2.0f); }
@@ -360,13 +332,12 @@ template <class A, class B> static FIB_DEV auto g_min(const A &a, const B &b)
 template <class T> static FIB_DEV T g_pow(const T &a, float e) { return vmap(a, [e](float x) { return powf(x, e); }); }
 template <class P, class T> static FIB_DEV T g_sqrt(const T &a) { return vmap(a, [](float x) { return P::sqrt(x); }); }
 
-// (1 + sign(x)) * 0.5 and (1 - sign(x)) * 0.5 (fenton.py:73-79): the three values {0, 0.5, 1}, produced as
-// clamp(0.5 +- x * 2^27, 0, 1) — one instruction, no compare (compares write SGPRs and issue at ~60 %
+// (1 + sign(x)) * 0.5 (fenton.py:73-75; G = 1 - H, :77-79, is formed from it): the three values {0, 0.5, 1}, produced as
+// clamp(0.5 + x * 2^27, 0, 1) — one instruction, no compare (compares write SGPRs and issue at ~60 %
 // of the plain-VALU rate, tools/ubench/valu2.hip).  Exact for every argument this model forms: x is
 // U - 0.23 or U - 0.3, an exact float difference whose nonzero magnitude is at least one ulp of the
 // threshold (2^-26), so |x| * 2^27 >= 2 whenever x != 0.
 template <class T> static FIB_DEV T heav(const T &x) { return vfma_sat(x, 134217728.0f, 0.5f); }
-template <class T> static FIB_DEV T heav_not(const T &x) { return vfma_sat(x, -134217728.0f, 0.5f); }
 
 // rush_larsen, ionic.py:115-123.  mdt = float(-dt)
 template <class P, class T>
@@ -421,7 +392,7 @@ struct Fenton {
     // while the stencil window's LDS reads are in flight was tried and bought nothing: with four waves per SIMD that
     // latency is covered already)
     template <class P, int MODE, int R>
-    static FIB_DEV void stepN_pre(float (&s)[R][NVAR], float (&dU)[R], const Consts &k)
+    static FIB_DEV void stepN(float (&s)[R][NVAR], const float (&U0)[R], const float (&lap)[R], const Consts &k, int)
     {
         vf<R> t[NVAR], d;
 #pragma unroll
@@ -429,26 +400,15 @@ struct Fenton {
 #pragma unroll
             for (int v = 0; v < NVAR; ++v) t[v].v[r] = s[r][v];
         pre<P, vf<R>>(t, d, k);
+        float dU[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             dU[r] = d.v[r];
 #pragma unroll
             for (int v = 1; v < NVAR; ++v) s[r][v] = t[v].v[r];
         }
-    }
-    template <class P, int MODE, int R>
-    static FIB_DEV void stepN_post(float (&s)[R][NVAR], const float (&dU)[R], const float (&U0)[R], const float (&lap)[R],
-                                   const Consts &k)
-    {
 #pragma unroll
         for (int r = 0; r < R; ++r) post<P, float>(s[r], dU[r], U0[r], lap[r], k);
-    }
-    template <class P, int MODE, int R>
-    static FIB_DEV void stepN(float (&s)[R][NVAR], const float (&U0)[R], const float (&lap)[R], const Consts &k, int)
-    {
-        float dU[R];
-        stepN_pre<P, MODE, R>(s, dU, k);
-        stepN_post<P, MODE, R>(s, dU, U0, lap, k);
     }
     // keep the per-step scalars in VGPRs: a VALU op with an SGPR source issues at ~60 % of the rate
     // of an all-VGPR one (tools/ubench/valu2.hip)

@@ -1,5 +1,6 @@
 """Diagnostic: the error of the Beeler-Reuter fast policy along the golden 64x64 trajectories (tests/golden/br_traj64_*.npz), per array
-and snapshot tick, for the build of the library named by FIBHIP_BR_LIBRARY (tools/r04_p.sh compares the FIB_BR_FEWER levels)."""
+and snapshot tick, for the build of the library named by FIBHIP_BR_LIBRARY (run it once per build to compare two versions of
+br_step.inc: profiles/r04_fewer_instructions.txt)."""
 import os, sys
 import numpy as np
 root = os.environ.get('GRAFT_REPO_ROOT', '/root/repo')
