@@ -15,6 +15,7 @@ SRC = os.path.join(HERE, 'csrc', 'fibhip.hip')
 HDR = os.path.join(ROOT, 'include', 'fibhip.h')
 
 FENTON4V, BR, COURT, COURT_US, CUSTOM = 0, 1, 2, 3, 4
+OBS_MAPS = ('first_up', 'last_up', 'prev_up', 'apd', 'count')     # enum fibhip_obs_map, in order
 CHEBY, SKIP, CHRONIC, FAST, ALLVARS, ROW_INTERLEAVED, ZEROPAD, HOLD = 1, 2, 4, 8, 16, 32, 64, 128
 
 # -ffp-contract=off: FMAs appear only where the source writes them (policy hook P::mad).
@@ -163,6 +164,10 @@ SYMBOLS = {
     'fibhip_trace_begin': ([_h], C.c_int),
     'fibhip_trace_end': ([_h, C.POINTER(TraceEvent), C.c_int], C.c_int),
     'fibhip_plan_tile': ([_h, _ip, _ip, _ip], C.c_int),
+    'fibhip_observe_begin': ([_h, C.c_int, C.c_float, C.c_float], C.c_int),
+    'fibhip_observe_get': ([_h, C.c_int, C.c_void_p], C.c_int),
+    'fibhip_observe_ticks': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_observe_end': ([_h], C.c_int),
     'fibhip_last_error': ([], C.c_char_p),
 }
 
@@ -638,3 +643,24 @@ class Stepper:
         """consecutive ticks one launch can cover (Courtemanche, fast policy, one device: 3; Fenton / Beeler-Reuter on a
         grid whose tiles are all resident at once: FIBHIP_MT_MAX, default 32; otherwise 1)"""
         return self._ck(self._L.fibhip_ticks_per_launch(self._h))
+
+    # ---- activation recorder (include/fibhip.h fibhip_observe_*) --------------------------------------------------
+    def observe_begin(self, var, up, down):
+        """attaches (or re-attaches, clearing the maps) the per-cell activation recorder on array `var`"""
+        self._ck(self._L.fibhip_observe_begin(self._h, int(var), float(up), float(down)))
+
+    def observe_get(self, which):
+        """one map as a [height, width] array: 'first_up', 'last_up', 'prev_up', 'apd' (float32) or 'count' (int32)"""
+        k = OBS_MAPS.index(which)
+        out = np.empty((self.height, self.width), np.int32 if which == 'count' else np.float32)
+        self._ck(self._L.fibhip_observe_get(self._h, k, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def observe_ticks(self):
+        """ticks observed since observe_begin"""
+        k = C.c_longlong()
+        self._ck(self._L.fibhip_observe_ticks(self._h, C.byref(k)))
+        return int(k.value)
+
+    def observe_end(self):
+        self._ck(self._L.fibhip_observe_end(self._h))

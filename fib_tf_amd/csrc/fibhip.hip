@@ -8,11 +8,13 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
+#include <limits>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -531,6 +533,12 @@ struct fibhip_ctx {
     size_t agg_stride;      // slab's pitch on row-block shards), `agg_stride` floats apart; or null
     bool use_agg, agg_dirty;
     bool agg_ghost_dirty;   // row-block shards: a halo exchange has rewritten the ghost rows' slow variables
+    // activation recorder (fibhip_observe_begin): while `obs`, commit_impl enqueues observe_kernel behind every tick
+    bool obs;
+    int obs_var;
+    float obs_up, obs_down;
+    float *obs_buf;         // 6 planes of `cells` (W-pitched): Vp | first_up | last_up | prev_up | apd | count (int32)
+    long long obs_k;        // observed ticks since the recorder was attached
 };
 
 static const void *consts_of(fibhip_ctx *h)
@@ -1022,6 +1030,7 @@ extern "C" int fibhip_destroy(fibhip_t h)
     if (h->phase3) hipFree(h->phase3);
     if (h->phi_dev) hipFree(h->phi_dev);
     if (h->agg) hipFree(h->agg);
+    if (h->obs_buf) hipFree(h->obs_buf);
     if (h->xbuf) hipFree(h->xbuf);
     if (h->epochs) hipFree(h->epochs);
     for (auto &r : h->trace) {
@@ -1620,11 +1629,15 @@ static bool mt_eligible(const fibhip_ctx *h, const Variant *v)
     const long tiles = (long)((h->d.width + v->TX - 1) / v->TX) * ((h->d.height + v->TY - 1) / v->TY);
     return tiles <= h->ncu && tiles <= MT_MAX_TILES && h->d.device < 16;
 }
+// (an attached activation recorder observes every tick through commit_impl: no multi-tick launches, hence no run-ahead
+// and no launched series either)
 static const Variant *mt_variant(const fibhip_ctx *h)
 {
-    if (h->plan.size() != 1 || h->fused_fn || !mt_eligible(h, h->plan[0].v)) return nullptr;
+    if (h->obs || h->plan.size() != 1 || h->fused_fn || !mt_eligible(h, h->plan[0].v)) return nullptr;
     return h->plan[0].v;
 }
+// consecutive ticks one plain launch may fuse (Courtemanche on aggregates: up to multi_max; one while a recorder is attached)
+static inline int multi_cap(const fibhip_ctx *h) { return h->obs ? 1 : h->multi_max; }
 
 static struct {
     std::mutex mu;
@@ -2038,6 +2051,36 @@ static int interior_impl(fibhip_t h)
     return 0;
 }
 
+// the activation recorder's update for the tick just committed (observed tick k = obs_k), on s0 behind it
+static int observe_enqueue(fibhip_ctx *h)
+{
+    const size_t n = h->cells;
+    const float *pot = h->slab[h->cur[h->obs_var]] + (size_t)h->obs_var * h->vstride;
+    ObsMaps m;
+    m.first = h->obs_buf + n;
+    m.last = h->obs_buf + 2 * n;
+    m.prev = h->obs_buf + 3 * n;
+    m.apd = h->obs_buf + 4 * n;
+    m.count = reinterpret_cast<int *>(h->obs_buf + 5 * n);
+    const float tick = (float)(h->d.dt * h->spt);
+    const float t0 = (float)((double)h->obs_k * h->d.dt * h->spt);
+    const bool vec = h->pitch == h->d.width && (reinterpret_cast<uintptr_t>(pot) & 15u) == 0;
+    const size_t threads = vec ? n / 4 + n % 4 : n;
+    const Geo g = base_geo(h);
+    if (int rc = trace_open(h, h->s0, "observe_kernel", 0, 0, 0, 0, 1)) return rc;
+    if (vec)
+        hipLaunchKernelGGL(observe_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->s0, g, pot, h->obs_buf, m,
+                           h->obs_up, h->obs_down, t0, tick);
+    else
+        hipLaunchKernelGGL(observe_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->s0, g, pot, h->obs_buf, m,
+                           h->obs_up, h->obs_down, t0, tick);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    h->obs_k++;
+    return 0;
+}
+
 static int commit_impl(fibhip_t h)
 {
     if (h->phase_of_tick != 2) return fail(FIBHIP_EINVAL, "step_commit: call step_interior first");
@@ -2047,6 +2090,9 @@ static int commit_impl(fibhip_t h)
     if (h->use_agg && ends_cycle(h)) h->agg_ghost_dirty = true;   // the exchange of this tick replaced the ghost rows
     h->cpos = (h->cpos + h->span) % h->cycle;
     h->phase_of_tick = 0;
+    // the recorder sees every tick on its own: while it is attached nothing fuses ticks (multi_cap, mt_variant), span is 1
+    if (h->obs)
+        if (int rc = observe_enqueue(h)) return rc;
     return 0;
 }
 
@@ -2087,7 +2133,7 @@ static int launch_pending(fibhip_t h, int n)
             return 0;
         }
     while (n > 0) {
-        int T = imin(h->multi_max, n);
+        int T = imin(multi_cap(h), n);
         if ((h->d.ghost_top || h->d.ghost_bottom) && T > 1) T = imax(1, imin(T, h->cycle - 1 - h->cpos));
         h->pending -= T;
         n -= T;
@@ -2266,7 +2312,7 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
         }
     }
     const int reserve = (h->fused_fn && !h->tracing) ? 1 : 0;
-    const int cap = ((h->multi_max > 1 && !h->tracing) ? h->multi_max - 1 : 0) + reserve;
+    const int cap = ((multi_cap(h) > 1 && !h->tracing) ? multi_cap(h) - 1 : 0) + reserve;
     if (cap > 0 && nticks > 0) {
         if (int rc = check_ready(h)) return rc;           // a deferred tick must not fail later, in someone else's call
         if (!h->tuned)                                    // (here, not inside a launch: the plans are being chosen)
@@ -2274,7 +2320,7 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
     }
     h->pending += nticks;
     while (h->pending > cap) {
-        int T = h->tracing ? 1 : imin(h->multi_max, h->pending - reserve);
+        int T = h->tracing ? 1 : imin(multi_cap(h), h->pending - reserve);
         if ((h->d.ghost_top || h->d.ghost_bottom) && T > 1) T = imax(1, imin(T, h->cycle - 1 - h->cpos));
         h->pending -= T;
         if (int rc = tick_multi(h, T)) return rc;
@@ -2876,7 +2922,7 @@ extern "C" int fibhip_ticks_per_launch(fibhip_t h)
 {
     if (!h) return fail(FIBHIP_EINVAL, "null handle");
     if (mt_variant(h)) return h->mt_max;
-    return h->multi_max;
+    return multi_cap(h);
 }
 
 extern "C" int fibhip_trace_begin(fibhip_t h)
@@ -2958,6 +3004,71 @@ extern "C" int fibhip_expect(fibhip_t h, int nticks)
     if (!h || nticks < 0) return fail(FIBHIP_EINVAL, "expect: bad argument");
     h->expect = nticks;
     h->expect_fresh = nticks > 0;
+    return 0;
+}
+
+// ---- activation recorder ------------------------------------------------------------------------------------------------
+extern "C" int fibhip_observe_begin(fibhip_t h, int var, float up, float down)
+{
+    NEED(h);
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "observe_begin: bad var %d", var);
+    if (std::isnan(up) || std::isnan(down) || down > up)
+        return fail(FIBHIP_EINVAL, "observe_begin: thresholds must be numbers with down <= up (got up %g, down %g)", up, down);
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "observe_begin: not on a row block (a handle with ghost rows)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "observe_begin inside an open tick");
+    // everything accepted so far runs unobserved and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // Vp is copied (the recorder must not start from the slab such a launch left void)
+    FLUSH(h);
+    SYNC_S0(h);
+    const size_t n = h->cells;
+    if (!h->obs_buf) HIPCHK(hipMalloc((void **)&h->obs_buf, 6 * n * sizeof(float)));
+    HIPCHK(hipMemcpy2DAsync(h->obs_buf, (size_t)h->d.width * sizeof(float), h->slab[h->cur[var]] + (size_t)var * h->vstride,
+                            (size_t)h->pitch * sizeof(float), (size_t)h->d.width * sizeof(float), (size_t)h->d.height,
+                            hipMemcpyDeviceToDevice, h->s0));
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    unsigned nan_bits;
+    memcpy(&nan_bits, &qnan, sizeof nan_bits);
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(h->obs_buf + n), (int)nan_bits, 4 * n, h->s0));   // first | last | prev | apd
+    HIPCHK(hipMemsetAsync(h->obs_buf + 5 * n, 0, n * sizeof(int), h->s0));                      // count
+    h->obs = true;
+    h->obs_var = var;
+    h->obs_up = up;
+    h->obs_down = down;
+    h->obs_k = 0;
+    return 0;
+}
+
+extern "C" int fibhip_observe_get(fibhip_t h, int which, void *dst)
+{
+    NEED(h);
+    FLUSH(h);
+    if (!h->obs) return fail(FIBHIP_EINVAL, "observe_get: no recorder attached (fibhip_observe_begin)");
+    if (!dst || which < 0 || which > FIBHIP_OBS_COUNT) return fail(FIBHIP_EINVAL, "observe_get: bad argument (which %d)", which);
+    if (!h->stage) HIPCHK(hipHostMalloc((void **)&h->stage, h->cells * sizeof(float), hipHostMallocDefault));
+    HIPCHK(hipMemcpyAsync(h->stage, h->obs_buf + (size_t)(1 + which) * h->cells, h->cells * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+    SYNC_S0(h);
+    memcpy(dst, h->stage, h->cells * sizeof(float));
+    return 0;
+}
+
+extern "C" int fibhip_observe_ticks(fibhip_t h, long long *k)
+{
+    if (!h || !k) return fail(FIBHIP_EINVAL, "observe_ticks: null argument");
+    if (!h->obs) return fail(FIBHIP_EINVAL, "observe_ticks: no recorder attached (fibhip_observe_begin)");
+    *k = h->obs_k + h->pending;                        // (ticks accepted but not launched yet are observed when they are)
+    return 0;
+}
+
+extern "C" int fibhip_observe_end(fibhip_t h)
+{
+    NEED(h);
+    FLUSH(h);                                          // the ticks accepted while attached are observed
+    if (h->obs_buf) {
+        HIPCHK(wait_stream(h->s0));
+        HIPCHK(hipFree(h->obs_buf));
+        h->obs_buf = nullptr;
+    }
+    h->obs = false;
     return 0;
 }
 

@@ -1377,6 +1377,66 @@ __global__ void court_inter_kernel(int n, const float *__restrict__ V, float *__
     }
 }
 
+// ---- activation recorder (fibhip_observe_begin): per-cell event maps, updated after every observed tick ----------------
+// Vp = the watched array at the end of the previous observed tick (the recorder's own plane), Vc = the array now.
+//   upstroke   Vp < up && Vc >= up:               t = t0 + ((up - Vp) / (Vc - Vp)) * tick;  prev = last; last = t;
+//                                                  first = t if count == 0;  count += 1
+//   downstroke Vp >= down && Vc < down, count > 0: t = t0 + ((Vp - down) / (Vp - Vc)) * tick; apd = t - last
+// float32, every operation rounded on its own (-ffp-contract=off, IEEE division); NaN compares false: no event.  With
+// down <= up the two cases exclude each other.  The maps are touched only where an event happens, so the steady traffic
+// is Vc read, Vp read and Vp written: 12 bytes per cell.
+struct ObsMaps {
+    float *first, *last, *prev, *apd;
+    int *count;
+};
+
+static FIB_DEV void observe_cell(float vp, float vc, size_t i, const ObsMaps &m, float up, float down, float t0, float tick)
+{
+    if (vp < up && vc >= up) {
+        const float t = t0 + ((up - vp) / (vc - vp)) * tick;
+        const int n = m.count[i];
+        m.prev[i] = m.last[i];
+        m.last[i] = t;
+        if (n == 0) m.first[i] = t;
+        m.count[i] = n + 1;
+    } else if (vp >= down && vc < down && m.count[i] > 0) {
+        const float t = t0 + ((vp - down) / (vp - vc)) * tick;
+        m.apd[i] = t - m.last[i];
+    }
+}
+
+// One element per thread and as many workgroups as that takes (the shape of copy_kernel below, the fastest streaming
+// shape measured; 512x512 = 256 workgroups, one per CU).  VEC: the watched array is contiguous (planar slab, pitch == W)
+// and 16-byte aligned — thread i < n/4 takes cells 4i .. 4i+3 with 16-byte loads and stores, the n % 4 threads after them
+// one cell each.  Otherwise (row-interleaved slab, or an unaligned array): one cell per thread, scalar.
+template <bool VEC>
+__global__ void __launch_bounds__(256) observe_kernel(Geo g, const float *__restrict__ pot, float *__restrict__ vprev, ObsMaps m,
+                                                      float up, float down, float t0, float tick)
+{
+    const size_t n = (size_t)g.H * g.W;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const size_t n4 = n / 4;
+        if (i < n4) {
+            const fib_v4f vc = reinterpret_cast<const fib_v4f *>(pot)[i];
+            const fib_v4f vp = reinterpret_cast<const fib_v4f *>(vprev)[i];
+            reinterpret_cast<fib_v4f *>(vprev)[i] = vc;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) observe_cell(vp[j], vc[j], 4 * i + j, m, up, down, t0, tick);
+        } else if (i < n4 + n % 4) {
+            const size_t e = 4 * n4 + (i - n4);
+            const float vc = pot[e], vp = vprev[e];
+            vprev[e] = vc;
+            observe_cell(vp, vc, e, m, up, down, t0, tick);
+        }
+    } else if (i < n) {
+        const size_t y = i / (size_t)g.W, x = i % (size_t)g.W;
+        const float vc = pot[y * (size_t)g.pitch + x], vp = vprev[i];
+        vprev[i] = vc;
+        observe_cell(vp, vc, i, m, up, down, t0, tick);
+    }
+}
+
 // plain streaming copy, one 16-byte element per thread and as many workgroups as that takes: the bandwidth yardstick
 // bench.py prints next to the roofline peak.  (tools/ubench/copybw.hip -> profiles/r02_copy_bandwidth_shapes.txt: this
 // shape reaches the 6.3 TB/s the microarch guide quotes; grid-stride loops with non-temporal accesses stay at 4.6-5.7,

@@ -213,6 +213,19 @@ class IonicModel:
             watch['last_spike'] = i
         watch['v0'] = v1
 
+    def record_activation(self, up=None, down=None, var=0):
+        """attaches an activation recorder (fib_tf_amd/activation.py) to this model's handle: per-cell maps of the first,
+        last and previous upstroke through `up`, the APD down to `down` and the number of upstrokes, updated on the device
+        after every tick.  Defaults: up at 50 %, down at 10 % of [min_v, max_v].  Call after define(); single device only
+        (row blocks raise NotImplementedError)."""
+        from .activation import ActivationRecorder
+        if not self.defined:
+            raise AssertionError('record_activation should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return ActivationRecorder(self, up=up, down=down, var=var)
+
     def millisecond_to_step(self, t):
         """milliseconds -> tick index returned by run(), ionic.py:247-252"""
         return int(t / (self.dt_per_step * self.dt))

@@ -324,6 +324,29 @@ int fibhip_trace_begin(fibhip_t h);
 int fibhip_trace_end(fibhip_t h, fibhip_trace_event *out, int max_events);   /* returns the number of events traced; the first */
                                                                               /* max_events of them are written (more = truncated) */
 
+/* Activation recorder: per-cell maps of local activation time, cycle length and action-potential duration, kept on the
+ * device and updated after every tick (no TensorFlow counterpart: the reference's drivers poll image(), ionic.py:207-224).
+ * It watches state array `var` against two thresholds down <= up (units of that array).  Its own plane Vp holds the array
+ * at the end of the previous observed tick (at observe_begin: the current state).  After observed tick k (k = 0 is the
+ * first tick after observe_begin), with Vc the array now, tick = (float)(dt * steps_per_tick) and
+ * t0 = (float)((double)k * dt * steps_per_tick), in float32, every operation rounded on its own, IEEE division:
+ *   upstroke   Vp < up && Vc >= up:               t = t0 + ((up - Vp) / (Vc - Vp)) * tick; prev_up = last_up; last_up = t;
+ *                                                  first_up = t if count == 0; count += 1
+ *   downstroke Vp >= down && Vc < down, count > 0: t = t0 + ((Vp - down) / (Vp - Vc)) * tick; apd = t - last_up
+ * and Vp = Vc.  first_up, last_up, prev_up, apd start as NaN, count (int32) as 0; NaN potentials record nothing.  Pacing
+ * and set_state between two ticks count as part of the next tick.  While a recorder is attached every tick is one plain
+ * launch (no multi-tick launches, no run-ahead) followed by the recorder's kernel.  Single-device handles only (no ghost
+ * rows).
+ *   fibhip_observe_begin  flushes and synchronises pending work, then attaches (again: re-attaches and clears the maps)
+ *   fibhip_observe_get    one map, [height*width] float32 (which = FIRST..APD) or int32 (COUNT); blocks like get_state
+ *   fibhip_observe_ticks  ticks observed since observe_begin (accepted ticks included)
+ *   fibhip_observe_end    detaches and frees the maps; fibhip_destroy does the same                                      */
+enum fibhip_obs_map { FIBHIP_OBS_FIRST_UP = 0, FIBHIP_OBS_LAST_UP = 1, FIBHIP_OBS_PREV_UP = 2, FIBHIP_OBS_APD = 3, FIBHIP_OBS_COUNT = 4 };
+int fibhip_observe_begin(fibhip_t h, int var, float up, float down);
+int fibhip_observe_get(fibhip_t h, int which, void *dst);
+int fibhip_observe_ticks(fibhip_t h, long long *k);
+int fibhip_observe_end(fibhip_t h);
+
 const char *fibhip_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)
