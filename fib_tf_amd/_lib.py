@@ -168,6 +168,10 @@ SYMBOLS = {
     'fibhip_observe_get': ([_h, C.c_int, C.c_void_p], C.c_int),
     'fibhip_observe_ticks': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_observe_end': ([_h], C.c_int),
+    'fibhip_electrode_begin': ([_h, C.c_int, C.c_int, _ip, _fp, C.c_int, C.c_longlong], C.c_int),
+    'fibhip_electrode_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_electrode_read': ([_h, C.c_longlong, C.c_longlong, _fp], C.c_int),
+    'fibhip_electrode_end': ([_h], C.c_int),
     'fibhip_last_error': ([], C.c_char_p),
 }
 
@@ -664,3 +668,41 @@ class Stepper:
 
     def observe_end(self):
         self._ck(self._L.fibhip_observe_end(self._h))
+
+    # ---- electrode recorder (include/fibhip.h fibhip_electrode_*) -------------------------------------------------
+    def electrode_begin(self, var, rects, patches, every=1, capacity=1):
+        """attaches (or re-attaches, with an empty trace) the electrode recorder on array `var`: `rects` is a list of
+        (r0, r1, c0, c1), `patches` the float32 weight arrays of those shapes; one sample every `every` ticks, `capacity`
+        samples at the most"""
+        rects = np.ascontiguousarray(rects, np.intc).reshape(-1, 4)
+        if len(patches) != len(rects):
+            raise ValueError('electrode_begin: %d rectangles but %d weight patches' % (len(rects), len(patches)))
+        flat = []
+        for (r0, r1, c0, c1), w in zip(rects, patches):
+            w = np.asarray(w, np.float32)
+            if w.shape != (r1 - r0, c1 - c0):
+                raise ValueError('electrode_begin: a patch of shape %s for rows [%d, %d) x columns [%d, %d)' % (w.shape, r0, r1, c0, c1))
+            flat.append(w.ravel())
+        weights = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(1), np.float32)
+        self._ck(self._L.fibhip_electrode_begin(self._h, int(var), len(rects), rects.ctypes.data_as(_ip), weights.ctypes.data_as(_fp),
+                                                int(every), int(capacity)))
+        self._el_n = len(rects)
+
+    def electrode_count(self):
+        """samples taken since electrode_begin (ticks accepted but not launched yet included)"""
+        k = C.c_longlong()
+        self._ck(self._L.fibhip_electrode_count(self._h, C.byref(k)))
+        return int(k.value)
+
+    def electrode_read(self, first=0, count=None):
+        """samples [first, first + count) as a float32 [count, n] array (count=None: all taken so far); blocks like
+        get_state, detaches nothing"""
+        if count is None:
+            count = self.electrode_count() - int(first)
+        n = getattr(self, '_el_n', 0)
+        out = np.empty((max(int(count), 0), n), np.float32)
+        self._ck(self._L.fibhip_electrode_read(self._h, int(first), int(count), out.ctypes.data_as(_fp)))
+        return out
+
+    def electrode_end(self):
+        self._ck(self._L.fibhip_electrode_end(self._h))

@@ -193,3 +193,7 @@ class BeelerReuter(IonicModel):
         """V scaled to 0..1 (br.py:337-343)"""
         v = self._V.eval()
         return (v - self.min_v) / (self.max_v - self.min_v)
+
+    def _image_affine(self):
+        span = float(self.max_v) - float(self.min_v)
+        return 1.0 / span, -float(self.min_v) / span

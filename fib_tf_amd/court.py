@@ -103,6 +103,10 @@ class Courtemanche(IonicModel):
         v = self._V.eval()
         return (v - self.min_v) / (self.max_v - self.min_v)
 
+    def _image_affine(self):
+        span = float(self.max_v) - float(self.min_v)
+        return 1.0 / span, -float(self.min_v) / span
+
 
 def cl_observer(i, cl):
     print('Observer: %d:\t%d' % (i, cl))

@@ -8,6 +8,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -539,6 +540,18 @@ struct fibhip_ctx {
     float obs_up, obs_down;
     float *obs_buf;         // 6 planes of `cells` (W-pitched): Vp | first_up | last_up | prev_up | apd | count (int32)
     long long obs_k;        // observed ticks since the recorder was attached
+    // electrode recorder (fibhip_electrode_begin): while `el`, no launch spans a sample tick (el_room) and the hooks on the
+    // plain and the multi-tick commit path (electrode_advance) enqueue electrode_kernel behind the launch that ends one
+    bool el;
+    int el_var, el_n, el_every;
+    long long el_cap;       // samples the trace holds
+    long long el_k;         // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
+    int el_nchunks, el_ncomb;       // workgroups of electrode_kernel / of electrode_combine_kernel (0: no electrode has several chunks)
+    ElChunk *el_chunks;     // device: the chunk table
+    ElComb *el_comb;        // device: the electrodes of several chunks
+    float *el_w;            // device: the weight patches, back to back
+    float *el_part;         // device: one partial per chunk of such electrodes
+    float *el_trace;        // device: [el_cap][el_n]
 };
 
 static const void *consts_of(fibhip_ctx *h)
@@ -1013,6 +1026,18 @@ static int create_impl(const fibhip_desc *desc, fibhip_ctx *&h)
 
 extern "C" int fibhip_comm_free(fibhip_t h);
 static void mt_forget(fibhip_ctx *h);
+static void electrode_free(fibhip_ctx *h)
+{
+    if (h->el_chunks) hipFree(h->el_chunks);
+    if (h->el_comb) hipFree(h->el_comb);
+    if (h->el_w) hipFree(h->el_w);
+    if (h->el_part) hipFree(h->el_part);
+    if (h->el_trace) hipFree(h->el_trace);
+    h->el_chunks = nullptr;
+    h->el_comb = nullptr;
+    h->el_w = h->el_part = h->el_trace = nullptr;
+    h->el = false;
+}
 
 extern "C" int fibhip_destroy(fibhip_t h)
 {
@@ -1031,6 +1056,7 @@ extern "C" int fibhip_destroy(fibhip_t h)
     if (h->phi_dev) hipFree(h->phi_dev);
     if (h->agg) hipFree(h->agg);
     if (h->obs_buf) hipFree(h->obs_buf);
+    electrode_free(h);
     if (h->xbuf) hipFree(h->xbuf);
     if (h->epochs) hipFree(h->epochs);
     for (auto &r : h->trace) {
@@ -1151,6 +1177,10 @@ static int recover(fibhip_ctx *h, unsigned id)
     __atomic_store_n(h->host_word + MT_GIVEUP_WORD, 0u, __ATOMIC_RELEASE);
     h->n_fallbacks++;
     h->n_replayed += lost;
+    // the samples queued behind the lost launches were taken from a void slab: the replay below (tick_now -> commit_impl)
+    // takes them again, into the same slots — the slot is the host's tick counter, so that counter goes back first.  (Every
+    // journal record is younger than the recorder: electrode_begin confirms, and so empties the journal, before it attaches.)
+    if (h->el) h->el_k -= lost;
     h->recovering = true;
     int rc = 0;
     for (int t = 0; t < lost && rc == 0; ++t) rc = tick_now(h);
@@ -1316,7 +1346,7 @@ extern "C" int fibhip_get_state_direct(fibhip_t h, int var, float *dst)
         L_next = imin(h->expect, h->mt_max);
         repeats = true;
     }
-    if (var >= 0 && h->ahead_ok && !h->tracing && (h->series_fresh || (h->expect > 0 && h->expect_fresh)) && repeats && L_next >= 2 &&
+    if (var >= 0 && h->ahead_ok && !h->el && !h->tracing && (h->series_fresh || (h->expect > 0 && h->expect_fresh)) && repeats && L_next >= 2 &&
         L_next <= h->mt_max && h->pitch == h->d.width && h->tuned) {
         if (const Variant *mv = mt_variant(h)) {
             const int L = L_next;
@@ -1636,8 +1666,12 @@ static const Variant *mt_variant(const fibhip_ctx *h)
     if (h->obs || h->plan.size() != 1 || h->fused_fn || !mt_eligible(h, h->plan[0].v)) return nullptr;
     return h->plan[0].v;
 }
-// consecutive ticks one plain launch may fuse (Courtemanche on aggregates: up to multi_max; one while a recorder is attached)
-static inline int multi_cap(const fibhip_ctx *h) { return h->obs ? 1 : h->multi_max; }
+// ticks up to and including the next sample tick of the electrode recorder: no launch may span one (INT_MAX: none attached)
+static inline int el_room(const fibhip_ctx *h) { return h->el ? h->el_every - (int)(h->el_k % h->el_every) : INT_MAX; }
+// consecutive ticks one plain launch may fuse (Courtemanche on aggregates: up to multi_max; one while an activation recorder
+// is attached; never across a sample tick of the electrode recorder)
+static inline int multi_cap(const fibhip_ctx *h) { return h->obs ? 1 : imin(h->multi_max, el_room(h)); }
+static int electrode_advance(fibhip_ctx *h, int ticks);
 
 static struct {
     std::mutex mu;
@@ -1743,6 +1777,8 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
     h->epoch_base += (unsigned)(T - 1);               // every tile raised its word once per tick boundary
     if (commit) memcpy(h->cur, nxt, sizeof nxt);
     if (nxt_out) memcpy(nxt_out, nxt, sizeof nxt);
+    // (the sample reads the state and writes the recorder's own buffers only: it may stand behind this unconfirmed launch)
+    if (commit && h->el) return electrode_advance(h, T);
     return 0;
 }
 
@@ -2081,18 +2117,48 @@ static int observe_enqueue(fibhip_ctx *h)
     return 0;
 }
 
+// The electrode recorder's hook behind a launch of `ticks` ticks (plain: commit_impl; multi-tick: mt_launch).  No launch
+// spans a sample tick (el_room), so a sample is due exactly when the counter lands on a multiple of `every`; it is enqueued
+// on s0 behind that launch and reads the state the handle has just moved to.  The slot is a kernel argument computed from the
+// host's counter, never a pointer kept on the device: a replay (recover()) writes the same slots again.
+static int electrode_advance(fibhip_ctx *h, int ticks)
+{
+    h->el_k += ticks;
+    if (h->el_k % h->el_every) return 0;
+    const long long s = h->el_k / h->el_every - 1;
+    if (s >= h->el_cap) return fail(FIBHIP_EINVAL, "electrode recorder: trace full");      // (fibhip_step refuses before this)
+    const float *x = h->slab[h->cur[h->el_var]] + (size_t)h->el_var * h->vstride;
+    float *row = h->el_trace + (size_t)s * h->el_n;
+    if (int rc = trace_open(h, h->s0, "electrode_kernel", 0, 0, 0, 0, 1)) return rc;
+    hipLaunchKernelGGL(electrode_kernel, dim3((unsigned)h->el_nchunks), dim3(EL_THREADS), 0, h->s0, x, h->pitch, h->el_chunks, h->el_w,
+                       row, h->el_part);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    if (h->el_ncomb) {
+        if (int rc = trace_open(h, h->s0, "electrode_combine_kernel", 0, 0, 0, 0, 1)) return rc;
+        hipLaunchKernelGGL(electrode_combine_kernel, dim3((unsigned)h->el_ncomb), dim3(256), 0, h->s0, h->el_comb, h->el_part, row);
+        HIPCHK(hipGetLastError());
+        if (int rc = trace_close(h, h->s0)) return rc;
+        h->launches++;
+    }
+    return 0;
+}
+
 static int commit_impl(fibhip_t h)
 {
     if (h->phase_of_tick != 2) return fail(FIBHIP_EINVAL, "step_commit: call step_interior first");
     if (split_tick(h, h->plan.back())) HIPCHK(hipStreamWaitEvent(h->s0, h->ev_int, 0));
     memcpy(h->cur, h->nxt, sizeof h->cur);
-    h->n_ticks += h->plan.empty() ? 1 : (h->plan[0].K > h->spt ? h->plan[0].K / h->spt : 1);
+    const int ticks = h->plan.empty() ? 1 : (h->plan[0].K > h->spt ? h->plan[0].K / h->spt : 1);
+    h->n_ticks += ticks;
     if (h->use_agg && ends_cycle(h)) h->agg_ghost_dirty = true;   // the exchange of this tick replaced the ghost rows
     h->cpos = (h->cpos + h->span) % h->cycle;
     h->phase_of_tick = 0;
     // the recorder sees every tick on its own: while it is attached nothing fuses ticks (multi_cap, mt_variant), span is 1
     if (h->obs)
         if (int rc = observe_enqueue(h)) return rc;
+    if (h->el) return electrode_advance(h, ticks);
     return 0;
 }
 
@@ -2124,7 +2190,7 @@ static int launch_pending(fibhip_t h, int n)
     if (n > 0 && !h->tracing)
         if (const Variant *v = mt_variant(h)) {
             while (n > 0) {
-                const int T = imin(h->mt_max, n);
+                const int T = imin(imin(h->mt_max, n), el_room(h));
                 h->pending -= T;
                 n -= T;
                 if (int rc = tick_mt(h, v, T)) return rc;
@@ -2216,6 +2282,7 @@ extern "C" int fibhip_step_edges(fibhip_t h)
     NEED(h);
     FLUSH(h);
     CONFIRM(h);
+    if (h->el && (h->el_k + 1) / h->el_every > h->el_cap) return fail(FIBHIP_EINVAL, "step_edges: trace full (electrode recorder)");
     return edges_impl(h);
 }
 
@@ -2252,10 +2319,14 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
     // / cancelled by flush() — after which ONE sample is not believed again until two equal series have been seen.
     // A caller that KNOWS its series says so (fibhip_expect: IonicModel.run() does, from its frame period and tick count) and
     // nothing is guessed: the declared ticks are launched at the first of them, mt_max at a time.
+    if (h->el && (h->el_k + h->pending + nticks) / h->el_every > h->el_cap)
+        return fail(FIBHIP_EINVAL, "step: trace full (the electrode recorder holds %lld samples; read it, then detach or re-attach)", h->el_cap);
     if (int rc = journal_bound(h)) return rc;
     bool repeats = false;
     int L_next = 0;
-    if (nticks > 0 && h->spec_n == 0 && h->mt_max > 1) {
+    // (run-ahead is off while an electrode recorder is attached — a launch that runs ahead is handed out tick by tick and may
+    // be stopped or recomputed, so a sample cannot be queued behind it: ahead_ok counts as false)
+    if (nticks > 0 && h->spec_n == 0 && h->mt_max > 1 && !h->el) {
         if (h->expect > 0) {
             L_next = imin(h->expect, h->mt_max);
             repeats = true;
@@ -2299,8 +2370,11 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
             if (int rc = autotune(h)) return rc;
         if (const Variant *v = mt_variant(h)) {
             h->pending += nticks;
-            while (h->pending >= h->mt_cur) {
-                const int T = imin(h->pending, h->mt_max);
+            // With an electrode recorder a launch goes out when the ticks up to the next sample tick are waiting (or mt_max of
+            // them) and ends there: between two samples the handle runs the fewest launches `every` allows, whatever the
+            // caller's call pattern.  (Without one: mt_cur, as described above.)
+            while (h->pending >= (h->el ? imin(el_room(h), h->mt_max) : h->mt_cur)) {
+                const int T = imin(imin(h->pending, h->mt_max), el_room(h));
                 h->pending -= T;
                 if (int rc = tick_mt(h, v, T)) return rc;
                 const bool first = h->mt_run == 0;
@@ -2312,14 +2386,16 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
         }
     }
     const int reserve = (h->fused_fn && !h->tracing) ? 1 : 0;
-    const int cap = ((multi_cap(h) > 1 && !h->tracing) ? multi_cap(h) - 1 : 0) + reserve;
+    // (multi_cap moves with the electrode recorder's tick counter: the bound is taken afresh for every launch)
+    auto held = [&] { return ((multi_cap(h) > 1 && !h->tracing) ? multi_cap(h) - 1 : 0) + reserve; };
+    const int cap = held();
     if (cap > 0 && nticks > 0) {
         if (int rc = check_ready(h)) return rc;           // a deferred tick must not fail later, in someone else's call
         if (!h->tuned)                                    // (here, not inside a launch: the plans are being chosen)
             if (int rc = autotune(h)) return rc;
     }
     h->pending += nticks;
-    while (h->pending > cap) {
+    while (h->pending > held()) {
         int T = h->tracing ? 1 : imin(multi_cap(h), h->pending - reserve);
         if ((h->d.ghost_top || h->d.ghost_bottom) && T > 1) T = imax(1, imin(T, h->cycle - 1 - h->cpos));
         h->pending -= T;
@@ -2399,7 +2475,9 @@ extern "C" int fibhip_step_mode(fibhip_t h, int mode)
 #if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
     if (h->d.model == FIBHIP_COURT && mode == Courtemanche::MODE_SLOW) {
         if (h->d.flags & FIBHIP_ALLVARS) return fail(FIBHIP_EINVAL, "step_slow: handle was created with FIBHIP_ALLVARS");
-        if (h->pending && h->fused_fn) {                  // the last deferred tick + slow as one launch
+        // (a sample of a SLOW array due at that tick must see it before 'slow', which belongs to the next tick: no fusing then)
+        const bool el_slow_sample = h->el && (h->el_k + h->pending) % h->el_every == 0 && !((Courtemanche::FAST_MASK >> h->el_var) & 1u);
+        if (h->pending && h->fused_fn && !el_slow_sample) {   // the last deferred tick + slow as one launch
             if (int rc = launch_pending(h, h->pending - 1)) return rc;
             h->pending = 0;
             const launch_fn plain = h->plan[0].fn;
@@ -3069,6 +3147,121 @@ extern "C" int fibhip_observe_end(fibhip_t h)
         h->obs_buf = nullptr;
     }
     h->obs = false;
+    return 0;
+}
+
+// ---- electrode recorder -------------------------------------------------------------------------------------------------
+extern "C" int fibhip_electrode_begin(fibhip_t h, int var, int n, const int *rects, const float *weights, int every, long long capacity)
+{
+    NEED(h);
+    if (!rects || !weights) return fail(FIBHIP_EINVAL, "electrode_begin: null argument");
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "electrode_begin: bad var %d", var);
+    if (n < 1 || n > FIBHIP_MAX_ELECTRODES) return fail(FIBHIP_EINVAL, "electrode_begin: 1 .. %d electrodes (got %d)", FIBHIP_MAX_ELECTRODES, n);
+    if (every < 1) return fail(FIBHIP_EINVAL, "electrode_begin: every must be >= 1 (got %d)", every);
+    if (capacity < 1 || capacity > (long long)(SIZE_MAX / sizeof(float) / (size_t)n))
+        return fail(FIBHIP_EINVAL, "electrode_begin: bad capacity %lld", capacity);
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "electrode_begin: not on a row block (a handle with ghost rows)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "electrode_begin inside an open tick");
+    // the chunk table: one chunk per patch of up to EL_CHUNK cells, larger patches in at most 256 equal chunks
+    std::vector<ElChunk> chunks;
+    std::vector<ElComb> combs;
+    size_t woff = 0;
+    int nparts = 0;
+    for (int e = 0; e < n; ++e) {
+        const int r0 = rects[4 * e], r1 = rects[4 * e + 1], c0 = rects[4 * e + 2], c1 = rects[4 * e + 3];
+        if (r0 < 0 || r1 > h->d.height || c0 < 0 || c1 > h->d.width || r0 >= r1 || c0 >= c1)
+            return fail(FIBHIP_EINVAL, "electrode_begin: electrode %d: rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid",
+                        e, r0, r1, c0, c1, h->d.height, h->d.width);
+        const size_t m = (size_t)(r1 - r0) * (size_t)(c1 - c0);
+        if (woff + m > 0x7FFFFFFFu) return fail(FIBHIP_EINVAL, "electrode_begin: more than 2^31 - 1 weights");
+        for (size_t i = 0; i < m; ++i)
+            if (!std::isfinite(weights[woff + i])) return fail(FIBHIP_EINVAL, "electrode_begin: electrode %d has a weight that is not finite", e);
+        const size_t cs = m <= EL_CHUNK ? m : (m + 255) / 256 > EL_CHUNK ? (m + 255) / 256 : (size_t)EL_CHUNK;
+        const int nc = (int)((m + cs - 1) / cs);                       // <= 256
+        if (nc > 1) {
+            ElComb cb;
+            cb.e = e; cb.part0 = nparts; cb.nparts = nc;
+            combs.push_back(cb);
+        }
+        for (int k = 0; k < nc; ++k) {
+            ElChunk c;
+            c.r0 = r0; c.c0 = c0; c.pw = c1 - c0;
+            c.first = (unsigned)((size_t)k * cs);
+            c.count = (unsigned)((size_t)(k + 1) * cs <= m ? cs : m - (size_t)k * cs);
+            c.woff = (unsigned)woff;
+            c.out = nc > 1 ? -1 - nparts++ : e;
+            chunks.push_back(c);
+        }
+        woff += m;
+    }
+    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick k = 0 is defined (the rule of fibhip_observe_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    electrode_free(h);
+    bool ok = hipMalloc((void **)&h->el_chunks, chunks.size() * sizeof(ElChunk)) == hipSuccess &&
+              hipMalloc((void **)&h->el_w, woff * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&h->el_trace, (size_t)capacity * (size_t)n * sizeof(float)) == hipSuccess;
+    if (ok && nparts)
+        ok = hipMalloc((void **)&h->el_comb, combs.size() * sizeof(ElComb)) == hipSuccess &&
+             hipMalloc((void **)&h->el_part, (size_t)nparts * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        electrode_free(h);
+        return fail(FIBHIP_ENOMEM, "electrode_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d electrodes)", capacity, n);
+    }
+    HIPCHK(hipMemcpyAsync(h->el_chunks, chunks.data(), chunks.size() * sizeof(ElChunk), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemcpyAsync(h->el_w, weights, woff * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    if (nparts) HIPCHK(hipMemcpyAsync(h->el_comb, combs.data(), combs.size() * sizeof(ElComb), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemsetAsync(h->el_trace, 0, (size_t)capacity * (size_t)n * sizeof(float), h->s0));
+    HIPCHK(wait_stream(h->s0));                        // `chunks`, `combs` and the caller's arrays are free again
+    h->el = true;
+    h->el_var = var;
+    h->el_n = n;
+    h->el_every = every;
+    h->el_cap = capacity;
+    h->el_k = 0;
+    h->el_nchunks = (int)chunks.size();
+    h->el_ncomb = (int)combs.size();
+    return 0;
+}
+
+extern "C" int fibhip_electrode_count(fibhip_t h, long long *samples)
+{
+    NEED(h);
+    if (!samples) return fail(FIBHIP_EINVAL, "electrode_count: null argument");
+    if (!h->el) return fail(FIBHIP_EINVAL, "electrode_count: no recorder attached (fibhip_electrode_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    *samples = (h->el_k + h->pending) / h->el_every;   // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+
+extern "C" int fibhip_electrode_read(fibhip_t h, long long first, long long count, float *dst)
+{
+    NEED(h);
+    if (!h->el) return fail(FIBHIP_EINVAL, "electrode_read: no recorder attached (fibhip_electrode_begin)");
+    FLUSH(h);
+    const long long taken = h->el_k / h->el_every;
+    if (first < 0 || count < 0 || first + count > taken)
+        return fail(FIBHIP_EINVAL, "electrode_read: samples [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "electrode_read: null destination");
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->n_fallbacks;
+        if (count > 0)
+            HIPCHK(hipMemcpyAsync(dst, h->el_trace + (size_t)first * h->el_n, (size_t)count * h->el_n * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        SYNC_S0(h);
+        if (h->n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and re-sampled, copy again)
+    }
+    return 0;
+}
+
+extern "C" int fibhip_electrode_end(fibhip_t h)
+{
+    NEED(h);
+    if (!h->el) return 0;
+    FLUSH(h);                                          // the ticks accepted while attached are sampled
+    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
+    electrode_free(h);
     return 0;
 }
 

@@ -1437,6 +1437,88 @@ __global__ void __launch_bounds__(256) observe_kernel(Geo g, const float *__rest
     }
 }
 
+// ---- electrode recorder (fibhip_electrode_begin): weighted sums of one state array over small patches ------------------
+// One workgroup of EL_THREADS threads per CHUNK of a patch (the host cuts patches at attach: one chunk up to EL_CHUNK cells,
+// larger patches into at most 256 equal chunks).  Thread t takes the chunk's cells t, t + EL_THREADS, ... in that order
+// into ONE float32 accumulator (product rounded, then added: -ffp-contract=off), EL_BATCH cells' loads in flight at a
+// time: the kernel is latency-bound (the reference's two Gaussian electrodes are 2 x 10 201 cells), so what counts is the
+// number of dependent memory round trips — two at that size.  Then 6 levels of __shfl_down inside each wave, the 16 wave
+// sums through LDS, 4 more levels by wave 0, one plain store: no term passes through more than ceil(cells / 1024) + 10
+// additions, in an order fixed by the chunk table alone.  An electrode of one chunk stores straight into its trace slot;
+// an electrode of several stores one partial per chunk, which electrode_combine_kernel (a second launch on the same
+// stream, only enqueued when such an electrode exists) adds in a fixed 8-level tree: together within the
+// ceil(m / 256) + 16 of include/fibhip.h.  No floating-point atomics anywhere.
+#define EL_THREADS 1024
+#define EL_BATCH 8
+#define EL_CHUNK 16384
+struct ElChunk {
+    int r0, c0, pw;         // the patch's first row and column in the grid, and its width
+    unsigned first, count;  // this chunk's cells [first, first + count) of the patch, row-major
+    unsigned woff;          // float offset of the patch in the weights
+    int out;                // >= 0: electrode index (store into the sample's row); < 0: partial slot -1 - out
+};
+struct ElComb {
+    int e, part0, nparts;   // electrode, its first partial slot, its chunks (<= 256)
+};
+
+static FIB_DEV float el_wave_sum(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(EL_THREADS) electrode_kernel(const float *__restrict__ x, int pitch, const ElChunk *__restrict__ chunks,
+                                                               const float *__restrict__ weights, float *__restrict__ row,
+                                                               float *__restrict__ part)
+{
+    __shared__ float wsum[EL_THREADS / 64];
+    const ElChunk c = chunks[blockIdx.x];
+    const float *__restrict__ w = weights + c.woff;
+    const unsigned end = c.first + c.count;
+    float acc = 0.f;
+    for (unsigned p0 = c.first + threadIdx.x; p0 < end; p0 += EL_BATCH * EL_THREADS) {
+        float xv[EL_BATCH], wv[EL_BATCH];
+#pragma unroll
+        for (int j = 0; j < EL_BATCH; ++j) {
+            const unsigned p = p0 + (unsigned)j * EL_THREADS;
+            const bool in = p < end;
+            const unsigned q = in ? p : c.first;                       // (an in-range address; the term is dropped below)
+            const unsigned r = q / (unsigned)c.pw, col = q - r * (unsigned)c.pw;
+            xv[j] = x[(size_t)(c.r0 + (int)r) * (size_t)pitch + (size_t)(c.c0 + (int)col)];
+            wv[j] = w[q];
+        }
+#pragma unroll
+        for (int j = 0; j < EL_BATCH; ++j)
+            if (p0 + (unsigned)j * EL_THREADS < end) acc += wv[j] * xv[j];
+    }
+    acc = el_wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float v = threadIdx.x < EL_THREADS / 64 ? wsum[threadIdx.x] : 0.f;
+#pragma unroll
+        for (int off = EL_THREADS / 128; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (threadIdx.x == 0) {
+            if (c.out >= 0) row[c.out] = v;
+            else part[-1 - c.out] = v;
+        }
+    }
+}
+
+// one 256-thread workgroup per electrode of several chunks: its partials, one per thread, through the same tree
+__global__ void __launch_bounds__(256) electrode_combine_kernel(const ElComb *__restrict__ combs, const float *__restrict__ part,
+                                                                float *__restrict__ row)
+{
+    __shared__ float wsum[4];
+    const ElComb c = combs[blockIdx.x];
+    float v = (int)threadIdx.x < c.nparts ? part[c.part0 + threadIdx.x] : 0.f;
+    v = el_wave_sum(v);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) row[c.e] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
 // plain streaming copy, one 16-byte element per thread and as many workgroups as that takes: the bandwidth yardstick
 // bench.py prints next to the roofline peak.  (tools/ubench/copybw.hip -> profiles/r02_copy_bandwidth_shapes.txt: this
 // shape reaches the 6.3 TB/s the microarch guide quotes; grid-stride loops with non-temporal accesses stay at 4.6-5.7,

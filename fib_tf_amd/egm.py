@@ -28,6 +28,137 @@ def record(model, mask1, mask2, im=None, every_ms=1.0, on_tick=None):
     return np.asarray(rows, dtype=np.float64)
 
 
+# ---- electrodes on the device (include/fibhip.h fibhip_electrode_*) --------------------------------------------------
+def crop_mask(mask):
+    """(rect, patch): rect = (r0, r1, c0, c1), the bounding box of the non-zero weights of a full [H, W] mask, and the
+    float32 weights inside it.  Exact with respect to the full-grid product: every dropped term is a zero."""
+    m = np.asarray(mask, np.float32)
+    if m.ndim != 2:
+        raise ValueError('crop_mask: a [height, width] mask is expected, got shape %s' % (m.shape,))
+    rows, cols = np.flatnonzero(np.any(m != 0, axis=1)), np.flatnonzero(np.any(m != 0, axis=0))
+    if rows.size == 0:
+        raise ValueError('crop_mask: the mask has no non-zero weight')
+    rect = (int(rows[0]), int(rows[-1]) + 1, int(cols[0]), int(cols[-1]) + 1)
+    return rect, np.ascontiguousarray(m[rect[0]:rect[1], rect[2]:rect[3]])
+
+
+class ElectrodeRecorder:
+    """electrode traces recorded on the device; see `IonicModel.record_electrodes`.
+
+        with model.record_electrodes([mask1, mask2], every=10) as rec:
+            for i in model.run():
+                ...
+            egm = rec.traces()                   # float64 [samples, 2]: mean(image() * mask) after ticks 9, 19, 29, ...
+
+    Every `every` ticks the library takes the weighted sum of state array `var` over the non-zero box of each mask and
+    appends it to a trace on the device; nothing is copied to the host until `traces()`.  Between two samples the handle keeps
+    its multi-tick launches.
+
+    `traces()` converts the raw sums through `model._image_affine()`: a model whose image() rescales the potential (a
+    traced model's image() is the user's own) must override that hook.  With var = 0 the hook is checked against image()
+    on the current state when the recorder is attached (two read-backs; `check_affine=False` skips them) and a mismatch
+    raises ValueError.  For any other `var` there is no image(): `traces()` returns mean(X_var * mask)."""
+
+    def __init__(self, model, masks, every=1, capacity=None, var=0, check_affine=True):
+        from .sharded import ShardedStepper
+        st = model._stepper
+        if st is None:
+            raise AssertionError('record_electrodes should be called after calling define')
+        if isinstance(st, ShardedStepper):
+            raise NotImplementedError('record_electrodes: electrode traces are recorded on a single device only; this model '
+                                      'runs as row blocks over %d ranks' % st.world)
+        masks = [np.asarray(m, np.float32) for m in masks]
+        for m in masks:
+            if m.shape != (model.height, model.width):
+                raise ValueError('record_electrodes: a mask of shape %s on a %d x %d grid' % (m.shape, model.height, model.width))
+        self.every = int(every)
+        if self.every < 1:
+            raise ValueError('record_electrodes: every must be >= 1')
+        if capacity is None:                     # the samples of a whole run of model.duration (whatever has run already), at least 1
+            ticks = int(model.duration / (model.dt_per_step * model.dt))
+            capacity = max(1, ticks // self.every)
+        self.capacity = int(capacity)
+        self.var = int(var)
+        crops = [crop_mask(m) for m in masks]
+        self.rects = [c[0] for c in crops]
+        self.weight_sums = np.array([np.sum(c[1], dtype=np.float64) for c in crops])
+        self.cells = model.height * model.width
+        self.affine = tuple(float(a) for a in model._image_affine()) if self.var == 0 else (1.0, 0.0)
+        if self.var == 0 and check_affine:
+            x = np.asarray(st.get_state(0), np.float64)
+            want = np.asarray(model.image(), np.float64)
+            got = self.affine[0] * x + self.affine[1]
+            tol = 1e-5 * (abs(self.affine[0]) * float(np.abs(x).max()) + abs(self.affine[1])) + 1e-30
+            if want.shape != got.shape or not np.all(np.abs(got - want) <= tol):
+                raise ValueError('record_electrodes: image() is not %g * X + %g on the current state: a model whose image() '
+                                 'rescales must override _image_affine()' % self.affine)
+        self._st = st
+        st.electrode_begin(self.var, self.rects, [c[1] for c in crops], self.every, self.capacity)
+        self.open = True
+
+    def _check(self):
+        if not self.open:
+            raise AssertionError('the electrode recorder has been closed')
+
+    def count(self):
+        """samples taken since the recorder was attached"""
+        self._check()
+        return self._st.electrode_count()
+
+    def convert(self, raw):
+        """raw float32 sums of w * X -> the reference's mean(image() * mask), in float64: image() = scale * X + offset
+        (IonicModel._image_affine), so the mean is (scale * raw + offset * sum(w)) / (H * W)"""
+        scale, offset = self.affine
+        return (scale * np.asarray(raw, np.float64) + offset * self.weight_sums) / self.cells
+
+    def traces(self, raw=False, first=0, count=None):
+        """float64 [samples, n]: mean(image() * mask) of every electrode at every sample taken so far (raw=True: the float32
+        sums of w * X as the device took them, as float64); `first`, `count`: a window of the samples"""
+        self._check()
+        got = self._st.electrode_read(first, count)
+        return got.astype(np.float64) if raw else self.convert(got)
+
+    def close(self):
+        """detaches the recorder and frees the trace"""
+        if self.open:
+            self.open = False
+            self._st.electrode_end()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def record_on_device(model, mask1, mask2, im=None, every_ms=1.0, on_tick=None):
+    """`record()` with the electrodes on the device: same signature, same stride rule, same sample times, same float64
+    [n, 2] result — without a grid read-back per sample (a model whose image() rescales must override `_image_affine()`:
+    see ElectrodeRecorder).  `record()` samples after ticks 0, stride, 2 * stride, ...; a recorder
+    samples after ticks every - 1, 2 * every - 1, ...  For stride 1 the two coincide.  For a larger stride the first tick is
+    recorded by a recorder of its own with every = 1 (one sample), and a second one with every = stride is attached after it:
+    its samples fall after ticks stride, 2 * stride, ..."""
+    stride = max(1, int(round(every_ms / (model.dt * model.dt_per_step))))
+    ticks = int(model.duration / (model.dt_per_step * model.dt))
+    if ticks < 1:
+        return np.zeros((0, 2), np.float64)
+    head = None
+    rec = model.record_electrodes([mask1, mask2], every=1, capacity=ticks if stride == 1 else 1)
+    try:
+        for i in model.run(im):
+            if on_tick is not None:
+                on_tick(i)
+            if stride > 1 and i == 0:
+                head = rec.traces()
+                rec.close()
+                rec = model.record_electrodes([mask1, mask2], every=stride, capacity=max(1, (ticks - 1) // stride))
+        out = rec.traces()
+    finally:
+        rec.close()
+    return out if head is None else np.concatenate([head, out])
+
+
 def _upstroke_time(trace, level):
     """first upward crossing of `level`, linearly interpolated, in samples; None if it never happens"""
     above = trace >= level

@@ -226,6 +226,26 @@ class IonicModel:
             ensure()
         return ActivationRecorder(self, up=up, down=down, var=var)
 
+    def record_electrodes(self, masks, every=1, capacity=None, var=0):
+        """attaches an electrode recorder (fib_tf_amd/egm.py) to this model's handle: every `every` ticks the weighted sum of
+        state array `var` under each full-grid `mask` (its non-zero box) is appended to a trace on the device;
+        `traces()` returns the reference's mean(image() * mask) for var = 0 — a model whose image() rescales must override
+        `_image_affine()`, which is checked against image() at attach — and mean(X_var * mask) otherwise.  Default capacity:
+        the samples of a whole run of `duration`.  Call after define(); single device only (row blocks raise
+        NotImplementedError)."""
+        from .egm import ElectrodeRecorder
+        if not self.defined:
+            raise AssertionError('record_electrodes should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return ElectrodeRecorder(self, masks, every=every, capacity=capacity, var=var)
+
+    def _image_affine(self):
+        """(scale, offset) with image() == scale * X + offset, X the array pot() names: what turns an electrode's raw sum
+        into mean(image() * mask).  Models whose image() rescales override it."""
+        return 1.0, 0.0
+
     def millisecond_to_step(self, t):
         """milliseconds -> tick index returned by run(), ionic.py:247-252"""
         return int(t / (self.dt_per_step * self.dt))

@@ -347,6 +347,43 @@ int fibhip_observe_get(fibhip_t h, int which, void *dst);
 int fibhip_observe_ticks(fibhip_t h, long long *k);
 int fibhip_observe_end(fibhip_t h);
 
+/* Electrode recorder: weighted sums of one state array over rectangular patches, taken on the device every `every` ticks
+ * and appended to a trace that stays on the device until it is read (the reference's electrodes: egm.py multiplies image()
+ * by a Gaussian mask and takes the mean, once per millisecond; court_ultra.py keeps phi-weighted means of the same kind).
+ * Electrode e is a rectangle [r0, r1) x [c0, c1) inside the grid and a dense float32 weight patch w_e of that shape,
+ * row-major.  A recorder holds n electrodes (1 .. FIBHIP_MAX_ELECTRODES), the watched array `var`, a stride every >= 1 and
+ * a capacity >= 1 in samples.  With k = ticks since electrode_begin (the first tick after it is k = 0), after every tick
+ * with (k + 1) % every == 0 sample s = (k + 1) / every - 1 is taken:
+ *     trace[s][e] = sum over (i, j) in rect_e of  w_e[i - r0, j - c0] * X_var[i, j]      (raw state values, float32)
+ * The sum is float32 in a FIXED order that depends on the rectangle alone: the same state gives the same bits on every run,
+ * whatever the launch plan (multi-tick launches on or off, after a recovered give-up, fused Courtemanche ticks).  No
+ * floating-point atomics.  Accuracy: every product is rounded to float32 (or fused), and no term passes through more than
+ * D(m) = ceil(m / 256) + 16 float32 additions, m = cells of the patch; hence against the exact sum S
+ *     |trace - S| <= g * sum |w * X|,   g = (D + 1) u / (1 - (D + 1) u),   u = 2^-24
+ * (the standard model: as long as no product underflows — a product below 2^-126 keeps fewer bits, below 2^-150 none).
+ * Pacing, set_state and step_slow / step_mode between two ticks belong to the next tick.  Patches of any size up to the
+ * whole grid are accepted.  The trace does not wrap: a fibhip_step that would take sample number `capacity` is refused with
+ * FIBHIP_EINVAL ("trace full") before anything of that call is enqueued, and the handle stays usable (read, detach,
+ * re-attach).  While a recorder is attached no launch spans a sample tick — between two samples the handle keeps its
+ * multi-tick launches, cut at the sample ticks — and nothing runs ahead of the caller; a handle without one runs as ever.
+ * A handle that runs multi-tick launches sends a launch only when the ticks up to the next sample tick (or as many as one
+ * launch takes) have been accepted: a caller that steps tick by tick without observing anything leaves the device idle for
+ * up to every - 1 of its calls; any call that observes the state launches what waits.  Courtemanche's tick is not fused
+ * with the 'slow' operation behind it when a sample of one of the slow arrays is due at that tick.
+ * Refused with FIBHIP_EINVAL: a row block (a handle with ghost rows), inside an open tick, a rectangle that is empty or not
+ * inside the grid, n, every, capacity or var out of range, null pointers, weights that are not finite.
+ *   fibhip_electrode_begin  flushes, synchronises and confirms pending work, copies rectangles (n x {r0, r1, c0, c1}) and
+ *                           weights (the patches back to back) to the device and attaches; again: re-attaches, empty trace
+ *   fibhip_electrode_count  samples taken so far (ticks accepted but not launched yet included)
+ *   fibhip_electrode_read   samples [first, first + count) as [count][n] float32; flushes and blocks like get_state; does not
+ *                           detach and does not reset the sample index, so a long run can be read in pieces
+ *   fibhip_electrode_end    detaches and frees the trace (no recorder attached: nothing); fibhip_destroy does the same      */
+#define FIBHIP_MAX_ELECTRODES 64
+int fibhip_electrode_begin(fibhip_t h, int var, int n, const int *rects, const float *weights, int every, long long capacity);
+int fibhip_electrode_count(fibhip_t h, long long *samples);
+int fibhip_electrode_read(fibhip_t h, long long first, long long count, float *dst);
+int fibhip_electrode_end(fibhip_t h);
+
 const char *fibhip_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)
