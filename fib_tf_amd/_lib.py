@@ -179,7 +179,9 @@ _lib = None
 
 
 DEPS = [SRC, HDR] + [os.path.join(HERE, "csrc", f) for f in ("kernels.hpp", "models.hpp", "fenton_step.inc", "br_step.inc",
-                                                             "court_step.inc", "court_inter.inc")]
+                                                             "court_step.inc", "court_inter.inc", "host_util.hpp", "launch.hpp",
+                                                             "ctx.hpp", "tick.inc", "sched.inc", "record.inc", "plan.inc", "comm.inc",
+                                                             "unit.inc")]
 
 
 def build(force=False, verbose=False):

@@ -1,0 +1,295 @@
+// ctx.hpp — the handle behind fibhip_t: what it owns, grouped by who changes it, and the few helpers every file reads it with.
+#pragma once
+
+constexpr int MT_MAX_TICKS = 32;          // default bound on the ticks of one launch (0.4 ms of Fenton 512x512)
+constexpr int AT_MT_TICKS = 8;           // autotune times a multi-tick candidate as one launch of this many ticks
+static const char *const MT_DEAD_MSG =
+    "a multi-tick launch gave up (a tile waited its full bound for a neighbouring tile: were all workgroups resident? is another "
+    "process holding the GPU?) and the state it started from could not be restored; the state of this handle is void — "
+    "FIBHIP_MT=0 runs one launch per tick";
+
+struct PlanItem {
+    int K;
+    launch_fn fn;
+    int TY, TX;
+    const Variant *v = nullptr;     // the table entry it came from (run-time module kernels carry their launch data there)
+};
+
+// a traced model's device code loaded at run time (fibhip_module_load)
+struct fibhip_module {
+    hipModule_t mod = nullptr;
+    int device = 0;
+    int nvar = 0, spt = 1, nmodes = 1, consts_bytes = 4;
+    unsigned masks[8] = {0};
+    int K = 1, TX = 64, TY = 4, R = 3, TYB = 0, K2 = 1, TX2 = 64, TY2 = 4, R2 = 4;   // plan hints of the generated header
+    std::vector<Variant> variants;
+};
+
+// ---- the scheduler's state (sched.inc) ---------------------------------------------------------------------------------
+// several TICKS per launch (strip_mt_kernel): grids whose tiles are all resident at once, one device, planar slab
+struct MtState {
+    float *xbuf;            // exchange buffer of 16-byte cells [2][nvar/4][cells], allocated on first use
+    unsigned *epochs;       // one epoch word per tile, 256 bytes apart, + three words behind them (MtArgs::err)
+    unsigned epoch_base;    // value of every epoch word between two launches
+    bool stale;             // the tiling may have changed since the words were last written: zero them first
+    int max;                // most ticks one launch advances (<= 1: never)
+    int cur;                // ticks the next launch waits for: 1 after any observation of the state, then see fibhip_step
+    unsigned *snap_flags;   // page-locked: one word per tile, raised by the tiles of a launch that carries a read-back
+    unsigned *snap_flags_dev;       // device address of snap_flags
+    unsigned *host_word;    // page-locked (behind snap_flags), read by tile 0 over PCIe: {launch id << 16 | n}, see ahead_settle
+    unsigned ids;           // launch ids cycle through 1 .. ids
+    unsigned seq;           // id of the last multi-tick launch (the host's word names the launch it is meant for)
+    bool inflight;          // a multi-tick launch has been issued since the give-up word was last read
+    unsigned wait_ms;       // a tile's bound on its wait for a neighbour (FIBHIP_MT_WAIT_MS, fibhip_set_mt_wait_ms); 0 = 2 s
+    long long n_launches, n_ticks;  // fibhip_launch_stats
+
+    // the three words behind the tiles' epoch words, MT_EPOCH_STRIDE apart: [0] the id of a launch whose tile gave up,
+    // [1] the host's word as tile 0 passed it on, [2] the tiles that stopped at the tick the host named
+    unsigned *give_up_word() const { return epochs + (size_t)MT_MAX_TILES * MT_EPOCH_STRIDE; }
+    unsigned *stop_count_word() const { return give_up_word() + 2 * MT_EPOCH_STRIDE; }
+    static constexpr size_t tail_bytes() { return 3 * MT_EPOCH_STRIDE * sizeof(unsigned); }
+    static constexpr size_t words_bytes() { return (size_t)MT_MAX_TILES * MT_EPOCH_STRIDE * sizeof(unsigned) + tail_bytes(); }
+    // the host-side word a tile that gave up writes its launch's id into (behind host_word)
+    unsigned *host_give_up() const { return host_word + MT_GIVEUP_WORD; }
+};
+
+// the caller's series: the ticks between two observations of the state
+struct Series {
+    int run;                // ticks launched since the last observation of the state
+    int hist[8], nhist;     // lengths of the last series of ticks, oldest first (predict_series)
+    bool fresh;             // ticks have run since the last observation of the state
+    bool trust;             // the caller has not broken a predicted series since its last two equal ones
+    int expect;             // ticks the caller has DECLARED to come in one series (fibhip_expect) and that have not been asked for yet, or 0
+    bool expect_fresh;      // ... none of them has been asked for yet: the observation the caller makes first does not end the series
+};
+
+// run-ahead: a caller that alternates series of n ticks with ONE read-back (run() with image() every n ticks) gets the
+// next n ticks launched BEFORE the read-back's copy is waited for; see ahead_read_back
+struct Ahead {
+    bool ok;                // nothing forbids it for good: not FIBHIP_AHEAD=0, not a caller-owned slab (fibhip_create), and no
+                            // raw pointer handed out (fibhip_state_ptr) — a caller that can write the state at any time
+    int n, used;            // ticks computed ahead of the caller / how many of them fibhip_step has handed out
+    unsigned id;            // ... of the launch that ran ahead
+    int nxt[FIB_MAXVAR];    // where the state lives once all of them are handed out
+    hipEvent_t ev;
+    unsigned snap_seq;
+    long long n_kept, n_redone;     // series launched ahead that the caller cut short: stopped in time / recomputed
+};
+
+// A multi-tick launch that gives up must not cost the run (ionic.py:202-204 has no such failure).  Every such launch since
+// the stream was last known good is remembered with the buffers it READ: a launch writes the other slab only and the
+// launches queued behind a failed one find the give-up word at their first boundary and leave without writing, so the
+// state the FIRST failed launch started from is intact when the host finds out (`recover`).
+struct MtRec {
+    unsigned id;        // the launch's id (the give-up word names it)
+    int T;              // ticks it advances (a launch that ran ahead and was stopped in time: the ticks it did)
+    bool counted;       // the handle's state has moved past these ticks (false: a run-ahead not handed out yet)
+    int src[FIB_MAXVAR];
+};
+struct Journal {
+    std::vector<MtRec> recs;
+    bool recovering;
+    long long n_fallbacks, n_replayed;      // launches that gave up and were recovered / ticks recomputed one launch per tick
+    long fake_giveup_at, fake_seen;         // test switch FIBHIP_MT_FAKE_GIVEUP=n: the n-th multi-tick launch finds the give-up word raised
+};
+
+// ---- the recorders (record.inc) ----------------------------------------------------------------------------------------
+// activation recorder (fibhip_observe_begin): while `on`, commit_impl enqueues observe_kernel behind every tick
+struct ObsRec {
+    bool on;
+    int var;
+    float up, down;
+    float *buf;             // 6 planes of `cells` (W-pitched): Vp | first_up | last_up | prev_up | apd | count (int32)
+    long long k;            // observed ticks since the recorder was attached
+};
+// electrode recorder (fibhip_electrode_begin): while `on`, no launch spans a sample tick (el_room) and the hooks on the
+// plain and the multi-tick commit path (electrode_advance) enqueue electrode_kernel behind the launch that ends one
+struct ElRec {
+    bool on;
+    int var, n, every;
+    long long cap;          // samples the trace holds
+    long long k;            // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
+    int nchunks, ncomb;     // workgroups of electrode_kernel / of electrode_combine_kernel (0: no electrode has several chunks)
+    ElChunk *chunks;        // device: the chunk table
+    ElComb *comb;           // device: the electrodes of several chunks
+    float *w;               // device: the weight patches, back to back
+    float *part;            // device: one partial per chunk of such electrodes
+    float *trace;           // device: [cap][n]
+};
+
+// fibhip_trace_begin / _end: the launches in between, each between two HIP events
+struct TraceRec {
+    hipEvent_t e0, e1;
+    char name[96];
+    int K, TX, TY, R, ticks;
+};
+
+struct fibhip_ctx {
+    fibhip_desc d;
+    int nvar, spt, mode;
+    size_t cells;
+    int pitch;              // floats between rows of one state array (W planar, nvar*W row-interleaved)
+    size_t vstride;         // floats between the first rows of consecutive state arrays (cells / W)
+    hipStream_t s0, s1;
+    bool own_s0;
+    float *slab[2];
+    bool own_slab;
+    float *phase3;          // dpy | dpx | q4 | r4 | dpy*r4 | dpx*r4, each `cells` floats
+    float *phi_dev;
+    bool has_phase;
+    int cur[FIB_MAXVAR];            // which slab holds variable v
+    int nxt[FIB_MAXVAR];            // where the tick in flight writes it (valid between edges and commit)
+    bool has_consts;
+    Fenton::Consts kf;
+    BeelerReuter::Consts kb;
+    Courtemanche::Consts kc;
+#ifdef FIB_CUSTOM_MODEL_INC
+    Custom::Consts ku;
+#endif
+    // ---- the plan (plan.inc) ----
+    std::vector<PlanItem> plan;
+    std::vector<PlanItem> plan_multi[4];    // [T]: the one-launch plan of T ticks, T = 2..multi_max
+    int multi_max;          // up to this many consecutive ticks go into one launch (1 = never; CourtAgg: 3)
+    launch_fn fused_fn;     // Courtemanche: tick + 'slow' in one launch, or null
+    bool tuned;             // the plan has been checked against the other tile shapes on this very geometry (autotune)
+    int ncu;                // compute units of the device
+    fibhip_module *mod;     // FIBHIP_CUSTOM on a run-time module (fibhip_module_load), or null
+    // ---- one tick (tick.inc) ----
+    hipEvent_t ev_main, ev_int, ev_t0, ev_t1;
+    int phase_of_tick;      // 0 idle, 1 edges issued, 2 interior issued
+    long launches, t_launches0;
+    long long n_ticks;      // fibhip_launch_stats
+    int own0, own1;         // owned local rows
+    bool whole_in_edges;    // this tick's last launch was issued entirely by step_edges
+    int cycle, cpos;        // ghost zone = cycle * steps_per_tick rows: the halo is exchanged every `cycle` ticks;
+                            // cpos = ticks done since the last exchange
+    int span;               // ticks the launch being issued covers (1; T while tick_multi fuses T Courtemanche ticks)
+    // ---- the scheduler (sched.inc) ----
+    int pending;            // ticks fibhip_step has accepted but not launched yet (see fibhip_step)
+    MtState mt;
+    Series series;
+    Ahead ahead;
+    Journal journal;
+    bool dead;              // a multi-tick launch gave up waiting and the state could not be restored: void
+    // ---- the recorders (record.inc) ----
+    ObsRec obs;
+    ElRec el;
+    std::vector<TraceRec> trace;
+    bool tracing;
+    // ---- the rest ----
+    DoneWord done;          // sync_s0's way of noticing the end of the stream's work
+    void *comm;             // ncclComm_t of the direct halo path (fibhip_comm_*), or null
+    float *probe_host;      // pinned
+    float *stage;           // pinned staging buffer for get_state/set_state (one array), allocated on first use
+    // Courtemanche, fast policy: the fast tick reads five per-cell aggregates of the slow
+    // variables (models.hpp CourtAgg) instead of the variables themselves.  'slow' rewrites them; any other write to the
+    // state (set_state) marks them stale and the next tick recomputes them first.
+    float *agg;             // CourtAgg::NAGG arrays laid out like the state arrays (planar, or row-interleaved at the
+    size_t agg_stride;      // slab's pitch on row-block shards), `agg_stride` floats apart; or null
+    bool use_agg, agg_dirty;
+    bool agg_ghost_dirty;   // row-block shards: a halo exchange has rewritten the ghost rows' slow variables
+};
+
+static const void *consts_of(fibhip_ctx *h)
+{
+    if (h->mod) return nullptr;                    // generated models carry their constants as literals
+    switch (h->d.model) {
+    case FIBHIP_FENTON4V: return &h->kf;
+    case FIBHIP_BR: return &h->kb;
+#ifdef FIB_CUSTOM_MODEL_INC
+    case FIBHIP_CUSTOM: return &h->ku;
+#endif
+    default: return &h->kc;
+    }
+}
+
+static Geo base_geo(const fibhip_ctx *h)
+{
+    Geo g;
+    g.H = h->d.height;
+    g.W = h->d.width;
+    g.pitch = h->pitch;
+    g.Hg = h->d.global_height;
+    g.row_off = h->d.row_offset;
+    g.r0 = 0;
+    g.r1 = h->d.height;
+    g.rb0 = g.rb1 = 0;
+    g.ty_a = 0;
+    g.tiles_x = g.ntiles = 0;
+    return g;
+}
+
+// tiles of TX x TY that cover `rows` rows of the handle's width (rows < 0: the whole block)
+static inline long tiles_of(const fibhip_ctx *h, int TX, int TY, long rows = -1)
+{
+    if (rows < 0) rows = h->d.height;
+    return (long)((h->d.width + TX - 1) / TX) * ((rows + TY - 1) / TY);
+}
+
+static inline bool is_shard(const fibhip_ctx *h) { return h->d.ghost_top || h->d.ghost_bottom; }
+// the shallower ghost zone of the sides that have one (0: no ghost rows at all)
+static inline int min_ghost(const fibhip_desc &d)
+{
+    return (d.ghost_top && d.ghost_bottom) ? imin(d.ghost_top, d.ghost_bottom) : imax(d.ghost_top, d.ghost_bottom);
+}
+
+// `c` launches a kernel of the handle's run-time module through launch_module, which lays the arguments out from these
+static inline void module_kernel(LaunchCtx &c, const fibhip_ctx *h, hipFunction_t kern, int kind, const Variant *v)
+{
+    c.kern = kern;
+    c.kind = kind;
+    c.K = v->K; c.TX = v->TX; c.TY = v->TY; c.NT = v->NT;
+    c.nvar = h->nvar;
+    c.consts_bytes = h->mod ? h->mod->consts_bytes : 0;
+}
+
+// ---- what every entry point starts with ---------------------------------------------------------------------------------
+#define NEED(h)                                                  \
+    do {                                                         \
+        if (!(h)) return fail(FIBHIP_EINVAL, "null handle");     \
+        if ((h)->dead) return fail(FIBHIP_EHIP, "%s", MT_DEAD_MSG);  \
+        HIPCHK(hipSetDevice((h)->d.device));                     \
+    } while (0)
+// launches the ticks fibhip_step may have left pending (sched.inc `flush`); every entry point that observes or changes the
+// state starts with it
+#define FLUSH(h)                                                                                   \
+    do {                                                                                           \
+        if (int rc_ = flush(h)) return rc_;                                                        \
+    } while (0)
+// waits until no unconfirmed multi-tick launch is in flight (sched.inc `confirm`): in front of whatever writes the state
+#define CONFIRM(h)                                                                                 \
+    do {                                                                                           \
+        if (int rc_ = confirm(h)) return rc_;                                                      \
+    } while (0)
+// waits for everything enqueued on the handle's stream; recovers from a multi-tick launch that gave up (sched.inc `sync_s0`)
+#define SYNC_S0(h)                                                                                 \
+    do {                                                                                           \
+        if (int rc_ = sync_s0(h)) return rc_;                                                      \
+    } while (0)
+
+// ---- timeline (fibhip_trace_begin / _end) ------------------------------------------------------------------------------
+static int trace_open(fibhip_ctx *h, hipStream_t st, const char *family, int K, int TX, int TY, int NT, int ticks)
+{
+    if (!h->tracing) return 0;
+    TraceRec r;
+    r.e0 = r.e1 = nullptr;
+    HIPCHK(hipEventCreate(&r.e0));
+    HIPCHK(hipEventCreate(&r.e1));
+    r.K = K; r.TX = TX; r.TY = TY; r.R = NT < 0 ? (NT < -32 ? -NT - 32 : -NT) : 0; r.ticks = ticks;
+    if (TX > 0 && NT < 0)
+        snprintf(r.name, sizeof r.name, "%s<K=%d, tile %dx%d, %d rows per wave%s>", family, K, TX, TY, r.R,
+                 ticks > 1 ? ", several ticks" : "");
+    else if (TX > 0)
+        snprintf(r.name, sizeof r.name, "%s<K=%d, tile %dx%d, %d threads>", family, K, TX, TY, NT);
+    else
+        snprintf(r.name, sizeof r.name, "%s", family);
+    HIPCHK(hipEventRecord(r.e0, st));
+    h->trace.push_back(r);
+    return 0;
+}
+static int trace_close(fibhip_ctx *h, hipStream_t st)
+{
+    if (!h->tracing || h->trace.empty()) return 0;
+    HIPCHK(hipEventRecord(h->trace.back().e1, st));
+    return 0;
+}

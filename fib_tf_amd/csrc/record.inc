@@ -1,0 +1,255 @@
+// record.inc — the two recorders that run on the device while a model runs: the per-cell activation maps
+// (fibhip_observe_*) and the electrode traces (fibhip_electrode_*).  Each is a hook behind a committed launch plus its entry
+// points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
+// (included by fibhip.hip, behind sched.inc)
+
+// the activation recorder's update for the tick just committed (observed tick k = obs_k), on s0 behind it
+static int observe_enqueue(fibhip_ctx *h)
+{
+    const size_t n = h->cells;
+    const float *pot = h->slab[h->cur[h->obs.var]] + (size_t)h->obs.var * h->vstride;
+    ObsMaps m;
+    m.first = h->obs.buf + n;
+    m.last = h->obs.buf + 2 * n;
+    m.prev = h->obs.buf + 3 * n;
+    m.apd = h->obs.buf + 4 * n;
+    m.count = reinterpret_cast<int *>(h->obs.buf + 5 * n);
+    const float tick = (float)(h->d.dt * h->spt);
+    const float t0 = (float)((double)h->obs.k * h->d.dt * h->spt);
+    const bool vec = h->pitch == h->d.width && (reinterpret_cast<uintptr_t>(pot) & 15u) == 0;
+    const size_t threads = vec ? n / 4 + n % 4 : n;
+    const Geo g = base_geo(h);
+    if (int rc = trace_open(h, h->s0, "observe_kernel", 0, 0, 0, 0, 1)) return rc;
+    if (vec)
+        hipLaunchKernelGGL(observe_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->s0, g, pot, h->obs.buf, m,
+                           h->obs.up, h->obs.down, t0, tick);
+    else
+        hipLaunchKernelGGL(observe_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->s0, g, pot, h->obs.buf, m,
+                           h->obs.up, h->obs.down, t0, tick);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    h->obs.k++;
+    return 0;
+}
+
+// The electrode recorder's hook behind a launch of `ticks` ticks (plain: commit_impl; multi-tick: mt_launch).  No launch
+// spans a sample tick (el_room), so a sample is due exactly when the counter lands on a multiple of `every`; it is enqueued
+// on s0 behind that launch and reads the state the handle has just moved to.  The slot is a kernel argument computed from the
+// host's counter, never a pointer kept on the device: a replay (recover()) writes the same slots again.
+static int electrode_advance(fibhip_ctx *h, int ticks)
+{
+    h->el.k += ticks;
+    if (h->el.k % h->el.every) return 0;
+    const long long s = h->el.k / h->el.every - 1;
+    if (s >= h->el.cap) return fail(FIBHIP_EINVAL, "electrode recorder: trace full");      // (fibhip_step refuses before this)
+    const float *x = h->slab[h->cur[h->el.var]] + (size_t)h->el.var * h->vstride;
+    float *row = h->el.trace + (size_t)s * h->el.n;
+    if (int rc = trace_open(h, h->s0, "electrode_kernel", 0, 0, 0, 0, 1)) return rc;
+    hipLaunchKernelGGL(electrode_kernel, dim3((unsigned)h->el.nchunks), dim3(EL_THREADS), 0, h->s0, x, h->pitch, h->el.chunks, h->el.w,
+                       row, h->el.part);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    if (h->el.ncomb) {
+        if (int rc = trace_open(h, h->s0, "electrode_combine_kernel", 0, 0, 0, 0, 1)) return rc;
+        hipLaunchKernelGGL(electrode_combine_kernel, dim3((unsigned)h->el.ncomb), dim3(256), 0, h->s0, h->el.comb, h->el.part, row);
+        HIPCHK(hipGetLastError());
+        if (int rc = trace_close(h, h->s0)) return rc;
+        h->launches++;
+    }
+    return 0;
+}
+
+static void electrode_free(fibhip_ctx *h)
+{
+    if (h->el.chunks) hipFree(h->el.chunks);
+    if (h->el.comb) hipFree(h->el.comb);
+    if (h->el.w) hipFree(h->el.w);
+    if (h->el.part) hipFree(h->el.part);
+    if (h->el.trace) hipFree(h->el.trace);
+    h->el.chunks = nullptr;
+    h->el.comb = nullptr;
+    h->el.w = h->el.part = h->el.trace = nullptr;
+    h->el.on = false;
+}
+
+// ---- activation recorder ------------------------------------------------------------------------------------------------
+extern "C" int fibhip_observe_begin(fibhip_t h, int var, float up, float down)
+{
+    NEED(h);
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "observe_begin: bad var %d", var);
+    if (std::isnan(up) || std::isnan(down) || down > up)
+        return fail(FIBHIP_EINVAL, "observe_begin: thresholds must be numbers with down <= up (got up %g, down %g)", up, down);
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "observe_begin: not on a row block (a handle with ghost rows)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "observe_begin inside an open tick");
+    // everything accepted so far runs unobserved and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // Vp is copied (the recorder must not start from the slab such a launch left void)
+    FLUSH(h);
+    SYNC_S0(h);
+    const size_t n = h->cells;
+    if (!h->obs.buf) HIPCHK(hipMalloc((void **)&h->obs.buf, 6 * n * sizeof(float)));
+    HIPCHK(hipMemcpy2DAsync(h->obs.buf, (size_t)h->d.width * sizeof(float), h->slab[h->cur[var]] + (size_t)var * h->vstride,
+                            (size_t)h->pitch * sizeof(float), (size_t)h->d.width * sizeof(float), (size_t)h->d.height,
+                            hipMemcpyDeviceToDevice, h->s0));
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    unsigned nan_bits;
+    memcpy(&nan_bits, &qnan, sizeof nan_bits);
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(h->obs.buf + n), (int)nan_bits, 4 * n, h->s0));   // first | last | prev | apd
+    HIPCHK(hipMemsetAsync(h->obs.buf + 5 * n, 0, n * sizeof(int), h->s0));                      // count
+    h->obs.on = true;
+    h->obs.var = var;
+    h->obs.up = up;
+    h->obs.down = down;
+    h->obs.k = 0;
+    return 0;
+}
+
+extern "C" int fibhip_observe_get(fibhip_t h, int which, void *dst)
+{
+    NEED(h);
+    FLUSH(h);
+    if (!h->obs.on) return fail(FIBHIP_EINVAL, "observe_get: no recorder attached (fibhip_observe_begin)");
+    if (!dst || which < 0 || which > FIBHIP_OBS_COUNT) return fail(FIBHIP_EINVAL, "observe_get: bad argument (which %d)", which);
+    if (!h->stage) HIPCHK(hipHostMalloc((void **)&h->stage, h->cells * sizeof(float), hipHostMallocDefault));
+    HIPCHK(hipMemcpyAsync(h->stage, h->obs.buf + (size_t)(1 + which) * h->cells, h->cells * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+    SYNC_S0(h);
+    memcpy(dst, h->stage, h->cells * sizeof(float));
+    return 0;
+}
+
+extern "C" int fibhip_observe_ticks(fibhip_t h, long long *k)
+{
+    if (!h || !k) return fail(FIBHIP_EINVAL, "observe_ticks: null argument");
+    if (!h->obs.on) return fail(FIBHIP_EINVAL, "observe_ticks: no recorder attached (fibhip_observe_begin)");
+    *k = h->obs.k + h->pending;                        // (ticks accepted but not launched yet are observed when they are)
+    return 0;
+}
+
+extern "C" int fibhip_observe_end(fibhip_t h)
+{
+    NEED(h);
+    FLUSH(h);                                          // the ticks accepted while attached are observed
+    if (h->obs.buf) {
+        HIPCHK(wait_stream(h->s0));
+        HIPCHK(hipFree(h->obs.buf));
+        h->obs.buf = nullptr;
+    }
+    h->obs.on = false;
+    return 0;
+}
+
+// ---- electrode recorder -------------------------------------------------------------------------------------------------
+extern "C" int fibhip_electrode_begin(fibhip_t h, int var, int n, const int *rects, const float *weights, int every, long long capacity)
+{
+    NEED(h);
+    if (!rects || !weights) return fail(FIBHIP_EINVAL, "electrode_begin: null argument");
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "electrode_begin: bad var %d", var);
+    if (n < 1 || n > FIBHIP_MAX_ELECTRODES) return fail(FIBHIP_EINVAL, "electrode_begin: 1 .. %d electrodes (got %d)", FIBHIP_MAX_ELECTRODES, n);
+    if (every < 1) return fail(FIBHIP_EINVAL, "electrode_begin: every must be >= 1 (got %d)", every);
+    if (capacity < 1 || capacity > (long long)(SIZE_MAX / sizeof(float) / (size_t)n))
+        return fail(FIBHIP_EINVAL, "electrode_begin: bad capacity %lld", capacity);
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "electrode_begin: not on a row block (a handle with ghost rows)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "electrode_begin inside an open tick");
+    // the chunk table: one chunk per patch of up to EL_CHUNK cells, larger patches in at most 256 equal chunks
+    std::vector<ElChunk> chunks;
+    std::vector<ElComb> combs;
+    size_t woff = 0;
+    int nparts = 0;
+    for (int e = 0; e < n; ++e) {
+        const int r0 = rects[4 * e], r1 = rects[4 * e + 1], c0 = rects[4 * e + 2], c1 = rects[4 * e + 3];
+        if (r0 < 0 || r1 > h->d.height || c0 < 0 || c1 > h->d.width || r0 >= r1 || c0 >= c1)
+            return fail(FIBHIP_EINVAL, "electrode_begin: electrode %d: rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid",
+                        e, r0, r1, c0, c1, h->d.height, h->d.width);
+        const size_t m = (size_t)(r1 - r0) * (size_t)(c1 - c0);
+        if (woff + m > 0x7FFFFFFFu) return fail(FIBHIP_EINVAL, "electrode_begin: more than 2^31 - 1 weights");
+        for (size_t i = 0; i < m; ++i)
+            if (!std::isfinite(weights[woff + i])) return fail(FIBHIP_EINVAL, "electrode_begin: electrode %d has a weight that is not finite", e);
+        const size_t cs = m <= EL_CHUNK ? m : (m + 255) / 256 > EL_CHUNK ? (m + 255) / 256 : (size_t)EL_CHUNK;
+        const int nc = (int)((m + cs - 1) / cs);                       // <= 256
+        if (nc > 1) {
+            ElComb cb;
+            cb.e = e; cb.part0 = nparts; cb.nparts = nc;
+            combs.push_back(cb);
+        }
+        for (int k = 0; k < nc; ++k) {
+            ElChunk c;
+            c.r0 = r0; c.c0 = c0; c.pw = c1 - c0;
+            c.first = (unsigned)((size_t)k * cs);
+            c.count = (unsigned)((size_t)(k + 1) * cs <= m ? cs : m - (size_t)k * cs);
+            c.woff = (unsigned)woff;
+            c.out = nc > 1 ? -1 - nparts++ : e;
+            chunks.push_back(c);
+        }
+        woff += m;
+    }
+    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick k = 0 is defined (the rule of fibhip_observe_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    electrode_free(h);
+    bool ok = hipMalloc((void **)&h->el.chunks, chunks.size() * sizeof(ElChunk)) == hipSuccess &&
+              hipMalloc((void **)&h->el.w, woff * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&h->el.trace, (size_t)capacity * (size_t)n * sizeof(float)) == hipSuccess;
+    if (ok && nparts)
+        ok = hipMalloc((void **)&h->el.comb, combs.size() * sizeof(ElComb)) == hipSuccess &&
+             hipMalloc((void **)&h->el.part, (size_t)nparts * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        electrode_free(h);
+        return fail(FIBHIP_ENOMEM, "electrode_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d electrodes)", capacity, n);
+    }
+    HIPCHK(hipMemcpyAsync(h->el.chunks, chunks.data(), chunks.size() * sizeof(ElChunk), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemcpyAsync(h->el.w, weights, woff * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    if (nparts) HIPCHK(hipMemcpyAsync(h->el.comb, combs.data(), combs.size() * sizeof(ElComb), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemsetAsync(h->el.trace, 0, (size_t)capacity * (size_t)n * sizeof(float), h->s0));
+    HIPCHK(wait_stream(h->s0));                        // `chunks`, `combs` and the caller's arrays are free again
+    h->el.on = true;
+    h->el.var = var;
+    h->el.n = n;
+    h->el.every = every;
+    h->el.cap = capacity;
+    h->el.k = 0;
+    h->el.nchunks = (int)chunks.size();
+    h->el.ncomb = (int)combs.size();
+    return 0;
+}
+
+extern "C" int fibhip_electrode_count(fibhip_t h, long long *samples)
+{
+    NEED(h);
+    if (!samples) return fail(FIBHIP_EINVAL, "electrode_count: null argument");
+    if (!h->el.on) return fail(FIBHIP_EINVAL, "electrode_count: no recorder attached (fibhip_electrode_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    *samples = (h->el.k + h->pending) / h->el.every;   // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+
+extern "C" int fibhip_electrode_read(fibhip_t h, long long first, long long count, float *dst)
+{
+    NEED(h);
+    if (!h->el.on) return fail(FIBHIP_EINVAL, "electrode_read: no recorder attached (fibhip_electrode_begin)");
+    FLUSH(h);
+    const long long taken = h->el.k / h->el.every;
+    if (first < 0 || count < 0 || first + count > taken)
+        return fail(FIBHIP_EINVAL, "electrode_read: samples [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "electrode_read: null destination");
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->journal.n_fallbacks;
+        if (count > 0)
+            HIPCHK(hipMemcpyAsync(dst, h->el.trace + (size_t)first * h->el.n, (size_t)count * h->el.n * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        SYNC_S0(h);
+        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and re-sampled, copy again)
+    }
+    return 0;
+}
+
+extern "C" int fibhip_electrode_end(fibhip_t h)
+{
+    NEED(h);
+    if (!h->el.on) return 0;
+    FLUSH(h);                                          // the ticks accepted while attached are sampled
+    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
+    electrode_free(h);
+    return 0;
+}

@@ -1,0 +1,124 @@
+// unit.inc — entry points that need no handle: the unit-level array ops of the parity tests and the device yardsticks.
+// (included by fibhip.hip)
+
+// IonicModel's building blocks as array ops on HOST arrays (copied through the device), for the
+// unit-level parity tests: op 0 enforce_boundary(a), 1 laplace(a [, phi]), 2 phase_field(pad(a), phi),
+// 3 rush_larsen(a=g, b=g_inf, c=tau, dt).
+extern "C" int fibhip_unit_op(int device, int op, int H, int W, const float *a, const float *b, const float *c,
+                              const float *phi, double dt, int fast, float *out)
+{
+    if (!a || !out || H < 3 || W < 3 || op < 0 || op > 3) return fail(FIBHIP_EINVAL, "unit_op: bad argument");
+    if (op == OP_RUSH_LARSEN && (!b || !c)) return fail(FIBHIP_EINVAL, "unit_op: rush_larsen needs g_inf and tau");
+    if (op == OP_PHASE && !phi) return fail(FIBHIP_EINVAL, "unit_op: phase_field needs phi");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(FIBHIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)H * W, B = n * sizeof(float);
+    float *d = nullptr;
+    HIPCHK(hipMalloc((void **)&d, 9 * B));          // a b c phi ph3[4] out
+    float *da = d, *db = d + n, *dc = d + 2 * n, *dphi = d + 3 * n, *dph3 = d + 4 * n, *dout = d + 8 * n;
+    int rc = 0;
+    do {
+        if (hipMemcpy(da, a, B, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(FIBHIP_EHIP, "unit_op: H2D failed"); break; }
+        if (b && hipMemcpy(db, b, B, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(FIBHIP_EHIP, "unit_op: H2D failed"); break; }
+        if (c && hipMemcpy(dc, c, B, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(FIBHIP_EHIP, "unit_op: H2D failed"); break; }
+        if (phi) {
+            if (hipMemcpy(dphi, phi, B, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(FIBHIP_EHIP, "unit_op: H2D failed"); break; }
+            Geo g;
+            g.H = g.Hg = H; g.W = W; g.pitch = W; g.row_off = 0; g.r0 = 0; g.r1 = H; g.rb0 = g.rb1 = g.ty_a = 0; g.tiles_x = g.ntiles = 0;
+            hipLaunchKernelGGL(phase_prep_kernel, dim3(256), dim3(256), 0, 0, g, dphi, dph3, dph3 + n, dph3 + 2 * n, dph3 + 3 * n,
+                               (float *)nullptr, (float *)nullptr);
+        }
+        const float mdt = (float)(-dt);
+        if (fast)
+            hipLaunchKernelGGL(unit_op_kernel<Fast>, dim3(256), dim3(256), 0, 0, op, H, W, da, db, dc, phi ? dph3 : nullptr, mdt, dout);
+        else
+            hipLaunchKernelGGL(unit_op_kernel<Exact>, dim3(256), dim3(256), 0, 0, op, H, W, da, db, dc, phi ? dph3 : nullptr, mdt, dout);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, B, hipMemcpyDeviceToHost) != hipSuccess) {
+            rc = fail(FIBHIP_EHIP, "unit_op: kernel or D2H failed");
+            break;
+        }
+    } while (0);
+    hipFree(d);
+    return rc;
+}
+
+extern "C" int fibhip_court_inter(int device, int n, const float *V, int fast, float *out)
+{
+    if (!V || !out || n <= 0) return fail(FIBHIP_EINVAL, "court_inter: bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(FIBHIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
+    HIPCHK(hipSetDevice(device));
+    float *d = nullptr;
+    HIPCHK(hipMalloc((void **)&d, (size_t)(1 + COURT_NINTER) * n * sizeof(float)));
+    int rc = 0;
+    do {
+        if (hipMemcpy(d, V, (size_t)n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { rc = fail(FIBHIP_EHIP, "court_inter: H2D failed"); break; }
+        const int blocks = (n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048;
+        if (fast)
+            hipLaunchKernelGGL(court_inter_kernel<Fast>, dim3(blocks), dim3(256), 0, 0, n, d, d + n);
+        else
+            hipLaunchKernelGGL(court_inter_kernel<Exact>, dim3(blocks), dim3(256), 0, 0, n, d, d + n);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpy(out, d + n, (size_t)COURT_NINTER * n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+            rc = fail(FIBHIP_EHIP, "court_inter: kernel or D2H failed");
+            break;
+        }
+    } while (0);
+    hipFree(d);
+    return rc;
+}
+
+extern "C" int fibhip_warm(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(FIBHIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(FIBHIP_EINVAL, "device %d out of range", device);
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(copy_kernel, dim3(1), dim3(256), 0, 0, (const fib_v4f *)nullptr, (fib_v4f *)nullptr, (size_t)0);   // n = 0: touches nothing
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(0));
+    return 0;
+}
+
+extern "C" int fibhip_copy_bandwidth(int device, size_t nbytes, int reps, float *gbs)
+{
+    if (!gbs || nbytes < (1u << 20) || reps < 1) return fail(FIBHIP_EINVAL, "copy_bandwidth: bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(FIBHIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
+    HIPCHK(hipSetDevice(device));
+    const size_t n = nbytes / sizeof(fib_v4f);
+    fib_v4f *a = nullptr, *b = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = 0;
+    do {
+        if (hipMalloc((void **)&a, n * sizeof(fib_v4f)) != hipSuccess || hipMalloc((void **)&b, n * sizeof(fib_v4f)) != hipSuccess ||
+            hipMemset(a, 0, n * sizeof(fib_v4f)) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
+            hipEventCreate(&e1) != hipSuccess) {
+            rc = fail(FIBHIP_EHIP, "copy_bandwidth: allocation failed");
+            break;
+        }
+        const unsigned grid = (unsigned)((n + 255) / 256);  // one 16-byte element per thread
+        hipLaunchKernelGGL(copy_kernel, dim3(grid), dim3(256), 0, 0, a, b, n);   // warm-up
+        float best = 1e30f;
+        for (int r = 0; r < reps; ++r) {
+            hipEventRecord(e0, 0);
+            hipLaunchKernelGGL(copy_kernel, dim3(grid), dim3(256), 0, 0, a, b, n);
+            hipEventRecord(e1, 0);
+            if (hipEventSynchronize(e1) != hipSuccess) { rc = fail(FIBHIP_EHIP, "copy_bandwidth: kernel failed"); break; }
+            float ms = 0.f;
+            hipEventElapsedTime(&ms, e0, e1);
+            if (ms < best) best = ms;
+        }
+        if (!rc) *gbs = (float)(2.0 * (double)(n * sizeof(fib_v4f)) / (best * 1e-3) / 1e9);   // bytes read + written
+    } while (0);
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    if (a) hipFree(a);
+    if (b) hipFree(b);
+    return rc;
+}
