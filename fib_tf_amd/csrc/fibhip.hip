@@ -465,6 +465,7 @@ extern "C" int fibhip_step_mode(fibhip_t h, int mode)
     (void)fast;
     if (h->mod) {
         FLUSH(h);
+        CONFIRM(h);                                       // (the update is in place: it must not stand behind an unconfirmed launch)
         for (const Variant &v : h->mod->variants)
             if (v.kind == MK_POINTWISE && v.mode == mode && v.fast == (fast ? 1 : 0) && mode >= 1)
                 return run_pointwise_mode(h, launch_module, &v);
@@ -473,6 +474,7 @@ extern "C" int fibhip_step_mode(fibhip_t h, int mode)
 #ifdef FIB_CUSTOM_MODEL_INC
     if (h->d.model == FIBHIP_CUSTOM) {
         FLUSH(h);
+        CONFIRM(h);
         launch_fn fn = mode >= 1 ? (fast ? custom_mode_fn<Fast, 1>(mode) : custom_mode_fn<Exact, 1>(mode)) : nullptr;
         if (!fn) return fail(FIBHIP_EINVAL, "step_mode: the traced model has no mode %d", mode);
         return run_pointwise_mode(h, fn);
@@ -491,6 +493,7 @@ extern "C" int fibhip_step_mode(fibhip_t h, int mode)
             return rc;
         }
         FLUSH(h);
+        CONFIRM(h);
         if (h->use_agg) {                                 // 'slow' on the state as it stands; the aggregates follow it
             h->agg_dirty = false;
             return run_pointwise_mode(h, launch_pointwise<CourtAgg, Fast, CourtAgg::MODE_SLOW>);
@@ -671,6 +674,9 @@ extern "C" int fibhip_state_ptr(fibhip_t h, int var, void **dev_ptr)
 {
     if (!h || !dev_ptr || var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "state_ptr: bad argument");
     FLUSH(h);
+    // the pointer names the CURRENT slab: a launch that gave up is recovered first (recovery moves the state back to the other
+    // slab), and what the caller writes through the pointer must not be what a later recovery returns to or replays over
+    CONFIRM(h);
     // the caller may write the state through this pointer at any time, between any two calls: nothing may run ahead of it
     // any more (a launch started before the caller asked for its ticks would read the state before such a write, or race it)
     h->ahead.ok = false;
@@ -726,6 +732,7 @@ extern "C" int fibhip_trace_begin(fibhip_t h)
 {
     NEED(h);
     FLUSH(h);
+    CONFIRM(h);                                           // every traced tick is a plain launch: none behind an unconfirmed one
     if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "trace_begin inside an open tick");
     for (auto &r : h->trace) {
         if (r.e0) hipEventDestroy(r.e0);

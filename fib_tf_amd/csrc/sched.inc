@@ -23,9 +23,16 @@ static int recover(fibhip_ctx *h, unsigned id)
         h->dead = true;
         return fail(FIBHIP_EHIP, "%s", MT_DEAD_MSG);
     }
+    // the ticks the state had moved past are taken off the counters of fibhip_launch_stats here: the replay below counts them
+    // again, as the plain ticks they now are
     int lost = 0;
     for (size_t j = i; j < h->journal.recs.size(); ++j)
-        if (h->journal.recs[j].counted) lost += h->journal.recs[j].T;
+        if (h->journal.recs[j].counted) {
+            lost += h->journal.recs[j].T;
+            h->mt.n_launches--;
+        }
+    h->mt.n_ticks -= lost;
+    h->n_ticks -= lost;
     memcpy(h->cur, h->journal.recs[i].src, sizeof h->cur);
     h->journal.recs.clear();
     h->mt.max = 1;                                    // (mt_variant() is null from here on: no run-ahead, no series either)
@@ -68,6 +75,14 @@ static int sync_s0(fibhip_ctx *h)
 // Nothing but another multi-tick launch is ever queued behind a multi-tick launch that has not been confirmed: a launch that
 // gave up leaves the state it started from intact only as long as whatever follows it writes nothing — multi-tick launches find
 // the give-up word and leave; a plain tick, a pace, a host write would not.  So those wait for the stream first.
+// The entry points that confirm, each right behind its flush: fibhip_set_phase, fibhip_set_state, fibhip_set_consts,
+// fibhip_pace, fibhip_step_mode (every branch: a pointwise update is in place), fibhip_step_edges, fibhip_state_ptr (the
+// pointer must name the slab the state is in AFTER a recovery, and the caller writes through it), fibhip_trace_begin (every
+// traced tick is a plain launch) — and inside the scheduler tick_mt for a launch of one tick and fibhip_step in front of its
+// plain launches.  The entry points that only READ synchronise behind their copy (sync_s0) and take the copy again when a
+// recovery happened in between: fibhip_get_state, fibhip_get_state_direct (both branches of ahead_read_back hand the frame
+// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read; fibhip_observe_begin,
+// fibhip_electrode_begin and fibhip_electrode_end synchronise outright.
 static int confirm(fibhip_ctx *h)
 {
     return (h->mt.inflight && h->mt.epochs) ? sync_s0(h) : 0;
@@ -248,9 +263,13 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
 
 // A caller that never synchronises must not grow the journal without bound: every 256 multi-tick launches the stream is
 // drained once (20 us in 100 ms of work) and the launches so far are confirmed — or the first that gave up is found.
+// The give-up word names a launch by its 16-bit id, and recover() looks the id up in the journal: the journal never holds more
+// records than a cycle of ids has distinct values (ids - 1: the id the host's word names is skipped), or the id of the launch
+// that gave up could also be that of an older one that ended well (FIBHIP_MT_IDS shortens the cycle, for the tests).
 static int journal_bound(fibhip_ctx *h)
 {
-    if (h->journal.recs.size() < 256 || h->ahead.n > 0) return 0;
+    const size_t most = h->mt.ids - 1u < 256u ? (size_t)(h->mt.ids - 1u) : (size_t)256;
+    if (h->journal.recs.size() < most || h->ahead.n > 0) return 0;
     return sync_s0(h);
 }
 
@@ -496,6 +515,14 @@ static int ahead_read_back(fibhip_ctx *h, int var, float *dst, bool *delivered)
     h->series.fresh = false;
     if (!in_launch) {
         HIPCHK(wait_event(h->ahead.ev));
+        // as below: a launch in front of the copy that gave up has said so in the host's memory before the copy ended, and
+        // the frame is then one of a void slab — nothing of the launch just started counts, the state is restored and
+        // recomputed and the caller copies the frame the plain way
+        if (__atomic_load_n(h->mt.host_give_up(), __ATOMIC_ACQUIRE) != 0u) {
+            ahead_drop(h);
+            SYNC_S0(h);
+            return 0;
+        }
         *delivered = true;
         return 0;
     }
@@ -631,6 +658,9 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
             return 0;
         }
     }
+    // plain launches from here on: none behind an unconfirmed multi-tick launch.  (Nothing to launch: nothing to wait for — a
+    // call of no ticks beside a launch that runs ahead leaves that launch to the call that settles it, flush().)
+    if (h->pending + nticks > 0) CONFIRM(h);
     const int reserve = (h->fused_fn && !h->tracing) ? 1 : 0;
     // (multi_cap moves with the electrode recorder's tick counter: the bound is taken afresh for every launch)
     auto held = [&] { return ((multi_cap(h) > 1 && !h->tracing) ? multi_cap(h) - 1 : 0) + reserve; };
