@@ -420,7 +420,7 @@ struct Fenton {
     }
     // the same with ONE scalar left where the compiler puts it (an SGPR: its one use per cell and sub-step issues a little
     // slower): for the kernel that would otherwise exceed its register budget by exactly one — the multi-tick kernel under
-    // the rounding-faithful policy, which spilled a register to scratch memory (kernels.hpp strip_body)
+    // the rounding-faithful policy, which spilled a register to scratch memory (strip_kernel.inc strip_body)
     static FIB_DEV Consts pinned_spare(const Consts &k)
     {
         Consts c = k;
@@ -441,7 +441,7 @@ struct Fenton {
     }
 };
 
-// the same kinetics behind fenton_simple.py's zero-padded convolution Laplacian (kernels.hpp ZeroPadOf)
+// the same kinetics behind fenton_simple.py's zero-padded convolution Laplacian (stencil.hpp ZeroPadOf)
 struct FentonZP : Fenton {
     static constexpr bool ZEROPAD = true;
 };

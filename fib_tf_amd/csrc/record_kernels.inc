@@ -1,0 +1,154 @@
+// record_kernels.inc — the streaming kernels behind a committed tick: the activation recorder, the electrode recorder, and the
+// plain copy whose shape they take (the bandwidth yardstick).  (included by kernels.hpp; the host side is record.inc)
+
+// ---- activation recorder (fibhip_observe_begin): per-cell event maps, updated after every observed tick ----------------
+// Vp = the watched array at the end of the previous observed tick (the recorder's own plane), Vc = the array now.
+//   upstroke   Vp < up && Vc >= up:               t = t0 + ((up - Vp) / (Vc - Vp)) * tick;  prev = last; last = t;
+//                                                  first = t if count == 0;  count += 1
+//   downstroke Vp >= down && Vc < down, count > 0: t = t0 + ((Vp - down) / (Vp - Vc)) * tick; apd = t - last
+// float32, every operation rounded on its own (-ffp-contract=off, IEEE division); NaN compares false: no event.  With
+// down <= up the two cases exclude each other.  The maps are touched only where an event happens, so the steady traffic
+// is Vc read, Vp read and Vp written: 12 bytes per cell.
+struct ObsMaps {
+    float *first, *last, *prev, *apd;
+    int *count;
+};
+
+static FIB_DEV void observe_cell(float vp, float vc, size_t i, const ObsMaps &m, float up, float down, float t0, float tick)
+{
+    if (vp < up && vc >= up) {
+        const float t = t0 + ((up - vp) / (vc - vp)) * tick;
+        const int n = m.count[i];
+        m.prev[i] = m.last[i];
+        m.last[i] = t;
+        if (n == 0) m.first[i] = t;
+        m.count[i] = n + 1;
+    } else if (vp >= down && vc < down && m.count[i] > 0) {
+        const float t = t0 + ((vp - down) / (vp - vc)) * tick;
+        m.apd[i] = t - m.last[i];
+    }
+}
+
+// One element per thread and as many workgroups as that takes (the shape of copy_kernel below, the fastest streaming
+// shape measured; 512x512 = 256 workgroups, one per CU).  VEC: the watched array is contiguous (planar slab, pitch == W)
+// and 16-byte aligned — thread i < n/4 takes cells 4i .. 4i+3 with 16-byte loads and stores, the n % 4 threads after them
+// one cell each.  Otherwise (row-interleaved slab, or an unaligned array): one cell per thread, scalar.
+template <bool VEC>
+__global__ void __launch_bounds__(256) observe_kernel(Geo g, const float *__restrict__ pot, float *__restrict__ vprev, ObsMaps m,
+                                                      float up, float down, float t0, float tick)
+{
+    const size_t n = (size_t)g.H * g.W;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const size_t n4 = n / 4;
+        if (i < n4) {
+            const fib_v4f vc = reinterpret_cast<const fib_v4f *>(pot)[i];
+            const fib_v4f vp = reinterpret_cast<const fib_v4f *>(vprev)[i];
+            reinterpret_cast<fib_v4f *>(vprev)[i] = vc;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) observe_cell(vp[j], vc[j], 4 * i + j, m, up, down, t0, tick);
+        } else if (i < n4 + n % 4) {
+            const size_t e = 4 * n4 + (i - n4);
+            const float vc = pot[e], vp = vprev[e];
+            vprev[e] = vc;
+            observe_cell(vp, vc, e, m, up, down, t0, tick);
+        }
+    } else if (i < n) {
+        const size_t y = i / (size_t)g.W, x = i % (size_t)g.W;
+        const float vc = pot[y * (size_t)g.pitch + x], vp = vprev[i];
+        vprev[i] = vc;
+        observe_cell(vp, vc, i, m, up, down, t0, tick);
+    }
+}
+
+// ---- electrode recorder (fibhip_electrode_begin): weighted sums of one state array over small patches ------------------
+// One workgroup of EL_THREADS threads per CHUNK of a patch (the host cuts patches at attach: one chunk up to EL_CHUNK cells,
+// larger patches into at most 256 equal chunks).  Thread t takes the chunk's cells t, t + EL_THREADS, ... in that order
+// into ONE float32 accumulator (product rounded, then added: -ffp-contract=off), EL_BATCH cells' loads in flight at a
+// time: the kernel is latency-bound (the reference's two Gaussian electrodes are 2 x 10 201 cells), so what counts is the
+// number of dependent memory round trips — two at that size.  Then 6 levels of __shfl_down inside each wave, the 16 wave
+// sums through LDS, 4 more levels by wave 0, one plain store: no term passes through more than ceil(cells / 1024) + 10
+// additions, in an order fixed by the chunk table alone.  An electrode of one chunk stores straight into its trace slot;
+// an electrode of several stores one partial per chunk, which electrode_combine_kernel (a second launch on the same
+// stream, only enqueued when such an electrode exists) adds in a fixed 8-level tree: together within the
+// ceil(m / 256) + 16 of include/fibhip.h.  No floating-point atomics anywhere.
+#define EL_THREADS 1024
+#define EL_BATCH 8
+#define EL_CHUNK 16384
+struct ElChunk {
+    int r0, c0, pw;         // the patch's first row and column in the grid, and its width
+    unsigned first, count;  // this chunk's cells [first, first + count) of the patch, row-major
+    unsigned woff;          // float offset of the patch in the weights
+    int out;                // >= 0: electrode index (store into the sample's row); < 0: partial slot -1 - out
+};
+struct ElComb {
+    int e, part0, nparts;   // electrode, its first partial slot, its chunks (<= 256)
+};
+
+static FIB_DEV float el_wave_sum(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(EL_THREADS) electrode_kernel(const float *__restrict__ x, int pitch, const ElChunk *__restrict__ chunks,
+                                                               const float *__restrict__ weights, float *__restrict__ row,
+                                                               float *__restrict__ part)
+{
+    __shared__ float wsum[EL_THREADS / 64];
+    const ElChunk c = chunks[blockIdx.x];
+    const float *__restrict__ w = weights + c.woff;
+    const unsigned end = c.first + c.count;
+    float acc = 0.f;
+    for (unsigned p0 = c.first + threadIdx.x; p0 < end; p0 += EL_BATCH * EL_THREADS) {
+        float xv[EL_BATCH], wv[EL_BATCH];
+#pragma unroll
+        for (int j = 0; j < EL_BATCH; ++j) {
+            const unsigned p = p0 + (unsigned)j * EL_THREADS;
+            const bool in = p < end;
+            const unsigned q = in ? p : c.first;                       // (an in-range address; the term is dropped below)
+            const unsigned r = q / (unsigned)c.pw, col = q - r * (unsigned)c.pw;
+            xv[j] = x[(size_t)(c.r0 + (int)r) * (size_t)pitch + (size_t)(c.c0 + (int)col)];
+            wv[j] = w[q];
+        }
+#pragma unroll
+        for (int j = 0; j < EL_BATCH; ++j)
+            if (p0 + (unsigned)j * EL_THREADS < end) acc += wv[j] * xv[j];
+    }
+    acc = el_wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float v = threadIdx.x < EL_THREADS / 64 ? wsum[threadIdx.x] : 0.f;
+#pragma unroll
+        for (int off = EL_THREADS / 128; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (threadIdx.x == 0) {
+            if (c.out >= 0) row[c.out] = v;
+            else part[-1 - c.out] = v;
+        }
+    }
+}
+
+// one 256-thread workgroup per electrode of several chunks: its partials, one per thread, through the same tree
+__global__ void __launch_bounds__(256) electrode_combine_kernel(const ElComb *__restrict__ combs, const float *__restrict__ part,
+                                                                float *__restrict__ row)
+{
+    __shared__ float wsum[4];
+    const ElComb c = combs[blockIdx.x];
+    float v = (int)threadIdx.x < c.nparts ? part[c.part0 + threadIdx.x] : 0.f;
+    v = el_wave_sum(v);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) row[c.e] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// plain streaming copy, one 16-byte element per thread and as many workgroups as that takes: the bandwidth yardstick
+// bench.py prints next to the roofline peak.  (tools/ubench/copybw.hip -> profiles/r02_copy_bandwidth_shapes.txt: this
+// shape reaches the 6.3 TB/s the microarch guide quotes; grid-stride loops with non-temporal accesses stay at 4.6-5.7,
+// reads alone run at 7.0, writes alone at 4.4 TB/s)
+__global__ void __launch_bounds__(256) copy_kernel(const fib_v4f *__restrict__ src, fib_v4f *__restrict__ dst, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+}

@@ -90,7 +90,7 @@ static int confirm(fibhip_ctx *h)
 
 // ---- several ticks per launch (strip_mt_kernel) -----------------------------------------------------------------
 // The tile program of a tick loops over T ticks inside one launch and re-reads only the rim of its compute box from its
-// eight neighbours between two ticks (kernels.hpp, MtArgs).  That needs every tile resident at the same time: the plan
+// eight neighbours between two ticks (strip_mt.hpp: the protocol and MtArgs; strip_kernel.inc: strip_body).  That needs every tile resident at the same time: the plan
 // must be ONE strip launch per tick whose tiles number at most the device's compute units — and no second such launch
 // of this process on the device at the same time (two half-resident grids would wait for each other until both
 // give up), which g_mt below guarantees.

@@ -239,7 +239,7 @@ int fibhip_comm_exchange(fibhip_t h, int up_rank, int down_rank);
 int fibhip_comm_free(fibhip_t h);
 
 /* Run-time modules: a traced model (FIBHIP_CUSTOM) without a compiler on the box and without a library of its own.
- * The caller compiles the model's DEVICE code in-process (hiprtc: the generated `struct Custom` + csrc/kernels.hpp,
+ * The caller compiles the model's DEVICE code in-process (hiprtc: the generated `struct Custom` + csrc/kernels.hpp and the kernel files it includes,
  * one name expression per kernel below) and hands the code object over; the stock library loads it and drives its
  * kernels with the same host logic as the built-in models.  `fibhip_desc.module` then selects it at fibhip_create.  */
 typedef struct fibhip_module_kernel {

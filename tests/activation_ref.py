@@ -1,4 +1,4 @@
-"""NumPy restatement of the activation recorder (include/fibhip.h fibhip_observe_*, csrc/kernels.hpp observe_kernel):
+"""NumPy restatement of the activation recorder (include/fibhip.h fibhip_observe_*, csrc/record_kernels.inc observe_kernel):
 feed it the watched array after every tick and it keeps the same five maps, bit for bit."""
 import numpy as np
 

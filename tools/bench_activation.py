@@ -1,4 +1,4 @@
-"""cost of the activation recorder (fib_tf_amd/activation.py, csrc/kernels.hpp observe_kernel):
+"""cost of the activation recorder (fib_tf_amd/activation.py, csrc/record_kernels.inc observe_kernel):
 
     python tools/bench_activation.py [--ticks K] [--configs fenton512,br512,fenton4096] [--out FILE]
 

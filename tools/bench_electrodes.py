@@ -1,4 +1,4 @@
-"""cost of the electrode recorder (fib_tf_amd/egm.py, csrc/kernels.hpp electrode_kernel) against polling:
+"""cost of the electrode recorder (fib_tf_amd/egm.py, csrc/record_kernels.inc electrode_kernel) against polling:
 
     python tools/bench_electrodes.py [--ticks K] [--configs fenton512,br512,fenton4096] [--strides 1,2,10] [--out FILE]
 
