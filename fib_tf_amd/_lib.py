@@ -172,6 +172,10 @@ SYMBOLS = {
     'fibhip_electrode_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_electrode_read': ([_h, C.c_longlong, C.c_longlong, _fp], C.c_int),
     'fibhip_electrode_end': ([_h], C.c_int),
+    'fibhip_tips_begin': ([_h, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_longlong], C.c_int),
+    'fibhip_tips_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_tips_read': ([_h, C.c_longlong, C.c_longlong, _ip, _ip], C.c_int),
+    'fibhip_tips_end': ([_h], C.c_int),
     'fibhip_last_error': ([], C.c_char_p),
 }
 
@@ -710,3 +714,41 @@ class Stepper:
 
     def electrode_end(self):
         self._ck(self._L.fibhip_electrode_end(self._h))
+
+    # ---- tip recorder (include/fibhip.h fibhip_tips_*) ------------------------------------------------------------
+    def tips_begin(self, var, var2, a0, b0, mask=None, every=1, max_tips=256, capacity=1):
+        """attaches (or re-attaches, with empty lists) the tip recorder on arrays `var`, `var2` with the levels `a0`, `b0`;
+        `mask`: [height, width], non-zero where a cell counts, or None; one sample every `every` ticks, `capacity` samples of
+        up to `max_tips` tips at the most"""
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.shape != (self.height, self.width):
+                raise ValueError('tips_begin: a mask of shape %s on a %d x %d grid' % (mask.shape, self.height, self.width))
+            mp = mask.ctypes.data_as(C.POINTER(C.c_ubyte))
+        self._ck(self._L.fibhip_tips_begin(self._h, int(var), int(var2), float(a0), float(b0), mp, int(every), int(max_tips),
+                                           int(capacity)))
+        self._tip_max = int(max_tips)
+
+    def tips_count(self):
+        """samples taken since tips_begin (ticks accepted but not launched yet included)"""
+        k = C.c_longlong()
+        self._ck(self._L.fibhip_tips_count(self._h, C.byref(k)))
+        return int(k.value)
+
+    def tips_read(self, first=0, count=None, records=True):
+        """samples [first, first + count) (count=None: all taken so far) as (counts, records): counts int32 [count, 3] =
+        n_pos, n_neg, stored; records int32 [count, max_tips, 4] = row, column, charge, 0, of which the first
+        min(stored, max_tips) of each sample are valid, in no fixed order (records=False: None).  Blocks like get_state,
+        detaches nothing"""
+        if count is None:
+            count = self.tips_count() - int(first)
+        n = max(int(count), 0)
+        counts = np.zeros((n, 3), np.int32)
+        recs = np.zeros((n, getattr(self, '_tip_max', 0), 4), np.int32) if records else None
+        self._ck(self._L.fibhip_tips_read(self._h, int(first), int(count), counts.ctypes.data_as(_ip),
+                                          recs.ctypes.data_as(_ip) if records else None))
+        return counts, recs
+
+    def tips_end(self):
+        self._ck(self._L.fibhip_tips_end(self._h))

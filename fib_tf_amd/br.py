@@ -61,6 +61,11 @@ def specialised_library(table32, build=True, verbose=False):
 class BeelerReuter(IonicModel):
     MODEL_ID = _lib.BR
     VAR_NAMES = ('V', 'C', 'M', 'H', 'J', 'D', 'F', 'XI')
+    # record_tips() defaults (var, var2, a0, b0): the potential V against the x1 gate XI, whose loop is the most open
+    # (normalised area 0.87; J 0.75, H 0.65, F 0.61).  From the parity oracle on the CPU, the 64 x 64 golden protocol
+    # (tests/golden/br_traj64_cheby: diff 0.809, hole (20, 30, 6), Chebyshev table, S1 only), cell (row 48, column 32) over
+    # 900 ticks: V in [-84.5044022, 10.8969154] mV, XI in [0.000109970199, 0.227818787]; each level is the midpoint.
+    tip_signals = (0, 7, -36.8037434, 0.113964379)
 
     def __init__(self, props):
         super().__init__(props)

@@ -30,6 +30,12 @@ class _Trend:
 class Courtemanche(IonicModel):
     MODEL_ID = _lib.COURT
     VAR_NAMES = tuple(n for n, _ in INITIAL)
+    # record_tips() defaults (var, var2, a0, b0): the potential V against the sodium inactivation gate _j_ (array 4, one of
+    # the arrays 'slow' assigns), whose loop is among the most open (normalised area 0.73, with _ui_, whose swing is 0.003;
+    # _xr_ 0.63).  From the parity oracle on the CPU, the 64 x 64 golden protocol (tests/golden/court_traj64: diff 0.809, hole
+    # (32, 32, 6), 'slow' every 10 ticks, S1 only), cell (row 16, column 32) over 5000 ticks: V in [-81.1813965, 7.47356892]
+    # mV, _j_ in [9.99999975e-06, 0.977499485]; each level is the midpoint.
+    tip_signals = (0, 4, -36.85391379, 0.488754743)
 
     def __init__(self, props):
         super().__init__(props)

@@ -26,6 +26,12 @@ class _InterVar:
 
 
 class Courtemanche(_Courtemanche):
+    # record_tips() defaults (var, var2, a0, b0), as in court.py: V against _j_ (normalised loop area 0.79; _xr_ 0.57).  From
+    # the parity oracle on the CPU, this variant's golden protocol (tests/golden/court_ultra_traj: 48 x 56, diff 1.5, holes
+    # (28, 24, 5) and (28, 24, 22, neg), single rate, S1 only), cell (row 24, column 12) over 5000 ticks: V in
+    # [-80.0922318, 39.8651848] mV, _j_ in [9.99999975e-06, 0.969333589]; each level is the midpoint.
+    tip_signals = (0, 4, -20.1135235, 0.484671795)
+
     def __init__(self, props):
         super().__init__(props)
         self.ultra_slow = bool(getattr(self, 'ultra_slow', False))

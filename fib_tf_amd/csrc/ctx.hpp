@@ -102,7 +102,7 @@ struct ObsRec {
     float *buf;             // 6 planes of `cells` (W-pitched): Vp | first_up | last_up | prev_up | apd | count (int32)
     long long k;            // observed ticks since the recorder was attached
 };
-// electrode recorder (fibhip_electrode_begin): while `on`, no launch spans a sample tick (el_room) and the hooks on the
+// electrode recorder (fibhip_electrode_begin): while `on`, no launch spans a sample tick (sample_room) and the hooks on the
 // plain and the multi-tick commit path (electrode_advance) enqueue electrode_kernel behind the launch that ends one
 struct ElRec {
     bool on;
@@ -115,6 +115,18 @@ struct ElRec {
     float *w;               // device: the weight patches, back to back
     float *part;            // device: one partial per chunk of such electrodes
     float *trace;           // device: [cap][n]
+};
+// tip recorder (fibhip_tips_begin): a sampler like the electrode recorder — no launch spans a sample tick (sample_room), and
+// the hook on the plain and the multi-tick commit path (tips_advance) enqueues tip_kernel behind the launch that ends one
+struct TipRec {
+    bool on;
+    int var, var2, every, max_tips;
+    float a0, b0;
+    long long cap;          // samples the lists hold
+    long long k;            // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
+    unsigned char *mask;    // device: [H][W], or null (every plaquette counts)
+    int *counts;            // device: [cap][3] = n_pos, n_neg, stored
+    int *records;           // device: [cap][max_tips][4] = row, col, charge, 0
 };
 
 // fibhip_trace_begin / _end: the launches in between, each between two HIP events
@@ -174,6 +186,7 @@ struct fibhip_ctx {
     // ---- the recorders (record.inc) ----
     ObsRec obs;
     ElRec el;
+    TipRec tip;
     std::vector<TraceRec> trace;
     bool tracing;
     // ---- the rest ----

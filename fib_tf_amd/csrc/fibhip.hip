@@ -31,7 +31,7 @@ using namespace fib;
 #include "ctx.hpp"          // fibhip_ctx and its parts, NEED / FLUSH / CONFIRM / SYNC_S0, the timeline
 #include "tick.inc"         // one tick: pointer tables, rows, edges / interior / commit
 #include "sched.inc"        // when ticks are launched: deferral, multi-tick launches, run-ahead, journal and recovery, fibhip_step
-#include "record.inc"       // activation and electrode recorders
+#include "record.inc"       // activation, electrode and tip recorders
 #include "plan.inc"         // build_plan, autotune
 #include "comm.inc"         // the RCCL halo path and fibhip_halo_plan
 // this file: create / destroy, state get / set, pointwise modes, pace / probe / sync / timing, run-time modules, accessors and
@@ -294,6 +294,7 @@ extern "C" int fibhip_destroy(fibhip_t h)
     if (h->agg) hipFree(h->agg);
     if (h->obs.buf) hipFree(h->obs.buf);
     electrode_free(h);
+    tips_free(h);
     if (h->mt.xbuf) hipFree(h->mt.xbuf);
     if (h->mt.epochs) hipFree(h->mt.epochs);
     for (auto &r : h->trace) {
@@ -483,7 +484,7 @@ extern "C" int fibhip_step_mode(fibhip_t h, int mode)
 #if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
     if (h->d.model == FIBHIP_COURT && mode == Courtemanche::MODE_SLOW) {
         if (h->d.flags & FIBHIP_ALLVARS) return fail(FIBHIP_EINVAL, "step_slow: handle was created with FIBHIP_ALLVARS");
-        if (h->pending && h->fused_fn && !el_slow_sample_due(h)) {   // the last deferred tick + slow as one launch
+        if (h->pending && h->fused_fn && !slow_sample_due(h)) {   // the last deferred tick + slow as one launch
             if (int rc = launch_pending(h, h->pending - 1)) return rc;
             h->pending = 0;
             const launch_fn plain = h->plan[0].fn;

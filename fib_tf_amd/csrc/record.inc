@@ -1,5 +1,5 @@
-// record.inc — the two recorders that run on the device while a model runs: the per-cell activation maps
-// (fibhip_observe_*) and the electrode traces (fibhip_electrode_*).  Each is a hook behind a committed launch plus its entry
+// record.inc — the three recorders that run on the device while a model runs: the per-cell activation maps
+// (fibhip_observe_*), the electrode traces (fibhip_electrode_*) and the spiral-tip lists (fibhip_tips_*).  Each is a hook behind a committed launch plus its entry
 // points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
 // (included by fibhip.hip, behind sched.inc)
 
@@ -34,7 +34,7 @@ static int observe_enqueue(fibhip_ctx *h)
 }
 
 // The electrode recorder's hook behind a launch of `ticks` ticks (plain: commit_impl; multi-tick: mt_launch).  No launch
-// spans a sample tick (el_room), so a sample is due exactly when the counter lands on a multiple of `every`; it is enqueued
+// spans a sample tick (sample_room), so a sample is due exactly when the counter lands on a multiple of `every`; it is enqueued
 // on s0 behind that launch and reads the state the handle has just moved to.  The slot is a kernel argument computed from the
 // host's counter, never a pointer kept on the device: a replay (recover()) writes the same slots again.
 static int electrode_advance(fibhip_ctx *h, int ticks)
@@ -72,6 +72,46 @@ static void electrode_free(fibhip_ctx *h)
     h->el.comb = nullptr;
     h->el.w = h->el.part = h->el.trace = nullptr;
     h->el.on = false;
+}
+
+// The tip recorder's hook, the electrode recorder's step for step: at a sample tick the sample's three counters are zeroed and
+// tip_kernel is enqueued behind them on s0.  Slot and counters are addressed from the host's counter, so a replay zeroes and
+// fills the same slot again; records beyond `stored` are never looked at, so the list itself is not cleared.
+static int tips_advance(fibhip_ctx *h, int ticks)
+{
+    h->tip.k += ticks;
+    if (h->tip.k % h->tip.every) return 0;
+    const long long s = h->tip.k / h->tip.every - 1;
+    if (s >= h->tip.cap) return fail(FIBHIP_EINVAL, "tip recorder: trace full");               // (fibhip_step refuses before this)
+    const float *a = h->slab[h->cur[h->tip.var]] + (size_t)h->tip.var * h->vstride;
+    const float *b = h->slab[h->cur[h->tip.var2]] + (size_t)h->tip.var2 * h->vstride;
+    int *cnt = h->tip.counts + 3 * (size_t)s;
+    int4 *rec = reinterpret_cast<int4 *>(h->tip.records) + (size_t)s * (size_t)h->tip.max_tips;
+    const Geo g = base_geo(h);
+    const bool vec = h->pitch == g.W && g.W % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
+    const size_t threads = (size_t)(g.H - 1) * (size_t)(vec ? g.W / 4 : g.W - 1);
+    HIPCHK(hipMemsetAsync(cnt, 0, 3 * sizeof(int), h->s0));
+    if (int rc = trace_open(h, h->s0, "tip_kernel", 0, 0, 0, 0, 1)) return rc;
+    if (vec)
+        hipLaunchKernelGGL(tip_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->s0, g, a, b, h->tip.a0, h->tip.b0,
+                           h->tip.mask, cnt, rec, h->tip.max_tips);
+    else
+        hipLaunchKernelGGL(tip_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->s0, g, a, b, h->tip.a0, h->tip.b0,
+                           h->tip.mask, cnt, rec, h->tip.max_tips);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    return 0;
+}
+
+static void tips_free(fibhip_ctx *h)
+{
+    if (h->tip.mask) hipFree(h->tip.mask);
+    if (h->tip.counts) hipFree(h->tip.counts);
+    if (h->tip.records) hipFree(h->tip.records);
+    h->tip.mask = nullptr;
+    h->tip.counts = h->tip.records = nullptr;
+    h->tip.on = false;
 }
 
 // ---- activation recorder ------------------------------------------------------------------------------------------------
@@ -251,5 +291,92 @@ extern "C" int fibhip_electrode_end(fibhip_t h)
     FLUSH(h);                                          // the ticks accepted while attached are sampled
     SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
     electrode_free(h);
+    return 0;
+}
+
+// ---- tip recorder -------------------------------------------------------------------------------------------------------
+extern "C" int fibhip_tips_begin(fibhip_t h, int var, int var2, float a0, float b0, const unsigned char *mask, int every, int max_tips,
+                                 long long capacity)
+{
+    NEED(h);
+    if (var < 0 || var >= h->nvar || var2 < 0 || var2 >= h->nvar) return fail(FIBHIP_EINVAL, "tips_begin: bad var %d / %d", var, var2);
+    if (var == var2) return fail(FIBHIP_EINVAL, "tips_begin: the two watched arrays must differ (got %d twice)", var);
+    if (std::isnan(a0) || std::isnan(b0)) return fail(FIBHIP_EINVAL, "tips_begin: the levels must be numbers");
+    if (every < 1) return fail(FIBHIP_EINVAL, "tips_begin: every must be >= 1 (got %d)", every);
+    if (max_tips < 1 || max_tips > FIBHIP_MAX_TIPS) return fail(FIBHIP_EINVAL, "tips_begin: 1 .. %d tips per sample (got %d)", FIBHIP_MAX_TIPS, max_tips);
+    if (capacity < 1 || capacity > (long long)(SIZE_MAX / (4 * sizeof(int)) / (size_t)max_tips))
+        return fail(FIBHIP_EINVAL, "tips_begin: bad capacity %lld", capacity);
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "tips_begin: not on a row block (a handle with ghost rows)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "tips_begin inside an open tick");
+    if (h->d.height < 2 || h->d.width < 2) return fail(FIBHIP_EINVAL, "tips_begin: a %d x %d grid has no plaquette", h->d.height, h->d.width);
+    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    tips_free(h);
+    bool ok = hipMalloc((void **)&h->tip.counts, (size_t)capacity * 3 * sizeof(int)) == hipSuccess &&
+              hipMalloc((void **)&h->tip.records, (size_t)capacity * (size_t)max_tips * 4 * sizeof(int)) == hipSuccess;
+    if (ok && mask) ok = hipMalloc((void **)&h->tip.mask, h->cells) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        tips_free(h);
+        return fail(FIBHIP_ENOMEM, "tips_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d tips)", capacity, max_tips);
+    }
+    if (mask) HIPCHK(hipMemcpyAsync(h->tip.mask, mask, h->cells, hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemsetAsync(h->tip.counts, 0, (size_t)capacity * 3 * sizeof(int), h->s0));
+    HIPCHK(wait_stream(h->s0));                        // the caller's mask is free again
+    h->tip.on = true;
+    h->tip.var = var;
+    h->tip.var2 = var2;
+    h->tip.a0 = a0;
+    h->tip.b0 = b0;
+    h->tip.every = every;
+    h->tip.max_tips = max_tips;
+    h->tip.cap = capacity;
+    h->tip.k = 0;
+    return 0;
+}
+
+extern "C" int fibhip_tips_count(fibhip_t h, long long *samples)
+{
+    NEED(h);
+    if (!samples) return fail(FIBHIP_EINVAL, "tips_count: null argument");
+    if (!h->tip.on) return fail(FIBHIP_EINVAL, "tips_count: no recorder attached (fibhip_tips_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    *samples = (h->tip.k + h->pending) / h->tip.every; // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+
+extern "C" int fibhip_tips_read(fibhip_t h, long long first, long long count, int *counts, int *records)
+{
+    NEED(h);
+    if (!h->tip.on) return fail(FIBHIP_EINVAL, "tips_read: no recorder attached (fibhip_tips_begin)");
+    FLUSH(h);
+    const long long taken = h->tip.k / h->tip.every;
+    if (first < 0 || count < 0 || first + count > taken)
+        return fail(FIBHIP_EINVAL, "tips_read: samples [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (count > 0 && !counts) return fail(FIBHIP_EINVAL, "tips_read: null destination");
+    const size_t per = (size_t)h->tip.max_tips * 4;
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->journal.n_fallbacks;
+        if (count > 0) {
+            HIPCHK(hipMemcpyAsync(counts, h->tip.counts + 3 * (size_t)first, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost, h->s0));
+            if (records)
+                HIPCHK(hipMemcpyAsync(records, h->tip.records + (size_t)first * per, (size_t)count * per * sizeof(int), hipMemcpyDeviceToHost,
+                                      h->s0));
+        }
+        SYNC_S0(h);
+        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and re-sampled, copy again)
+    }
+    return 0;
+}
+
+extern "C" int fibhip_tips_end(fibhip_t h)
+{
+    NEED(h);
+    if (!h->tip.on) return 0;
+    FLUSH(h);                                          // the ticks accepted while attached are sampled
+    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
+    tips_free(h);
     return 0;
 }

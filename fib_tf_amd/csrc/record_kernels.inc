@@ -143,6 +143,126 @@ __global__ void __launch_bounds__(256) electrode_combine_kernel(const ElComb *__
     if (threadIdx.x == 0) row[c.e] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
+// ---- tip recorder (fibhip_tips_begin): the phase singularities of (A - a0, B - b0), compacted ---------------------------
+// A plaquette (i, j) has the corners (i,j) -> (i,j+1) -> (i+1,j+1) -> (i+1,j) -> (i,j); a = A - a0 and b = B - b0 are float32
+// subtractions.  An edge (a1,b1) -> (a2,b2) crosses the positive a half-axis upwards when b1 < 0 <= b2 and
+// cross = a1 b2 - a2 b1 > 0, downwards when b2 < 0 <= b1 and cross < 0.  Both products of two float32 numbers are exact in
+// double (48 bits), so the rounded difference has the exact sign, fused or not.  NaN compares false: no crossing.  The charge
+// of the plaquette is the number of upward minus the number of downward crossings, in {-1, 0, +1}.
+static FIB_DEV int tip_edge(float a1, float b1, float a2, float b2)
+{
+    const double cross = (double)a1 * (double)b2 - (double)a2 * (double)b1;
+    int w = 0;
+    if (b1 < 0.f && b2 >= 0.f && cross > 0.0) w = 1;
+    if (b2 < 0.f && b1 >= 0.f && cross < 0.0) w = -1;
+    return w;
+}
+// corners in the order above: 0 = (i,j), 1 = (i,j+1), 2 = (i+1,j+1), 3 = (i+1,j)
+static FIB_DEV int tip_charge(const float a[4], const float b[4])
+{
+    return tip_edge(a[0], b[0], a[1], b[1]) + tip_edge(a[1], b[1], a[2], b[2]) + tip_edge(a[2], b[2], a[3], b[3]) +
+           tip_edge(a[3], b[3], a[0], b[0]);
+}
+
+// One sample's output: cnt = {n_pos, n_neg, stored} (zeroed by the host in front of the launch), rec = [max_tips] records of
+// {row, col, charge, 0}.  Tips are rare, so each WAVE compacts its hits: a ballot per plaquette slot, one integer atomicAdd of
+// the wave's hit count on `stored` by lane 0 (which returns the wave's base), and every hit lane stores its record at
+// base + its rank among the wave's hits while that is below max_tips.  n_pos and n_neg are added the same way, one atomic per
+// wave that has such hits, and so stay exact when the list is cut.  The order of the records is the order of arrival.
+// NP plaquettes per thread (w[p] = 0: none there).  Every lane of the wave must come here (no early return in front).
+template <int NP>
+static FIB_DEV void tip_emit(const int (&w)[NP], int row, const int (&col)[NP], int *__restrict__ cnt, int4 *__restrict__ rec, int max_tips)
+{
+    unsigned long long hit[NP];
+    int total = 0, pos = 0;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        hit[p] = __ballot(w[p] != 0);
+        total += __popcll(hit[p]);
+        pos += __popcll(__ballot(w[p] > 0));
+    }
+    if (total == 0) return;                                   // (wave-uniform)
+    const int lane = (int)(threadIdx.x & 63u);
+    int base = 0;
+    if (lane == 0) {
+        base = atomicAdd(&cnt[2], total);
+        if (pos) atomicAdd(&cnt[0], pos);
+        if (total - pos) atomicAdd(&cnt[1], total - pos);
+    }
+    base = __shfl(base, 0, 64);
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int at = base + __popcll(hit[p] & below);
+        if (w[p] != 0 && at < max_tips) rec[at] = make_int4(row, col[p], w[p], 0);
+        base += __popcll(hit[p]);
+    }
+}
+
+// One pass over the plaquettes, in the shape of copy_kernel: as many 256-thread workgroups as it takes, nothing in LDS.
+// VEC (planar slab, pitch == W, W a multiple of 4, both arrays 16-byte aligned): a thread takes the four plaquettes whose
+// upper-left cells are (i, 4g .. 4g+3): one 16-byte load per array and row plus the cell to their right (the last group of a
+// row has none and three plaquettes), the mask as one 32-bit load and one byte per row.  Otherwise (row-interleaved slab, or
+// a width that leaves rows unaligned): one plaquette per thread, scalar.  Row i + 1 is loaded again by the thread of the
+// plaquette below: that thread is in the same or the next workgroup, so the second read comes from the cache.
+template <bool VEC>
+__global__ void __launch_bounds__(256) tip_kernel(Geo g, const float *__restrict__ A, const float *__restrict__ B, float a0, float b0,
+                                                  const unsigned char *__restrict__ mask, int *__restrict__ cnt, int4 *__restrict__ rec,
+                                                  int max_tips)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t pitch = (size_t)g.pitch;
+    if (VEC) {
+        const size_t w4 = (size_t)g.W / 4;
+        const size_t i = t / w4, c = 4 * (t % w4);
+        int w[4] = {0, 0, 0, 0};
+        const int col[4] = {(int)c, (int)c + 1, (int)c + 2, (int)c + 3};
+        if (i + 1 < (size_t)g.H) {
+            const bool last = c + 4 >= (size_t)g.W;                   // no cell to the right: three plaquettes
+            const size_t up = i * pitch + c, dn = up + pitch;
+            float a[2][5], b[2][5];
+            bool in[2][5];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const size_t at = r ? dn : up;
+                const fib_v4f va = *reinterpret_cast<const fib_v4f *>(A + at), vb = *reinterpret_cast<const fib_v4f *>(B + at);
+                const unsigned m = mask ? *reinterpret_cast<const unsigned *>(mask + (i + r) * (size_t)g.W + c) : 0x01010101u;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    a[r][j] = va[j] - a0;
+                    b[r][j] = vb[j] - b0;
+                    in[r][j] = ((m >> (8 * j)) & 0xFFu) != 0;
+                }
+                a[r][4] = last ? 0.f : A[at + 4] - a0;
+                b[r][4] = last ? 0.f : B[at + 4] - b0;
+                in[r][4] = !last && (!mask || mask[(i + r) * (size_t)g.W + c + 4] != 0);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float pa[4] = {a[0][j], a[0][j + 1], a[1][j + 1], a[1][j]};
+                const float pb[4] = {b[0][j], b[0][j + 1], b[1][j + 1], b[1][j]};
+                if (in[0][j] && in[0][j + 1] && in[1][j + 1] && in[1][j]) w[j] = tip_charge(pa, pb);
+            }
+        }
+        tip_emit<4>(w, (int)i, col, cnt, rec, max_tips);
+    } else {
+        const size_t wp = (size_t)g.W - 1;                            // plaquettes per row
+        const size_t i = t / wp, c = t % wp;
+        int w[1] = {0};
+        const int col[1] = {(int)c};
+        if (i + 1 < (size_t)g.H) {
+            const size_t up = i * pitch + c, dn = up + pitch;
+            const size_t mu = i * (size_t)g.W + c, md = mu + (size_t)g.W;
+            if (!mask || (mask[mu] && mask[mu + 1] && mask[md + 1] && mask[md])) {
+                const float pa[4] = {A[up] - a0, A[up + 1] - a0, A[dn + 1] - a0, A[dn] - a0};
+                const float pb[4] = {B[up] - b0, B[up + 1] - b0, B[dn + 1] - b0, B[dn] - b0};
+                w[0] = tip_charge(pa, pb);
+            }
+        }
+        tip_emit<1>(w, (int)i, col, cnt, rec, max_tips);
+    }
+}
+
 // plain streaming copy, one 16-byte element per thread and as many workgroups as that takes: the bandwidth yardstick
 // bench.py prints next to the roofline peak.  (tools/ubench/copybw.hip -> profiles/r02_copy_bandwidth_shapes.txt: this
 // shape reaches the 6.3 TB/s the microarch guide quotes; grid-stride loops with non-temporal accesses stay at 4.6-5.7,

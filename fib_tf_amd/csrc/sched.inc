@@ -44,8 +44,10 @@ static int recover(fibhip_ctx *h, unsigned id)
     h->journal.n_replayed += lost;
     // the samples queued behind the lost launches were taken from a void slab: the replay below (tick_now -> commit_impl)
     // takes them again, into the same slots — the slot is the host's tick counter, so that counter goes back first.  (Every
-    // journal record is younger than the recorder: electrode_begin confirms, and so empties the journal, before it attaches.)
+    // journal record is younger than the recorder: electrode_begin and tips_begin confirm, and so empty the journal, before
+    // they attach.)
     if (h->el.on) h->el.k -= lost;
+    if (h->tip.on) h->tip.k -= lost;
     h->journal.recovering = true;
     int rc = 0;
     for (int t = 0; t < lost && rc == 0; ++t) rc = tick_now(h);
@@ -81,8 +83,8 @@ static int sync_s0(fibhip_ctx *h)
 // traced tick is a plain launch) — and inside the scheduler tick_mt for a launch of one tick and fibhip_step in front of its
 // plain launches.  The entry points that only READ synchronise behind their copy (sync_s0) and take the copy again when a
 // recovery happened in between: fibhip_get_state, fibhip_get_state_direct (both branches of ahead_read_back hand the frame
-// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read; fibhip_observe_begin,
-// fibhip_electrode_begin and fibhip_electrode_end synchronise outright.
+// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read; fibhip_observe_begin,
+// fibhip_electrode_begin / _end and fibhip_tips_begin / _end synchronise outright.
 static int confirm(fibhip_ctx *h)
 {
     return (h->mt.inflight && h->mt.epochs) ? sync_s0(h) : 0;
@@ -135,29 +137,43 @@ static const Variant *mt_variant(const fibhip_ctx *h)
 // Every constraint an attached recorder (record.inc) puts on the launches is stated HERE and nowhere else:
 //  * activation recorder (h->obs.on): it observes every tick through commit_impl, so nothing fuses ticks — no multi-tick
 //    launches (mt_variant, above, is null: hence no run-ahead and no launched series either), one tick per plain launch (multi_cap);
-//  * electrode recorder (h->el.on): no launch spans a sample tick (el_room bounds next_launch_ticks and multi_cap); nothing runs
-//    ahead (may_run_ahead: a launch that runs ahead is handed out tick by tick and may be stopped or recomputed, so a sample
-//    cannot be queued behind it, DESIGN.md section 11); a sample of a SLOW Courtemanche array is taken before 'slow' rides on
-//    its tick (el_slow_sample_due).
-// ticks up to and including the next sample tick of the electrode recorder: no launch may span one (INT_MAX: none attached)
-static inline int el_room(const fibhip_ctx *h) { return h->el.on ? h->el.every - (int)(h->el.k % h->el.every) : INT_MAX; }
+//  * the samplers — electrode recorder (h->el.on) and tip recorder (h->tip.on), each with a stride of its own: no launch
+//    spans a sample tick of either (sample_room, the minimum over the attached ones, bounds next_launch_ticks and multi_cap);
+//    nothing runs ahead (may_run_ahead: a launch that runs ahead is handed out tick by tick and may be stopped or recomputed,
+//    so a sample cannot be queued behind it, DESIGN.md section 11); a sample of a SLOW Courtemanche array is taken before
+//    'slow' rides on its tick (slow_sample_due).
+static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on; }
+// ticks up to and including the next sample tick of one sampler (INT_MAX: not attached)
+static inline int room_of(bool on, int every, long long k) { return on ? every - (int)(k % every) : INT_MAX; }
+// ... and of any attached sampler: no launch may span one
+static inline int sample_room(const fibhip_ctx *h)
+{
+    return imin(room_of(h->el.on, h->el.every, h->el.k), room_of(h->tip.on, h->tip.every, h->tip.k));
+}
 // consecutive ticks one plain launch may fuse (Courtemanche on aggregates: up to multi_max; one while an activation recorder
-// is attached; never across a sample tick of the electrode recorder)
-static inline int multi_cap(const fibhip_ctx *h) { return h->obs.on ? 1 : imin(h->multi_max, el_room(h)); }
+// is attached; never across a sample tick)
+static inline int multi_cap(const fibhip_ctx *h) { return h->obs.on ? 1 : imin(h->multi_max, sample_room(h)); }
 // ticks of the next multi-tick launch when `waiting` ticks wait for it
-static inline int next_launch_ticks(const fibhip_ctx *h, int waiting) { return imin(imin(waiting, h->mt.max), el_room(h)); }
+static inline int next_launch_ticks(const fibhip_ctx *h, int waiting) { return imin(imin(waiting, h->mt.max), sample_room(h)); }
 // the last pending tick ends on a sample of an array 'slow' assigns: the sample must see it before 'slow', which belongs to the
 // next tick — the two are not fused then (fibhip_step_mode)
-static inline bool el_slow_sample_due(const fibhip_ctx *h)
+static inline bool slow_sample_due(const fibhip_ctx *h)
 {
 #if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
-    return h->el.on && (h->el.k + h->pending) % h->el.every == 0 && !((Courtemanche::FAST_MASK >> h->el.var) & 1u);
+    auto slow = [](int var) { return !((Courtemanche::FAST_MASK >> var) & 1u); };
+    if (h->el.on && (h->el.k + h->pending) % h->el.every == 0 && slow(h->el.var)) return true;
+    return h->tip.on && (h->tip.k + h->pending) % h->tip.every == 0 && (slow(h->tip.var) || slow(h->tip.var2));
 #else
     return false;
 #endif
 }
-// the trace holds the samples of `more` further ticks (pending ones included)
-static inline bool el_has_room(const fibhip_ctx *h, int more) { return !h->el.on || (h->el.k + more) / h->el.every <= h->el.cap; }
+// the sampler that has no slot left for the samples of `more` further ticks (pending ones included), or null
+static inline const char *sampler_full(const fibhip_ctx *h, int more)
+{
+    if (h->el.on && (h->el.k + more) / h->el.every > h->el.cap) return "electrode";
+    if (h->tip.on && (h->tip.k + more) / h->tip.every > h->tip.cap) return "tip";
+    return nullptr;
+}
 
 static struct {
     std::mutex mu;
@@ -257,7 +273,9 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
     if (commit) memcpy(h->cur, nxt, sizeof nxt);
     if (nxt_out) memcpy(nxt_out, nxt, sizeof nxt);
     // (the sample reads the state and writes the recorder's own buffers only: it may stand behind this unconfirmed launch)
-    if (commit && h->el.on) return electrode_advance(h, T);
+    if (commit && h->el.on)
+        if (int rc = electrode_advance(h, T)) return rc;
+    if (commit && h->tip.on) return tips_advance(h, T);
     return 0;
 }
 
@@ -344,9 +362,9 @@ static bool may_run_ahead(const fibhip_ctx *h, int L, bool repeats, AheadFrom fr
 {
     // the series is worth a launch of its own and fits one (this implies mt.max > 1)
     if (L < 2 || L > h->mt.max) return false;
-    // nothing forbids it: the switch and the caller's access to the state (Ahead::ok), no launch ahead already, no electrode
-    // recorder (see "what the recorders ask of the scheduler"), no timeline being taken (every launch there is the caller's own)
-    if (!h->ahead.ok || h->ahead.n != 0 || h->el.on || h->tracing) return false;
+    // nothing forbids it: the switch and the caller's access to the state (Ahead::ok), no launch ahead already, no sampler
+    // (see "what the recorders ask of the scheduler"), no timeline being taken (every launch there is the caller's own)
+    if (!h->ahead.ok || h->ahead.n != 0 || sampling(h) || h->tracing) return false;
     // the launch is the one the handle would make anyway: its plan is chosen (`tuned`, which is only ever set behind
     // check_ready — so has_consts holds with it and is stated for the reader, not tested twice), the slab is planar.
     // Nothing accepted is still waiting and no tick is open: fibhip_step refuses an open tick and tests `pending` here; at the
@@ -575,7 +593,7 @@ extern "C" int fibhip_step_edges(fibhip_t h)
     NEED(h);
     FLUSH(h);
     CONFIRM(h);
-    if (!el_has_room(h, 1)) return fail(FIBHIP_EINVAL, "step_edges: trace full (electrode recorder)");
+    if (const char *who = sampler_full(h, 1)) return fail(FIBHIP_EINVAL, "step_edges: trace full (%s recorder)", who);
     return edges_impl(h);
 }
 
@@ -612,11 +630,12 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
     // / cancelled by flush() — after which ONE sample is not believed again until two equal series have been seen.
     // A caller that KNOWS its series says so (fibhip_expect: IonicModel.run() does, from its frame period and tick count) and
     // nothing is guessed: the declared ticks are launched at the first of them, mt.max at a time.
-    if (!el_has_room(h, h->pending + nticks))
-        return fail(FIBHIP_EINVAL, "step: trace full (the electrode recorder holds %lld samples; read it, then detach or re-attach)", h->el.cap);
+    if (const char *who = sampler_full(h, h->pending + nticks))
+        return fail(FIBHIP_EINVAL, "step: trace full (the %s recorder holds %lld samples; read it, then detach or re-attach)", who,
+                    who[0] == 'e' ? h->el.cap : h->tip.cap);
     if (int rc = journal_bound(h)) return rc;
     // (the guards in front are may_run_ahead's own, taken first because most calls end at one of them)
-    if (nticks > 0 && h->ahead.n == 0 && h->mt.max > 1 && !h->el.on) {
+    if (nticks > 0 && h->ahead.n == 0 && h->mt.max > 1 && !sampling(h)) {
         bool repeats = false;
         int L = 0;
         if (h->series.expect > 0) {
@@ -643,10 +662,10 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
             if (int rc = autotune(h)) return rc;
         if (const Variant *v = mt_variant(h)) {
             h->pending += nticks;
-            // With an electrode recorder a launch goes out when the ticks up to the next sample tick are waiting (or mt.max of
+            // With a sampler attached a launch goes out when the ticks up to the next sample tick are waiting (or mt.max of
             // them) and ends there: between two samples the handle runs the fewest launches `every` allows, whatever the
             // caller's call pattern.  (Without one: mt.cur, as described above.)
-            while (h->pending >= (h->el.on ? imin(el_room(h), h->mt.max) : h->mt.cur)) {
+            while (h->pending >= (sampling(h) ? imin(sample_room(h), h->mt.max) : h->mt.cur)) {
                 const int T = next_launch_ticks(h, h->pending);
                 h->pending -= T;
                 if (int rc = tick_mt(h, v, T)) return rc;
@@ -662,7 +681,7 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
     // call of no ticks beside a launch that runs ahead leaves that launch to the call that settles it, flush().)
     if (h->pending + nticks > 0) CONFIRM(h);
     const int reserve = (h->fused_fn && !h->tracing) ? 1 : 0;
-    // (multi_cap moves with the electrode recorder's tick counter: the bound is taken afresh for every launch)
+    // (multi_cap moves with the samplers' tick counters: the bound is taken afresh for every launch)
     auto held = [&] { return ((multi_cap(h) > 1 && !h->tracing) ? multi_cap(h) - 1 : 0) + reserve; };
     const int cap = held();
     if (cap > 0 && nticks > 0) {

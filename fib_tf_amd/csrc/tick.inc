@@ -6,6 +6,7 @@ static int autotune(fibhip_ctx *h);                               // plan.inc: t
 // the recorders' hooks behind a committed tick (record.inc)
 static int observe_enqueue(fibhip_ctx *h);
 static int electrode_advance(fibhip_ctx *h, int ticks);
+static int tips_advance(fibhip_ctx *h, int ticks);
 
 // ------------------------------------------------------------------------------------------
 // stepping
@@ -272,7 +273,9 @@ static int commit_impl(fibhip_t h)
     // the recorder sees every tick on its own: while it is attached nothing fuses ticks (multi_cap, mt_variant), span is 1
     if (h->obs.on)
         if (int rc = observe_enqueue(h)) return rc;
-    if (h->el.on) return electrode_advance(h, ticks);
+    if (h->el.on)
+        if (int rc = electrode_advance(h, ticks)) return rc;
+    if (h->tip.on) return tips_advance(h, ticks);
     return 0;
 }
 

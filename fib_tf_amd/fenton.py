@@ -11,6 +11,11 @@ from .ionic import IonicModel
 class Fenton4v(IonicModel):
     MODEL_ID = _lib.FENTON4V
     VAR_NAMES = ('U', 'V', 'W', 'S')
+    # record_tips() defaults (var, var2, a0, b0): the potential U against the v gate, whose loop is the most open of the three
+    # (normalised area 0.73; w 0.61, s 0.49).  From the parity oracle on the CPU, the 64 x 64 golden protocol
+    # (tests/golden/fenton_traj64: diff 1.5, hole (32, 32, 6), S1 only), cell (row 16, column 32) over 500 ticks: U in
+    # [0.000101302518, 0.982612491], v in [2.41633049e-23, 1]; each level is the midpoint.
+    tip_signals = (0, 1, 0.4913568965, 0.5)
 
     def __init__(self, props):
         IonicModel.__init__(self, props)

@@ -241,6 +241,22 @@ class IonicModel:
             ensure()
         return ElectrodeRecorder(self, masks, every=every, capacity=capacity, var=var)
 
+    def record_tips(self, var2=None, levels=None, every=1, max_tips=256, capacity=None, var=0, mask=None):
+        """attaches a tip recorder (fib_tf_amd/tips.py) to this model's handle: every `every` ticks the phase singularities of
+        (X[var] - levels[0], X[var2] - levels[1]) — the spiral tips, with their charge — are found on the device and kept
+        there, up to `max_tips` per sample, until `tips()` / `counts()` read them.  `var2` and `levels` default to the
+        model's `tip_signals = (var, var2, a0, b0)`; a model without that attribute (a traced model) must pass them.
+        `mask` defaults to `phase > 0.5` when the model has a phase field: only plaquettes whose four corners are inside
+        count.  Default capacity: the samples of a whole run of `duration`.  Call after define(); single device only (row
+        blocks raise NotImplementedError)."""
+        from .tips import TipRecorder
+        if not self.defined:
+            raise AssertionError('record_tips should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return TipRecorder(self, var2=var2, levels=levels, every=every, max_tips=max_tips, capacity=capacity, var=var, mask=mask)
+
     def _image_affine(self):
         """(scale, offset) with image() == scale * X + offset, X the array pot() names: what turns an electrode's raw sum
         into mean(image() * mask).  Models whose image() rescales override it."""

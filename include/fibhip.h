@@ -384,6 +384,45 @@ int fibhip_electrode_count(fibhip_t h, long long *samples);
 int fibhip_electrode_read(fibhip_t h, long long first, long long count, float *dst);
 int fibhip_electrode_end(fibhip_t h);
 
+/* Tip recorder: the phase singularities (spiral-wave tips, rotors) of two state arrays of the same tick, found on the device
+ * every `every` ticks and kept there as compacted lists until they are read.  A = X[var] and B = X[var2] (var != var2) are
+ * watched against the levels a0, b0: the state-space phase atan2(B - b0, A - a0).  The definition is exact integer
+ * arithmetic on float32 inputs (restated in NumPy in tests/tip_ref.py; the device equals it bit for bit).  For every plaquette
+ * with upper-left cell (i, j), 0 <= i < height - 1, 0 <= j < width - 1, take the corners in the order
+ * (i,j) -> (i,j+1) -> (i+1,j+1) -> (i+1,j) -> (i,j) and at each a = A - a0, b = B - b0 (float32 subtractions).  For each of the
+ * four edges (a1,b1) -> (a2,b2), cross = (double)a1 * (double)b2 - (double)a2 * (double)b1 (both products are exact in double,
+ * so the sign is the exact sign):
+ *     upward edge   (b1 < 0 && b2 >= 0): w += 1 if cross > 0
+ *     downward edge (b2 < 0 && b1 >= 0): w -= 1 if cross < 0
+ * NaN compares false: no crossing.  w in {-1, 0, +1} is the plaquette's charge; a tip is a plaquette with w != 0, at the
+ * plaquette centre (i + 0.5, j + 0.5).  With a mask ([height*width] bytes) a plaquette counts only if all four corners have
+ * a non-zero mask.  Sample s is taken after the tick with (k + 1) % every == 0, k = ticks since tips_begin: s = (k + 1) / every
+ * - 1, the electrode recorder's rule.  Per sample the device keeps three int32 counters — n_pos, n_neg (tips of charge +1 /
+ * -1: exact whatever max_tips is) and stored = n_pos + n_neg — and the first min(stored, max_tips) records {row i, column j,
+ * charge, 0} in the order of arrival, which is not fixed: sort them.  stored > max_tips means the list was cut.
+ * Pacing, set_state and step_slow / step_mode between two ticks belong to the next tick.  The lists do not wrap: a fibhip_step
+ * that would take sample number `capacity` is refused with FIBHIP_EINVAL ("trace full") before anything of that call is
+ * enqueued.  What holds for the electrode recorder holds here: no launch spans a sample tick, multi-tick launches go on
+ * between two samples, nothing runs ahead, a launch goes out when the ticks up to the next sample tick have been accepted,
+ * and Courtemanche's tick is not fused with 'slow' when a sample of a slow array (var or var2) is due at that tick.  Both
+ * recorders may be attached at once, each with its own stride.
+ * Refused with FIBHIP_EINVAL: a row block, inside an open tick, var or var2 out of range or equal, levels that are not
+ * numbers, every < 1, max_tips outside 1 .. FIBHIP_MAX_TIPS, capacity < 1 or too large, a grid without a plaquette.
+ *   fibhip_tips_begin  flushes, synchronises and confirms pending work, copies the mask (or none: NULL) and attaches; again:
+ *                      re-attaches, empty lists
+ *   fibhip_tips_count  samples taken so far (ticks accepted but not launched yet included)
+ *   fibhip_tips_read   samples [first, first + count): counts as [count][3] = n_pos, n_neg, stored, and (unless NULL) records
+ *                      as [count][max_tips][4]; flushes and blocks like get_state; does not detach
+ *   fibhip_tips_end    detaches and frees (no recorder attached: nothing); fibhip_destroy does the same                       */
+#define FIBHIP_MAX_TIPS 65536
+int fibhip_tips_begin(fibhip_t h, int var, int var2, float a0, float b0, const unsigned char *mask /* [H*W] or NULL */,
+                      int every, int max_tips, long long capacity);
+int fibhip_tips_count(fibhip_t h, long long *samples);
+int fibhip_tips_read(fibhip_t h, long long first, long long count,
+                     int *counts  /* [count][3] = n_pos, n_neg, stored (may exceed max_tips: the list was cut) */,
+                     int *records /* [count][max_tips][4], the first min(stored, max_tips) of each sample valid; may be NULL */);
+int fibhip_tips_end(fibhip_t h);
+
 const char *fibhip_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)
