@@ -653,7 +653,8 @@ class Stepper:
 
     def ticks_per_launch(self):
         """consecutive ticks one launch can cover (Courtemanche, fast policy, one device: 3; Fenton / Beeler-Reuter on a
-        grid whose tiles are all resident at once: FIBHIP_MT_MAX, default 32; otherwise 1)"""
+        grid whose tiles are all resident at once: FIBHIP_MT_MAX, default 32, and 256 while a series of 128 ticks or more
+        declared with expect() is running; otherwise 1)"""
         return self._ck(self._L.fibhip_ticks_per_launch(self._h))
 
     # ---- activation recorder (include/fibhip.h fibhip_observe_*) --------------------------------------------------

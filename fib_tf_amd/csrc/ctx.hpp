@@ -1,7 +1,19 @@
 // ctx.hpp — the handle behind fibhip_t: what it owns, grouped by who changes it, and the few helpers every file reads it with.
 #pragma once
 
-constexpr int MT_MAX_TICKS = 32;          // default bound on the ticks of one launch (0.4 ms of Fenton 512x512)
+constexpr int MT_MAX_TICKS = 32;          // default bound on the ticks of one launch of a predicted or undeclared series
+constexpr int MT_MAX_TICKS_DECLARED = 256;      // ... of a launch whose ticks the caller has all DECLARED (fibhip_expect): the smallest setting
+                                                // within 0.3 % of the best measured one (profiles/series_launch_ab.txt); see launch_cap
+// A declaration shorter than this keeps the launches it had, MT_MAX_TICKS at a time (run() with a frame every 10 ticks, the
+// 20-tick regions of the driver, a 70-tick series as 32 + 32 + 6): the gain was measured on series of thousands of ticks, and
+// the launches of short declared series are what their callers and the suite have seen so far.
+constexpr int MT_DECLARED_MIN_TICKS = 128;
+constexpr int MT_MAX_TICKS_ENV = 4096;          // the most FIBHIP_MT_MAX accepts (MT_CANCEL, 0xFFFF, is not a tick count)
+// ticks in unconfirmed launches before the stream is drained once (journal_bound): what 256 launches of MT_MAX_TICKS hold,
+// 0.1 s of Fenton 512x512 — whatever waits behind them (confirm(), the frame poll of ahead_read_back) waits that long at most
+constexpr int MT_MAX_TICKS_IN_FLIGHT = 256 * MT_MAX_TICKS;
+static_assert(MT_MAX_TICKS <= MT_MAX_TICKS_DECLARED && MT_MAX_TICKS_DECLARED <= MT_MAX_TICKS_ENV && MT_MAX_TICKS_ENV < (int)MT_CANCEL,
+              "a launch's tick count shares its 16 bits with MT_CANCEL");
 constexpr int AT_MT_TICKS = 8;           // autotune times a multi-tick candidate as one launch of this many ticks
 static const char *const MT_DEAD_MSG =
     "a multi-tick launch gave up (a tile waited its full bound for a neighbouring tile: were all workgroups resident? is another "
@@ -33,6 +45,7 @@ struct MtState {
     unsigned epoch_base;    // value of every epoch word between two launches
     bool stale;             // the tiling may have changed since the words were last written: zero them first
     int max;                // most ticks one launch advances (<= 1: never)
+    int max_declared;       // ... when the caller has declared every one of them (>= max by default; FIBHIP_MT_MAX sets both; 1 with max)
     int cur;                // ticks the next launch waits for: 1 after any observation of the state, then see fibhip_step
     unsigned *snap_flags;   // page-locked: one word per tile, raised by the tiles of a launch that carries a read-back
     unsigned *snap_flags_dev;       // device address of snap_flags
@@ -60,7 +73,9 @@ struct Series {
     bool fresh;             // ticks have run since the last observation of the state
     bool trust;             // the caller has not broken a predicted series since its last two equal ones
     int expect;             // ticks the caller has DECLARED to come in one series (fibhip_expect) and that have not been asked for yet, or 0
+    int covered;            // the last so many of the `pending` ticks were declared when fibhip_step accepted them
     bool expect_fresh;      // ... none of them has been asked for yet: the observation the caller makes first does not end the series
+    bool expect_long;       // the declaration held MT_DECLARED_MIN_TICKS or more when it was made: its launches take the declared cap
 };
 
 // run-ahead: a caller that alternates series of n ticks with ONE read-back (run() with image() every n ticks) gets the
@@ -88,6 +103,7 @@ struct MtRec {
 };
 struct Journal {
     std::vector<MtRec> recs;
+    long long ticks;        // ... and the ticks they hold (journal_bound)
     bool recovering;
     long long n_fallbacks, n_replayed;      // launches that gave up and were recovered / ticks recomputed one launch per tick
     long fake_giveup_at, fake_seen;         // test switch FIBHIP_MT_FAKE_GIVEUP=n: the n-th multi-tick launch finds the give-up word raised

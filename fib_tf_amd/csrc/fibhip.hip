@@ -230,9 +230,10 @@ static int create_impl(const fibhip_desc *desc, fibhip_ctx *&h)
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, desc->device));
         h->ncu = prop.multiProcessorCount;
-        // FIBHIP_MT=0 switches multi-tick launches off, FIBHIP_MT_MAX bounds the ticks of one launch
+        // FIBHIP_MT=0 switches multi-tick launches off, FIBHIP_MT_MAX bounds the ticks of one launch (both caps: launch_cap)
         const char *e = getenv("FIBHIP_MT"), *em = getenv("FIBHIP_MT_MAX");
-        h->mt.max = (e && atoi(e) == 0) ? 1 : (em && atoi(em) > 0 ? imin(atoi(em), 4096) : MT_MAX_TICKS);
+        const int env_max = (em && atoi(em) > 0) ? imin(atoi(em), MT_MAX_TICKS_ENV) : 0;
+        h->mt.max = (e && atoi(e) == 0) ? 1 : (env_max ? env_max : MT_MAX_TICKS);
         if (interleaved || desc->ghost_top || desc->ghost_bottom || (long long)h->cells * ((nv + 3) / 4 * 4) * 8 >= (1LL << 31))
             h->mt.max = 1;
         // a process-wide CU mask takes compute units away that multiProcessorCount still reports: the tiles of a grid
@@ -242,6 +243,7 @@ static int create_impl(const fibhip_desc *desc, fibhip_ctx *&h)
             const char *m = getenv(var);
             if (m && *m) h->mt.max = 1;
         }
+        h->mt.max_declared = h->mt.max <= 1 ? 1 : (env_max ? env_max : MT_MAX_TICKS_DECLARED);
     }
     h->agg_dirty = true;
 #if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
@@ -725,7 +727,7 @@ extern "C" int fibhip_plan_tile(fibhip_t h, int *tile_w, int *tile_h, int *rows_
 extern "C" int fibhip_ticks_per_launch(fibhip_t h)
 {
     if (!h) return fail(FIBHIP_EINVAL, "null handle");
-    if (mt_variant(h)) return h->mt.max;
+    if (mt_variant(h)) return launch_cap(h, h->series.expect > 0);      // (a declared series is running: its cap)
     return multi_cap(h);
 }
 

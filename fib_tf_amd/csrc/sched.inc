@@ -14,7 +14,9 @@
 // A multi-tick launch gave up (the give-up word names it).  The stream is idle.  The launch wrote the other slab only, and
 // every multi-tick launch queued behind it left at its first boundary without writing: the state it STARTED from is where its
 // journal record says.  Go back there, switch multi-tick launches off for this handle, and recompute — one launch per tick,
-// bit-identical by construction — the ticks the handle's state had already moved past.
+// bit-identical by construction — the ticks the handle's state had already moved past.  (The replay stays one launch per tick
+// however long the lost launches were: the fallback leaves no multi-tick launch to replay with, mt.max is 1 from here on.
+// Its cost is bounded by what the journal holds, MT_MAX_TICKS_IN_FLIGHT ticks and one launch: journal_bound.)
 static int recover(fibhip_ctx *h, unsigned id)
 {
     size_t i = 0;
@@ -35,7 +37,8 @@ static int recover(fibhip_ctx *h, unsigned id)
     h->n_ticks -= lost;
     memcpy(h->cur, h->journal.recs[i].src, sizeof h->cur);
     h->journal.recs.clear();
-    h->mt.max = 1;                                    // (mt_variant() is null from here on: no run-ahead, no series either)
+    h->journal.ticks = 0;
+    h->mt.max = h->mt.max_declared = 1;               // (mt_variant() is null from here on: no run-ahead, no series either)
     h->mt.cur = 1;
     h->mt.stale = true;
     HIPCHK(hipMemsetAsync(h->mt.give_up_word(), 0, MtState::tail_bytes(), h->s0));
@@ -71,6 +74,7 @@ static int sync_s0(fibhip_ctx *h)
         const unsigned gave_up = __atomic_load_n(h->mt.host_give_up(), __ATOMIC_ACQUIRE);
         if (gave_up) return recover(h, gave_up);
         h->journal.recs.clear();                           // every launch so far has ended, and ended well
+        h->journal.ticks = 0;
     }
     return 0;
 }
@@ -153,8 +157,29 @@ static inline int sample_room(const fibhip_ctx *h)
 // consecutive ticks one plain launch may fuse (Courtemanche on aggregates: up to multi_max; one while an activation recorder
 // is attached; never across a sample tick)
 static inline int multi_cap(const fibhip_ctx *h) { return h->obs.on ? 1 : imin(h->multi_max, sample_room(h)); }
-// ticks of the next multi-tick launch when `waiting` ticks wait for it
-static inline int next_launch_ticks(const fibhip_ctx *h, int waiting) { return imin(imin(waiting, h->mt.max), sample_room(h)); }
+// The two caps on the ticks of one multi-tick launch.  A predicted series, and the 2, 4, ... ticks of a caller that just keeps
+// stepping, may be broken at any call: MT_MAX_TICKS (mt.max).  Ticks the caller has DECLARED (fibhip_expect), in a series of
+// MT_DECLARED_MIN_TICKS or more (Series::expect_long; a shorter one keeps the launches it had), go out
+// MT_MAX_TICKS_DECLARED (mt.max_declared) at a time: a launch's first and last tick cost what no tick boundary inside it does
+// (the prologue that reads the tile, the write-back and its drain, the kernel boundary: DESIGN.md section 6), and a declared
+// launch is as cheap to stop as a short one — the tiles read the host's word at every tick (ahead_settle).
+static inline int launch_cap(const fibhip_ctx *h, bool declared)
+{
+    return declared && h->series.expect_long ? h->mt.max_declared : h->mt.max;
+}
+// every pending tick was declared when it was accepted (Series::covered counts from the youngest)
+static inline bool pending_declared(const fibhip_ctx *h) { return h->pending > 0 && h->series.covered >= h->pending; }
+// ticks of the next multi-tick launch when `waiting` of the pending ticks wait for it
+static inline int next_launch_ticks(const fibhip_ctx *h, int waiting)
+{
+    return imin(imin(waiting, launch_cap(h, pending_declared(h))), sample_room(h));
+}
+// `T` of the pending ticks are being launched (the oldest)
+static inline void take_pending(fibhip_ctx *h, int T)
+{
+    h->pending -= T;
+    h->series.covered = imin(h->series.covered, h->pending);
+}
 // the last pending tick ends on a sample of an array 'slow' assigns: the sample must see it before 'slow', which belongs to the
 // next tick — the two are not fused then (fibhip_step_mode)
 static inline bool slow_sample_due(const fibhip_ctx *h)
@@ -241,6 +266,7 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
         rec.counted = commit;
         memcpy(rec.src, h->cur, sizeof rec.src);
         h->journal.recs.push_back(rec);
+        h->journal.ticks += T;
         if (h->journal.fake_giveup_at > 0 && ++h->journal.fake_seen == h->journal.fake_giveup_at) {
             // test switch: this launch finds the give-up word raised in its name — what its tiles would have written had one
             // of them waited out its bound — and leaves at its first boundary, like every launch behind it
@@ -279,15 +305,18 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
     return 0;
 }
 
-// A caller that never synchronises must not grow the journal without bound: every 256 multi-tick launches the stream is
+// A caller that never synchronises must not grow the journal without bound: every 256 multi-tick launches, or
+// MT_MAX_TICKS_IN_FLIGHT ticks if that is sooner (launches of a declared series), the stream is
 // drained once (20 us in 100 ms of work) and the launches so far are confirmed — or the first that gave up is found.
+// The bound in ticks is also what keeps every wait behind unconfirmed launches short whatever a launch holds: confirm(),
+// the stop of ahead_settle and the frame poll of ahead_read_back wait for that many ticks and one launch at most.
 // The give-up word names a launch by its 16-bit id, and recover() looks the id up in the journal: the journal never holds more
 // records than a cycle of ids has distinct values (ids - 1: the id the host's word names is skipped), or the id of the launch
 // that gave up could also be that of an older one that ended well (FIBHIP_MT_IDS shortens the cycle, for the tests).
 static int journal_bound(fibhip_ctx *h)
 {
     const size_t most = h->mt.ids - 1u < 256u ? (size_t)(h->mt.ids - 1u) : (size_t)256;
-    if (h->journal.recs.size() < most || h->ahead.n > 0) return 0;
+    if ((h->journal.recs.size() < most && h->journal.ticks < MT_MAX_TICKS_IN_FLIGHT) || h->ahead.n > 0) return 0;
     return sync_s0(h);
 }
 
@@ -331,7 +360,7 @@ static int launch_pending(fibhip_t h, int n)
         if (const Variant *v = mt_variant(h)) {
             while (n > 0) {
                 const int T = next_launch_ticks(h, n);
-                h->pending -= T;
+                take_pending(h, T);
                 n -= T;
                 if (int rc = tick_mt(h, v, T)) return rc;
                 h->series.run += T;
@@ -340,7 +369,7 @@ static int launch_pending(fibhip_t h, int n)
         }
     while (n > 0) {
         const int T = cycle_clamp(h, imin(multi_cap(h), n));
-        h->pending -= T;
+        take_pending(h, T);
         n -= T;
         if (int rc = tick_multi(h, T)) return rc;
     }
@@ -355,13 +384,14 @@ static int launch_pending(fibhip_t h, int n)
 enum AheadFrom { AHEAD_FROM_STEP, AHEAD_FROM_READ_BACK };
 
 // May a launch of the L ticks this handle expects next start now, ahead of the caller's calls?  `repeats`: L rests on a
-// repetition of the caller's series or on its declaration, not on one sample.  (What belongs to the CALL rather than to the
+// repetition of the caller's series or on its declaration, not on one sample; `declared`: on its declaration, which covers
+// all L ticks (launch_cap).  (What belongs to the CALL rather than to the
 // handle stays with the caller: fibhip_step asks only when the call leaves part of the series open, 0 < nticks < L; the
 // read-back only for one array, var >= 0.)
-static bool may_run_ahead(const fibhip_ctx *h, int L, bool repeats, AheadFrom from)
+static bool may_run_ahead(const fibhip_ctx *h, int L, bool repeats, bool declared, AheadFrom from)
 {
     // the series is worth a launch of its own and fits one (this implies mt.max > 1)
-    if (L < 2 || L > h->mt.max) return false;
+    if (L < 2 || L > launch_cap(h, declared)) return false;
     // nothing forbids it: the switch and the caller's access to the state (Ahead::ok), no launch ahead already, no sampler
     // (see "what the recorders ask of the scheduler"), no timeline being taken (every launch there is the caller's own)
     if (!h->ahead.ok || h->ahead.n != 0 || sampling(h) || h->tracing) return false;
@@ -403,6 +433,7 @@ static void ahead_adopt(fibhip_ctx *h, int ticks)
 {
     for (auto &r : h->journal.recs)                 // (the launch's journal record: what it did)
         if (r.id == h->ahead.id) {
+            h->journal.ticks -= r.T - ticks;
             r.T = ticks;
             r.counted = true;
         }
@@ -458,7 +489,7 @@ static int ahead_settle(fibhip_ctx *h)
     }
     ahead_drop(h);
     h->series.run -= redo;
-    h->pending += redo;
+    h->pending += redo;                             // (in front of whatever is pending: Series::covered stands)
     if (redo > 0) {
         h->ahead.n_redone++;
         h->series.trust = false;                    // ONE sample is not believed again until two equal series were seen
@@ -512,11 +543,12 @@ static int ahead_read_back(fibhip_ctx *h, int var, float *dst, bool *delivered)
     if (int rc = journal_bound(h)) return rc;
     bool repeats = false;
     int L = predict_series(h, &repeats);
-    if (h->series.expect > 0 && h->series.expect_fresh) {   // the caller has said how many ticks it will ask for next (fibhip_expect)
-        L = imin(h->series.expect, h->mt.max);
+    const bool declared = h->series.expect > 0 && h->series.expect_fresh;
+    if (declared) {                                         // the caller has said how many ticks it will ask for next (fibhip_expect)
+        L = imin(h->series.expect, launch_cap(h, true));
         repeats = true;
     }
-    if (var < 0 || !may_run_ahead(h, L, repeats, AHEAD_FROM_READ_BACK)) return 0;
+    if (var < 0 || !may_run_ahead(h, L, repeats, declared, AHEAD_FROM_READ_BACK)) return 0;
     const Variant *mv = mt_variant(h);
     if (!mv) return 0;
     void *dev_dst = nullptr;
@@ -629,7 +661,10 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
     // from here: the ticks are handed out below call by call, and a caller that does anything else first gets them recomputed
     // / cancelled by flush() — after which ONE sample is not believed again until two equal series have been seen.
     // A caller that KNOWS its series says so (fibhip_expect: IonicModel.run() does, from its frame period and tick count) and
-    // nothing is guessed: the declared ticks are launched at the first of them, mt.max at a time.
+    // nothing is guessed: the declared ticks are launched at the first of them, mt.max_declared at a time (launch_cap: 256 by
+    // default against the 32 of everything above.  At Fenton 512x512 the 5000 declared ticks of a benchmark region take
+    // 11.58 us per tick as 157 launches of 32 and 11.44 as 20 of 256, 1.2 %; the kernel trace shows no gap between two
+    // launches either way, a launch's first and last tick are what costs — profiles/series_launch_ab.txt).
     if (const char *who = sampler_full(h, h->pending + nticks))
         return fail(FIBHIP_EINVAL, "step: trace full (the %s recorder holds %lld samples; read it, then detach or re-attach)", who,
                     who[0] == 'e' ? h->el.cap : h->tip.cap);
@@ -637,23 +672,28 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
     // (the guards in front are may_run_ahead's own, taken first because most calls end at one of them)
     if (nticks > 0 && h->ahead.n == 0 && h->mt.max > 1 && !sampling(h)) {
         bool repeats = false;
+        const bool declared = h->series.expect > 0;
         int L = 0;
-        if (h->series.expect > 0) {
-            L = imin(h->series.expect, h->mt.max);
+        if (declared) {
+            L = imin(h->series.expect, launch_cap(h, true));
             repeats = true;
         } else if (h->series.run == 0) {
             L = predict_series(h, &repeats);
         }
-        if (nticks < L && may_run_ahead(h, L, repeats, AHEAD_FROM_STEP))
+        if (nticks < L && may_run_ahead(h, L, repeats, declared, AHEAD_FROM_STEP))
             if (const Variant *v = mt_variant(h))
                 if (int rc = ahead_begin(h, v, L)) return rc;
     }
+    int covered = 0;                                   // how many of this call's ticks the declaration covers (its first)
     if (h->series.expect > 0 && nticks > 0) {          // (the declared series has begun / goes on)
-        h->series.expect = imax(0, h->series.expect - nticks);
+        covered = imin(nticks, h->series.expect);
+        h->series.expect -= covered;
         h->series.expect_fresh = false;
     }
     if (h->ahead.n > 0 && nticks > 0) {                // ticks that have been computed ahead already
-        nticks -= ahead_take(h, nticks);
+        const int took = ahead_take(h, nticks);
+        nticks -= took;
+        covered = imax(0, covered - took);
         if (nticks == 0) return 0;
     }
     if (h->mt.max > 1 && nticks > 0 && !h->tracing) {
@@ -662,12 +702,14 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
             if (int rc = autotune(h)) return rc;
         if (const Variant *v = mt_variant(h)) {
             h->pending += nticks;
+            // (a call that goes past the end of its declaration leaves undeclared ticks behind the declared ones: none counts)
+            h->series.covered = covered == nticks ? h->series.covered + covered : 0;
             // With a sampler attached a launch goes out when the ticks up to the next sample tick are waiting (or mt.max of
             // them) and ends there: between two samples the handle runs the fewest launches `every` allows, whatever the
             // caller's call pattern.  (Without one: mt.cur, as described above.)
-            while (h->pending >= (sampling(h) ? imin(sample_room(h), h->mt.max) : h->mt.cur)) {
+            while (h->pending >= (sampling(h) ? imin(sample_room(h), launch_cap(h, pending_declared(h))) : h->mt.cur)) {
                 const int T = next_launch_ticks(h, h->pending);
-                h->pending -= T;
+                take_pending(h, T);
                 if (int rc = tick_mt(h, v, T)) return rc;
                 const bool first = h->series.run == 0;
                 h->series.run += T;
@@ -692,7 +734,7 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
     h->pending += nticks;
     while (h->pending > held()) {
         const int T = cycle_clamp(h, h->tracing ? 1 : imin(multi_cap(h), h->pending - reserve));
-        h->pending -= T;
+        take_pending(h, T);
         if (int rc = tick_multi(h, T)) return rc;
     }
     return 0;
@@ -703,5 +745,6 @@ extern "C" int fibhip_expect(fibhip_t h, int nticks)
     if (!h || nticks < 0) return fail(FIBHIP_EINVAL, "expect: bad argument");
     h->series.expect = nticks;
     h->series.expect_fresh = nticks > 0;
+    h->series.expect_long = nticks >= MT_DECLARED_MIN_TICKS;
     return 0;
 }
