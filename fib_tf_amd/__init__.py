@@ -12,5 +12,6 @@ from .fenton import Fenton4v                    # noqa: F401
 from .br import BeelerReuter                    # noqa: F401
 from .court import Courtemanche                 # noqa: F401
 from . import tips                              # noqa: F401  (TipRecorder, link: spiral tips recorded on the device)
+from . import frames                            # noqa: F401  (FrameRecorder: the movie cube recorded on the device)
 
 __all__ = ['IonicModel', 'Fenton4v', 'BeelerReuter', 'Courtemanche']

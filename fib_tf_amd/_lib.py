@@ -16,6 +16,8 @@ HDR = os.path.join(ROOT, 'include', 'fibhip.h')
 
 FENTON4V, BR, COURT, COURT_US, CUSTOM = 0, 1, 2, 3, 4
 OBS_MAPS = ('first_up', 'last_up', 'prev_up', 'apd', 'count')     # enum fibhip_obs_map, in order
+FRAME_REDUCE = ('point', 'mean')                                  # enum fibhip_frame_reduce, in order
+FRAME_FORMAT = ('float32', 'uint8')                               # enum fibhip_frame_format, in order
 CHEBY, SKIP, CHRONIC, FAST, ALLVARS, ROW_INTERLEAVED, ZEROPAD, HOLD = 1, 2, 4, 8, 16, 32, 64, 128
 
 # -ffp-contract=off: FMAs appear only where the source writes them (policy hook P::mad).
@@ -176,6 +178,12 @@ SYMBOLS = {
     'fibhip_tips_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_tips_read': ([_h, C.c_longlong, C.c_longlong, _ip, _ip], C.c_int),
     'fibhip_tips_end': ([_h], C.c_int),
+    'fibhip_frames_begin': ([_h, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, C.c_int, C.c_int, C.c_int,
+                             C.c_longlong], C.c_int),
+    'fibhip_frames_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_frames_shape': ([_h, _ip, _ip, _ip], C.c_int),
+    'fibhip_frames_read': ([_h, C.c_longlong, C.c_longlong, C.c_void_p], C.c_int),
+    'fibhip_frames_end': ([_h], C.c_int),
     'fibhip_last_error': ([], C.c_char_p),
 }
 
@@ -753,3 +761,46 @@ class Stepper:
 
     def tips_end(self):
         self._ck(self._L.fibhip_tips_end(self._h))
+
+    # ---- frame recorder (include/fibhip.h fibhip_frames_*) --------------------------------------------------------
+    def frames_begin(self, var=0, window=None, block=(1, 1), reduce='mean', lo=0.0, span=1.0, weight=None, fmt='float32', every=1,
+                     first=None, capacity=1):
+        """attaches (or re-attaches, with an empty cube) the frame recorder on array `var`: `window` = (r0, r1, c0, c1) (None:
+        the whole grid), `block` = (by, bx), `reduce` 'point' / 'mean', the levels of y = (X - lo) / span, `weight` an
+        [height, width] float32 plane or None, `fmt` 'float32' / 'uint8'; a frame after ticks first, first + every, ...
+        (first=None: every), `capacity` frames at the most"""
+        win = np.ascontiguousarray((0, self.height, 0, self.width) if window is None else window, np.intc).reshape(4)
+        wp = None
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, np.float32)
+            if weight.shape != (self.height, self.width):
+                raise ValueError('frames_begin: a weight plane of shape %s on a %d x %d grid' % (weight.shape, self.height, self.width))
+            wp = weight.ctypes.data_as(_fp)
+        self._ck(self._L.fibhip_frames_begin(self._h, int(var), win.ctypes.data_as(_ip), int(block[0]), int(block[1]),
+                                             FRAME_REDUCE.index(reduce), float(lo), float(span), wp, FRAME_FORMAT.index(fmt),
+                                             int(every), int(every if first is None else first), int(capacity)))
+
+    def frames_count(self):
+        """frames taken since frames_begin (ticks accepted but not launched yet included)"""
+        k = C.c_longlong()
+        self._ck(self._L.fibhip_frames_count(self._h, C.byref(k)))
+        return int(k.value)
+
+    def frames_shape(self):
+        """(oh, ow, dtype) of the attached recorder's frames"""
+        oh, ow, bpp = C.c_int(), C.c_int(), C.c_int()
+        self._ck(self._L.fibhip_frames_shape(self._h, C.byref(oh), C.byref(ow), C.byref(bpp)))
+        return int(oh.value), int(ow.value), np.dtype(np.uint8 if bpp.value == 1 else np.float32)
+
+    def frames_read(self, first=0, count=None):
+        """frames [first, first + count) as a [count, oh, ow] array of float32 or uint8 (count=None: all taken so far); blocks
+        like get_state, detaches nothing"""
+        if count is None:
+            count = self.frames_count() - int(first)
+        oh, ow, dtype = self.frames_shape()
+        out = np.empty((max(int(count), 0), oh, ow), dtype)
+        self._ck(self._L.fibhip_frames_read(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def frames_end(self):
+        self._ck(self._L.fibhip_frames_end(self._h))

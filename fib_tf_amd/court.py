@@ -109,6 +109,10 @@ class Courtemanche(IonicModel):
         v = self._V.eval()
         return (v - self.min_v) / (self.max_v - self.min_v)
 
+    def _frame_levels(self):
+        from .frames import round_levels
+        return round_levels(self.min_v, self.max_v)
+
     def _image_affine(self):
         span = float(self.max_v) - float(self.min_v)
         return 1.0 / span, -float(self.min_v) / span

@@ -145,6 +145,22 @@ struct TipRec {
     int *records;           // device: [cap][max_tips][4] = row, col, charge, 0
 };
 
+// frame recorder (fibhip_frames_begin): the third sampler — no launch spans a sample tick (sample_room), and the hook on the
+// plain and the multi-tick commit path (frames_advance) enqueues frame_kernel behind the launch that ends one
+struct FrRec {
+    bool on;
+    int var, every;
+    int r0, c0, oh, ow, by, bx;     // the window's first cell, the frame's shape in pixels, the block
+    int reduce, format;             // FIBHIP_FRAME_POINT / _MEAN, FIBHIP_FRAME_F32 / _U8
+    float lo, span;
+    long long cap;          // frames the cube holds
+    long long k;            // every - first + the ticks LAUNCHED since the recorder was attached: a sample is due at every multiple
+                            // of `every`, as for the other samplers (recover() rewinds it by the ticks it replays)
+    float *w;               // device: the weight plane [H][W], or null
+    unsigned char *cube;    // device: [cap][oh][ow] float32 or uint8
+    size_t frame_bytes() const { return (size_t)oh * (size_t)ow * (format == FIBHIP_FRAME_U8 ? 1u : 4u); }
+};
+
 // fibhip_trace_begin / _end: the launches in between, each between two HIP events
 struct TraceRec {
     hipEvent_t e0, e1;
@@ -203,6 +219,7 @@ struct fibhip_ctx {
     ObsRec obs;
     ElRec el;
     TipRec tip;
+    FrRec fr;
     std::vector<TraceRec> trace;
     bool tracing;
     // ---- the rest ----

@@ -1,5 +1,6 @@
-// record.inc — the three recorders that run on the device while a model runs: the per-cell activation maps
-// (fibhip_observe_*), the electrode traces (fibhip_electrode_*) and the spiral-tip lists (fibhip_tips_*).  Each is a hook behind a committed launch plus its entry
+// record.inc — the four recorders that run on the device while a model runs: the per-cell activation maps
+// (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*) and the movie cube
+// (fibhip_frames_*).  Each is a hook behind a committed launch plus its entry
 // points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
 // (included by fibhip.hip, behind sched.inc)
 
@@ -112,6 +113,59 @@ static void tips_free(fibhip_ctx *h)
     h->tip.mask = nullptr;
     h->tip.counts = h->tip.records = nullptr;
     h->tip.on = false;
+}
+
+// The frame recorder's hook, the tip recorder's step for step.  Its counter started at every - first (fibhip_frames_begin), so
+// a sample is due when it lands on a multiple of `every`, like the others'; the frame's slot in the cube is a kernel argument
+// computed from that counter, so a replay fills the same slot again.
+template <bool U8, bool MEAN>
+static void frame_launch(const FrameArgs &a, bool vec, size_t threads, hipStream_t st)
+{
+    const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+    if (vec) hipLaunchKernelGGL((frame_kernel<U8, MEAN, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((frame_kernel<U8, MEAN, false>), grid, block, 0, st, a);
+}
+
+static int frames_advance(fibhip_ctx *h, int ticks)
+{
+    FrRec &f = h->fr;
+    f.k += ticks;
+    if (f.k % f.every) return 0;
+    const long long s = f.k / f.every - 1;
+    if (s >= f.cap) return fail(FIBHIP_EINVAL, "frame recorder: trace full");                 // (fibhip_step refuses before this)
+    FrameArgs a;
+    a.x = h->slab[h->cur[f.var]] + (size_t)f.var * h->vstride;
+    a.w = f.w;
+    a.out = f.cube + (size_t)s * f.frame_bytes();
+    a.pitch = h->pitch;
+    a.wpitch = h->d.width;
+    a.r0 = f.r0; a.c0 = f.c0; a.oh = f.oh; a.ow = f.ow; a.by = f.by; a.bx = f.bx;
+    a.lo = f.lo; a.span = f.span;
+    // every row of the window starts 16-byte aligned in the array and in the weight plane, and so does every row of the frame
+    // (four pixels are 16 bytes of a float32 frame and 4 bytes of an 8-bit one)
+    const bool u8 = f.format == FIBHIP_FRAME_U8, mean = f.reduce == FIBHIP_FRAME_MEAN;
+    const bool vec = h->pitch == h->d.width && h->d.width % 4 == 0 && f.c0 % 4 == 0 && f.ow % 4 == 0 &&
+                     ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.w)) & 15u) == 0 &&
+                     (reinterpret_cast<uintptr_t>(a.out) & (u8 ? 3u : 15u)) == 0;
+    const size_t threads = (size_t)f.oh * (size_t)(vec ? f.ow / 4 : f.ow);
+    if (int rc = trace_open(h, h->s0, "frame_kernel", 0, 0, 0, 0, 1)) return rc;
+    if (u8 && mean) frame_launch<true, true>(a, vec, threads, h->s0);
+    else if (u8) frame_launch<true, false>(a, vec, threads, h->s0);
+    else if (mean) frame_launch<false, true>(a, vec, threads, h->s0);
+    else frame_launch<false, false>(a, vec, threads, h->s0);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    return 0;
+}
+
+static void frames_free(fibhip_ctx *h)
+{
+    if (h->fr.w) hipFree(h->fr.w);
+    if (h->fr.cube) hipFree(h->fr.cube);
+    h->fr.w = nullptr;
+    h->fr.cube = nullptr;
+    h->fr.on = false;
 }
 
 // ---- activation recorder ------------------------------------------------------------------------------------------------
@@ -378,5 +432,109 @@ extern "C" int fibhip_tips_end(fibhip_t h)
     FLUSH(h);                                          // the ticks accepted while attached are sampled
     SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
     tips_free(h);
+    return 0;
+}
+
+// ---- frame recorder -----------------------------------------------------------------------------------------------------
+extern "C" int fibhip_frames_begin(fibhip_t h, int var, const int *window, int by, int bx, int reduce, float lo, float span,
+                                   const float *weight, int format, int every, int first, long long capacity)
+{
+    NEED(h);
+    if (!window) return fail(FIBHIP_EINVAL, "frames_begin: null window");
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "frames_begin: bad var %d", var);
+    const int r0 = window[0], r1 = window[1], c0 = window[2], c1 = window[3];
+    if (r0 < 0 || r1 > h->d.height || c0 < 0 || c1 > h->d.width || r0 >= r1 || c0 >= c1)
+        return fail(FIBHIP_EINVAL, "frames_begin: the window rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", r0, r1,
+                    c0, c1, h->d.height, h->d.width);
+    if (by < 1 || by > FIBHIP_MAX_FRAME_BLOCK || bx < 1 || bx > FIBHIP_MAX_FRAME_BLOCK)
+        return fail(FIBHIP_EINVAL, "frames_begin: a block is 1 .. %d cells each way (got %d x %d)", FIBHIP_MAX_FRAME_BLOCK, by, bx);
+    const int oh = (r1 - r0) / by, ow = (c1 - c0) / bx;
+    if (oh < 1 || ow < 1)
+        return fail(FIBHIP_EINVAL, "frames_begin: a window of %d x %d cells holds no block of %d x %d", r1 - r0, c1 - c0, by, bx);
+    if (reduce != FIBHIP_FRAME_POINT && reduce != FIBHIP_FRAME_MEAN) return fail(FIBHIP_EINVAL, "frames_begin: bad reduction %d", reduce);
+    if (format != FIBHIP_FRAME_F32 && format != FIBHIP_FRAME_U8) return fail(FIBHIP_EINVAL, "frames_begin: bad format %d", format);
+    if (std::isnan(lo)) return fail(FIBHIP_EINVAL, "frames_begin: the level lo must be a number");
+    if (!std::isfinite(span) || span == 0.f) return fail(FIBHIP_EINVAL, "frames_begin: span must be finite and not zero (got %g)", span);
+    if (every < 1) return fail(FIBHIP_EINVAL, "frames_begin: every must be >= 1 (got %d)", every);
+    if (first < 1 || first > every) return fail(FIBHIP_EINVAL, "frames_begin: first must be 1 .. every = %d (got %d)", every, first);
+    const size_t per = (size_t)oh * (size_t)ow * (format == FIBHIP_FRAME_U8 ? 1u : 4u);
+    if (capacity < 1 || capacity > (long long)(SIZE_MAX / 2 / per)) return fail(FIBHIP_EINVAL, "frames_begin: bad capacity %lld", capacity);
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "frames_begin: not on a row block (a handle with ghost rows)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "frames_begin inside an open tick");
+    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick 0 is defined (the rule of fibhip_electrode_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    frames_free(h);
+    bool ok = hipMalloc((void **)&h->fr.cube, (size_t)capacity * per) == hipSuccess;
+    if (ok && weight) ok = hipMalloc((void **)&h->fr.w, h->cells * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        frames_free(h);
+        return fail(FIBHIP_ENOMEM, "frames_begin: hipMalloc of the cube failed (%lld frames of %d x %d, %zu bytes each)", capacity, oh, ow, per);
+    }
+    if (weight) {
+        HIPCHK(hipMemcpyAsync(h->fr.w, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
+        HIPCHK(wait_stream(h->s0));                    // the caller's plane is free again
+    }
+    h->fr.on = true;
+    h->fr.var = var;
+    h->fr.every = every;
+    h->fr.r0 = r0; h->fr.c0 = c0; h->fr.oh = oh; h->fr.ow = ow; h->fr.by = by; h->fr.bx = bx;
+    h->fr.reduce = reduce;
+    h->fr.format = format;
+    h->fr.lo = lo;
+    h->fr.span = span;
+    h->fr.cap = capacity;
+    h->fr.k = every - first;                           // sample s follows tick first + s * every, ticks counted from 1 here
+    return 0;
+}
+
+extern "C" int fibhip_frames_count(fibhip_t h, long long *samples)
+{
+    NEED(h);
+    if (!samples) return fail(FIBHIP_EINVAL, "frames_count: null argument");
+    if (!h->fr.on) return fail(FIBHIP_EINVAL, "frames_count: no recorder attached (fibhip_frames_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    *samples = (h->fr.k + h->pending) / h->fr.every;   // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+
+extern "C" int fibhip_frames_shape(fibhip_t h, int *oh, int *ow, int *bytes_per_pixel)
+{
+    if (!h) return fail(FIBHIP_EINVAL, "null handle");
+    if (!h->fr.on) return fail(FIBHIP_EINVAL, "frames_shape: no recorder attached (fibhip_frames_begin)");
+    if (oh) *oh = h->fr.oh;
+    if (ow) *ow = h->fr.ow;
+    if (bytes_per_pixel) *bytes_per_pixel = h->fr.format == FIBHIP_FRAME_U8 ? 1 : 4;
+    return 0;
+}
+
+extern "C" int fibhip_frames_read(fibhip_t h, long long first, long long count, void *dst)
+{
+    NEED(h);
+    if (!h->fr.on) return fail(FIBHIP_EINVAL, "frames_read: no recorder attached (fibhip_frames_begin)");
+    FLUSH(h);
+    const long long taken = h->fr.k / h->fr.every;
+    if (first < 0 || count < 0 || first + count > taken)
+        return fail(FIBHIP_EINVAL, "frames_read: frames [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "frames_read: null destination");
+    const size_t per = h->fr.frame_bytes();
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->journal.n_fallbacks;
+        if (count > 0) HIPCHK(hipMemcpyAsync(dst, h->fr.cube + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost, h->s0));
+        SYNC_S0(h);
+        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and re-sampled, copy again)
+    }
+    return 0;
+}
+
+extern "C" int fibhip_frames_end(fibhip_t h)
+{
+    NEED(h);
+    if (!h->fr.on) return 0;
+    FLUSH(h);                                          // the ticks accepted while attached are sampled
+    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
+    frames_free(h);
     return 0;
 }

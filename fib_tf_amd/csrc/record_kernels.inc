@@ -1,4 +1,4 @@
-// record_kernels.inc — the streaming kernels behind a committed tick: the activation recorder, the electrode recorder, and the
+// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip and frame recorders, and the
 // plain copy whose shape they take (the bandwidth yardstick).  (included by kernels.hpp; the host side is record.inc)
 
 // ---- activation recorder (fibhip_observe_begin): per-cell event maps, updated after every observed tick ----------------
@@ -260,6 +260,135 @@ __global__ void __launch_bounds__(256) tip_kernel(Geo g, const float *__restrict
             }
         }
         tip_emit<1>(w, (int)i, col, cnt, rec, max_tips);
+    }
+}
+
+// ---- frame recorder (fibhip_frames_begin): a window of one state array as a frame of the movie cube ---------------------
+// Per cell, float32, every operation rounded on its own (-ffp-contract=off, IEEE division):  y = (X - lo) / span, then
+// y = y * w where a weight plane is given.  A pixel is a block of by x bx cells: POINT takes y of its upper-left cell; MEAN sums
+// each block row left to right (the row's first cell starts the sum), adds the row sums top to bottom (the first row's sum
+// starts the total) and divides by (float)(by * bx) — an order fixed by the block alone.  F32 stores the pixel; U8 stores
+// (unsigned char)(q * 255.0f + 0.5f), q the pixel with NaN -> 0, clamped to [0, 1].
+struct FrameArgs {
+    const float *x;         // the watched array (its first row), `pitch` floats between rows
+    const float *w;         // the weight plane [H][W] (wpitch floats between rows), or null
+    void *out;              // this sample's frame: [oh][ow] float32 or uint8
+    int pitch, wpitch;
+    int r0, c0, oh, ow, by, bx;
+    float lo, span;
+};
+
+static FIB_DEV float frame_cell(float x, float lo, float span) { return (x - lo) / span; }
+static FIB_DEV unsigned frame_u8(float p)
+{
+    float q = p != p ? 0.f : p;
+    q = q < 0.f ? 0.f : (q > 1.f ? 1.f : q);
+    return (unsigned)(unsigned char)(q * 255.0f + 0.5f);
+}
+
+// One pass in the shape of copy_kernel: as many 256-thread workgroups as it takes, nothing in LDS, no atomics.
+// VEC (planar slab, every row of the window starts 16-byte aligned in the array and in the weight plane, ow a multiple of 4):
+// a thread makes four consecutive pixels of one frame row.  It walks the 4 * bx cells under them as bx 16-byte pieces per
+// block row, left to right, one 16-byte load of the state and one of the weights per piece, and stores the four pixels with
+// one 16-byte (F32) or one 32-bit (U8) store.  At full resolution (bx = 1) consecutive lanes read consecutive pieces; a wider
+// block makes a lane's pieces consecutive and a wave's loads of one block row cover one contiguous span, every byte of
+// which is used.  The cell -> pixel bookkeeping (pos, k) depends on the loop counters alone: wave-uniform, kept in scalar
+// registers; the four accumulators are addressed by selects, never by a run-time index (no scratch).
+// Otherwise (row-interleaved slab, a window or a width that leaves rows unaligned, ow not a multiple of 4): one pixel per
+// thread, scalar loads and one scalar store.
+template <bool U8, bool MEAN, bool VEC>
+__global__ void __launch_bounds__(256) frame_kernel(FrameArgs a)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const float n_cells = (float)(a.by * a.bx);
+    if (VEC) {
+        const size_t ow4 = (size_t)a.ow / 4;
+        if (t >= (size_t)a.oh * ow4) return;
+        const size_t oy = t / ow4, g = t % ow4;
+        const size_t row0 = (size_t)a.r0 + oy * (size_t)a.by, col0 = (size_t)a.c0 + 4 * g * (size_t)a.bx;
+        float pix[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!MEAN || (a.by == 1 && a.bx == 1)) {
+            if (a.bx == 1) {
+                const size_t at = row0 * (size_t)a.pitch + col0;
+                const fib_v4f v = *reinterpret_cast<const fib_v4f *>(a.x + at);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pix[e] = frame_cell(v[e], a.lo, a.span);
+                if (a.w) {
+                    const fib_v4f wv = *reinterpret_cast<const fib_v4f *>(a.w + row0 * (size_t)a.wpitch + col0);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) pix[e] = pix[e] * wv[e];
+                }
+            } else {                                                  // POINT under a wider block: the four upper-left cells only
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const size_t c = col0 + (size_t)e * (size_t)a.bx;
+                    pix[e] = frame_cell(a.x[row0 * (size_t)a.pitch + c], a.lo, a.span);
+                    if (a.w) pix[e] = pix[e] * a.w[row0 * (size_t)a.wpitch + c];
+                }
+            }
+            if (MEAN) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pix[e] = pix[e] / n_cells;
+            }
+        } else {
+            for (int dy = 0; dy < a.by; ++dy) {
+                const size_t xr = (row0 + (size_t)dy) * (size_t)a.pitch + col0, wr = (row0 + (size_t)dy) * (size_t)a.wpitch + col0;
+                float rs[4] = {0.f, 0.f, 0.f, 0.f};
+                int pos = 0, k = 0;                                   // the cell's place in its pixel, and the pixel: wave-uniform
+                for (int j = 0; j < a.bx; ++j) {
+                    const fib_v4f v = *reinterpret_cast<const fib_v4f *>(a.x + xr + 4 * (size_t)j);
+                    fib_v4f wv = {1.f, 1.f, 1.f, 1.f};
+                    if (a.w) wv = *reinterpret_cast<const fib_v4f *>(a.w + wr + 4 * (size_t)j);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float y = frame_cell(v[e], a.lo, a.span);
+                        if (a.w) y = y * wv[e];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            if (k == q) rs[q] = pos == 0 ? y : rs[q] + y;
+                        if (++pos == a.bx) {
+                            pos = 0;
+                            ++k;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pix[q] = dy == 0 ? rs[q] : pix[q] + rs[q];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) pix[q] = pix[q] / n_cells;
+        }
+        const size_t o = oy * (size_t)a.ow + 4 * g;
+        if (U8) {
+            const unsigned packed = frame_u8(pix[0]) | (frame_u8(pix[1]) << 8) | (frame_u8(pix[2]) << 16) | (frame_u8(pix[3]) << 24);
+            *reinterpret_cast<unsigned *>(static_cast<unsigned char *>(a.out) + o) = packed;
+        } else {
+            fib_v4f p4 = {pix[0], pix[1], pix[2], pix[3]};
+            *reinterpret_cast<fib_v4f *>(static_cast<float *>(a.out) + o) = p4;
+        }
+    } else {
+        if (t >= (size_t)a.oh * (size_t)a.ow) return;
+        const size_t oy = t / (size_t)a.ow, ox = t % (size_t)a.ow;
+        const size_t row0 = (size_t)a.r0 + oy * (size_t)a.by, col0 = (size_t)a.c0 + ox * (size_t)a.bx;
+        float pix = 0.f;
+        if (!MEAN) {
+            pix = frame_cell(a.x[row0 * (size_t)a.pitch + col0], a.lo, a.span);
+            if (a.w) pix = pix * a.w[row0 * (size_t)a.wpitch + col0];
+        } else {
+            for (int dy = 0; dy < a.by; ++dy) {
+                const size_t xr = (row0 + (size_t)dy) * (size_t)a.pitch + col0, wr = (row0 + (size_t)dy) * (size_t)a.wpitch + col0;
+                float rs = 0.f;
+                for (int dx = 0; dx < a.bx; ++dx) {
+                    float y = frame_cell(a.x[xr + (size_t)dx], a.lo, a.span);
+                    if (a.w) y = y * a.w[wr + (size_t)dx];
+                    rs = dx == 0 ? y : rs + y;
+                }
+                pix = dy == 0 ? rs : pix + rs;
+            }
+            pix = pix / n_cells;
+        }
+        if (U8) static_cast<unsigned char *>(a.out)[t] = (unsigned char)frame_u8(pix);
+        else static_cast<float *>(a.out)[t] = pix;
     }
 }
 

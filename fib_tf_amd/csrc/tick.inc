@@ -7,6 +7,7 @@ static int autotune(fibhip_ctx *h);                               // plan.inc: t
 static int observe_enqueue(fibhip_ctx *h);
 static int electrode_advance(fibhip_ctx *h, int ticks);
 static int tips_advance(fibhip_ctx *h, int ticks);
+static int frames_advance(fibhip_ctx *h, int ticks);
 
 // ------------------------------------------------------------------------------------------
 // stepping
@@ -275,7 +276,9 @@ static int commit_impl(fibhip_t h)
         if (int rc = observe_enqueue(h)) return rc;
     if (h->el.on)
         if (int rc = electrode_advance(h, ticks)) return rc;
-    if (h->tip.on) return tips_advance(h, ticks);
+    if (h->tip.on)
+        if (int rc = tips_advance(h, ticks)) return rc;
+    if (h->fr.on) return frames_advance(h, ticks);
     return 0;
 }
 

@@ -257,6 +257,30 @@ class IonicModel:
             ensure()
         return TipRecorder(self, var2=var2, levels=levels, every=every, max_tips=max_tips, capacity=capacity, var=var, mask=mask)
 
+    def record_frames(self, every=1, first=None, window=None, block=(1, 1), reduce='mean', fmt='float32', var=0, weight='phase',
+                      levels=None, capacity=None):
+        """attaches a frame recorder (fib_tf_amd/frames.py) to this model's handle: after ticks first, first + every, ... (first
+        defaults to every; first=1 is run(im)'s own cadence) the rows and columns `window` = (r0, r1, c0, c1) of state array
+        `var` are written on the device, as one frame, into a cube kept there until `frames()` / `save()` read it.  A pixel is
+        a `block` = (by, bx) of cells reduced by `reduce` ('mean' or 'point') of y = (X - lo) / span, times `weight` ('phase':
+        the model's phase field if it has one; None; or an [height, width] array), stored as `fmt` 'float32' or 'uint8'.
+        `levels` = (lo, span) defaults to `_frame_levels()`; for var = 0 they are checked against image() on the current
+        state, bit for bit.  Default capacity: the frames of a whole run of `duration`.  Call after define(); single device
+        only (row blocks raise NotImplementedError)."""
+        from .frames import FrameRecorder
+        if not self.defined:
+            raise AssertionError('record_frames should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return FrameRecorder(self, every=every, first=first, window=window, block=block, reduce=reduce, fmt=fmt, var=var,
+                             weight=weight, levels=levels, capacity=capacity)
+
+    def _frame_levels(self):
+        """(lo, span) with image() == (X - lo) / span in float32, X the array pot() names: what a frame recorder maps the
+        state with.  Models whose image() rescales override it."""
+        return 0.0, 1.0
+
     def _image_affine(self):
         """(scale, offset) with image() == scale * X + offset, X the array pot() names: what turns an electrode's raw sum
         into mean(image() * mask).  Models whose image() rescales override it."""

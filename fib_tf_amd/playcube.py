@@ -14,15 +14,17 @@ from .screen import Screen
 
 
 def play(cube, title='reentry!', loops=1, delay=0.025, png_pattern=None, screen=None):
-    """show every frame of `cube` ([n, h, w], values 0..1) `loops` times; returns the Screen"""
+    """show every frame of `cube` ([n, h, w], values 0..1, or uint8 grey levels shown as value / 255) `loops` times; returns
+    the Screen"""
     x = np.load(cube) if isinstance(cube, str) else np.asarray(cube)
+    grey = x.dtype == np.uint8                       # a cube recorded as 8-bit grey (frames.FrameRecorder, fmt='uint8')
     if x.ndim != 3:
         raise ValueError('cube must be [frames, height, width], got shape %s' % (x.shape,))
     n, h, w = x.shape
     sc = screen if screen is not None else Screen(h, w, title, png_pattern=png_pattern)
     i = 0
     while i < n * loops and not sc.peek():
-        sc.imshow(x[i % n, :, :])
+        sc.imshow(x[i % n, :, :] / np.float32(255) if grey else x[i % n, :, :])
         if delay:
             sleep(delay)
         i += 1

@@ -423,6 +423,49 @@ int fibhip_tips_read(fibhip_t h, long long first, long long count,
                      int *records /* [count][max_tips][4], the first min(stored, max_tips) of each sample valid; may be NULL */);
 int fibhip_tips_end(fibhip_t h);
 
+/* Frame recorder: the movie.  Every `every` ticks a window of ONE state array is written on the device, as a frame, into a
+ * cube that stays there until it is read (the reference's run(im) paints image() * phase every dt_per_plot sub-steps and its
+ * drivers collect the frames into cube.npy).  Parameters: the watched array `var`; a window rows [r0, r1) x columns [c0, c1)
+ * inside the grid; a block (by, bx), each 1 .. FIBHIP_MAX_FRAME_BLOCK; a reduction, POINT or MEAN; two float32 levels lo and
+ * span (lo a number, span finite and not zero); a weight plane [height*width] float32 or NULL; a format, F32 or U8; every >= 1;
+ * first in 1 .. every; capacity >= 1 frames.  A frame has oh = (r1 - r0) / by rows of ow = (c1 - c0) / bx pixels (integer
+ * division: trailing cells are dropped; both must be >= 1).  Restated in NumPy in tests/frame_ref.py; the device equals that
+ * bit for bit.  Per cell, in float32, every operation rounded on its own (no contraction, correctly rounded division):
+ *     y = (X - lo) / span;      y = y * w   when a weight plane is given
+ * With lo = (float)min_v, span = (float)(max_v - min_v), w = the phase field this is image() * phase of the stock models.
+ *     POINT  the pixel is y of the block's upper-left cell
+ *     MEAN   every block row is summed left to right, starting from its first cell; the row sums are added top to bottom,
+ *            starting from the first row's; the total is divided by (float)(by * bx).  The order depends on the block alone:
+ *            the same state gives the same bits under every launch plan.
+ *     F32    stores the pixel
+ *     U8     stores (unsigned char)(q * 255.0f + 0.5f), truncated, q = the pixel with NaN replaced by 0, then clamped to [0, 1]
+ * Sample s follows tick number first + s * every, ticks counted from 1 at frames_begin: first = every is the cadence of the
+ * electrode and tip recorders, first = 1 that of run(im) (a frame after ticks 0, every, 2 * every, ... of its loop).  Pacing,
+ * set_state and step_slow / step_mode between two ticks belong to the next tick.  The cube does not wrap: a fibhip_step that
+ * would take frame number `capacity` is refused with FIBHIP_EINVAL ("trace full") before anything of that call is enqueued.
+ * What holds for the electrode and tip recorders holds here: no launch spans a sample tick, multi-tick launches go on between
+ * two samples, nothing runs ahead, a launch goes out when the ticks up to the next sample tick have been accepted, and
+ * Courtemanche's tick is not fused with 'slow' when a frame of a slow array is due at that tick.  All three may be attached
+ * at once, each with its own stride.
+ * Refused with FIBHIP_EINVAL: a row block, inside an open tick, and every argument outside the ranges above; a cube that cannot
+ * be allocated: FIBHIP_ENOMEM.
+ *   fibhip_frames_begin  flushes, synchronises and confirms pending work, copies the weight plane and attaches; again:
+ *                        re-attaches, empty cube
+ *   fibhip_frames_count  frames taken so far (ticks accepted but not launched yet included)
+ *   fibhip_frames_shape  oh, ow and the bytes per pixel (4 or 1) of the attached recorder
+ *   fibhip_frames_read   frames [first, first + count) as [count][oh][ow] float32 or uint8; flushes and blocks like get_state;
+ *                        does not detach
+ *   fibhip_frames_end    detaches and frees the cube (no recorder attached: nothing); fibhip_destroy does the same            */
+#define FIBHIP_MAX_FRAME_BLOCK 16
+enum fibhip_frame_reduce { FIBHIP_FRAME_POINT = 0, FIBHIP_FRAME_MEAN = 1 };
+enum fibhip_frame_format { FIBHIP_FRAME_F32 = 0, FIBHIP_FRAME_U8 = 1 };
+int fibhip_frames_begin(fibhip_t h, int var, const int *window /* r0, r1, c0, c1 */, int by, int bx, int reduce, float lo, float span,
+                        const float *weight /* [H*W] or NULL */, int format, int every, int first, long long capacity);
+int fibhip_frames_count(fibhip_t h, long long *samples);
+int fibhip_frames_shape(fibhip_t h, int *oh, int *ow, int *bytes_per_pixel);
+int fibhip_frames_read(fibhip_t h, long long first, long long count, void *dst);
+int fibhip_frames_end(fibhip_t h);
+
 const char *fibhip_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)
