@@ -13,5 +13,6 @@ from .br import BeelerReuter                    # noqa: F401
 from .court import Courtemanche                 # noqa: F401
 from . import tips                              # noqa: F401  (TipRecorder, link: spiral tips recorded on the device)
 from . import frames                            # noqa: F401  (FrameRecorder: the movie cube recorded on the device)
+from . import stats                             # noqa: F401  (StatsRecorder: tissue statistics recorded on the device)
 
 __all__ = ['IonicModel', 'Fenton4v', 'BeelerReuter', 'Courtemanche']

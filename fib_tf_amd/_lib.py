@@ -18,6 +18,8 @@ FENTON4V, BR, COURT, COURT_US, CUSTOM = 0, 1, 2, 3, 4
 OBS_MAPS = ('first_up', 'last_up', 'prev_up', 'apd', 'count')     # enum fibhip_obs_map, in order
 FRAME_REDUCE = ('point', 'mean')                                  # enum fibhip_frame_reduce, in order
 FRAME_FORMAT = ('float32', 'uint8')                               # enum fibhip_frame_format, in order
+STAT_KINDS = ('sum', 'min', 'max', 'below', 'above', 'nonfinite')  # enum fibhip_stat_kind, in order
+MAX_STAT_COLS, MAX_STAT_COLS_PER_ARRAY = 64, 8
 CHEBY, SKIP, CHRONIC, FAST, ALLVARS, ROW_INTERLEAVED, ZEROPAD, HOLD = 1, 2, 4, 8, 16, 32, 64, 128
 
 # -ffp-contract=off: FMAs appear only where the source writes them (policy hook P::mad).
@@ -107,6 +109,10 @@ class HaloMsg(C.Structure):
     _fields_ = [('offset', C.c_longlong), ('count', C.c_longlong), ('peer', C.c_int), ('send', C.c_int)]
 
 
+class StatCol(C.Structure):
+    _fields_ = [('var', C.c_int), ('kind', C.c_int), ('level', C.c_float)]
+
+
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
 _h = C.c_void_p
@@ -184,6 +190,10 @@ SYMBOLS = {
     'fibhip_frames_shape': ([_h, _ip, _ip, _ip], C.c_int),
     'fibhip_frames_read': ([_h, C.c_longlong, C.c_longlong, C.c_void_p], C.c_int),
     'fibhip_frames_end': ([_h], C.c_int),
+    'fibhip_stats_begin': ([_h, C.c_int, C.POINTER(StatCol), _fp, C.POINTER(C.c_ubyte), C.c_int, C.c_longlong], C.c_int),
+    'fibhip_stats_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_stats_read': ([_h, C.c_longlong, C.c_longlong, C.POINTER(C.c_double)], C.c_int),
+    'fibhip_stats_end': ([_h], C.c_int),
     'fibhip_last_error': ([], C.c_char_p),
 }
 
@@ -804,3 +814,45 @@ class Stepper:
 
     def frames_end(self):
         self._ck(self._L.fibhip_frames_end(self._h))
+
+    # ---- statistics recorder (include/fibhip.h fibhip_stats_*) ----------------------------------------------------
+    def stats_begin(self, cols, weight=None, mask=None, every=1, capacity=1):
+        """attaches the statistics recorder: `cols` is a list of (var, kind, level) with kind one of STAT_KINDS (or its
+        number), `weight` an [height, width] float32 plane or None (what SUM columns weigh with), `mask` an [height, width]
+        array, non-zero where a cell counts for the other kinds, or None; one row of float64 every `every` ticks, `capacity`
+        rows at the most"""
+        arr = (StatCol * max(len(cols), 1))()
+        for i, (var, kind, level) in enumerate(cols):
+            arr[i].var, arr[i].kind = int(var), STAT_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+            arr[i].level = float(level)
+        wp = mp = None
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, np.float32)
+            if weight.shape != (self.height, self.width):
+                raise ValueError('stats_begin: a weight plane of shape %s on a %d x %d grid' % (weight.shape, self.height, self.width))
+            wp = weight.ctypes.data_as(_fp)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.shape != (self.height, self.width):
+                raise ValueError('stats_begin: a mask of shape %s on a %d x %d grid' % (mask.shape, self.height, self.width))
+            mp = mask.ctypes.data_as(C.POINTER(C.c_ubyte))
+        self._ck(self._L.fibhip_stats_begin(self._h, len(cols), arr, wp, mp, int(every), int(capacity)))
+        self._st_n = len(cols)
+
+    def stats_count(self):
+        """samples taken since stats_begin (ticks accepted but not launched yet included)"""
+        k = C.c_longlong()
+        self._ck(self._L.fibhip_stats_count(self._h, C.byref(k)))
+        return int(k.value)
+
+    def stats_read(self, first=0, count=None):
+        """samples [first, first + count) as a float64 [count, ncols] array (count=None: all taken so far); blocks like
+        get_state, detaches nothing"""
+        if count is None:
+            count = self.stats_count() - int(first)
+        out = np.empty((max(int(count), 0), getattr(self, '_st_n', 0)), np.float64)
+        self._ck(self._L.fibhip_stats_read(self._h, int(first), int(count), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def stats_end(self):
+        self._ck(self._L.fibhip_stats_end(self._h))

@@ -101,6 +101,39 @@ def cl_observer(m, cyclelengths, i0, i, cl):
         print('%d:\t%d\t%.3f\t%.3f' % (i + i0, cl, mean_na, mean_ca))
 
 
+def image_level(m, cutoff):
+    """the float32 level L with  image() < cutoff  <=>  V < L  for every float32 V (NaN is in neither): image() is
+    (V - lo) / span in float32 (`_frame_levels`), which never decreases with V, so the cells below the cutoff are the cells
+    below the smallest V that reaches it.  Found by walking float32 neighbours from lo + cutoff * span."""
+    lo, span = (np.float32(v) for v in m._frame_levels())
+    cut = np.float32(cutoff)
+
+    def below(v):
+        return (np.float32(v) - lo) / span < cut
+    L = np.float32(float(lo) + float(cutoff) * float(span))
+    while not below(L):
+        L = np.nextafter(L, np.float32(-np.inf))
+    while below(L):
+        L = np.nextafter(L, np.float32(np.inf))
+    return float(L)
+
+
+def record_observables(m, every=1, capacity=None):
+    """the reference observer's whole-tissue numbers, recorded on the device every `every` ticks (fib_tf_amd/stats.py) instead
+    of polled: the ϕ-weighted means of `_Na_i_` and `_f_Ca_` — and of `_us_` with `ultra_slow` — that `cl_observer`
+    (court_ultra.py:465-486) takes from whole arrays read back, ρ (court_ultra.py:504-509: the share of the tissue, phase >
+    1e-3, whose image() is below 0.2, -55 mV) as the column 'V_frac_below', and a count of cells that are not finite.
+    The observer's two means of FUNCTIONS of V (us_infinity, tau_us) are not recorded: a mean of f(V) is not f of a mean, and
+    the recorder takes statistics of state arrays only.  Returns the StatsRecorder (a context manager)."""
+    if m.phase is None:
+        raise AssertionError('record_observables: the observer weighs with the phase field; this model has none')
+    cols = [('_Na_i_', 'mean'), ('_f_Ca_', 'mean')]
+    if m.ultra_slow:
+        cols.append(('_us_', 'mean'))
+    cols += [('V', 'frac_below', image_level(m, 0.2)), ('V', 'nonfinite')]
+    return m.record_stats(cols, every=every, weight='phase', mask=np.asarray(m.phase) > 1e-3, capacity=capacity)
+
+
 def run_small(config, im, cyclelengths, radius=50, i0=0, state_file='state_small'):
     """the two-stage protocol's first stage (court_ultra.py:489-512): annular domain, S1-S2, checkpoint"""
     m = Courtemanche(config)

@@ -161,6 +161,25 @@ struct FrRec {
     size_t frame_bytes() const { return (size_t)oh * (size_t)ow * (format == FIBHIP_FRAME_U8 ? 1u : 4u); }
 };
 
+// statistics recorder (fibhip_stats_begin): the fourth sampler — no launch spans a sample tick (sample_room), and the hook on
+// the plain and the multi-tick commit path (stats_advance) enqueues stats_kernel and stats_combine_kernel behind the launch
+// that ends one
+struct StRec {
+    bool on;
+    int ncols, narr, every;
+    int vars[FIB_MAXVAR];   // the distinct arrays the columns name, in order of first appearance (slow_sample_due)
+    long long cap;          // samples the trace holds
+    long long k;            // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
+    int nchunks;            // chunks of one array: stats_kernel's grid is (nchunks, narr)
+    StChunk *chunks;        // device: the chunk table
+    StArr *arrs;            // device: the columns of every array
+    StCol *cols;            // device: where column c of a row comes from
+    float *w;               // device: the weight plane [H][W], or null
+    unsigned char *mask;    // device: [H][W], or null
+    unsigned long long *part;       // device: [narr][ST_SLOTS][nchunks], one partial per (column, chunk)
+    double *trace;          // device: [cap][ncols]
+};
+
 // fibhip_trace_begin / _end: the launches in between, each between two HIP events
 struct TraceRec {
     hipEvent_t e0, e1;
@@ -220,6 +239,7 @@ struct fibhip_ctx {
     ElRec el;
     TipRec tip;
     FrRec fr;
+    StRec st;
     std::vector<TraceRec> trace;
     bool tracing;
     // ---- the rest ----

@@ -1,6 +1,6 @@
-// record.inc — the four recorders that run on the device while a model runs: the per-cell activation maps
-// (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*) and the movie cube
-// (fibhip_frames_*).  Each is a hook behind a committed launch plus its entry
+// record.inc — the five recorders that run on the device while a model runs: the per-cell activation maps
+// (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
+// (fibhip_frames_*) and the tissue statistics (fibhip_stats_*).  Each is a hook behind a committed launch plus its entry
 // points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
 // (included by fibhip.hip, behind sched.inc)
 
@@ -166,6 +166,75 @@ static void frames_free(fibhip_ctx *h)
     h->fr.w = nullptr;
     h->fr.cube = nullptr;
     h->fr.on = false;
+}
+
+static_assert(ST_SLOTS == FIBHIP_MAX_STAT_COLS_PER_ARRAY && (int)ST_KINDS == (int)FIBHIP_STAT_NONFINITE + 1 && (int)ST_SUM == (int)FIBHIP_STAT_SUM &&
+                  (int)ST_BELOW == (int)FIBHIP_STAT_BELOW && ST_MAX_CHUNKS == 4 * 64 && ST_MIN_CHUNK % 4 == 0,
+              "stats_kernel's constants follow include/fibhip.h; stats_combine_kernel folds four chunks per lane of one wave");
+// The statistics recorder's hook, the electrode recorder's step for step: at a sample tick stats_kernel is enqueued on s0 behind
+// the launch that ended there (one partial per column and chunk), and stats_combine_kernel behind it (the sample's row).  The
+// row's slot is a kernel argument computed from the host's counter, so a replay (recover()) writes the same slot again; the
+// partials are rewritten whole by every sample.
+static int stats_advance(fibhip_ctx *h, int ticks)
+{
+    StRec &r = h->st;
+    r.k += ticks;
+    if (r.k % r.every) return 0;
+    const long long s = r.k / r.every - 1;
+    if (s >= r.cap) return fail(FIBHIP_EINVAL, "statistics recorder: trace full");             // (fibhip_step refuses before this)
+    StArgs a;
+    a.slab0 = h->slab[0];
+    a.slab1 = h->slab[1];
+    a.cur_mask = 0u;
+    uintptr_t align = reinterpret_cast<uintptr_t>(r.w) | reinterpret_cast<uintptr_t>(r.mask);
+    for (int i = 0; i < r.narr; ++i) {
+        const int v = r.vars[i];
+        if (h->cur[v]) a.cur_mask |= 1u << v;
+        align |= reinterpret_cast<uintptr_t>(h->slab[h->cur[v]] + (size_t)v * h->vstride);
+    }
+    a.W = h->d.width;
+    a.pitch = h->pitch;
+    a.vstride = h->vstride;
+    a.chunks = r.chunks;
+    a.arrs = r.arrs;
+    a.w = r.w;
+    a.mask = r.mask;
+    a.part = r.part;
+    a.nchunks = r.nchunks;
+    // (the chunk table was cut for the vector path exactly when pitch == W and W % 4 == 0; the pointers are looked at here)
+    const bool vec = h->pitch == h->d.width && h->d.width % 4 == 0 && (align & 15u) == 0;
+    const dim3 grid((unsigned)r.nchunks, (unsigned)r.narr);
+    if (int rc = trace_open(h, h->s0, "stats_kernel", 0, 0, 0, 0, 1)) return rc;
+    if (vec) hipLaunchKernelGGL(stats_kernel<true>, grid, dim3(ST_THREADS), 0, h->s0, a);
+    else hipLaunchKernelGGL(stats_kernel<false>, grid, dim3(ST_THREADS), 0, h->s0, a);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    if (int rc = trace_open(h, h->s0, "stats_combine_kernel", 0, 0, 0, 0, 1)) return rc;
+    hipLaunchKernelGGL(stats_combine_kernel, dim3(1), dim3(256), 0, h->s0, r.cols, r.ncols, r.part, r.nchunks, r.trace + (size_t)s * r.ncols);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    return 0;
+}
+
+static void stats_free(fibhip_ctx *h)
+{
+    if (h->st.chunks) hipFree(h->st.chunks);
+    if (h->st.arrs) hipFree(h->st.arrs);
+    if (h->st.cols) hipFree(h->st.cols);
+    if (h->st.w) hipFree(h->st.w);
+    if (h->st.mask) hipFree(h->st.mask);
+    if (h->st.part) hipFree(h->st.part);
+    if (h->st.trace) hipFree(h->st.trace);
+    h->st.chunks = nullptr;
+    h->st.arrs = nullptr;
+    h->st.cols = nullptr;
+    h->st.w = nullptr;
+    h->st.mask = nullptr;
+    h->st.part = nullptr;
+    h->st.trace = nullptr;
+    h->st.on = false;
 }
 
 // ---- activation recorder ------------------------------------------------------------------------------------------------
@@ -536,5 +605,146 @@ extern "C" int fibhip_frames_end(fibhip_t h)
     FLUSH(h);                                          // the ticks accepted while attached are sampled
     SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
     frames_free(h);
+    return 0;
+}
+
+// ---- statistics recorder ------------------------------------------------------------------------------------------------
+extern "C" int fibhip_stats_begin(fibhip_t h, int ncols, const fibhip_stat_col *cols, const float *weight, const unsigned char *mask,
+                                  int every, long long capacity)
+{
+    NEED(h);
+    if (!cols) return fail(FIBHIP_EINVAL, "stats_begin: null argument");
+    if (ncols < 1 || ncols > FIBHIP_MAX_STAT_COLS) return fail(FIBHIP_EINVAL, "stats_begin: 1 .. %d columns (got %d)", FIBHIP_MAX_STAT_COLS, ncols);
+    std::vector<StArr> arrs;
+    std::vector<StCol> table;
+    bool need_w = false, need_m = false;
+    for (int c = 0; c < ncols; ++c) {
+        const fibhip_stat_col &col = cols[c];
+        if (col.var < 0 || col.var >= h->nvar) return fail(FIBHIP_EINVAL, "stats_begin: column %d: bad var %d", c, col.var);
+        if (col.kind < 0 || col.kind >= ST_KINDS) return fail(FIBHIP_EINVAL, "stats_begin: column %d: unknown kind %d", c, col.kind);
+        if ((col.kind == FIBHIP_STAT_BELOW || col.kind == FIBHIP_STAT_ABOVE) && std::isnan(col.level))
+            return fail(FIBHIP_EINVAL, "stats_begin: column %d: the level must be a number", c);
+        size_t a = 0;
+        while (a < arrs.size() && arrs[a].var != col.var) ++a;
+        if (a == arrs.size()) {
+            StArr n;
+            memset(&n, 0, sizeof n);
+            n.var = col.var;
+            arrs.push_back(n);
+        }
+        StArr &A = arrs[a];
+        if (A.ncols == FIBHIP_MAX_STAT_COLS_PER_ARRAY)
+            return fail(FIBHIP_EINVAL, "stats_begin: column %d: more than %d columns on array %d", c, FIBHIP_MAX_STAT_COLS_PER_ARRAY, col.var);
+        A.kind[A.ncols] = col.kind;
+        A.level[A.ncols] = col.level;
+        (col.kind == FIBHIP_STAT_SUM ? A.need_w : A.need_m) = 1;
+        (col.kind == FIBHIP_STAT_SUM ? need_w : need_m) = true;
+        StCol t;
+        t.arr = (int)a; t.slot = A.ncols; t.kind = col.kind; t.pad = 0;
+        table.push_back(t);
+        A.ncols++;
+    }
+    if (every < 1) return fail(FIBHIP_EINVAL, "stats_begin: every must be >= 1 (got %d)", every);
+    if (capacity < 1 || capacity > (long long)(SIZE_MAX / sizeof(double) / (size_t)ncols))
+        return fail(FIBHIP_EINVAL, "stats_begin: bad capacity %lld", capacity);
+    if (weight)
+        for (size_t i = 0; i < h->cells; ++i)
+            if (!std::isfinite(weight[i]))
+                return fail(FIBHIP_EINVAL, "stats_begin: the weight plane has a value that is not finite (row %zu, column %zu)",
+                            i / (size_t)h->d.width, i % (size_t)h->d.width);
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "stats_begin: not on a row block (a handle with ghost rows)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "stats_begin inside an open tick");
+    if (h->st.on) return fail(FIBHIP_EINVAL, "stats_begin: a recorder is attached already (fibhip_stats_end first)");
+    // stats_kernel counts cells in 32 bits, and a thread looks up to one batch beyond its chunk's end before it drops the cell
+    if (h->cells > (size_t)UINT_MAX - 4u * ST_VBATCH * ST_THREADS)
+        return fail(FIBHIP_EINVAL, "stats_begin: a grid of %zu cells is too large for the recorder's 32-bit cell index", h->cells);
+    // the chunk table, from H, W and the pitch alone: at most ST_MAX_CHUNKS equal chunks of at least ST_MIN_CHUNK cells, a
+    // multiple of four cells each where the vector path may run (so that every chunk starts 16-byte aligned there)
+    std::vector<StChunk> chunks;
+    {
+        const size_t n = h->cells;
+        size_t cs = (n + ST_MAX_CHUNKS - 1) / ST_MAX_CHUNKS;
+        if (cs < ST_MIN_CHUNK) cs = ST_MIN_CHUNK;
+        if (h->pitch == h->d.width && h->d.width % 4 == 0) cs = (cs + 3) / 4 * 4;
+        for (size_t first = 0; first < n; first += cs) {
+            StChunk c;
+            c.first = (unsigned)first;
+            c.count = (unsigned)(first + cs <= n ? cs : n - first);
+            chunks.push_back(c);
+        }
+    }
+    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    stats_free(h);
+    StRec &r = h->st;
+    bool ok = hipMalloc((void **)&r.chunks, chunks.size() * sizeof(StChunk)) == hipSuccess &&
+              hipMalloc((void **)&r.arrs, arrs.size() * sizeof(StArr)) == hipSuccess &&
+              hipMalloc((void **)&r.cols, table.size() * sizeof(StCol)) == hipSuccess &&
+              hipMalloc((void **)&r.part, arrs.size() * ST_SLOTS * chunks.size() * sizeof(unsigned long long)) == hipSuccess &&
+              hipMalloc((void **)&r.trace, (size_t)capacity * (size_t)ncols * sizeof(double)) == hipSuccess;
+    if (ok && weight && need_w) ok = hipMalloc((void **)&r.w, h->cells * sizeof(float)) == hipSuccess;
+    if (ok && mask && need_m) ok = hipMalloc((void **)&r.mask, h->cells) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        stats_free(h);
+        return fail(FIBHIP_ENOMEM, "stats_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d columns)", capacity, ncols);
+    }
+    HIPCHK(hipMemcpyAsync(r.chunks, chunks.data(), chunks.size() * sizeof(StChunk), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemcpyAsync(r.arrs, arrs.data(), arrs.size() * sizeof(StArr), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemcpyAsync(r.cols, table.data(), table.size() * sizeof(StCol), hipMemcpyHostToDevice, h->s0));
+    if (r.w) HIPCHK(hipMemcpyAsync(r.w, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    if (r.mask) HIPCHK(hipMemcpyAsync(r.mask, mask, h->cells, hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemsetAsync(r.trace, 0, (size_t)capacity * (size_t)ncols * sizeof(double), h->s0));
+    HIPCHK(wait_stream(h->s0));                        // the tables and the caller's planes are free again
+    r.on = true;
+    r.ncols = ncols;
+    r.narr = (int)arrs.size();
+    for (int a = 0; a < r.narr; ++a) r.vars[a] = arrs[a].var;
+    r.every = every;
+    r.cap = capacity;
+    r.k = 0;
+    r.nchunks = (int)chunks.size();
+    return 0;
+}
+
+extern "C" int fibhip_stats_count(fibhip_t h, long long *samples)
+{
+    NEED(h);
+    if (!samples) return fail(FIBHIP_EINVAL, "stats_count: null argument");
+    if (!h->st.on) return fail(FIBHIP_EINVAL, "stats_count: no recorder attached (fibhip_stats_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    *samples = (h->st.k + h->pending) / h->st.every;   // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+
+extern "C" int fibhip_stats_read(fibhip_t h, long long first, long long count, double *dst)
+{
+    NEED(h);
+    if (!h->st.on) return fail(FIBHIP_EINVAL, "stats_read: no recorder attached (fibhip_stats_begin)");
+    FLUSH(h);
+    const long long taken = h->st.k / h->st.every;
+    if (first < 0 || count < 0 || first + count > taken)
+        return fail(FIBHIP_EINVAL, "stats_read: samples [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "stats_read: null destination");
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->journal.n_fallbacks;
+        if (count > 0)
+            HIPCHK(hipMemcpyAsync(dst, h->st.trace + (size_t)first * h->st.ncols, (size_t)count * h->st.ncols * sizeof(double),
+                                  hipMemcpyDeviceToHost, h->s0));
+        SYNC_S0(h);
+        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and re-sampled, copy again)
+    }
+    return 0;
+}
+
+extern "C" int fibhip_stats_end(fibhip_t h)
+{
+    NEED(h);
+    if (!h->st.on) return 0;
+    FLUSH(h);                                          // the ticks accepted while attached are sampled
+    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
+    stats_free(h);
     return 0;
 }

@@ -1,4 +1,4 @@
-// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip and frame recorders, and the
+// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame and statistics recorders, and the
 // plain copy whose shape they take (the bandwidth yardstick).  (included by kernels.hpp; the host side is record.inc)
 
 // ---- activation recorder (fibhip_observe_begin): per-cell event maps, updated after every observed tick ----------------
@@ -389,6 +389,218 @@ __global__ void __launch_bounds__(256) frame_kernel(FrameArgs a)
         }
         if (U8) static_cast<unsigned char *>(a.out)[t] = (unsigned char)frame_u8(pix);
         else static_cast<float *>(a.out)[t] = pix;
+    }
+}
+
+// ---- statistics recorder (fibhip_stats_begin): whole-tissue scalars of several state arrays, one row per sample -----------
+// A column is {array, kind, level}; the host groups the columns by array (StArr: up to ST_SLOTS columns each) and cuts the
+// H x W cells, row-major, into chunks (StChunk) from H, W and the pitch alone.  Grid (chunks, arrays): a workgroup of
+// ST_THREADS threads walks ONE chunk of ONE array once and evaluates every column on that array, so each array named is read
+// once per sample; the weight plane is read where the array has a SUM column, the mask where it has any other.
+//   SUM        acc = acc + (double)w * (double)x over the cells with w != 0 (w = 1 without a plane): the product of two float32
+//              is exact in double, the addition is rounded on its own (-ffp-contract=off: no fma)
+//   MIN, MAX   over the masked cells, `x < acc` / `x > acc` from +inf / -inf: a NaN compares false and is ignored
+//   BELOW, ABOVE, NONFINITE   32-bit counts per thread, 64-bit from the wave on
+// VEC (planar slab, pitch == W, W a multiple of 4, every pointer 16-byte aligned): thread t takes the chunk's 16-byte groups
+// t, t + ST_THREADS, ... with ST_VBATCH groups' loads in flight, the mask as one 32-bit load per group.  Otherwise thread t
+// takes the cells t, t + ST_THREADS, ... one load each, ST_SBATCH in flight.  A cell beyond the chunk's end gets w = 0 and
+// mask = 0 (and an in-range address), which drops it from every column.  The kernel is a pure streaming read.
+// The accumulators of the up to ST_SLOTS columns are addressed by fully unrolled loops only (a run-time index would put them
+// in scratch: frame_kernel's note); the column's kind is wave-uniform, so the switch is a scalar branch per batch, not per
+// cell.  Per thread the order is fixed; then six levels of __shfl_down in each wave, the wave results through LDS, a fixed
+// tree over the four of them by one thread per column, and ONE plain 64-bit store per (column, chunk) into the partials
+// [array][slot][chunk].  stats_combine_kernel — a second launch on the same stream, the launch-boundary reduce that makes
+// float sums reproducible bit for bit — folds the chunks of every column in a fixed tree and writes the sample's row.
+// No floating-point atomics, no atomics at all.
+#define ST_THREADS 256
+#define ST_VBATCH 4
+#define ST_SBATCH 8
+#define ST_SLOTS 8              // columns on one array
+#define ST_MAX_CHUNKS 256       // chunks of one array: what stats_combine_kernel folds per column, four per lane
+#define ST_MIN_CHUNK 1024       // cells (a multiple of 4): one 16-byte group per thread
+enum { ST_SUM = 0, ST_MIN = 1, ST_MAX = 2, ST_BELOW = 3, ST_ABOVE = 4, ST_NONFINITE = 5, ST_KINDS = 6 };
+struct StChunk {
+    unsigned first, count;      // cells [first, first + count) of the grid, row-major; both multiples of 4 on the VEC path
+};
+struct StArr {
+    int var, ncols;
+    int need_w, need_m;         // a SUM column / a column of any other kind
+    int kind[ST_SLOTS];
+    float level[ST_SLOTS];
+};
+struct StCol {
+    int arr, slot, kind, pad;   // where column c of the row comes from
+};
+struct StArgs {
+    const float *slab0, *slab1;
+    unsigned cur_mask;          // bit v: array v lives in slab1
+    int W, pitch;
+    unsigned long long vstride;
+    const StChunk *chunks;
+    const StArr *arrs;
+    const float *w;             // [H][W] or null
+    const unsigned char *mask;  // [H][W] or null
+    unsigned long long *part;   // [narr][ST_SLOTS][nchunks]
+    int nchunks;
+};
+
+static FIB_DEV unsigned long long st_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
+static FIB_DEV double st_dbl(unsigned long long b) { return __longlong_as_double((long long)b); }
+static FIB_DEV unsigned long long st_identity(int kind)
+{
+    return kind == ST_MIN ? st_bits(__builtin_huge_val()) : kind == ST_MAX ? st_bits(-__builtin_huge_val()) : 0ull;
+}
+// a (the earlier operand) combined with b: a double sum, the smaller / larger double (no NaN gets this far), or an integer sum
+static FIB_DEV unsigned long long st_fold(int kind, unsigned long long a, unsigned long long b)
+{
+    if (kind == ST_SUM) return st_bits(st_dbl(a) + st_dbl(b));
+    if (kind == ST_MIN) return st_dbl(b) < st_dbl(a) ? b : a;
+    if (kind == ST_MAX) return st_dbl(b) > st_dbl(a) ? b : a;
+    return a + b;
+}
+static FIB_DEV unsigned long long st_wave_fold(int kind, unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = st_fold(kind, v, __shfl_down(v, off, 64));
+    return v;
+}
+
+// N cells of one thread (x, weight, mask: registers) into the accumulators of the array's columns
+template <int N>
+static FIB_DEV void st_take(const StArr *__restrict__ d, const float (&x)[N], const float (&w)[N], const bool (&m)[N],
+                            double (&sd)[ST_SLOTS], unsigned (&sn)[ST_SLOTS])
+{
+    const int ncols = d->ncols;
+#pragma unroll
+    for (int j = 0; j < ST_SLOTS; ++j) {
+        if (j >= ncols) continue;                                     // (wave-uniform, like `kind`)
+        const int kind = d->kind[j];
+        const float level = d->level[j];
+        if (kind == ST_SUM) {
+#pragma unroll
+            for (int e = 0; e < N; ++e)
+                if (w[e] != 0.f) sd[j] = sd[j] + (double)w[e] * (double)x[e];
+        } else if (kind == ST_MIN) {
+#pragma unroll
+            for (int e = 0; e < N; ++e)
+                if (m[e] && (double)x[e] < sd[j]) sd[j] = (double)x[e];
+        } else if (kind == ST_MAX) {
+#pragma unroll
+            for (int e = 0; e < N; ++e)
+                if (m[e] && (double)x[e] > sd[j]) sd[j] = (double)x[e];
+        } else if (kind == ST_BELOW) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) sn[j] += (m[e] && x[e] < level) ? 1u : 0u;
+        } else if (kind == ST_ABOVE) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) sn[j] += (m[e] && x[e] > level) ? 1u : 0u;
+        } else {
+#pragma unroll
+            for (int e = 0; e < N; ++e) sn[j] += (m[e] && !(__builtin_fabsf(x[e]) < __builtin_huge_valf())) ? 1u : 0u;
+        }
+    }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(ST_THREADS) stats_kernel(StArgs a)
+{
+    __shared__ unsigned long long wres[ST_THREADS / 64][ST_SLOTS];
+    const StArr *__restrict__ d = a.arrs + blockIdx.y;
+    const StChunk c = a.chunks[blockIdx.x];
+    const float *__restrict__ x = (((a.cur_mask >> d->var) & 1u) ? a.slab1 : a.slab0) + (size_t)d->var * (size_t)a.vstride;
+    const float *__restrict__ wp = d->need_w ? a.w : nullptr;
+    const unsigned char *__restrict__ mp = d->need_m ? a.mask : nullptr;
+    const unsigned end = c.first + c.count;
+    double sd[ST_SLOTS];
+    unsigned sn[ST_SLOTS];
+#pragma unroll
+    for (int j = 0; j < ST_SLOTS; ++j) {
+        sd[j] = j < d->ncols ? st_dbl(st_identity(d->kind[j])) : 0.0;
+        sn[j] = 0u;
+    }
+    if (VEC) {
+        for (unsigned p0 = c.first + 4u * threadIdx.x; p0 < end; p0 += 4u * ST_VBATCH * ST_THREADS) {
+            fib_v4f xv[ST_VBATCH], wv[ST_VBATCH];
+            unsigned mv[ST_VBATCH];
+#pragma unroll
+            for (int b = 0; b < ST_VBATCH; ++b) {
+                const unsigned p = p0 + 4u * (unsigned)b * ST_THREADS;
+                const bool in = p < end;
+                const unsigned q = in ? p : c.first;                  // (an in-range address; the cells are dropped below)
+                xv[b] = *reinterpret_cast<const fib_v4f *>(x + q);
+                const fib_v4f one = {1.f, 1.f, 1.f, 1.f};
+                wv[b] = wp ? *reinterpret_cast<const fib_v4f *>(wp + q) : one;
+                mv[b] = mp ? *reinterpret_cast<const unsigned *>(mp + q) : 0x01010101u;
+                if (!in) {
+                    const fib_v4f zero = {0.f, 0.f, 0.f, 0.f};
+                    wv[b] = zero;
+                    mv[b] = 0u;
+                }
+            }
+            float xs[4 * ST_VBATCH], ws[4 * ST_VBATCH];
+            bool ms[4 * ST_VBATCH];
+#pragma unroll
+            for (int b = 0; b < ST_VBATCH; ++b)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    xs[4 * b + e] = xv[b][e];
+                    ws[4 * b + e] = wv[b][e];
+                    ms[4 * b + e] = ((mv[b] >> (8 * e)) & 0xFFu) != 0u;
+                }
+            st_take<4 * ST_VBATCH>(d, xs, ws, ms, sd, sn);
+        }
+    } else {
+        for (unsigned p0 = c.first + threadIdx.x; p0 < end; p0 += ST_SBATCH * ST_THREADS) {
+            float xs[ST_SBATCH], ws[ST_SBATCH];
+            bool ms[ST_SBATCH];
+#pragma unroll
+            for (int b = 0; b < ST_SBATCH; ++b) {
+                const unsigned p = p0 + (unsigned)b * ST_THREADS;
+                const bool in = p < end;
+                const unsigned q = in ? p : c.first;
+                const unsigned r = q / (unsigned)a.W, col = q - r * (unsigned)a.W;
+                xs[b] = x[(size_t)r * (size_t)a.pitch + col];
+                const float wq = wp ? wp[q] : 1.f;
+                const bool mq = mp ? mp[q] != 0 : true;
+                ws[b] = in ? wq : 0.f;
+                ms[b] = in && mq;
+            }
+            st_take<ST_SBATCH>(d, xs, ws, ms, sd, sn);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < ST_SLOTS; ++j) {
+        if (j >= d->ncols) continue;
+        const int kind = d->kind[j];
+        const unsigned long long v = st_wave_fold(kind, kind <= ST_MAX ? st_bits(sd[j]) : (unsigned long long)sn[j]);
+        if ((threadIdx.x & 63) == 0) wres[threadIdx.x >> 6][j] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < d->ncols) {
+        const int kind = a.arrs[blockIdx.y].kind[threadIdx.x];         // (from memory: the slot is a run-time index here)
+        const unsigned long long v = st_fold(kind, st_fold(kind, wres[0][threadIdx.x], wres[1][threadIdx.x]),
+                                             st_fold(kind, wres[2][threadIdx.x], wres[3][threadIdx.x]));
+        a.part[((size_t)blockIdx.y * ST_SLOTS + threadIdx.x) * (size_t)a.nchunks + blockIdx.x] = v;
+    }
+}
+
+// ONE workgroup of four waves; wave v folds the columns v, v + 4, ...: lane l takes the partials of chunks 4l .. 4l + 3 as
+// (p0 . p1) . (p2 . p3) (the identity where the array has fewer chunks), then the six levels of the wave.  Counts are stored
+// converted to double, which is exact.
+__global__ void __launch_bounds__(256) stats_combine_kernel(const StCol *__restrict__ cols, int ncols, const unsigned long long *__restrict__ part,
+                                                            int nchunks, double *__restrict__ row)
+{
+    const int lane = (int)(threadIdx.x & 63u);
+    for (int c = (int)(threadIdx.x >> 6); c < ncols; c += 4) {
+        const StCol col = cols[c];
+        const unsigned long long *__restrict__ p = part + ((size_t)col.arr * ST_SLOTS + (size_t)col.slot) * (size_t)nchunks;
+        const unsigned long long id = st_identity(col.kind);
+        unsigned long long q[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q[e] = 4 * lane + e < nchunks ? p[4 * lane + e] : id;
+        unsigned long long v = st_fold(col.kind, st_fold(col.kind, q[0], q[1]), st_fold(col.kind, q[2], q[3]));
+        v = st_wave_fold(col.kind, v);
+        if (lane == 0) row[c] = col.kind <= ST_MAX ? st_dbl(v) : (double)v;
     }
 }
 

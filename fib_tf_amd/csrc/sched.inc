@@ -47,11 +47,12 @@ static int recover(fibhip_ctx *h, unsigned id)
     h->journal.n_replayed += lost;
     // the samples queued behind the lost launches were taken from a void slab: the replay below (tick_now -> commit_impl)
     // takes them again, into the same slots — the slot is the host's tick counter, so that counter goes back first.  (Every
-    // journal record is younger than the recorder: electrode_begin, tips_begin and frames_begin confirm, and so empty the
-    // journal, before they attach.)
+    // journal record is younger than the recorder: electrode_begin, tips_begin, frames_begin and stats_begin confirm, and so
+    // empty the journal, before they attach.)
     if (h->el.on) h->el.k -= lost;
     if (h->tip.on) h->tip.k -= lost;
     if (h->fr.on) h->fr.k -= lost;
+    if (h->st.on) h->st.k -= lost;
     h->journal.recovering = true;
     int rc = 0;
     for (int t = 0; t < lost && rc == 0; ++t) rc = tick_now(h);
@@ -88,8 +89,9 @@ static int sync_s0(fibhip_ctx *h)
 // traced tick is a plain launch) — and inside the scheduler tick_mt for a launch of one tick and fibhip_step in front of its
 // plain launches.  The entry points that only READ synchronise behind their copy (sync_s0) and take the copy again when a
 // recovery happened in between: fibhip_get_state, fibhip_get_state_direct (both branches of ahead_read_back hand the frame
-// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read, fibhip_frames_read; fibhip_observe_begin,
-// fibhip_electrode_begin / _end, fibhip_tips_begin / _end and fibhip_frames_begin / _end synchronise outright.
+// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read, fibhip_frames_read, fibhip_stats_read; fibhip_observe_begin,
+// fibhip_electrode_begin / _end, fibhip_tips_begin / _end, fibhip_frames_begin / _end and fibhip_stats_begin / _end synchronise
+// outright.
 static int confirm(fibhip_ctx *h)
 {
     return (h->mt.inflight && h->mt.epochs) ? sync_s0(h) : 0;
@@ -142,20 +144,20 @@ static const Variant *mt_variant(const fibhip_ctx *h)
 // Every constraint an attached recorder (record.inc) puts on the launches is stated HERE and nowhere else:
 //  * activation recorder (h->obs.on): it observes every tick through commit_impl, so nothing fuses ticks — no multi-tick
 //    launches (mt_variant, above, is null: hence no run-ahead and no launched series either), one tick per plain launch (multi_cap);
-//  * the samplers — electrode recorder (h->el.on), tip recorder (h->tip.on) and frame recorder (h->fr.on; its counter starts
-//    at every - first, so that its first sample may come early), each with a stride of its own: no launch
+//  * the samplers — electrode recorder (h->el.on), tip recorder (h->tip.on), frame recorder (h->fr.on; its counter starts
+//    at every - first, so that its first sample may come early) and statistics recorder (h->st.on), each with a stride of its own: no launch
 //    spans a sample tick of either (sample_room, the minimum over the attached ones, bounds next_launch_ticks and multi_cap);
 //    nothing runs ahead (may_run_ahead: a launch that runs ahead is handed out tick by tick and may be stopped or recomputed,
 //    so a sample cannot be queued behind it, DESIGN.md section 11); a sample of a SLOW Courtemanche array is taken before
 //    'slow' rides on its tick (slow_sample_due).
-static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on || h->fr.on; }
+static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on || h->fr.on || h->st.on; }
 // ticks up to and including the next sample tick of one sampler (INT_MAX: not attached)
 static inline int room_of(bool on, int every, long long k) { return on ? every - (int)(k % every) : INT_MAX; }
 // ... and of any attached sampler: no launch may span one
 static inline int sample_room(const fibhip_ctx *h)
 {
     return imin(imin(room_of(h->el.on, h->el.every, h->el.k), room_of(h->tip.on, h->tip.every, h->tip.k)),
-                room_of(h->fr.on, h->fr.every, h->fr.k));
+                imin(room_of(h->fr.on, h->fr.every, h->fr.k), room_of(h->st.on, h->st.every, h->st.k)));
 }
 // consecutive ticks one plain launch may fuse (Courtemanche on aggregates: up to multi_max; one while an activation recorder
 // is attached; never across a sample tick)
@@ -191,17 +193,27 @@ static inline bool slow_sample_due(const fibhip_ctx *h)
     auto slow = [](int var) { return !((Courtemanche::FAST_MASK >> var) & 1u); };
     if (h->el.on && (h->el.k + h->pending) % h->el.every == 0 && slow(h->el.var)) return true;
     if (h->tip.on && (h->tip.k + h->pending) % h->tip.every == 0 && (slow(h->tip.var) || slow(h->tip.var2))) return true;
-    return h->fr.on && (h->fr.k + h->pending) % h->fr.every == 0 && slow(h->fr.var);
+    if (h->fr.on && (h->fr.k + h->pending) % h->fr.every == 0 && slow(h->fr.var)) return true;
+    if (h->st.on && (h->st.k + h->pending) % h->st.every == 0)
+        for (int a = 0; a < h->st.narr; ++a)
+            if (slow(h->st.vars[a])) return true;
+    return false;
 #else
     return false;
 #endif
 }
-// the sampler that has no slot left for the samples of `more` further ticks (pending ones included), or null
-static inline const char *sampler_full(const fibhip_ctx *h, int more)
+// the sampler that has no slot left for the samples of `more` further ticks (pending ones included), or null; `cap`: the samples
+// it holds
+static inline const char *sampler_full(const fibhip_ctx *h, int more, long long *cap = nullptr)
 {
-    if (h->el.on && (h->el.k + more) / h->el.every > h->el.cap) return "electrode";
-    if (h->tip.on && (h->tip.k + more) / h->tip.every > h->tip.cap) return "tip";
-    if (h->fr.on && (h->fr.k + more) / h->fr.every > h->fr.cap) return "frame";
+    const struct { bool on; long long k; int every; long long cap; const char *name; } s[] = {
+        {h->el.on, h->el.k, h->el.every, h->el.cap, "electrode"}, {h->tip.on, h->tip.k, h->tip.every, h->tip.cap, "tip"},
+        {h->fr.on, h->fr.k, h->fr.every, h->fr.cap, "frame"}, {h->st.on, h->st.k, h->st.every, h->st.cap, "statistics"}};
+    for (const auto &r : s)
+        if (r.on && (r.k + more) / r.every > r.cap) {
+            if (cap) *cap = r.cap;
+            return r.name;
+        }
     return nullptr;
 }
 
@@ -308,7 +320,9 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
         if (int rc = electrode_advance(h, T)) return rc;
     if (commit && h->tip.on)
         if (int rc = tips_advance(h, T)) return rc;
-    if (commit && h->fr.on) return frames_advance(h, T);
+    if (commit && h->fr.on)
+        if (int rc = frames_advance(h, T)) return rc;
+    if (commit && h->st.on) return stats_advance(h, T);
     return 0;
 }
 
@@ -672,9 +686,9 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
     // default against the 32 of everything above.  At Fenton 512x512 the 5000 declared ticks of a benchmark region take
     // 11.58 us per tick as 157 launches of 32 and 11.44 as 20 of 256, 1.2 %; the kernel trace shows no gap between two
     // launches either way, a launch's first and last tick are what costs — profiles/series_launch_ab.txt).
-    if (const char *who = sampler_full(h, h->pending + nticks))
-        return fail(FIBHIP_EINVAL, "step: trace full (the %s recorder holds %lld samples; read it, then detach or re-attach)", who,
-                    who[0] == 'e' ? h->el.cap : who[0] == 't' ? h->tip.cap : h->fr.cap);
+    long long full_cap = 0;
+    if (const char *who = sampler_full(h, h->pending + nticks, &full_cap))
+        return fail(FIBHIP_EINVAL, "step: trace full (the %s recorder holds %lld samples; read it, then detach or re-attach)", who, full_cap);
     if (int rc = journal_bound(h)) return rc;
     // (the guards in front are may_run_ahead's own, taken first because most calls end at one of them)
     if (nticks > 0 && h->ahead.n == 0 && h->mt.max > 1 && !sampling(h)) {

@@ -8,6 +8,7 @@ static int observe_enqueue(fibhip_ctx *h);
 static int electrode_advance(fibhip_ctx *h, int ticks);
 static int tips_advance(fibhip_ctx *h, int ticks);
 static int frames_advance(fibhip_ctx *h, int ticks);
+static int stats_advance(fibhip_ctx *h, int ticks);
 
 // ------------------------------------------------------------------------------------------
 // stepping
@@ -278,7 +279,9 @@ static int commit_impl(fibhip_t h)
         if (int rc = electrode_advance(h, ticks)) return rc;
     if (h->tip.on)
         if (int rc = tips_advance(h, ticks)) return rc;
-    if (h->fr.on) return frames_advance(h, ticks);
+    if (h->fr.on)
+        if (int rc = frames_advance(h, ticks)) return rc;
+    if (h->st.on) return stats_advance(h, ticks);
     return 0;
 }
 

@@ -276,6 +276,23 @@ class IonicModel:
         return FrameRecorder(self, every=every, first=first, window=window, block=block, reduce=reduce, fmt=fmt, var=var,
                              weight=weight, levels=levels, capacity=capacity)
 
+    def record_stats(self, columns, every=1, weight='phase', mask=None, capacity=None):
+        """attaches a statistics recorder (fib_tf_amd/stats.py) to this model's handle: every `every` ticks one row of
+        whole-tissue scalars is taken on the device and kept there until `table()` / `raw()` read it.  `columns` is a list of
+        (array, kind) or (array, kind, level), `array` a name or an index of VAR_NAMES, `kind` one of 'sum', 'mean' (weighted
+        by `weight`: 'phase' = the model's phase field if it has one, None, or an [height, width] array), 'min', 'max',
+        'below', 'above', 'frac_below', 'frac_above', 'nonfinite' (over the cells of `mask`, which defaults to phase > 0.5
+        when the model has a phase field).  Up to 64 columns, 8 on one array; each array is read once per sample.  Default
+        capacity: the samples of a whole run of `duration`.  Call after define(); single device only (row blocks raise
+        NotImplementedError)."""
+        from .stats import StatsRecorder
+        if not self.defined:
+            raise AssertionError('record_stats should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return StatsRecorder(self, columns, every=every, weight=weight, mask=mask, capacity=capacity)
+
     def _frame_levels(self):
         """(lo, span) with image() == (X - lo) / span in float32, X the array pot() names: what a frame recorder maps the
         state with.  Models whose image() rescales override it."""

@@ -466,6 +466,51 @@ int fibhip_frames_shape(fibhip_t h, int *oh, int *ow, int *bytes_per_pixel);
 int fibhip_frames_read(fibhip_t h, long long first, long long count, void *dst);
 int fibhip_frames_end(fibhip_t h);
 
+/* Statistics recorder: whole-tissue scalars of several state arrays at once, taken on the device every `every` ticks and appended,
+ * one row per sample, to a trace that stays on the device until it is read (the reference's court_ultra.py keeps phase-weighted
+ * means of _Na_i_, _f_Ca_ and _us_ and the repolarised share of the tissue by reading whole arrays back; ionic.py has a NaN
+ * detector commented out).  A recorder has ncols columns, 1 .. FIBHIP_MAX_STAT_COLS, at most FIBHIP_MAX_STAT_COLS_PER_ARRAY of
+ * them on the same array; a column is {var, kind, level}.  It has an optional float32 weight plane [height*width], an optional
+ * byte mask [height*width] (non-zero: the cell counts) and a stride every >= 1.  With k = ticks since stats_begin (the first
+ * tick after it is k = 0), after every tick with (k + 1) % every == 0 sample s = (k + 1) / every - 1 is taken — the rule of the
+ * electrode and tip recorders.  One sample is one row of ncols float64 values (restated in NumPy in tests/stats_ref.py):
+ *     SUM        sum of (double)w * (double)X over the cells with w != 0; without a weight plane w = 1.  The product of two
+ *                float32 numbers is exact in double; every addition is a float64 addition rounded on its own (the product is
+ *                NOT fused into it: no fma), in an order fixed by height, width and the pitch alone.  No floating-point atomics.
+ *                A NaN or Inf under a non-zero weight propagates; under a zero weight it is not looked at.  Against the exact
+ *                sum S of the n terms: |SUM - S| <= n * 2^-53 * sum |w * X|.
+ *     MIN, MAX   over the cells with mask != 0 (all cells without a mask), ignoring NaN; +-Inf take part.  No such cell (or
+ *                NaN only): +inf for MIN, -inf for MAX.  -0 and +0 compare equal; which of them is stored is not specified.
+ *     BELOW, ABOVE   the number of masked cells with X < level / X > level, compared in float32.  NaN counts in neither.
+ *     NONFINITE  the number of masked cells whose X is NaN or +-Inf.
+ * Counts are accumulated as integers (64-bit where they are combined) and stored converted to double, which is exact.  The
+ * same state gives the same bytes under every launch plan: multi-tick launches on or off, run-ahead on or off, a forced tile
+ * shape, after a recovered give-up.  The row of a sample is addressed from the host's tick counter, so a replay writes the same
+ * row again.  Pacing, set_state and step_slow / step_mode between two ticks belong to the next tick.  The trace does not wrap:
+ * a fibhip_step that would take sample number `capacity` is refused with FIBHIP_EINVAL ("trace full") before anything of that
+ * call is enqueued.  What holds for the other samplers holds here: no launch spans a sample tick, multi-tick launches go on
+ * between two samples, nothing runs ahead, a launch goes out when the ticks up to the next sample tick have been accepted, and
+ * Courtemanche's tick is not fused with 'slow' when a sample is due at that tick and any column names a slow array.  The
+ * recorder may be attached beside every other recorder, each with its own stride.
+ * Refused with FIBHIP_EINVAL, the message naming the offender: var out of range, an unknown kind, a NaN level on BELOW or ABOVE,
+ * a weight that is not finite, more than FIBHIP_MAX_STAT_COLS_PER_ARRAY columns on one array, ncols out of range, every < 1,
+ * capacity < 1, a second stats_begin without a stats_end, inside an open tick, a row block (a handle with ghost rows).
+ *   fibhip_stats_begin  flushes, synchronises and confirms pending work, copies the planes and attaches
+ *   fibhip_stats_count  samples taken so far (ticks accepted but not launched yet included)
+ *   fibhip_stats_read   samples [first, first + count) as [count][ncols] float64; flushes and blocks like get_state; does not
+ *                       detach and does not reset the sample index
+ *   fibhip_stats_end    detaches and frees the trace (no recorder attached: nothing); fibhip_destroy does the same             */
+#define FIBHIP_MAX_STAT_COLS 64
+#define FIBHIP_MAX_STAT_COLS_PER_ARRAY 8
+enum fibhip_stat_kind { FIBHIP_STAT_SUM = 0, FIBHIP_STAT_MIN = 1, FIBHIP_STAT_MAX = 2, FIBHIP_STAT_BELOW = 3, FIBHIP_STAT_ABOVE = 4,
+                        FIBHIP_STAT_NONFINITE = 5 };
+typedef struct { int var; int kind; float level; } fibhip_stat_col;     /* kind: FIBHIP_STAT_SUM ... _NONFINITE */
+int fibhip_stats_begin(fibhip_t h, int ncols, const fibhip_stat_col *cols, const float *weight /* [H*W] or NULL */,
+                       const unsigned char *mask /* [H*W] or NULL */, int every, long long capacity);
+int fibhip_stats_count(fibhip_t h, long long *samples);
+int fibhip_stats_read(fibhip_t h, long long first, long long count, double *dst /* [count][ncols] */);
+int fibhip_stats_end(fibhip_t h);
+
 const char *fibhip_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)
