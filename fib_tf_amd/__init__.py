@@ -14,5 +14,6 @@ from .court import Courtemanche                 # noqa: F401
 from . import tips                              # noqa: F401  (TipRecorder, link: spiral tips recorded on the device)
 from . import frames                            # noqa: F401  (FrameRecorder: the movie cube recorded on the device)
 from . import stats                             # noqa: F401  (StatsRecorder: tissue statistics recorded on the device)
+from . import stimulus                          # noqa: F401  (Stimulus, StimulusProgram: pacing protocols run on the device)
 
 __all__ = ['IonicModel', 'Fenton4v', 'BeelerReuter', 'Courtemanche']

@@ -20,6 +20,9 @@ FRAME_REDUCE = ('point', 'mean')                                  # enum fibhip_
 FRAME_FORMAT = ('float32', 'uint8')                               # enum fibhip_frame_format, in order
 STAT_KINDS = ('sum', 'min', 'max', 'below', 'above', 'nonfinite')  # enum fibhip_stat_kind, in order
 MAX_STAT_COLS, MAX_STAT_COLS_PER_ARRAY = 64, 8
+STIM_MODES = ('max', 'add')                                       # enum fibhip_stim_mode, in order
+STIM_SHAPES = ('rect', 'plane')                                   # enum fibhip_stim_shape, in order
+MAX_STIM_ENTRIES, MAX_STIM_PLANES = 64, 8
 CHEBY, SKIP, CHRONIC, FAST, ALLVARS, ROW_INTERLEAVED, ZEROPAD, HOLD = 1, 2, 4, 8, 16, 32, 64, 128
 
 # -ffp-contract=off: FMAs appear only where the source writes them (policy hook P::mad).
@@ -113,6 +116,12 @@ class StatCol(C.Structure):
     _fields_ = [('var', C.c_int), ('kind', C.c_int), ('level', C.c_float)]
 
 
+class StimEntry(C.Structure):
+    _fields_ = [('var', C.c_int), ('mode', C.c_int), ('shape', C.c_int), ('r0', C.c_int), ('r1', C.c_int), ('c0', C.c_int),
+                ('c1', C.c_int), ('v', C.c_float), ('floor', C.c_float), ('plane', C.c_int), ('first', C.c_int), ('period', C.c_int),
+                ('count', C.c_int), ('hold', C.c_int)]
+
+
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
 _h = C.c_void_p
@@ -194,6 +203,9 @@ SYMBOLS = {
     'fibhip_stats_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_stats_read': ([_h, C.c_longlong, C.c_longlong, C.POINTER(C.c_double)], C.c_int),
     'fibhip_stats_end': ([_h], C.c_int),
+    'fibhip_stim_begin': ([_h, C.c_int, C.POINTER(StimEntry), C.c_int, _fp], C.c_int),
+    'fibhip_stim_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_stim_end': ([_h], C.c_int),
     'fibhip_last_error': ([], C.c_char_p),
 }
 
@@ -856,3 +868,38 @@ class Stepper:
 
     def stats_end(self):
         self._ck(self._L.fibhip_stats_end(self._h))
+
+    # ---- stimulus program (include/fibhip.h fibhip_stim_*) --------------------------------------------------------
+    def stim_begin(self, entries, planes=None):
+        """attaches a stimulus program: `entries` is a list of dicts with the fields of fibhip_stim_entry (`mode` 'max' / 'add'
+        or its number, `shape` 'rect' / 'plane' or its number; fields left out are 0, hold and count 1), `planes` a list of
+        [height, width] float32 arrays the 'plane' entries index"""
+        arr = (StimEntry * max(len(entries), 1))()
+        for i, e in enumerate(entries):
+            d = dict(e)
+            mode, shape = d.pop('mode', 0), d.pop('shape', 0)
+            arr[i].mode = STIM_MODES.index(mode) if isinstance(mode, str) else int(mode)
+            arr[i].shape = STIM_SHAPES.index(shape) if isinstance(shape, str) else int(shape)
+            arr[i].hold, arr[i].count = int(d.pop('hold', 1)), int(d.pop('count', 1))
+            arr[i].v, arr[i].floor = float(d.pop('v', 0.0)), float(d.pop('floor', 0.0))
+            for k, val in d.items():
+                if k not in ('var', 'r0', 'r1', 'c0', 'c1', 'plane', 'first', 'period'):
+                    raise ValueError('stim_begin: entry %d: unknown field %r' % (i, k))
+                setattr(arr[i], k, int(val))
+        pp, stack = None, None
+        if planes is not None and len(planes):
+            for p in planes:
+                if np.shape(p) != (self.height, self.width):
+                    raise ValueError('stim_begin: a plane of shape %s on a %d x %d grid' % (np.shape(p), self.height, self.width))
+            stack = np.ascontiguousarray(np.stack([np.asarray(p, np.float32) for p in planes]), np.float32)
+            pp = stack.ctypes.data_as(_fp)
+        self._ck(self._L.fibhip_stim_begin(self._h, len(entries), arr, 0 if stack is None else len(stack), pp))
+
+    def stim_count(self):
+        """events applied since stim_begin (flushes: the ticks accepted so far are launched first)"""
+        k = C.c_longlong()
+        self._ck(self._L.fibhip_stim_count(self._h, C.byref(k)))
+        return int(k.value)
+
+    def stim_end(self):
+        self._ck(self._L.fibhip_stim_end(self._h))

@@ -180,6 +180,27 @@ struct StRec {
     double *trace;          // device: [cap][ncols]
 };
 
+// stimulus program (fibhip_stim_begin): the actuator beside the recorders — no launch spans an event tick (stim_room, a term of
+// sample_room), and the hook on the plain and the multi-tick commit path (stim_advance) enqueues stim_kernel behind the launch
+// that ends one, behind the samples of that tick
+struct StimEntry {
+    int var, mode;
+    long long first, period, count, hold;   // fibhip_stim_entry's, validated
+    int plane;              // index into StimRec::planes, or -1: a rectangle
+    int r0, r1, c0, c1;     // rectangle
+    float v, floor;
+    int b_r0, b_r1, b_c0, b_c1;     // the visit box (empty: b_r0 == b_r1), cut at attach
+    bool slow;              // Courtemanche on aggregates: the entry names an array the aggregates are formed from
+};
+struct StimRec {
+    bool on;
+    long long k;            // ticks LAUNCHED since the program was attached (recover() rewinds it by the ticks it replays)
+    long long next;         // the tick count (k) of the next event tick, LLONG_MAX: no event left; follows from k and the entries
+                            // alone (stim_next): set at attach, in stim_advance and in recover()
+    std::vector<StimEntry> entries;
+    float *planes;          // device: the planes, [nplanes][H][W], or null
+};
+
 // fibhip_trace_begin / _end: the launches in between, each between two HIP events
 struct TraceRec {
     hipEvent_t e0, e1;
@@ -240,6 +261,7 @@ struct fibhip_ctx {
     TipRec tip;
     FrRec fr;
     StRec st;
+    StimRec stim;
     std::vector<TraceRec> trace;
     bool tracing;
     // ---- the rest ----

@@ -1,7 +1,7 @@
 // record.inc — the five recorders that run on the device while a model runs: the per-cell activation maps
 // (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
-// (fibhip_frames_*) and the tissue statistics (fibhip_stats_*).  Each is a hook behind a committed launch plus its entry
-// points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
+// (fibhip_frames_*) and the tissue statistics (fibhip_stats_*) — and the stimulus program (fibhip_stim_*), the one hook that
+// writes the state.  Each is a hook behind a committed launch plus its entry points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
 // (included by fibhip.hip, behind sched.inc)
 
 // the activation recorder's update for the tick just committed (observed tick k = obs_k), on s0 behind it
@@ -235,6 +235,84 @@ static void stats_free(fibhip_ctx *h)
     h->st.part = nullptr;
     h->st.trace = nullptr;
     h->st.on = false;
+}
+
+static_assert(STIM_MAX_DUE <= FIBHIP_MAX_STIM_ENTRIES && (int)STIM_MAX == (int)FIBHIP_STIM_MAX && (int)STIM_ADD == (int)FIBHIP_STIM_ADD,
+              "stim_kernel's constants follow include/fibhip.h");
+// The stimulus program's hook behind a launch of `ticks` ticks (plain: commit_impl; multi-tick: mt_launch), behind the samples of
+// that tick.  No launch spans an event tick (stim_room), so the entries due are those of the tick the counter has landed on.
+// They go out in program order, grouped by array (stable: see stim_kernel), STIM_MAX_DUE per launch, on s0 behind the launch
+// that ended there — WITHOUT confirming it.  `behind_mt`: that launch is a multi-tick launch, which nobody may have confirmed:
+// stim_kernel is then handed the give-up word and writes nothing once a launch in front of it gave up, so the state such a
+// launch started from stays intact; recover() rewinds the counter and the replay comes through here again.  Behind a PLAIN tick
+// the kernel gets no word: every plain tick is issued behind a confirmed stream, and the device's word has a life of its own
+// outside multi-tick launches (an autotune candidate that gave up leaves it raised until the next mt_launch zeroes it,
+// plan.inc) — a stimulus must not be dropped for that.  What is due follows from the host's counter alone: nothing about the
+// program lives on the device but the planes.
+static int stim_advance(fibhip_ctx *h, int ticks, bool behind_mt)
+{
+    StimRec &r = h->stim;
+    r.k += ticks;
+    if (r.k < r.next) return 0;                                     // (no launch spans an event tick: k lands on it or stays below)
+    std::vector<const StimEntry *> due;
+    for (const StimEntry &e : r.entries)
+        if (stim_due(e, r.k)) due.push_back(&e);
+    r.next = stim_next(r);
+    if (due.empty()) return 0;
+    std::stable_sort(due.begin(), due.end(), [](const StimEntry *a, const StimEntry *b) { return a->var < b->var; });
+    const int W = h->d.width;
+    for (size_t first = 0; first < due.size(); first += STIM_MAX_DUE) {
+        const size_t n = due.size() - first < (size_t)STIM_MAX_DUE ? due.size() - first : (size_t)STIM_MAX_DUE;
+        StimArgs a;
+        memset(&a, 0, sizeof a);
+        a.r0 = a.c0 = INT_MAX;
+        uintptr_t align = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const StimEntry &e = *due[first + i];
+            StimDue &d = a.e[i];
+            d.x = h->slab[h->cur[e.var]] + (size_t)e.var * h->vstride;
+            d.plane = e.plane >= 0 ? r.planes + (size_t)e.plane * h->cells : nullptr;
+            d.mode = e.mode;
+            d.load = i == 0 || due[first + i - 1]->var != e.var;
+            d.store = i + 1 == n || due[first + i + 1]->var != e.var;
+            d.b_r0 = e.b_r0; d.b_r1 = e.b_r1; d.b_c0 = e.b_c0; d.b_c1 = e.b_c1;
+            d.r0 = e.r0; d.r1 = e.r1; d.c0 = e.c0; d.c1 = e.c1;
+            d.v = e.v; d.floor = e.floor;
+            align |= reinterpret_cast<uintptr_t>(d.x) | reinterpret_cast<uintptr_t>(d.plane);
+            if (e.b_r0 < e.b_r1) {
+                a.r0 = imin(a.r0, e.b_r0); a.r1 = imax(a.r1, e.b_r1);
+                a.c0 = imin(a.c0, e.b_c0); a.c1 = imax(a.c1, e.b_c1);
+            }
+            if (e.slow && h->use_agg) h->agg_dirty = true;          // as fibhip_set_state: the next tick forms the aggregates afresh
+        }
+        if (a.r0 >= a.r1) continue;                                 // (planes that leave every cell untouched: nothing to visit)
+        a.n = (int)n;
+        a.W = W;
+        a.pitch = h->pitch;
+        a.give_up = behind_mt && h->mt.epochs ? h->mt.give_up_word() : nullptr;
+        const bool vec = h->pitch == W && W % 4 == 0 && (align & 15u) == 0;
+        if (vec) {
+            a.c0 = a.c0 / 4 * 4;
+            a.c1 = (a.c1 + 3) / 4 * 4;                              // (<= W: W is a multiple of 4)
+        }
+        const size_t threads = (size_t)(a.r1 - a.r0) * (size_t)((a.c1 - a.c0) / (vec ? 4 : 1));
+        const dim3 grid((unsigned)((threads + 255) / 256));
+        if (int rc = trace_open(h, h->s0, "stim_kernel", 0, 0, 0, 0, 1)) return rc;
+        if (vec) hipLaunchKernelGGL(stim_kernel<true>, grid, dim3(256), 0, h->s0, a);
+        else hipLaunchKernelGGL(stim_kernel<false>, grid, dim3(256), 0, h->s0, a);
+        HIPCHK(hipGetLastError());
+        if (int rc = trace_close(h, h->s0)) return rc;
+        h->launches++;
+    }
+    return 0;
+}
+
+static void stim_free(fibhip_ctx *h)
+{
+    if (h->stim.planes) hipFree(h->stim.planes);
+    h->stim.planes = nullptr;
+    h->stim.entries.clear();
+    h->stim.on = false;
 }
 
 // ---- activation recorder ------------------------------------------------------------------------------------------------
@@ -746,5 +824,110 @@ extern "C" int fibhip_stats_end(fibhip_t h)
     FLUSH(h);                                          // the ticks accepted while attached are sampled
     SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
     stats_free(h);
+    return 0;
+}
+
+// ---- stimulus program ---------------------------------------------------------------------------------------------------
+extern "C" int fibhip_stim_begin(fibhip_t h, int n, const fibhip_stim_entry *entries, int nplanes, const float *planes)
+{
+    NEED(h);
+    if (!entries) return fail(FIBHIP_EINVAL, "stim_begin: null argument");
+    if (n < 1 || n > FIBHIP_MAX_STIM_ENTRIES) return fail(FIBHIP_EINVAL, "stim_begin: 1 .. %d entries (got %d)", FIBHIP_MAX_STIM_ENTRIES, n);
+    if (nplanes < 0 || nplanes > FIBHIP_MAX_STIM_PLANES || (nplanes > 0 && !planes))
+        return fail(FIBHIP_EINVAL, "stim_begin: 0 .. %d planes (got %d%s)", FIBHIP_MAX_STIM_PLANES, nplanes, nplanes > 0 && !planes ? ", null" : "");
+    const int H = h->d.height, W = h->d.width;
+    const float ninf = -std::numeric_limits<float>::infinity();
+    std::vector<StimEntry> list;
+    for (int i = 0; i < n; ++i) {
+        const fibhip_stim_entry &s = entries[i];
+        StimEntry e;
+        memset(&e, 0, sizeof e);
+        if (s.var < 0 || s.var >= h->nvar) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: bad var %d", i, s.var);
+        if (s.mode != FIBHIP_STIM_MAX && s.mode != FIBHIP_STIM_ADD) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: unknown mode %d", i, s.mode);
+        if (s.shape != FIBHIP_STIM_RECT && s.shape != FIBHIP_STIM_PLANE) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: unknown shape %d", i, s.shape);
+        if (s.first < 0) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: first must be >= 0 (got %d)", i, s.first);
+        if (s.hold < 1) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: hold must be >= 1 (got %d)", i, s.hold);
+        if (s.period < 0 || s.count < 0) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: period and count must be >= 0 (got %d, %d)", i, s.period, s.count);
+        if (s.period == 0 && s.count != 1) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: period 0 means one event: count must be 1 (got %d)", i, s.count);
+        if (s.period > 0 && s.hold > s.period) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: hold %d > period %d", i, s.hold, s.period);
+        e.var = s.var; e.mode = s.mode;
+        e.first = s.first; e.period = s.period; e.count = s.count; e.hold = s.hold;
+        const float untouched = s.mode == FIBHIP_STIM_MAX ? ninf : 0.f;
+        if (s.shape == FIBHIP_STIM_RECT) {
+            if (s.r0 < 0 || s.r1 > H || s.c0 < 0 || s.c1 > W || s.r0 >= s.r1 || s.c0 >= s.c1)
+                return fail(FIBHIP_EINVAL, "stim_begin: entry %d: rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", i, s.r0,
+                            s.r1, s.c0, s.c1, H, W);
+            if (!std::isfinite(s.v)) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: v must be finite (got %g)", i, s.v);
+            if (!(std::isfinite(s.floor) || (s.mode == FIBHIP_STIM_MAX && s.floor == ninf)))
+                return fail(FIBHIP_EINVAL, "stim_begin: entry %d: floor must be finite%s (got %g)", i, s.mode == FIBHIP_STIM_MAX ? " or -inf" : "", s.floor);
+            e.plane = -1;
+            e.r0 = s.r0; e.r1 = s.r1; e.c0 = s.c0; e.c1 = s.c1;
+            e.v = s.v; e.floor = s.floor;
+            const bool outside_untouched = s.floor == untouched;
+            e.b_r0 = outside_untouched ? s.r0 : 0; e.b_r1 = outside_untouched ? s.r1 : H;
+            e.b_c0 = outside_untouched ? s.c0 : 0; e.b_c1 = outside_untouched ? s.c1 : W;
+        } else {
+            if (s.plane < 0 || s.plane >= nplanes) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: plane %d of %d", i, s.plane, nplanes);
+            e.plane = s.plane;
+            const float *p = planes + (size_t)s.plane * h->cells;
+            int r0 = H, r1 = 0, c0 = W, c1 = 0;
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x)
+                    if (!(p[(size_t)y * W + x] == untouched)) {         // (a NaN is not "untouched")
+                        r0 = imin(r0, y); r1 = imax(r1, y + 1);
+                        c0 = imin(c0, x); c1 = imax(c1, x + 1);
+                    }
+            if (r0 >= r1) r0 = r1 = c0 = c1 = 0;
+            e.b_r0 = r0; e.b_r1 = r1; e.b_c0 = c0; e.b_c1 = c1;
+        }
+#if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
+        e.slow = h->d.model == FIBHIP_COURT && !((Courtemanche::FAST_MASK >> s.var) & 1u);
+#endif
+        list.push_back(e);
+    }
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "stim_begin: not on a row block (a handle with ghost rows)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "stim_begin inside an open tick");
+    if (h->stim.on) return fail(FIBHIP_EINVAL, "stim_begin: a program is attached already (fibhip_stim_end first)");
+    // everything accepted so far runs unstimulated and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    stim_free(h);
+    if (nplanes > 0) {
+        const size_t bytes = (size_t)nplanes * h->cells * sizeof(float);
+        if (hipMalloc((void **)&h->stim.planes, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            h->stim.planes = nullptr;
+            return fail(FIBHIP_ENOMEM, "stim_begin: hipMalloc of %d planes failed", nplanes);
+        }
+        HIPCHK(hipMemcpyAsync(h->stim.planes, planes, bytes, hipMemcpyHostToDevice, h->s0));
+        HIPCHK(wait_stream(h->s0));                    // the caller's planes are free again
+    }
+    h->stim.entries.swap(list);
+    h->stim.k = 0;
+    h->stim.next = stim_next(h->stim);
+    h->stim.on = true;
+    return 0;
+}
+
+extern "C" int fibhip_stim_count(fibhip_t h, long long *applied)
+{
+    NEED(h);
+    if (!applied) return fail(FIBHIP_EINVAL, "stim_count: null argument");
+    if (!h->stim.on) return fail(FIBHIP_EINVAL, "stim_count: no program attached (fibhip_stim_begin)");
+    FLUSH(h);                                          // the ticks accepted so far are launched, their events applied
+    long long total = 0;
+    for (const StimEntry &e : h->stim.entries) total += stim_events_upto(e, h->stim.k);
+    *applied = total;
+    return 0;
+}
+
+extern "C" int fibhip_stim_end(fibhip_t h)
+{
+    NEED(h);
+    if (!h->stim.on) return 0;
+    FLUSH(h);                                          // the events of the ticks accepted while attached are applied
+    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the program
+    stim_free(h);
     return 0;
 }

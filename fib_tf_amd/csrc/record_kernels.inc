@@ -613,3 +613,101 @@ __global__ void __launch_bounds__(256) copy_kernel(const fib_v4f *__restrict__ s
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) dst[i] = src[i];
 }
+
+// ---- stimulus program (fibhip_stim_begin): the entries due after one tick, applied to the state in ONE pass -------------------
+// The one kernel here that WRITES the state: the actuator beside the five sensors above.  An entry is a mode (MAX: X = fmaxf(X, S),
+// pace_kernel's operation; ADD: X = X + S, one float32 addition rounded on its own under -ffp-contract=off), a target array and a
+// shape that gives S per cell: a rectangle (v inside, `floor` outside) or a plane [H][W].  A cell whose S is the mode's
+// "untouched" value (-inf for MAX, +-0 for ADD) is not changed at all, whatever its bits; the host has cut each entry's VISIT
+// box around the cells that are not (fibhip_stim_begin) and the launch covers the union of the due entries' boxes.
+// The due entries — at most STIM_MAX_DUE, the host issues further launches in program order beyond that — travel BY VALUE in the
+// kernel argument and are walked by a fully unrolled loop: every field is wave-uniform and stays in scalar registers (a run-time
+// index into a per-thread copy would put it in scratch: frame_kernel's note).  The host has grouped them by array (stable: the
+// program order of the entries on one array stands, entries on different arrays touch different memory and commute) and marked
+// where an array's run begins (`load`) and ends (`store`): a thread loads its cells of an array once and stores them once,
+// whatever the number of entries.  VEC (planar slab, W a multiple of 4, every pointer 16-byte aligned; the union box widened
+// to whole groups of four columns): four consecutive cells of one row per thread, 16-byte loads and stores of the state and
+// the planes.  Otherwise (odd widths, rows that start unaligned, the row-interleaved slab): one cell per thread.  No LDS, no
+// atomics.  `give_up`: the give-up word of the multi-tick launches (null: the handle never made one) — a launch in front that
+// gave up left the word raised, the state it started from is what recover() goes back to, and this kernel then writes NOTHING,
+// like the multi-tick launches queued behind such a launch (sched.inc, the rule above confirm()).
+#define STIM_MAX_DUE 8
+enum { STIM_MAX = 0, STIM_ADD = 1 };
+struct StimDue {
+    float *x;               // the target array in the slab that holds it now (its first row), `pitch` floats between rows
+    const float *plane;     // S per cell, [H][W], or null: a rectangle
+    int mode;               // STIM_MAX / STIM_ADD
+    int load, store;        // first / last entry of its array's run in this launch
+    int b_r0, b_r1, b_c0, b_c1;     // the visit box: outside it the entry leaves every cell untouched
+    int r0, r1, c0, c1;     // rectangle: S = v inside, floor outside
+    float v, floor;
+};
+struct StimArgs {
+    StimDue e[STIM_MAX_DUE];
+    int n;
+    int W, pitch;
+    int r0, r1, c0, c1;     // the union of the due entries' visit boxes (VEC: c0 and c1 multiples of 4)
+    const unsigned *give_up;
+};
+
+static FIB_DEV float stim_cell(float x, float s, int mode)
+{
+    if (mode == STIM_MAX) return s == -__builtin_huge_valf() ? x : fmaxf(x, s);
+    return s == 0.f ? x : x + s;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) stim_kernel(StimArgs a)
+{
+    constexpr int N = VEC ? 4 : 1;
+    if (a.give_up && *a.give_up != 0u) return;                        // (wave-uniform: one scalar load)
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t per_row = (size_t)(a.c1 - a.c0) / N;
+    if (t >= (size_t)(a.r1 - a.r0) * per_row) return;
+    const int y = a.r0 + (int)(t / per_row), x0 = a.c0 + N * (int)(t % per_row);
+    const size_t at = (size_t)y * (size_t)a.pitch + (size_t)x0;
+    float x[N];
+#pragma unroll
+    for (int i = 0; i < STIM_MAX_DUE; ++i) {
+        if (i >= a.n) continue;                                       // (wave-uniform, like every field of a.e[i])
+        const StimDue &d = a.e[i];
+        if (d.load) {
+            if (VEC) {
+                const fib_v4f v = *reinterpret_cast<const fib_v4f *>(d.x + at);
+#pragma unroll
+                for (int j = 0; j < N; ++j) x[j] = v[j];
+            } else {
+                x[0] = d.x[at];
+            }
+        }
+        if (y >= d.b_r0 && y < d.b_r1 && x0 + N > d.b_c0 && x0 < d.b_c1) {
+            float s[N];
+            if (d.plane) {
+                const size_t pat = (size_t)y * (size_t)a.W + (size_t)x0;
+                if (VEC) {
+                    const fib_v4f v = *reinterpret_cast<const fib_v4f *>(d.plane + pat);
+#pragma unroll
+                    for (int j = 0; j < N; ++j) s[j] = v[j];
+                } else {
+                    s[0] = d.plane[pat];
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < N; ++j) s[j] = (y >= d.r0 && y < d.r1 && x0 + j >= d.c0 && x0 + j < d.c1) ? d.v : d.floor;
+            }
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+                if (x0 + j >= d.b_c0 && x0 + j < d.b_c1) x[j] = stim_cell(x[j], s[j], d.mode);
+        }
+        if (d.store) {
+            if (VEC) {
+                fib_v4f v;
+#pragma unroll
+                for (int j = 0; j < N; ++j) v[j] = x[j];
+                *reinterpret_cast<fib_v4f *>(d.x + at) = v;
+            } else {
+                d.x[at] = x[0];
+            }
+        }
+    }
+}

@@ -17,6 +17,7 @@
 // bit-identical by construction — the ticks the handle's state had already moved past.  (The replay stays one launch per tick
 // however long the lost launches were: the fallback leaves no multi-tick launch to replay with, mt.max is 1 from here on.
 // Its cost is bounded by what the journal holds, MT_MAX_TICKS_IN_FLIGHT ticks and one launch: journal_bound.)
+static long long stim_next(const StimRec &r);                     // (below, with the scheduler's other questions to the program)
 static int recover(fibhip_ctx *h, unsigned id)
 {
     size_t i = 0;
@@ -53,6 +54,12 @@ static int recover(fibhip_ctx *h, unsigned id)
     if (h->tip.on) h->tip.k -= lost;
     if (h->fr.on) h->fr.k -= lost;
     if (h->st.on) h->st.k -= lost;
+    // ... and the stimuli queued behind them wrote nothing (stim_kernel leaves when it finds the give-up word raised): the replay
+    // applies the events of the replayed ticks again, and no others — the events of older ticks stand in the restored state
+    if (h->stim.on) {
+        h->stim.k -= lost;
+        h->stim.next = stim_next(h->stim);
+    }
     h->journal.recovering = true;
     int rc = 0;
     for (int t = 0; t < lost && rc == 0; ++t) rc = tick_now(h);
@@ -149,16 +156,70 @@ static const Variant *mt_variant(const fibhip_ctx *h)
 //    spans a sample tick of either (sample_room, the minimum over the attached ones, bounds next_launch_ticks and multi_cap);
 //    nothing runs ahead (may_run_ahead: a launch that runs ahead is handed out tick by tick and may be stopped or recomputed,
 //    so a sample cannot be queued behind it, DESIGN.md section 11); a sample of a SLOW Courtemanche array is taken before
-//    'slow' rides on its tick (slow_sample_due).
+//    'slow' rides on its tick (slow_sample_due);
+//  * the stimulus program (h->stim.on), the one hook that WRITES the state: no launch spans an event tick (stim_room, one more
+//    term of sample_room), and while events are still to come a launch goes out when the ticks up to the next one are waiting
+//    (cutting); nothing runs ahead while a program is attached (may_run_ahead: a stimulus cannot be queued behind a launch that
+//    may be stopped or recomputed); a tick with an event due is never fused with the 'slow' behind it, whatever array the event
+//    names — the stimulus comes right after its tick (slow_sample_due).  The stimulus is queued behind its launch WITHOUT
+//    confirming it: stim_kernel writes nothing once a launch in front of it gave up (the rule above confirm()).
 static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on || h->fr.on || h->st.on; }
 // ticks up to and including the next sample tick of one sampler (INT_MAX: not attached)
 static inline int room_of(bool on, int every, long long k) { return on ? every - (int)(k % every) : INT_MAX; }
-// ... and of any attached sampler: no launch may span one
+// Is entry `e` due right after the n-th tick since attach (n >= 1)?  The events of an entry follow the ticks number
+// first + 1 + j * period + d, j = 0 .. count - 1 (count == 0: without end), d = 0 .. hold - 1 (include/fibhip.h).
+static inline bool stim_due(const StimEntry &e, long long n)
+{
+    const long long m = n - (e.first + 1);
+    if (m < 0) return false;
+    if (e.period == 0) return m < e.hold;
+    return m % e.period < e.hold && (e.count == 0 || m / e.period < e.count);
+}
+// the events of entry `e` that follow the ticks 1 .. n
+static inline long long stim_events_upto(const StimEntry &e, long long n)
+{
+    const long long m = n - (e.first + 1);
+    if (m < 0) return 0;
+    if (e.period == 0) return m + 1 < e.hold ? m + 1 : e.hold;
+    const long long full = m / e.period, rem = m % e.period;
+    if (e.count != 0 && full >= e.count) return e.count * e.hold;
+    return full * e.hold + (rem + 1 < e.hold ? rem + 1 : e.hold);
+}
+// the tick count of the program's next event tick behind the r.k ticks launched so far (LLONG_MAX: no event left).  Walks the
+// entries, so it is kept in StimRec::next and asked only where the counter moves: at attach, in stim_advance and in recover().
+static long long stim_next(const StimRec &r)
+{
+    const long long k = r.k;
+    long long best = LLONG_MAX;
+    for (const StimEntry &e : r.entries) {
+        long long next = LLONG_MAX;
+        if (k < e.first + 1) next = e.first + 1;
+        else if (stim_due(e, k + 1)) next = k + 1;
+        else if (e.period > 0) {                                   // the start of the next train element, if there is one
+            const long long j = (k + 1 - (e.first + 1)) / e.period + 1;
+            if (e.count == 0 || j < e.count) next = e.first + 1 + j * e.period;
+        }
+        if (next < best) best = next;
+    }
+    return best;
+}
+// ticks up to and including the next event tick of the attached program (INT_MAX: none attached, or no event left): one compare
+// on the host's per-call path
+static inline int stim_room(const fibhip_ctx *h)
+{
+    if (!h->stim.on || h->stim.next == LLONG_MAX) return INT_MAX;
+    const long long room = h->stim.next - h->stim.k;
+    return room < (long long)INT_MAX ? (int)room : INT_MAX;
+}
+// ... and of any attached sampler, and of the stimulus program: no launch may span one
 static inline int sample_room(const fibhip_ctx *h)
 {
-    return imin(imin(room_of(h->el.on, h->el.every, h->el.k), room_of(h->tip.on, h->tip.every, h->tip.k)),
-                imin(room_of(h->fr.on, h->fr.every, h->fr.k), room_of(h->st.on, h->st.every, h->st.k)));
+    return imin(imin(imin(room_of(h->el.on, h->el.every, h->el.k), room_of(h->tip.on, h->tip.every, h->tip.k)),
+                     imin(room_of(h->fr.on, h->fr.every, h->fr.k), room_of(h->st.on, h->st.every, h->st.k))),
+                stim_room(h));
 }
+// launches are cut at ticks still to come: a launch goes out when the ticks up to the next cut are waiting (fibhip_step)
+static inline bool cutting(const fibhip_ctx *h) { return sampling(h) || stim_room(h) != INT_MAX; }
 // consecutive ticks one plain launch may fuse (Courtemanche on aggregates: up to multi_max; one while an activation recorder
 // is attached; never across a sample tick)
 static inline int multi_cap(const fibhip_ctx *h) { return h->obs.on ? 1 : imin(h->multi_max, sample_room(h)); }
@@ -190,6 +251,8 @@ static inline void take_pending(fibhip_ctx *h, int T)
 static inline bool slow_sample_due(const fibhip_ctx *h)
 {
 #if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
+    // (a stimulus due after the last pending tick comes before 'slow' too, whatever array it names)
+    if (h->stim.on && h->stim.k + h->pending == h->stim.next) return true;
     auto slow = [](int var) { return !((Courtemanche::FAST_MASK >> var) & 1u); };
     if (h->el.on && (h->el.k + h->pending) % h->el.every == 0 && slow(h->el.var)) return true;
     if (h->tip.on && (h->tip.k + h->pending) % h->tip.every == 0 && (slow(h->tip.var) || slow(h->tip.var2))) return true;
@@ -322,7 +385,11 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
         if (int rc = tips_advance(h, T)) return rc;
     if (commit && h->fr.on)
         if (int rc = frames_advance(h, T)) return rc;
-    if (commit && h->st.on) return stats_advance(h, T);
+    if (commit && h->st.on)
+        if (int rc = stats_advance(h, T)) return rc;
+    // (the stimulus WRITES the state, the slab this launch wrote; it leaves without writing when this launch or one in front
+    // of it gave up — so the state the first such launch started from stays intact, as behind a multi-tick launch)
+    if (commit && h->stim.on) return stim_advance(h, T, true);
     return 0;
 }
 
@@ -415,7 +482,7 @@ static bool may_run_ahead(const fibhip_ctx *h, int L, bool repeats, bool declare
     if (L < 2 || L > launch_cap(h, declared)) return false;
     // nothing forbids it: the switch and the caller's access to the state (Ahead::ok), no launch ahead already, no sampler
     // (see "what the recorders ask of the scheduler"), no timeline being taken (every launch there is the caller's own)
-    if (!h->ahead.ok || h->ahead.n != 0 || sampling(h) || h->tracing) return false;
+    if (!h->ahead.ok || h->ahead.n != 0 || sampling(h) || h->stim.on || h->tracing) return false;
     // the launch is the one the handle would make anyway: its plan is chosen (`tuned`, which is only ever set behind
     // check_ready — so has_consts holds with it and is stated for the reader, not tested twice), the slab is planar.
     // Nothing accepted is still waiting and no tick is open: fibhip_step refuses an open tick and tests `pending` here; at the
@@ -691,7 +758,7 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
         return fail(FIBHIP_EINVAL, "step: trace full (the %s recorder holds %lld samples; read it, then detach or re-attach)", who, full_cap);
     if (int rc = journal_bound(h)) return rc;
     // (the guards in front are may_run_ahead's own, taken first because most calls end at one of them)
-    if (nticks > 0 && h->ahead.n == 0 && h->mt.max > 1 && !sampling(h)) {
+    if (nticks > 0 && h->ahead.n == 0 && h->mt.max > 1 && !sampling(h) && !h->stim.on) {
         bool repeats = false;
         const bool declared = h->series.expect > 0;
         int L = 0;
@@ -725,10 +792,10 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
             h->pending += nticks;
             // (a call that goes past the end of its declaration leaves undeclared ticks behind the declared ones: none counts)
             h->series.covered = covered == nticks ? h->series.covered + covered : 0;
-            // With a sampler attached a launch goes out when the ticks up to the next sample tick are waiting (or mt.max of
+            // With a sampler attached (or a stimulus program with events to come) a launch goes out when the ticks up to the next sample tick are waiting (or mt.max of
             // them) and ends there: between two samples the handle runs the fewest launches `every` allows, whatever the
             // caller's call pattern.  (Without one: mt.cur, as described above.)
-            while (h->pending >= (sampling(h) ? imin(sample_room(h), launch_cap(h, pending_declared(h))) : h->mt.cur)) {
+            while (h->pending >= (cutting(h) ? imin(sample_room(h), launch_cap(h, pending_declared(h))) : h->mt.cur)) {
                 const int T = next_launch_ticks(h, h->pending);
                 take_pending(h, T);
                 if (int rc = tick_mt(h, v, T)) return rc;

@@ -293,6 +293,21 @@ class IonicModel:
             ensure()
         return StatsRecorder(self, columns, every=every, weight=weight, mask=mask, capacity=capacity)
 
+    def program_stimuli(self, stimuli):
+        """attaches a stimulus program (fib_tf_amd/stimulus.py) to this model's handle: a list of `Stimulus` entries — a site of
+        any shape, a value, the tick (or millisecond) of its first event, a period, a count, a hold, 'max' or 'add', any state
+        array — that the library applies on the device, each right after its tick, without a call per stimulus; `s1_train`,
+        `s1s2` and `burst` build the usual protocols.  Tick 0 is the first tick after this call: an entry with at_tick=i comes
+        where `for i in model.run(): if i == s2: model.fire_op('s2')` puts it.  add_pace_op / fire_op work as ever, also while
+        a program is attached.  Call after define(); single device only (row blocks raise NotImplementedError)."""
+        from .stimulus import StimulusProgram
+        if not self.defined:
+            raise AssertionError('program_stimuli should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return StimulusProgram(self, stimuli)
+
     def _frame_levels(self):
         """(lo, span) with image() == (X - lo) / span in float32, X the array pot() names: what a frame recorder maps the
         state with.  Models whose image() rescales override it."""

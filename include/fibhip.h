@@ -511,6 +511,60 @@ int fibhip_stats_count(fibhip_t h, long long *samples);
 int fibhip_stats_read(fibhip_t h, long long first, long long count, double *dst /* [count][ncols] */);
 int fibhip_stats_end(fibhip_t h);
 
+/* Stimulus program: stimuli applied on the device at programmed ticks, from sites of any shape, without a call per stimulus
+ * (the reference's only stimulus is add_pace_op / fire_op, fired from the caller's loop body: `if i == s2: fire_op('s2')`;
+ * fibhip_pace stands in for it and stays as it is).  A program is 1 .. FIBHIP_MAX_STIM_ENTRIES entries
+ * {var, mode, shape, first, period, count, hold} and up to FIBHIP_MAX_STIM_PLANES float32 planes [height*width].  Restated in
+ * NumPy in tests/stim_ref.py; the device equals that bit for bit.
+ * Event ticks.  With k = ticks since stim_begin (the first tick after it is k = 0), entry e is applied right after the tick that
+ * makes k + 1 == first + 1 + j * period + d, for j = 0 .. count - 1 and d = 0 .. hold - 1.  first >= 0; hold >= 1; period == 0
+ * means one event (count must be 1); count == 0 with period > 0 means without end; hold <= period when period > 0.  first = i is
+ * "after tick i of the loop", where `for i in m.run(): if i == s2: m.fire_op('s2')` puts it; a stimulus before any tick stays
+ * fibhip_pace's job.
+ * Modes, on the cells of array `var` (any state array; 0 is the potential), S the entry's value at the cell:
+ *     MAX   X = fmaxf(X, S)       fibhip_pace's operation (NumPy: np.fmax)
+ *     ADD   X = X + S             one float32 addition, rounded on its own
+ * A cell whose S is the mode's "untouched" value — -inf for MAX, +0 or -0 for ADD — is not written: its bits stay whatever they
+ * are (a NaN stays that NaN, -0 stays -0).
+ * Shapes.
+ *     RECT   rows [r0, r1) x columns [c0, c1), inside the grid and not empty: S = v inside (finite), `floor` outside (finite; -inf
+ *            for MAX).  MAX with floor = min_v is fibhip_pace(r0, r1, c0, c1, v, min_v), bit for bit; floor = -inf (MAX) or 0 (ADD)
+ *            leaves the outside untouched.
+ *     PLANE  S = planes[plane][cell].  At attach the host takes the bounding box of the cells that are not "untouched"; only that
+ *            box is visited.
+ * Order.  The entries due after the same tick are applied in program order in one launch (eight entries per launch; a thread
+ * reads each of its cells once and writes it once, whatever the number of entries).  Samples of the samplers and the activation
+ * recorder's update of that tick come first: a stimulus belongs to the next tick, as fibhip_pace between two ticks does.
+ * Courtemanche: a tick with an event due is never fused with the fibhip_step_slow behind it (the stimulus comes right after its
+ * tick, before anything the caller does next), and on a handle that runs on aggregates an entry on one of the 17 slow arrays
+ * marks them stale, as fibhip_set_state does.
+ * Launches.  No launch spans an event tick; between events the handle keeps its multi-tick launches, and a launch goes out when
+ * the ticks up to the next event have been accepted (the samplers' rule).  Nothing runs ahead of the caller while a program is
+ * attached.  The stimulus is queued on the handle's stream behind the launch that ends at its tick; nothing waits for it.  A
+ * multi-tick launch that gave up is recovered as ever: the replay applies the events of the replayed ticks again and no others.
+ * The same program gives the same bytes under every launch plan.
+ * Refused with FIBHIP_EINVAL, the message naming the entry: var, mode, shape or plane index out of range, a rectangle that is
+ * empty or not inside the grid, v or floor that is not finite (floor = -inf is MAX's "untouched"), first < 0, hold < 1, hold >
+ * period, period == 0 with count != 1, negative period or count; n or nplanes out of range, a second stim_begin without a
+ * stim_end, inside an open tick, a row block (a handle with ghost rows).
+ *   fibhip_stim_begin  flushes, synchronises and confirms pending work, copies the planes and attaches
+ *   fibhip_stim_count  flushes, then the number of events applied so far (every (entry, tick) pair counts once)
+ *   fibhip_stim_end    flushes, synchronises, detaches and frees (no program attached: nothing); fibhip_destroy frees too       */
+#define FIBHIP_MAX_STIM_ENTRIES 64
+#define FIBHIP_MAX_STIM_PLANES 8
+enum fibhip_stim_mode { FIBHIP_STIM_MAX = 0, FIBHIP_STIM_ADD = 1 };
+enum fibhip_stim_shape { FIBHIP_STIM_RECT = 0, FIBHIP_STIM_PLANE = 1 };
+typedef struct fibhip_stim_entry {
+    int var, mode, shape;       /* state array; FIBHIP_STIM_MAX / _ADD; FIBHIP_STIM_RECT / _PLANE */
+    int r0, r1, c0, c1;         /* RECT */
+    float v, floor;             /* RECT */
+    int plane;                  /* PLANE: index into the planes */
+    int first, period, count, hold;
+} fibhip_stim_entry;
+int fibhip_stim_begin(fibhip_t h, int n, const fibhip_stim_entry *entries, int nplanes, const float *planes /* [nplanes][H*W] or NULL */);
+int fibhip_stim_count(fibhip_t h, long long *applied);
+int fibhip_stim_end(fibhip_t h);
+
 const char *fibhip_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)
