@@ -15,5 +15,6 @@ from . import tips                              # noqa: F401  (TipRecorder, link
 from . import frames                            # noqa: F401  (FrameRecorder: the movie cube recorded on the device)
 from . import stats                             # noqa: F401  (StatsRecorder: tissue statistics recorded on the device)
 from . import stimulus                          # noqa: F401  (Stimulus, StimulusProgram: pacing protocols run on the device)
+from . import triggers                          # noqa: F401  (Sensor, Trigger, TriggerProgram: triggered stimulation on the device)
 
 __all__ = ['IonicModel', 'Fenton4v', 'BeelerReuter', 'Courtemanche']

@@ -23,6 +23,10 @@ MAX_STAT_COLS, MAX_STAT_COLS_PER_ARRAY = 64, 8
 STIM_MODES = ('max', 'add')                                       # enum fibhip_stim_mode, in order
 STIM_SHAPES = ('rect', 'plane')                                   # enum fibhip_stim_shape, in order
 MAX_STIM_ENTRIES, MAX_STIM_PLANES = 64, 8
+TRIG_EDGES = ('rise', 'fall')                                     # enum fibhip_trig_edge, in order
+TRIG_SITES = ('rect', 'mask')                                     # enum fibhip_trig_site, in order
+TRIG_FIELDS = ('c', 'a', 't', 'n', 'cause', 'fired')              # enum fibhip_trig_field, in order: one row of the log
+MAX_TRIG_SENSORS, MAX_TRIG_RULES, TRIG_MAX_TIME = 8, 8, 1 << 24
 CHEBY, SKIP, CHRONIC, FAST, ALLVARS, ROW_INTERLEAVED, ZEROPAD, HOLD = 1, 2, 4, 8, 16, 32, 64, 128
 
 # -ffp-contract=off: FMAs appear only where the source writes them (policy hook P::mad).
@@ -122,6 +126,18 @@ class StimEntry(C.Structure):
                 ('count', C.c_int), ('hold', C.c_int)]
 
 
+class TrigSensor(C.Structure):
+    _fields_ = [('var', C.c_int), ('level', C.c_float), ('need', C.c_int), ('site', C.c_int), ('r0', C.c_int), ('r1', C.c_int),
+                ('c0', C.c_int), ('c1', C.c_int)]
+
+
+class TrigRule(C.Structure):
+    _fields_ = [('sensor', C.c_int), ('edge', C.c_int), ('arm', C.c_int), ('blank', C.c_int), ('escape', C.c_int), ('max_det', C.c_int),
+                ('delay', C.c_int), ('count', C.c_int), ('period', C.c_int), ('hold', C.c_int), ('var', C.c_int), ('mode', C.c_int),
+                ('shape', C.c_int), ('r0', C.c_int), ('r1', C.c_int), ('c0', C.c_int), ('c1', C.c_int), ('v', C.c_float), ('floor', C.c_float),
+                ('plane', C.c_int)]
+
+
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
 _h = C.c_void_p
@@ -206,6 +222,11 @@ SYMBOLS = {
     'fibhip_stim_begin': ([_h, C.c_int, C.POINTER(StimEntry), C.c_int, _fp], C.c_int),
     'fibhip_stim_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_stim_end': ([_h], C.c_int),
+    'fibhip_trig_begin': ([_h, C.c_int, C.POINTER(TrigSensor), C.POINTER(C.c_ubyte), C.c_int, C.POINTER(TrigRule), C.c_int, _fp, C.c_int,
+                           C.c_longlong], C.c_int),
+    'fibhip_trig_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_trig_read': ([_h, C.c_longlong, C.c_longlong, _ip], C.c_int),
+    'fibhip_trig_end': ([_h], C.c_int),
     'fibhip_last_error': ([], C.c_char_p),
 }
 
@@ -903,3 +924,71 @@ class Stepper:
 
     def stim_end(self):
         self._ck(self._L.fibhip_stim_end(self._h))
+
+    # ---- trigger program (include/fibhip.h fibhip_trig_*) ---------------------------------------------------------
+    def trig_begin(self, sensors, rules, planes=None, every=1, capacity=4096):
+        """attaches a trigger program: `sensors` is a list of dicts with the fields of fibhip_trig_sensor (`site` 'rect' with r0,
+        r1, c0, c1, or 'mask' with `mask`, a [height, width] array whose non-zero cells are the site), `rules` a list of dicts
+        with the fields of fibhip_trig_rule (`edge` 'rise' / 'fall', `mode` 'max' / 'add', `shape` 'rect' / 'plane', or their
+        numbers; fields left out are 0, count and hold 1), `planes` the [height, width] float32 arrays the 'plane' stimuli index"""
+        sa = (TrigSensor * max(len(sensors), 1))()
+        masks = []
+        for i, q in enumerate(sensors[:MAX_TRIG_SENSORS]):
+            d = dict(q)
+            site = d.pop('site', 0)
+            sa[i].site = TRIG_SITES.index(site) if isinstance(site, str) else int(site)
+            sa[i].level, sa[i].need = float(d.pop('level', 0.0)), int(d.pop('need', 1))
+            mask = d.pop('mask', None)
+            if sa[i].site == 1:
+                if mask is None or np.shape(mask) != (self.height, self.width):
+                    raise ValueError('trig_begin: sensor %d: a mask of shape %s on a %d x %d grid' % (i, np.shape(mask), self.height, self.width))
+                masks.append((np.asarray(mask) != 0).astype(np.uint8))
+            for k, val in d.items():
+                if k not in ('var', 'r0', 'r1', 'c0', 'c1'):
+                    raise ValueError('trig_begin: sensor %d: unknown field %r' % (i, k))
+                setattr(sa[i], k, int(val))
+        ra = (TrigRule * max(len(rules), 1))()
+        for i, q in enumerate(rules[:MAX_TRIG_RULES]):
+            d = dict(q)
+            edge, mode, shape = d.pop('edge', 0), d.pop('mode', 0), d.pop('shape', 0)
+            ra[i].edge = TRIG_EDGES.index(edge) if isinstance(edge, str) else int(edge)
+            ra[i].mode = STIM_MODES.index(mode) if isinstance(mode, str) else int(mode)
+            ra[i].shape = STIM_SHAPES.index(shape) if isinstance(shape, str) else int(shape)
+            ra[i].hold, ra[i].count = int(d.pop('hold', 1)), int(d.pop('count', 1))
+            ra[i].v, ra[i].floor = float(d.pop('v', 0.0)), float(d.pop('floor', 0.0))
+            for k, val in d.items():
+                if k not in ('sensor', 'arm', 'blank', 'escape', 'max_det', 'delay', 'period', 'var', 'r0', 'r1', 'c0', 'c1', 'plane'):
+                    raise ValueError('trig_begin: rule %d: unknown field %r' % (i, k))
+                setattr(ra[i], k, int(val))
+        mp, mstack = None, None
+        if masks:
+            mstack = np.ascontiguousarray(np.stack(masks), np.uint8)
+            mp = mstack.ctypes.data_as(C.POINTER(C.c_ubyte))
+        pp, stack = None, None
+        if planes is not None and len(planes):
+            for p in planes:
+                if np.shape(p) != (self.height, self.width):
+                    raise ValueError('trig_begin: a plane of shape %s on a %d x %d grid' % (np.shape(p), self.height, self.width))
+            stack = np.ascontiguousarray(np.stack([np.asarray(p, np.float32) for p in planes]), np.float32)
+            pp = stack.ctypes.data_as(_fp)
+        self._ck(self._L.fibhip_trig_begin(self._h, len(sensors), sa, mp, len(rules), ra, 0 if stack is None else len(stack), pp, int(every),
+                                           int(capacity)))
+        self._trig_n = len(rules)
+
+    def trig_count(self):
+        """samples taken since trig_begin (ticks accepted but not launched yet included)"""
+        k = C.c_longlong()
+        self._ck(self._L.fibhip_trig_count(self._h, C.byref(k)))
+        return int(k.value)
+
+    def trig_read(self, first=0, count=None):
+        """rows [first, first + count) of the log as an int32 [count, nrules, 6] array — c, a, t, n, cause, fired — (count=None:
+        all taken so far); blocks like get_state, detaches nothing"""
+        if count is None:
+            count = self.trig_count() - int(first)
+        out = np.empty((max(int(count), 0), getattr(self, '_trig_n', 0), len(TRIG_FIELDS)), np.int32)
+        self._ck(self._L.fibhip_trig_read(self._h, int(first), int(count), out.ctypes.data_as(_ip)))
+        return out
+
+    def trig_end(self):
+        self._ck(self._L.fibhip_trig_end(self._h))

@@ -201,6 +201,28 @@ struct StimRec {
     float *planes;          // device: the planes, [nplanes][H][W], or null
 };
 
+// trigger program (fibhip_trig_begin): the closed loop — a sampler (no launch spans a sample tick: sample_room) whose hook on the
+// plain and the multi-tick commit path (trig_advance, behind stim_advance) enqueues sense_kernel, trigger_kernel and the gated
+// apply behind the launch that ends a sample tick.  The automaton's state IS the log on the device: row s follows from row
+// s - 1 and the state alone, and the host knows only the slot (k / every)
+struct TrigRec {
+    bool on;
+    int nsensors, nrules, every;
+    long long cap;          // samples the log holds
+    long long k;            // ticks LAUNCHED since the program was attached (recover() rewinds it by the ticks it replays)
+    bool cut_vec;           // the item tables' [1] entries may be used (pitch == W, W a multiple of 4)
+    int max_chunks[2];      // sense_kernel's grid.x, scalar / VEC
+    std::vector<StimEntry> stims;   // rule r's stimulus (first / period / count / hold unused: the automaton times it)
+    int vars[TRIG_MAX];     // the sensors' arrays
+    SenseSite *sites;       // device: the sensors
+    TrigRule *rules;        // device: the rules
+    unsigned char *masks;   // device: the mask sensors' masks, [nmasks][H][W], or null
+    float *planes;          // device: the stimulus planes, [nplanes][H][W], or null
+    unsigned *part;         // device: [nsensors][SENSE_MAX_CHUNKS]
+    int *rows;              // device: [cap][nrules][TRIG_ROW]
+    unsigned *fire;         // device: [cap], bit r: rule r fires after sample s
+};
+
 // fibhip_trace_begin / _end: the launches in between, each between two HIP events
 struct TraceRec {
     hipEvent_t e0, e1;
@@ -262,6 +284,7 @@ struct fibhip_ctx {
     FrRec fr;
     StRec st;
     StimRec stim;
+    TrigRec trig;
     std::vector<TraceRec> trace;
     bool tracing;
     // ---- the rest ----

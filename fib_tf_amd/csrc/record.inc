@@ -1,7 +1,7 @@
 // record.inc — the five recorders that run on the device while a model runs: the per-cell activation maps
 // (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
-// (fibhip_frames_*) and the tissue statistics (fibhip_stats_*) — and the stimulus program (fibhip_stim_*), the one hook that
-// writes the state.  Each is a hook behind a committed launch plus its entry points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
+// (fibhip_frames_*) and the tissue statistics (fibhip_stats_*) — and the two hooks that write the state: the stimulus program
+// (fibhip_stim_*) and the trigger program (fibhip_trig_*), which senses, decides and fires on the device.  Each is a hook behind a committed launch plus its entry points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
 // (included by fibhip.hip, behind sched.inc)
 
 // the activation recorder's update for the tick just committed (observed tick k = obs_k), on s0 behind it
@@ -237,6 +237,62 @@ static void stats_free(fibhip_ctx *h)
     h->st.on = false;
 }
 
+// What the stimulus program and the trigger program share.  stim_entry_from: one stimulus {var, mode, shape, rectangle, v, floor,
+// plane} as the caller gave it -> a validated StimEntry with its visit box cut (the timing fields are the caller's); `who` and
+// `what` name the entry point and the thing ("stim_begin", "entry" / "trig_begin", "rule") in the message.  stim_due_fill: a
+// StimEntry -> the StimDue a kernel takes by value, on the slab that holds the array now.
+static int stim_entry_from(const fibhip_ctx *h, const char *who, const char *what, int i, int var, int mode, int shape, int r0, int r1, int c0,
+                           int c1, float v, float floor, int plane, int nplanes, const float *planes, StimEntry &e)
+{
+    const int H = h->d.height, W = h->d.width;
+    const float ninf = -std::numeric_limits<float>::infinity();
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "%s: %s %d: bad var %d", who, what, i, var);
+    if (mode != FIBHIP_STIM_MAX && mode != FIBHIP_STIM_ADD) return fail(FIBHIP_EINVAL, "%s: %s %d: unknown mode %d", who, what, i, mode);
+    if (shape != FIBHIP_STIM_RECT && shape != FIBHIP_STIM_PLANE) return fail(FIBHIP_EINVAL, "%s: %s %d: unknown shape %d", who, what, i, shape);
+    e.var = var; e.mode = mode;
+    const float untouched = mode == FIBHIP_STIM_MAX ? ninf : 0.f;
+    if (shape == FIBHIP_STIM_RECT) {
+        if (r0 < 0 || r1 > H || c0 < 0 || c1 > W || r0 >= r1 || c0 >= c1)
+            return fail(FIBHIP_EINVAL, "%s: %s %d: rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", who, what, i, r0, r1, c0,
+                        c1, H, W);
+        if (!std::isfinite(v)) return fail(FIBHIP_EINVAL, "%s: %s %d: v must be finite (got %g)", who, what, i, v);
+        if (!(std::isfinite(floor) || (mode == FIBHIP_STIM_MAX && floor == ninf)))
+            return fail(FIBHIP_EINVAL, "%s: %s %d: floor must be finite%s (got %g)", who, what, i, mode == FIBHIP_STIM_MAX ? " or -inf" : "", floor);
+        e.plane = -1;
+        e.r0 = r0; e.r1 = r1; e.c0 = c0; e.c1 = c1;
+        e.v = v; e.floor = floor;
+        const bool outside_untouched = floor == untouched;
+        e.b_r0 = outside_untouched ? r0 : 0; e.b_r1 = outside_untouched ? r1 : H;
+        e.b_c0 = outside_untouched ? c0 : 0; e.b_c1 = outside_untouched ? c1 : W;
+    } else {
+        if (plane < 0 || plane >= nplanes) return fail(FIBHIP_EINVAL, "%s: %s %d: plane %d of %d", who, what, i, plane, nplanes);
+        e.plane = plane;
+        const float *p = planes + (size_t)plane * h->cells;
+        int b_r0 = H, b_r1 = 0, b_c0 = W, b_c1 = 0;
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x)
+                if (!(p[(size_t)y * W + x] == untouched)) {         // (a NaN is not "untouched")
+                    b_r0 = imin(b_r0, y); b_r1 = imax(b_r1, y + 1);
+                    b_c0 = imin(b_c0, x); b_c1 = imax(b_c1, x + 1);
+                }
+        if (b_r0 >= b_r1) b_r0 = b_r1 = b_c0 = b_c1 = 0;
+        e.b_r0 = b_r0; e.b_r1 = b_r1; e.b_c0 = b_c0; e.b_c1 = b_c1;
+    }
+#if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
+    e.slow = h->d.model == FIBHIP_COURT && !((Courtemanche::FAST_MASK >> var) & 1u);
+#endif
+    return 0;
+}
+static void stim_due_fill(const fibhip_ctx *h, const StimEntry &e, float *planes, StimDue &d)
+{
+    d.x = h->slab[h->cur[e.var]] + (size_t)e.var * h->vstride;
+    d.plane = e.plane >= 0 ? planes + (size_t)e.plane * h->cells : nullptr;
+    d.mode = e.mode;
+    d.b_r0 = e.b_r0; d.b_r1 = e.b_r1; d.b_c0 = e.b_c0; d.b_c1 = e.b_c1;
+    d.r0 = e.r0; d.r1 = e.r1; d.c0 = e.c0; d.c1 = e.c1;
+    d.v = e.v; d.floor = e.floor;
+}
+
 static_assert(STIM_MAX_DUE <= FIBHIP_MAX_STIM_ENTRIES && (int)STIM_MAX == (int)FIBHIP_STIM_MAX && (int)STIM_ADD == (int)FIBHIP_STIM_ADD,
               "stim_kernel's constants follow include/fibhip.h");
 // The stimulus program's hook behind a launch of `ticks` ticks (plain: commit_impl; multi-tick: mt_launch), behind the samples of
@@ -270,14 +326,9 @@ static int stim_advance(fibhip_ctx *h, int ticks, bool behind_mt)
         for (size_t i = 0; i < n; ++i) {
             const StimEntry &e = *due[first + i];
             StimDue &d = a.e[i];
-            d.x = h->slab[h->cur[e.var]] + (size_t)e.var * h->vstride;
-            d.plane = e.plane >= 0 ? r.planes + (size_t)e.plane * h->cells : nullptr;
-            d.mode = e.mode;
+            stim_due_fill(h, e, r.planes, d);
             d.load = i == 0 || due[first + i - 1]->var != e.var;
             d.store = i + 1 == n || due[first + i + 1]->var != e.var;
-            d.b_r0 = e.b_r0; d.b_r1 = e.b_r1; d.b_c0 = e.b_c0; d.b_c1 = e.b_c1;
-            d.r0 = e.r0; d.r1 = e.r1; d.c0 = e.c0; d.c1 = e.c1;
-            d.v = e.v; d.floor = e.floor;
             align |= reinterpret_cast<uintptr_t>(d.x) | reinterpret_cast<uintptr_t>(d.plane);
             if (e.b_r0 < e.b_r1) {
                 a.r0 = imin(a.r0, e.b_r0); a.r1 = imax(a.r1, e.b_r1);
@@ -313,6 +364,115 @@ static void stim_free(fibhip_ctx *h)
     h->stim.planes = nullptr;
     h->stim.entries.clear();
     h->stim.on = false;
+}
+
+static_assert(TRIG_MAX == FIBHIP_MAX_TRIG_SENSORS && TRIG_MAX == FIBHIP_MAX_TRIG_RULES && TRIG_MAX <= STIM_MAX_DUE && TRIG_ROW == FIBHIP_TRIG_ROW &&
+                  (int)TRIG_RISE == (int)FIBHIP_TRIG_RISE && (int)TRIG_FALL == (int)FIBHIP_TRIG_FALL && SENSE_MAX_CHUNKS == 4 * 64 &&
+                  SENSE_MIN_CHUNK % SENSE_THREADS == 0,
+              "the trigger kernels' constants follow include/fibhip.h; trigger_kernel folds four chunks per lane of one wave");
+// The trigger program's hook behind a launch of `ticks` ticks, behind the samples and the programmed stimuli of that tick.  At a
+// sample tick three launches go out on s0 behind the launch that ended there, WITHOUT confirming it: sense_kernel (one partial
+// count per sensor and chunk), trigger_kernel (row s of the log and the fire mask of sample s) and the gated apply (the rules'
+// stimuli, all by value; entry r is rule r's).  The slot s is a kernel argument computed from the host's counter, so a replay
+// (recover()) writes the same rows again.  `behind_mt`: as for stim_advance — the gated apply is handed the give-up word and
+// writes nothing once a launch in front of it gave up.
+static int trig_advance(fibhip_ctx *h, int ticks, bool behind_mt)
+{
+    TrigRec &r = h->trig;
+    r.k += ticks;
+    if (r.k % r.every) return 0;
+    const long long s = r.k / r.every - 1;
+    if (s >= r.cap) return fail(FIBHIP_EINVAL, "trigger program: log full");                    // (fibhip_step refuses before this)
+    const int W = h->d.width;
+    SenseArgs a;
+    a.slab0 = h->slab[0];
+    a.slab1 = h->slab[1];
+    a.cur_mask = 0u;
+    uintptr_t align = reinterpret_cast<uintptr_t>(r.masks);
+    for (int i = 0; i < r.nsensors; ++i) {
+        const int v = r.vars[i];
+        if (h->cur[v]) a.cur_mask |= 1u << v;
+        align |= reinterpret_cast<uintptr_t>(h->slab[h->cur[v]] + (size_t)v * h->vstride);
+    }
+    a.W = W;
+    a.pitch = h->pitch;
+    a.vstride = h->vstride;
+    a.cells = h->cells;
+    a.sites = r.sites;
+    a.masks = r.masks;
+    a.part = r.part;
+    const bool vec = r.cut_vec && (align & 15u) == 0;
+    {
+        const dim3 grid((unsigned)r.max_chunks[vec], (unsigned)r.nsensors);
+        if (int rc = trace_open(h, h->s0, vec ? "sense_kernel<true>" : "sense_kernel<false>", 0, 0, 0, 0, 1)) return rc;
+        if (vec) hipLaunchKernelGGL(sense_kernel<true>, grid, dim3(SENSE_THREADS), 0, h->s0, a);
+        else hipLaunchKernelGGL(sense_kernel<false>, grid, dim3(SENSE_THREADS), 0, h->s0, a);
+        HIPCHK(hipGetLastError());
+        if (int rc = trace_close(h, h->s0)) return rc;
+        h->launches++;
+    }
+    if (int rc = trace_open(h, h->s0, "trigger_kernel", 0, 0, 0, 0, 1)) return rc;
+    hipLaunchKernelGGL(trigger_kernel, dim3(1), dim3(256), 0, h->s0, r.sites, r.nsensors, vec ? 1 : 0, r.part, r.rules, r.nrules, r.rows, r.fire, (int)s);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    // the gated apply: the union of the rules' visit boxes, every sample (its workgroups leave after two scalar loads when no
+    // rule fires)
+    StimArgs g;
+    memset(&g, 0, sizeof g);
+    g.r0 = g.c0 = INT_MAX;
+    uintptr_t galign = 0;
+    for (int i = 0; i < r.nrules; ++i) {
+        const StimEntry &e = r.stims[i];
+        StimDue &d = g.e[i];
+        stim_due_fill(h, e, r.planes, d);
+        d.load = d.store = 1;
+        galign |= reinterpret_cast<uintptr_t>(d.x) | reinterpret_cast<uintptr_t>(d.plane);
+        if (e.b_r0 < e.b_r1) {
+            g.r0 = imin(g.r0, e.b_r0); g.r1 = imax(g.r1, e.b_r1);
+            g.c0 = imin(g.c0, e.b_c0); g.c1 = imax(g.c1, e.b_c1);
+        }
+    }
+    if (g.r0 >= g.r1) return 0;                                     // (planes that leave every cell untouched: nothing to visit)
+    g.n = r.nrules;
+    g.W = W;
+    g.pitch = h->pitch;
+    g.give_up = behind_mt && h->mt.epochs ? h->mt.give_up_word() : nullptr;
+    const bool gvec = h->pitch == W && W % 4 == 0 && (galign & 15u) == 0;
+    if (gvec) {
+        g.c0 = g.c0 / 4 * 4;
+        g.c1 = (g.c1 + 3) / 4 * 4;                                  // (<= W: W is a multiple of 4)
+    }
+    const size_t threads = (size_t)(g.r1 - g.r0) * (size_t)((g.c1 - g.c0) / (gvec ? 4 : 1));
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (int rc = trace_open(h, h->s0, gvec ? "stim_gated_kernel<true>" : "stim_gated_kernel<false>", 0, 0, 0, 0, 1)) return rc;
+    if (gvec) hipLaunchKernelGGL(stim_gated_kernel<true>, grid, dim3(256), 0, h->s0, g, (const unsigned *)(r.fire + s));
+    else hipLaunchKernelGGL(stim_gated_kernel<false>, grid, dim3(256), 0, h->s0, g, (const unsigned *)(r.fire + s));
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    return 0;
+}
+
+static void trig_free(fibhip_ctx *h)
+{
+    TrigRec &r = h->trig;
+    if (r.sites) hipFree(r.sites);
+    if (r.rules) hipFree(r.rules);
+    if (r.masks) hipFree(r.masks);
+    if (r.planes) hipFree(r.planes);
+    if (r.part) hipFree(r.part);
+    if (r.rows) hipFree(r.rows);
+    if (r.fire) hipFree(r.fire);
+    r.sites = nullptr;
+    r.rules = nullptr;
+    r.masks = nullptr;
+    r.planes = nullptr;
+    r.part = nullptr;
+    r.rows = nullptr;
+    r.fire = nullptr;
+    r.stims.clear();
+    r.on = false;
 }
 
 // ---- activation recorder ------------------------------------------------------------------------------------------------
@@ -835,54 +995,19 @@ extern "C" int fibhip_stim_begin(fibhip_t h, int n, const fibhip_stim_entry *ent
     if (n < 1 || n > FIBHIP_MAX_STIM_ENTRIES) return fail(FIBHIP_EINVAL, "stim_begin: 1 .. %d entries (got %d)", FIBHIP_MAX_STIM_ENTRIES, n);
     if (nplanes < 0 || nplanes > FIBHIP_MAX_STIM_PLANES || (nplanes > 0 && !planes))
         return fail(FIBHIP_EINVAL, "stim_begin: 0 .. %d planes (got %d%s)", FIBHIP_MAX_STIM_PLANES, nplanes, nplanes > 0 && !planes ? ", null" : "");
-    const int H = h->d.height, W = h->d.width;
-    const float ninf = -std::numeric_limits<float>::infinity();
     std::vector<StimEntry> list;
     for (int i = 0; i < n; ++i) {
         const fibhip_stim_entry &s = entries[i];
         StimEntry e;
         memset(&e, 0, sizeof e);
-        if (s.var < 0 || s.var >= h->nvar) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: bad var %d", i, s.var);
-        if (s.mode != FIBHIP_STIM_MAX && s.mode != FIBHIP_STIM_ADD) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: unknown mode %d", i, s.mode);
-        if (s.shape != FIBHIP_STIM_RECT && s.shape != FIBHIP_STIM_PLANE) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: unknown shape %d", i, s.shape);
         if (s.first < 0) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: first must be >= 0 (got %d)", i, s.first);
         if (s.hold < 1) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: hold must be >= 1 (got %d)", i, s.hold);
         if (s.period < 0 || s.count < 0) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: period and count must be >= 0 (got %d, %d)", i, s.period, s.count);
         if (s.period == 0 && s.count != 1) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: period 0 means one event: count must be 1 (got %d)", i, s.count);
         if (s.period > 0 && s.hold > s.period) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: hold %d > period %d", i, s.hold, s.period);
-        e.var = s.var; e.mode = s.mode;
         e.first = s.first; e.period = s.period; e.count = s.count; e.hold = s.hold;
-        const float untouched = s.mode == FIBHIP_STIM_MAX ? ninf : 0.f;
-        if (s.shape == FIBHIP_STIM_RECT) {
-            if (s.r0 < 0 || s.r1 > H || s.c0 < 0 || s.c1 > W || s.r0 >= s.r1 || s.c0 >= s.c1)
-                return fail(FIBHIP_EINVAL, "stim_begin: entry %d: rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", i, s.r0,
-                            s.r1, s.c0, s.c1, H, W);
-            if (!std::isfinite(s.v)) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: v must be finite (got %g)", i, s.v);
-            if (!(std::isfinite(s.floor) || (s.mode == FIBHIP_STIM_MAX && s.floor == ninf)))
-                return fail(FIBHIP_EINVAL, "stim_begin: entry %d: floor must be finite%s (got %g)", i, s.mode == FIBHIP_STIM_MAX ? " or -inf" : "", s.floor);
-            e.plane = -1;
-            e.r0 = s.r0; e.r1 = s.r1; e.c0 = s.c0; e.c1 = s.c1;
-            e.v = s.v; e.floor = s.floor;
-            const bool outside_untouched = s.floor == untouched;
-            e.b_r0 = outside_untouched ? s.r0 : 0; e.b_r1 = outside_untouched ? s.r1 : H;
-            e.b_c0 = outside_untouched ? s.c0 : 0; e.b_c1 = outside_untouched ? s.c1 : W;
-        } else {
-            if (s.plane < 0 || s.plane >= nplanes) return fail(FIBHIP_EINVAL, "stim_begin: entry %d: plane %d of %d", i, s.plane, nplanes);
-            e.plane = s.plane;
-            const float *p = planes + (size_t)s.plane * h->cells;
-            int r0 = H, r1 = 0, c0 = W, c1 = 0;
-            for (int y = 0; y < H; ++y)
-                for (int x = 0; x < W; ++x)
-                    if (!(p[(size_t)y * W + x] == untouched)) {         // (a NaN is not "untouched")
-                        r0 = imin(r0, y); r1 = imax(r1, y + 1);
-                        c0 = imin(c0, x); c1 = imax(c1, x + 1);
-                    }
-            if (r0 >= r1) r0 = r1 = c0 = c1 = 0;
-            e.b_r0 = r0; e.b_r1 = r1; e.b_c0 = c0; e.b_c1 = c1;
-        }
-#if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
-        e.slow = h->d.model == FIBHIP_COURT && !((Courtemanche::FAST_MASK >> s.var) & 1u);
-#endif
+        if (int rc = stim_entry_from(h, "stim_begin", "entry", i, s.var, s.mode, s.shape, s.r0, s.r1, s.c0, s.c1, s.v, s.floor, s.plane, nplanes, planes, e))
+            return rc;
         list.push_back(e);
     }
     if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "stim_begin: not on a row block (a handle with ghost rows)");
@@ -929,5 +1054,187 @@ extern "C" int fibhip_stim_end(fibhip_t h)
     FLUSH(h);                                          // the events of the ticks accepted while attached are applied
     SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the program
     stim_free(h);
+    return 0;
+}
+
+// ---- trigger program ----------------------------------------------------------------------------------------------------
+extern "C" int fibhip_trig_begin(fibhip_t h, int nsensors, const fibhip_trig_sensor *sensors, const unsigned char *masks, int nrules,
+                                 const fibhip_trig_rule *rules, int nplanes, const float *planes, int every, long long capacity)
+{
+    NEED(h);
+    if (!sensors || !rules) return fail(FIBHIP_EINVAL, "trig_begin: null argument");
+    if (nsensors < 1 || nsensors > FIBHIP_MAX_TRIG_SENSORS)
+        return fail(FIBHIP_EINVAL, "trig_begin: 1 .. %d sensors (got %d)", FIBHIP_MAX_TRIG_SENSORS, nsensors);
+    if (nrules < 1 || nrules > FIBHIP_MAX_TRIG_RULES) return fail(FIBHIP_EINVAL, "trig_begin: 1 .. %d rules (got %d)", FIBHIP_MAX_TRIG_RULES, nrules);
+    if (nplanes < 0 || nplanes > FIBHIP_MAX_STIM_PLANES || (nplanes > 0 && !planes))
+        return fail(FIBHIP_EINVAL, "trig_begin: 0 .. %d planes (got %d%s)", FIBHIP_MAX_STIM_PLANES, nplanes, nplanes > 0 && !planes ? ", null" : "");
+    if (every < 1) return fail(FIBHIP_EINVAL, "trig_begin: every must be >= 1 (got %d)", every);
+    if (capacity < 1 || capacity > (long long)INT_MAX) return fail(FIBHIP_EINVAL, "trig_begin: bad capacity %lld", capacity);
+    const int H = h->d.height, W = h->d.width;
+    if (h->cells > (size_t)INT_MAX) return fail(FIBHIP_EINVAL, "trig_begin: a grid of %zu cells is too large for the 32-bit counts", h->cells);
+    const bool cut_vec = h->pitch == W && W % 4 == 0;
+    std::vector<SenseSite> sites;
+    int nmasks = 0, max_chunks[2] = {1, 1}, vars[TRIG_MAX] = {0};
+    for (int i = 0; i < nsensors; ++i) {
+        const fibhip_trig_sensor &q = sensors[i];
+        SenseSite d;
+        memset(&d, 0, sizeof d);
+        if (q.var < 0 || q.var >= h->nvar) return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: bad var %d", i, q.var);
+        if (std::isnan(q.level)) return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: the level must be a number", i);
+        long long cells_of_site = 0;
+        if (q.site == FIBHIP_TRIG_RECT) {
+            if (q.r0 < 0 || q.r1 > H || q.c0 < 0 || q.c1 > W || q.r0 >= q.r1 || q.c0 >= q.c1)
+                return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", i, q.r0,
+                            q.r1, q.c0, q.c1, H, W);
+            d.r0 = q.r0; d.r1 = q.r1; d.c0 = q.c0; d.c1 = q.c1;
+            d.mask = -1;
+            cells_of_site = (long long)(q.r1 - q.r0) * (q.c1 - q.c0);
+        } else if (q.site == FIBHIP_TRIG_MASK) {
+            if (!masks) return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: a mask site without masks", i);
+            const unsigned char *m = masks + (size_t)nmasks * h->cells;
+            int r0 = H, r1 = 0, c0 = W, c1 = 0;
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x)
+                    if (m[(size_t)y * W + x]) {
+                        r0 = imin(r0, y); r1 = imax(r1, y + 1);
+                        c0 = imin(c0, x); c1 = imax(c1, x + 1);
+                        ++cells_of_site;
+                    }
+            if (cells_of_site == 0) return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: the mask holds no cell", i);
+            d.r0 = r0; d.r1 = r1; d.c0 = c0; d.c1 = c1;
+            d.mask = nmasks++;
+        } else {
+            return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: unknown site kind %d", i, q.site);
+        }
+        if (q.need < 1 || q.need > cells_of_site)
+            return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: need must be 1 .. %lld, the cells of the site (got %d)", i, cells_of_site, q.need);
+        d.var = q.var; d.level = q.level; d.need = q.need;
+        vars[i] = q.var;
+        for (int v = 0; v < 2; ++v) {
+            const unsigned per_row = v ? (unsigned)(((d.c1 + 3) / 4 * 4 - d.c0 / 4 * 4) / 4) : (unsigned)(d.c1 - d.c0);
+            const unsigned items = (unsigned)(d.r1 - d.r0) * per_row;
+            unsigned pc = (items + SENSE_MAX_CHUNKS - 1) / SENSE_MAX_CHUNKS;
+            pc = (pc + SENSE_THREADS - 1) / SENSE_THREADS * SENSE_THREADS;
+            if (pc < SENSE_MIN_CHUNK) pc = SENSE_MIN_CHUNK;
+            d.per_row[v] = per_row; d.items[v] = items; d.per_chunk[v] = pc;
+            d.nchunks[v] = (int)((items + pc - 1) / pc);                // (<= SENSE_MAX_CHUNKS: pc >= items / SENSE_MAX_CHUNKS)
+            max_chunks[v] = imax(max_chunks[v], d.nchunks[v]);
+        }
+        sites.push_back(d);
+    }
+    std::vector<TrigRule> table;
+    std::vector<StimEntry> stims;
+    for (int i = 0; i < nrules; ++i) {
+        const fibhip_trig_rule &q = rules[i];
+        if (q.sensor < 0 || q.sensor >= nsensors) return fail(FIBHIP_EINVAL, "trig_begin: rule %d: sensor %d of %d", i, q.sensor, nsensors);
+        if (q.edge != FIBHIP_TRIG_RISE && q.edge != FIBHIP_TRIG_FALL) return fail(FIBHIP_EINVAL, "trig_begin: rule %d: unknown edge %d", i, q.edge);
+        const int times[] = {q.arm, q.blank, q.escape, q.max_det, q.delay, q.period};
+        for (int t : times)
+            if (t < 0 || t > FIBHIP_TRIG_MAX_TIME)
+                return fail(FIBHIP_EINVAL, "trig_begin: rule %d: arm, blank, escape, max_det, delay and period must be 0 .. %d", i, FIBHIP_TRIG_MAX_TIME);
+        if (q.count < 1 || q.count > FIBHIP_TRIG_MAX_TIME || q.hold < 1 || q.hold > FIBHIP_TRIG_MAX_TIME)
+            return fail(FIBHIP_EINVAL, "trig_begin: rule %d: count and hold must be >= 1 (got %d, %d)", i, q.count, q.hold);
+        if (q.period == 0 && q.count != 1) return fail(FIBHIP_EINVAL, "trig_begin: rule %d: period 0 means one pulse: count must be 1 (got %d)", i, q.count);
+        if (q.period > 0 && q.hold > q.period) return fail(FIBHIP_EINVAL, "trig_begin: rule %d: hold %d > period %d", i, q.hold, q.period);
+        const long long train = (long long)q.delay + (long long)(q.count - 1) * q.period + q.hold;
+        if ((long long)q.blank < train)
+            return fail(FIBHIP_EINVAL, "trig_begin: rule %d: blank %d is too short: a train must not be cut by a new detection, blank >= delay + (count - 1) * period + hold = %lld",
+                        i, q.blank, train);
+        TrigRule k = {q.sensor, q.edge, q.arm, q.blank, q.escape, q.max_det, q.delay, q.count, q.period, q.hold};
+        table.push_back(k);
+        // the stimulus: the stimulus program's rules for an entry
+        StimEntry e;
+        memset(&e, 0, sizeof e);
+        if (int rc = stim_entry_from(h, "trig_begin", "rule", i, q.var, q.mode, q.shape, q.r0, q.r1, q.c0, q.c1, q.v, q.floor, q.plane, nplanes, planes, e))
+            return rc;
+#if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
+        // the host cannot know when a rule fires, so it cannot mark the aggregates stale: on a handle that runs on them a rule's
+        // stimulus names one of the four fast arrays
+        if (h->use_agg && h->d.model == FIBHIP_COURT && !((Courtemanche::FAST_MASK >> q.var) & 1u))
+            return fail(FIBHIP_EINVAL, "trig_begin: rule %d: array %d is one of the slow arrays the aggregates are formed from (a triggered stimulus "
+                        "cannot name it on a handle that runs on aggregates)", i, q.var);
+#endif
+        stims.push_back(e);
+    }
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "trig_begin: not on a row block (a handle with ghost rows)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "trig_begin inside an open tick");
+    if (h->trig.on) return fail(FIBHIP_EINVAL, "trig_begin: a program is attached already (fibhip_trig_end first)");
+    // everything accepted so far runs unsensed and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // sample 0 is defined (the rule of fibhip_electrode_begin) — every journal record is younger than the program
+    FLUSH(h);
+    SYNC_S0(h);
+    trig_free(h);
+    TrigRec &r = h->trig;
+    bool ok = hipMalloc((void **)&r.sites, sites.size() * sizeof(SenseSite)) == hipSuccess &&
+              hipMalloc((void **)&r.rules, table.size() * sizeof(TrigRule)) == hipSuccess &&
+              hipMalloc((void **)&r.part, (size_t)nsensors * SENSE_MAX_CHUNKS * sizeof(unsigned)) == hipSuccess &&
+              hipMalloc((void **)&r.rows, (size_t)capacity * (size_t)nrules * TRIG_ROW * sizeof(int)) == hipSuccess &&
+              hipMalloc((void **)&r.fire, (size_t)capacity * sizeof(unsigned)) == hipSuccess;
+    if (ok && nmasks > 0) ok = hipMalloc((void **)&r.masks, (size_t)nmasks * h->cells) == hipSuccess;
+    if (ok && nplanes > 0) ok = hipMalloc((void **)&r.planes, (size_t)nplanes * h->cells * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        trig_free(h);
+        return fail(FIBHIP_ENOMEM, "trig_begin: hipMalloc of the program's buffers failed (%lld samples of %d rules)", capacity, nrules);
+    }
+    HIPCHK(hipMemcpyAsync(r.sites, sites.data(), sites.size() * sizeof(SenseSite), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemcpyAsync(r.rules, table.data(), table.size() * sizeof(TrigRule), hipMemcpyHostToDevice, h->s0));
+    if (r.masks) HIPCHK(hipMemcpyAsync(r.masks, masks, (size_t)nmasks * h->cells, hipMemcpyHostToDevice, h->s0));
+    if (r.planes) HIPCHK(hipMemcpyAsync(r.planes, planes, (size_t)nplanes * h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemsetAsync(r.part, 0, (size_t)nsensors * SENSE_MAX_CHUNKS * sizeof(unsigned), h->s0));
+    HIPCHK(hipMemsetAsync(r.rows, 0, (size_t)capacity * (size_t)nrules * TRIG_ROW * sizeof(int), h->s0));
+    HIPCHK(hipMemsetAsync(r.fire, 0, (size_t)capacity * sizeof(unsigned), h->s0));
+    HIPCHK(wait_stream(h->s0));                        // the tables and the caller's masks and planes are free again
+    r.on = true;
+    r.nsensors = nsensors;
+    r.nrules = nrules;
+    r.every = every;
+    r.cap = capacity;
+    r.k = 0;
+    r.cut_vec = cut_vec;
+    r.max_chunks[0] = max_chunks[0];
+    r.max_chunks[1] = max_chunks[1];
+    memcpy(r.vars, vars, sizeof vars);
+    r.stims.swap(stims);
+    return 0;
+}
+
+extern "C" int fibhip_trig_count(fibhip_t h, long long *samples)
+{
+    NEED(h);
+    if (!samples) return fail(FIBHIP_EINVAL, "trig_count: null argument");
+    if (!h->trig.on) return fail(FIBHIP_EINVAL, "trig_count: no program attached (fibhip_trig_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    *samples = (h->trig.k + h->pending) / h->trig.every;   // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+
+extern "C" int fibhip_trig_read(fibhip_t h, long long first, long long count, int *dst)
+{
+    NEED(h);
+    if (!h->trig.on) return fail(FIBHIP_EINVAL, "trig_read: no program attached (fibhip_trig_begin)");
+    FLUSH(h);
+    const long long taken = h->trig.k / h->trig.every;
+    if (first < 0 || count < 0 || first + count > taken)
+        return fail(FIBHIP_EINVAL, "trig_read: samples [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "trig_read: null destination");
+    const size_t row = (size_t)h->trig.nrules * TRIG_ROW;
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->journal.n_fallbacks;
+        if (count > 0)
+            HIPCHK(hipMemcpyAsync(dst, h->trig.rows + (size_t)first * row, (size_t)count * row * sizeof(int), hipMemcpyDeviceToHost, h->s0));
+        SYNC_S0(h);
+        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered, the rows rewritten, copy again)
+    }
+    return 0;
+}
+
+extern "C" int fibhip_trig_end(fibhip_t h)
+{
+    NEED(h);
+    if (!h->trig.on) return 0;
+    FLUSH(h);                                          // the ticks accepted while attached are sensed, their stimuli applied
+    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the program
+    trig_free(h);
     return 0;
 }

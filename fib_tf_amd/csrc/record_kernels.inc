@@ -711,3 +711,196 @@ __global__ void __launch_bounds__(256) stim_kernel(StimArgs a)
         }
     }
 }
+
+// ---- trigger program (fibhip_trig_begin): sense a site, decide, fire — three small launches behind a sample tick -------------
+// sense_kernel counts, per sensor, the cells of its site with X > level (strict float32 compare: a NaN does not count).  The
+// count is an INTEGER and independent of order — a decision must not hang on the rounding of a float sum — so there is no fixed
+// tree here: wave ballots, popcounts, integer adds.  Grid (chunks, sensors): a workgroup of SENSE_THREADS threads walks one
+// chunk of the items of one sensor's box, row-major (an item: VEC — planar slab, W a multiple of 4, every pointer 16-byte
+// aligned, the box widened to whole groups of four columns — four consecutive cells of one row, one 16-byte load and the
+// mask's four bytes as one 32-bit load; otherwise one cell).  The loop is wave-uniform (an item beyond the chunk's end gets an
+// in-range address and a false predicate), each predicate goes through __ballot and the popcount lands in a scalar register;
+// lane 0 of each wave hands its count through LDS, one thread adds the four and writes ONE plain 32-bit vector store per
+// (sensor, chunk).  Workgroups beyond a sensor's last chunk leave at once.  No atomics, no float arithmetic at all.
+#define TRIG_MAX 8                  // sensors / rules of one program (== STIM_MAX_DUE: the rules' stimuli fit one launch)
+#define SENSE_THREADS 256
+#define SENSE_MAX_CHUNKS 256        // chunks of one sensor: what trigger_kernel folds, four per lane of one wave
+#define SENSE_MIN_CHUNK 1024        // items (a multiple of SENSE_THREADS)
+struct SenseSite {
+    int var;
+    float level;
+    int need;
+    int r0, r1, c0, c1;             // the site's box: the cells inside it count (and where the mask is not 0, if there is one)
+    int mask;                       // index into the masks, or -1: the rectangle itself
+    // [0]: one cell per item; [1]: VEC, columns [c0 / 4 * 4, (c1 + 3) / 4 * 4) in groups of four
+    unsigned per_row[2], items[2], per_chunk[2];
+    int nchunks[2];
+};
+struct SenseArgs {
+    const float *slab0, *slab1;
+    unsigned cur_mask;              // bit v: array v lives in slab1
+    int W, pitch;
+    unsigned long long vstride, cells;
+    const SenseSite *sites;
+    const unsigned char *masks;     // [nmasks][H][W] or null
+    unsigned *part;                 // [nsensors][SENSE_MAX_CHUNKS]
+};
+
+template <bool VEC>
+__global__ void __launch_bounds__(SENSE_THREADS) sense_kernel(SenseArgs a)
+{
+    constexpr int N = VEC ? 4 : 1;
+    __shared__ unsigned wres[SENSE_THREADS / 64];
+    const SenseSite *__restrict__ d = a.sites + blockIdx.y;               // (wave-uniform: scalar loads)
+    if ((int)blockIdx.x >= d->nchunks[VEC]) return;
+    const float *__restrict__ x = (((a.cur_mask >> d->var) & 1u) ? a.slab1 : a.slab0) + (size_t)d->var * (size_t)a.vstride;
+    const unsigned char *__restrict__ mp = d->mask >= 0 ? a.masks + (size_t)d->mask * (size_t)a.cells : nullptr;
+    const float level = d->level;
+    const int r0 = d->r0, c0 = d->c0, c1 = d->c1, cv0 = VEC ? c0 / 4 * 4 : c0;
+    const unsigned per_row = d->per_row[VEC], items = d->items[VEC], per_chunk = d->per_chunk[VEC];
+    const unsigned first = blockIdx.x * per_chunk;                        // (< items: blockIdx.x < nchunks)
+    const unsigned end = items - first < per_chunk ? items : first + per_chunk;
+    unsigned count = 0u;                                                  // (wave-uniform: sums of popcounts)
+    for (unsigned base = first; base < end; base += SENSE_THREADS) {
+        const unsigned t = base + threadIdx.x;
+        const bool in = t < end;
+        const unsigned q = in ? t : first;                                // (an in-range address; the predicate drops it)
+        const int y = r0 + (int)(q / per_row), x0 = cv0 + N * (int)(q % per_row);
+        const size_t at = (size_t)y * (size_t)a.pitch + (size_t)x0, mat = (size_t)y * (size_t)a.W + (size_t)x0;
+        float xs[N];
+        unsigned m;
+        if (VEC) {
+            const fib_v4f v = *reinterpret_cast<const fib_v4f *>(x + at);
+#pragma unroll
+            for (int j = 0; j < N; ++j) xs[j] = v[j];
+            m = mp ? *reinterpret_cast<const unsigned *>(mp + mat) : 0x01010101u;
+        } else {
+            xs[0] = x[at];
+            m = mp ? (unsigned)mp[mat] : 1u;
+        }
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const bool hit = in && x0 + j >= c0 && x0 + j < c1 && ((m >> (8 * j)) & 0xFFu) != 0u && xs[j] > level;
+            count += (unsigned)__popcll(__ballot(hit));
+        }
+    }
+    if ((threadIdx.x & 63u) == 0u) wres[threadIdx.x >> 6] = count;
+    __syncthreads();
+    if (threadIdx.x == 0) a.part[(size_t)blockIdx.y * SENSE_MAX_CHUNKS + blockIdx.x] = (wres[0] + wres[1]) + (wres[2] + wres[3]);
+}
+
+// trigger_kernel: ONE workgroup of four waves; the waves 1 .. 3 only fold (they leave behind the barrier), wave 0 folds and then
+// runs the rules, one per lane.  Wave w folds the partials of the sensors w, w + 4 (lane l: chunks 4l .. 4l + 3,
+// then six levels of __shfl_down; integer adds, so the order is free) into c_s and a_s = (c_s >= need).  Then thread r < nrules
+// runs rule r's automaton (include/fibhip.h: the normative text; tests/trigger_ref.py: the restatement) from row s - 1 — the
+// virtual row a = -1, t = -1, n = 0 when s == 0 — and the sensor's a_s, writes row s = {c, a, t, n, cause, fired} and, through
+// one ballot, the fire-mask word of sample s (bit r: rule r fires).  The slot s is a kernel ARGUMENT computed from the host's
+// counter: nothing on the device says where the log ends, so a replay (recover()) rewrites the rows of the lost samples in
+// place, each from a predecessor that is older than the lost launch or already rewritten.
+enum { TRIG_RISE = 0, TRIG_FALL = 1, TRIG_ROW = 6 };
+struct TrigRule {
+    int sensor, edge, arm, blank, escape, max_det, delay, count, period, hold;
+};
+__global__ void __launch_bounds__(256) trigger_kernel(const SenseSite *__restrict__ sites, int nsensors, int vec, const unsigned *__restrict__ part,
+                                                      const TrigRule *__restrict__ rules, int nrules, int *__restrict__ rows,
+                                                      unsigned *__restrict__ fire, int s)
+{
+    __shared__ int cs[TRIG_MAX];
+    const int lane = (int)(threadIdx.x & 63u);
+    for (int i = (int)(threadIdx.x >> 6); i < nsensors; i += 4) {
+        const int nchunks = sites[i].nchunks[vec];
+        const unsigned *__restrict__ p = part + (size_t)i * SENSE_MAX_CHUNKS;
+        unsigned v = 0u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v += 4 * lane + e < nchunks ? p[4 * lane + e] : 0u;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) cs[i] = (int)v;
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64u) return;
+    const int r = (int)threadIdx.x;
+    bool fired = false;
+    if (r < nrules) {
+        const TrigRule k = rules[r];
+        const int c = cs[k.sensor], a = c >= sites[k.sensor].need ? 1 : 0;
+        int pa = -1, pt = -1, pn = 0;
+        if (s > 0) {
+            const int *__restrict__ p = rows + ((size_t)(s - 1) * (size_t)nrules + (size_t)r) * TRIG_ROW;
+            pa = p[1]; pt = p[2]; pn = p[3];
+        }
+        const bool e = pa >= 0 && (k.edge == TRIG_RISE ? (pa == 0 && a == 1) : (pa == 1 && a == 0));
+        const bool listen = s >= k.arm && (k.max_det == 0 || pn < k.max_det) && (pt < 0 || pt + 1 >= k.blank);
+        const bool quiet = k.escape > 0 && listen && ((pt < 0 ? s - k.arm : pt) + 1 >= k.escape);
+        const bool det = listen && (e || quiet);
+        const int cause = det ? (e ? 1 : 2) : 0;
+        const int t = det ? 0 : (pt < 0 ? -1 : pt + 1);
+        const int n = pn + (det ? 1 : 0);
+        const int u = t - k.delay;
+        fired = t >= 0 && u >= 0 && (k.period == 0 ? u < k.hold : (u / k.period < k.count && u % k.period < k.hold));
+        int *__restrict__ o = rows + ((size_t)s * (size_t)nrules + (size_t)r) * TRIG_ROW;
+        o[0] = c; o[1] = a; o[2] = t; o[3] = n; o[4] = cause; o[5] = fired ? 1 : 0;
+    }
+    const unsigned long long f = __ballot(fired);
+    if (r == 0) fire[s] = (unsigned)f;
+}
+
+// The gated apply: stim_kernel's operations on the rules' stimuli — all of them by value in every launch (TRIG_MAX ==
+// STIM_MAX_DUE), entry r is rule r's, walked by the same fully unrolled loop (every field wave-uniform, in scalar registers).  It
+// reads the give-up word first (null behind a plain tick), then the fire mask of sample s: both wave-uniform scalar loads.  It
+// leaves without writing when a launch in front gave up — the mask it would read was then made from a void slab — or when no
+// rule fires.  An entry whose bit is clear is skipped; one whose bit is set loads, changes and stores its own cells inside its
+// visit box (a skipped neighbour cannot load or store for it, so the `load` / `store` marks of stim_kernel are not used; entries
+// on one array follow each other in rule order through memory, each thread its own cells).  A sibling of stim_kernel rather than
+// a template parameter of it: stim_kernel<true / false> stay exactly the code they were.  No LDS, no atomics.
+template <bool VEC>
+__global__ void __launch_bounds__(256) stim_gated_kernel(StimArgs a, const unsigned *__restrict__ fire)
+{
+    constexpr int N = VEC ? 4 : 1;
+    if (a.give_up && *a.give_up != 0u) return;
+    const unsigned f = *fire;
+    if (f == 0u) return;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t per_row = (size_t)(a.c1 - a.c0) / N;
+    if (t >= (size_t)(a.r1 - a.r0) * per_row) return;
+    const int y = a.r0 + (int)(t / per_row), x0 = a.c0 + N * (int)(t % per_row);
+    const size_t at = (size_t)y * (size_t)a.pitch + (size_t)x0;
+#pragma unroll
+    for (int i = 0; i < STIM_MAX_DUE; ++i) {
+        if (i >= a.n || !((f >> i) & 1u)) continue;                   // (wave-uniform, like every field of a.e[i])
+        const StimDue &d = a.e[i];
+        if (!(y >= d.b_r0 && y < d.b_r1 && x0 + N > d.b_c0 && x0 < d.b_c1)) continue;
+        float x[N], s[N];
+        if (VEC) {
+            const fib_v4f v = *reinterpret_cast<const fib_v4f *>(d.x + at);
+#pragma unroll
+            for (int j = 0; j < N; ++j) x[j] = v[j];
+        } else {
+            x[0] = d.x[at];
+        }
+        if (d.plane) {
+            const size_t pat = (size_t)y * (size_t)a.W + (size_t)x0;
+            if (VEC) {
+                const fib_v4f v = *reinterpret_cast<const fib_v4f *>(d.plane + pat);
+#pragma unroll
+                for (int j = 0; j < N; ++j) s[j] = v[j];
+            } else {
+                s[0] = d.plane[pat];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < N; ++j) s[j] = (y >= d.r0 && y < d.r1 && x0 + j >= d.c0 && x0 + j < d.c1) ? d.v : d.floor;
+        }
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+            if (x0 + j >= d.b_c0 && x0 + j < d.b_c1) x[j] = stim_cell(x[j], s[j], d.mode);
+        if (VEC) {
+            fib_v4f v;
+#pragma unroll
+            for (int j = 0; j < N; ++j) v[j] = x[j];
+            *reinterpret_cast<fib_v4f *>(d.x + at) = v;
+        } else {
+            d.x[at] = x[0];
+        }
+    }
+}

@@ -60,6 +60,13 @@ static int recover(fibhip_ctx *h, unsigned id)
         h->stim.k -= lost;
         h->stim.next = stim_next(h->stim);
     }
+    // ... and the trigger program: its automaton's state is the log itself, row s a pure function of row s - 1 and the state.
+    // The rows the lost samples wrote were made from a void slab, and the gated apply behind them wrote nothing (it reads the
+    // give-up word first).  The counter goes back, and the replay rewrites those rows IN ORDER, each from a predecessor that is
+    // older than the lost launch (good: trig_begin confirms before it attaches, and every row older than the journal's first
+    // record was made behind a launch that ended well) or has just been rewritten.  So a detection is never lost and never
+    // doubled, and a delay or a train that straddles the lost launch goes on as in the untouched run (DESIGN.md section 16).
+    if (h->trig.on) h->trig.k -= lost;
     h->journal.recovering = true;
     int rc = 0;
     for (int t = 0; t < lost && rc == 0; ++t) rc = tick_now(h);
@@ -162,8 +169,12 @@ static const Variant *mt_variant(const fibhip_ctx *h)
 //    (cutting); nothing runs ahead while a program is attached (may_run_ahead: a stimulus cannot be queued behind a launch that
 //    may be stopped or recomputed); a tick with an event due is never fused with the 'slow' behind it, whatever array the event
 //    names — the stimulus comes right after its tick (slow_sample_due).  The stimulus is queued behind its launch WITHOUT
-//    confirming it: stim_kernel writes nothing once a launch in front of it gave up (the rule above confirm()).
-static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on || h->fr.on || h->st.on; }
+//    confirming it: stim_kernel writes nothing once a launch in front of it gave up (the rule above confirm());
+//  * the trigger program (h->trig.on): a sampler with a stride of its own like the four above (a term of sampling and
+//    sample_room, so launches are cut at its samples and nothing runs ahead), whose sample also WRITES the state: sense, decide
+//    and the gated apply come behind the programmed stimuli of the tick, unconfirmed like them (the gated apply reads the
+//    give-up word first); every sample tick comes before the 'slow' behind it (slow_sample_due), whatever arrays it names.
+static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on || h->fr.on || h->st.on || h->trig.on; }
 // ticks up to and including the next sample tick of one sampler (INT_MAX: not attached)
 static inline int room_of(bool on, int every, long long k) { return on ? every - (int)(k % every) : INT_MAX; }
 // Is entry `e` due right after the n-th tick since attach (n >= 1)?  The events of an entry follow the ticks number
@@ -216,7 +227,7 @@ static inline int sample_room(const fibhip_ctx *h)
 {
     return imin(imin(imin(room_of(h->el.on, h->el.every, h->el.k), room_of(h->tip.on, h->tip.every, h->tip.k)),
                      imin(room_of(h->fr.on, h->fr.every, h->fr.k), room_of(h->st.on, h->st.every, h->st.k))),
-                stim_room(h));
+                imin(stim_room(h), room_of(h->trig.on, h->trig.every, h->trig.k)));
 }
 // launches are cut at ticks still to come: a launch goes out when the ticks up to the next cut are waiting (fibhip_step)
 static inline bool cutting(const fibhip_ctx *h) { return sampling(h) || stim_room(h) != INT_MAX; }
@@ -253,6 +264,8 @@ static inline bool slow_sample_due(const fibhip_ctx *h)
 #if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
     // (a stimulus due after the last pending tick comes before 'slow' too, whatever array it names)
     if (h->stim.on && h->stim.k + h->pending == h->stim.next) return true;
+    // (... and so does a sample of the trigger program: tick, sense / stimulus, slow)
+    if (h->trig.on && (h->trig.k + h->pending) % h->trig.every == 0) return true;
     auto slow = [](int var) { return !((Courtemanche::FAST_MASK >> var) & 1u); };
     if (h->el.on && (h->el.k + h->pending) % h->el.every == 0 && slow(h->el.var)) return true;
     if (h->tip.on && (h->tip.k + h->pending) % h->tip.every == 0 && (slow(h->tip.var) || slow(h->tip.var2))) return true;
@@ -271,7 +284,8 @@ static inline const char *sampler_full(const fibhip_ctx *h, int more, long long 
 {
     const struct { bool on; long long k; int every; long long cap; const char *name; } s[] = {
         {h->el.on, h->el.k, h->el.every, h->el.cap, "electrode"}, {h->tip.on, h->tip.k, h->tip.every, h->tip.cap, "tip"},
-        {h->fr.on, h->fr.k, h->fr.every, h->fr.cap, "frame"}, {h->st.on, h->st.k, h->st.every, h->st.cap, "statistics"}};
+        {h->fr.on, h->fr.k, h->fr.every, h->fr.cap, "frame"}, {h->st.on, h->st.k, h->st.every, h->st.cap, "statistics"},
+        {h->trig.on, h->trig.k, h->trig.every, h->trig.cap, "trigger"}};
     for (const auto &r : s)
         if (r.on && (r.k + more) / r.every > r.cap) {
             if (cap) *cap = r.cap;
@@ -389,7 +403,10 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
         if (int rc = stats_advance(h, T)) return rc;
     // (the stimulus WRITES the state, the slab this launch wrote; it leaves without writing when this launch or one in front
     // of it gave up — so the state the first such launch started from stays intact, as behind a multi-tick launch)
-    if (commit && h->stim.on) return stim_advance(h, T, true);
+    if (commit && h->stim.on)
+        if (int rc = stim_advance(h, T, true)) return rc;
+    // (... and so does the trigger program's gated apply; its rows are rewritten by the replay)
+    if (commit && h->trig.on) return trig_advance(h, T, true);
     return 0;
 }
 

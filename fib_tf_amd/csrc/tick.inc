@@ -10,6 +10,7 @@ static int tips_advance(fibhip_ctx *h, int ticks);
 static int frames_advance(fibhip_ctx *h, int ticks);
 static int stats_advance(fibhip_ctx *h, int ticks);
 static int stim_advance(fibhip_ctx *h, int ticks, bool behind_mt);       // ... and the stimulus program's, behind them
+static int trig_advance(fibhip_ctx *h, int ticks, bool behind_mt);       // ... and the trigger program's, last: it senses what the stimulus left
 
 // ------------------------------------------------------------------------------------------
 // stepping
@@ -287,7 +288,10 @@ static int commit_impl(fibhip_t h)
     // the stimulus comes last: the recorders saw the state as the tick left it, the stimulus belongs to the next tick
     // (a plain tick never stands behind an unconfirmed multi-tick launch — tick_mt, fibhip_step and recover() confirm first — so
     // its stimulus has no give-up word to look at)
-    if (h->stim.on) return stim_advance(h, ticks, false);
+    if (h->stim.on)
+        if (int rc = stim_advance(h, ticks, false)) return rc;
+    // ... and the trigger program after that: its sensors see this tick's programmed stimulus, its own stimuli follow
+    if (h->trig.on) return trig_advance(h, ticks, false);
     return 0;
 }
 

@@ -308,6 +308,23 @@ class IonicModel:
             ensure()
         return StimulusProgram(self, stimuli)
 
+    def trigger_stimuli(self, rules, every=1, capacity=None):
+        """attaches a trigger program (fib_tf_amd/triggers.py) to this model's handle: a list of `Trigger` rules — a `Sensor`
+        (a site, a level, the cells that must be above it), an edge ('rise': an arrival, 'fall': the waveback), a delay, a
+        blanking time, an escape interval and the stimulus to fire — that the library senses, decides and applies on the
+        device every `every` ticks, without the host reading the state; `s2_on_waveback`, `demand_pacer` and
+        `burst_on_arrival` build the usual protocols.  Sample s follows tick (s + 1) * every - 1 after this call.  It may be
+        attached beside every recorder and beside a `program_stimuli` program (whose stimulus of a tick the sensors see).
+        Default capacity: the samples of a whole run of `duration`.  Call after define(); single device only (row blocks raise
+        NotImplementedError)."""
+        from .triggers import TriggerProgram
+        if not self.defined:
+            raise AssertionError('trigger_stimuli should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return TriggerProgram(self, rules, every=every, capacity=capacity)
+
     def _frame_levels(self):
         """(lo, span) with image() == (X - lo) / span in float32, X the array pot() names: what a frame recorder maps the
         state with.  Models whose image() rescales override it."""

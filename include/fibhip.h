@@ -565,6 +565,88 @@ int fibhip_stim_begin(fibhip_t h, int n, const fibhip_stim_entry *entries, int n
 int fibhip_stim_count(fibhip_t h, long long *applied);
 int fibhip_stim_end(fibhip_t h);
 
+/* Trigger program: triggered stimulation — sense a site, decide, fire a stimulus, all on the device.  A stimulus program
+ * (above) applies each entry at a tick fixed before the run; a trigger program applies a stimulus at a time that depends on the
+ * STATE: an S2 a fixed delay after the S1 waveback has passed a probe, a demand pacer that fires when nothing arrived within an
+ * escape interval, a burst on detection of an arrival.  A program is 1 .. FIBHIP_MAX_TRIG_SENSORS sensors, 1 ..
+ * FIBHIP_MAX_TRIG_RULES rules, a stride `every` >= 1 in ticks and a `capacity` in samples.  One program per handle.  Restated in
+ * NumPy in tests/trigger_ref.py; the device equals that bit for bit — everything here is integer arithmetic on float32
+ * comparisons, there is no tolerance.
+ * Samples.  Sample s = 0, 1, ... is taken after tick (s + 1) * every - 1 since trig_begin (the first tick after it is tick 0):
+ * the other samplers' cadence.  ALL times of a rule are in samples.
+ * Order on a tick.  The recorders' samples and the activation recorder's update come first, then the stimuli of an attached
+ * stimulus program due after that tick, then sense, decide and the triggered stimuli: a sensor therefore SEES that tick's
+ * programmed stimulus.  Courtemanche: a sample tick is never fused with the fibhip_step_slow behind it (tick, sense / stimulus,
+ * slow).
+ * Sensor {var, level, need, site}: site is FIBHIP_TRIG_RECT (rows [r0, r1) x columns [c0, c1), inside the grid, not empty) or
+ * FIBHIP_TRIG_MASK (the cells where the sensor's uint8 mask [height*width] is not 0; the masks of the MASK sensors lie back to
+ * back in `masks`, in sensor order; the host cuts each mask's bounding box at attach).  The count is
+ *     c = #{cells of the site with X_var > level}        a strict float32 comparison: a NaN does not count
+ * and the sensor is active when a = (c >= need), 1 <= need <= cells of the site.  An integer, independent of order — deliberately
+ * not a float sum: the electrode sums carry an error bound, a decision must not.
+ * Rule {sensor, edge, arm, blank, escape, max_det, delay, count, period, hold} + a stimulus {var, mode, shape, r0, r1, c0, c1, v,
+ * floor, plane}: fibhip_stim_entry's fields with its rules (MAX / ADD, RECT / PLANE, the "untouched" value of a mode).  Per rule,
+ * row s of the log holds the int32 fields {c, a, t, n, cause, fired}: the sensor's count and activity, samples since the last
+ * detection (-1: none yet), detections so far, the cause of a detection at this sample (0 none, 1 an edge, 2 the escape
+ * interval) and whether the stimulus is applied after this sample.  The virtual row -1 is a = -1 (unknown), t = -1, n = 0.
+ * With p the previous row:
+ *     e       = p.a >= 0 and (edge == RISE ? (p.a == 0 and a == 1) : (p.a == 1 and a == 0))
+ *     listen  = s >= arm and (max_det == 0 or p.n < max_det) and (p.t < 0 or p.t + 1 >= blank)
+ *     quiet   = escape > 0 and listen and ((p.t < 0 ? s - arm : p.t) + 1 >= escape)
+ *     det     = listen and (e or quiet);   cause = det ? (e ? 1 : 2) : 0
+ *     t       = det ? 0 : (p.t < 0 ? -1 : p.t + 1);      n = p.n + det
+ *     u       = t - delay
+ *     fired   = t >= 0 and u >= 0 and (period == 0 ? u < hold : (u / period < count and u % period < hold))
+ * (the first sample is never an edge: its predecessor is unknown).  The stimuli of the rules with `fired` are applied right after
+ * sample s, in rule order, with the stimulus program's operations: a triggered MAX on a rectangle floored at min_v equals
+ * fibhip_pace bit for bit.
+ * Launches.  No launch spans a sample tick; between samples the handle keeps its multi-tick launches, a launch goes out when the
+ * ticks up to the next sample have been accepted, nothing runs ahead of the caller while a program is attached.  A sample is
+ * three small launches queued on the handle's stream behind the launch that ends at its tick; nothing waits for them.  A
+ * multi-tick launch that gave up is recovered as ever: the replay rewrites the rows of the replayed samples in order, the
+ * stimuli behind the lost launch wrote nothing — no detection is lost or doubled.  The same program gives the same bytes under
+ * every launch plan.  The rows stay on the device until they are read; a fibhip_step that would overflow `capacity` is refused
+ * before it enqueues anything.
+ * Refused with FIBHIP_EINVAL, the message naming the sensor or rule: counts, var, site, edge, mode, shape or plane out of range;
+ * a level that is NaN; need outside 1 .. cells of the site; a time that is negative or above FIBHIP_TRIG_MAX_TIME; count < 1,
+ * hold < 1, hold > period when period > 0, period == 0 with count != 1; blank < delay + (count - 1) * period + hold (a train is
+ * never cut by a new detection); every < 1, a bad capacity; a second trig_begin without a trig_end; inside an open tick; a row
+ * block (a handle with ghost rows); on a Courtemanche handle that runs on aggregates, a rule whose stimulus names one of the 17
+ * slow arrays (the host cannot know when it fires, so it cannot mark the aggregates stale; the four fast arrays are fine).
+ *   fibhip_trig_begin  flushes, synchronises and confirms pending work, copies masks and planes and attaches
+ *   fibhip_trig_count  the samples taken so far (ticks accepted but not launched yet count)
+ *   fibhip_trig_read   flushes, copies rows [first, first + count) out as [count][nrules][FIBHIP_TRIG_ROW] int32, synchronises;
+ *                      copies again when a launch in front had given up and was recovered
+ *   fibhip_trig_end    flushes, synchronises, detaches and frees (no program attached: nothing); fibhip_destroy frees too       */
+#define FIBHIP_MAX_TRIG_SENSORS 8
+#define FIBHIP_MAX_TRIG_RULES 8
+#define FIBHIP_TRIG_ROW 6
+#define FIBHIP_TRIG_MAX_TIME (1 << 24)
+enum fibhip_trig_edge { FIBHIP_TRIG_RISE = 0, FIBHIP_TRIG_FALL = 1 };
+enum fibhip_trig_site { FIBHIP_TRIG_RECT = 0, FIBHIP_TRIG_MASK = 1 };
+enum fibhip_trig_field { FIBHIP_TRIG_C = 0, FIBHIP_TRIG_A = 1, FIBHIP_TRIG_T = 2, FIBHIP_TRIG_N = 3, FIBHIP_TRIG_CAUSE = 4, FIBHIP_TRIG_FIRED = 5 };
+typedef struct fibhip_trig_sensor {
+    int var;
+    float level;
+    int need;
+    int site;                   /* FIBHIP_TRIG_RECT / _MASK */
+    int r0, r1, c0, c1;         /* RECT */
+} fibhip_trig_sensor;
+typedef struct fibhip_trig_rule {
+    int sensor, edge;           /* index of the sensor; FIBHIP_TRIG_RISE / _FALL */
+    int arm, blank, escape, max_det, delay, count, period, hold;       /* in samples */
+    int var, mode, shape;       /* the stimulus: fibhip_stim_entry's fields */
+    int r0, r1, c0, c1;
+    float v, floor;
+    int plane;
+} fibhip_trig_rule;
+int fibhip_trig_begin(fibhip_t h, int nsensors, const fibhip_trig_sensor *sensors, const unsigned char *masks /* [nmasks][H*W] or NULL */,
+                      int nrules, const fibhip_trig_rule *rules, int nplanes, const float *planes /* [nplanes][H*W] or NULL */, int every,
+                      long long capacity);
+int fibhip_trig_count(fibhip_t h, long long *samples);
+int fibhip_trig_read(fibhip_t h, long long first, long long count, int *dst /* [count][nrules][6] */);
+int fibhip_trig_end(fibhip_t h);
+
 const char *fibhip_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)
