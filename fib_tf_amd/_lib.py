@@ -197,6 +197,8 @@ SYMBOLS = {
     'fibhip_trace_begin': ([_h], C.c_int),
     'fibhip_trace_end': ([_h, C.POINTER(TraceEvent), C.c_int], C.c_int),
     'fibhip_plan_tile': ([_h, _ip, _ip, _ip], C.c_int),
+    'fibhip_variant_count': ([], C.c_int),
+    'fibhip_variant_info': ([C.c_int, _ip], C.c_int),
     'fibhip_observe_begin': ([_h, C.c_int, C.c_float, C.c_float], C.c_int),
     'fibhip_observe_get': ([_h, C.c_int, C.c_void_p], C.c_int),
     'fibhip_observe_ticks': ([_h, C.POINTER(C.c_longlong)], C.c_int),
@@ -449,6 +451,25 @@ def unit_op(op, a, b=None, c=None, phi=None, dt=0.0, fast=False, device=0):
     check(lib().fibhip_unit_op(device, op, H, W, _ptr(a), _ptr(b), _ptr(c), _ptr(phi), float(dt), int(fast),
                                _ptr(out)))
     return out
+
+
+VARIANT_FIELDS = ('model', 'mode', 'fast', 'phase', 'K', 'TX', 'TY', 'NT', 'kind', 'has_mt')   # fibhip_variant_info, in order
+VM_FENTON_ZP, VM_COURT_AGG = 100, 101                   # table ids of the two kernel models that are no fibhip_model
+MK_TICK, MK_STRIP, MK_POINTWISE, MK_STRIP_MT, MK_ROWS = range(5)
+
+
+def variants(L=None):
+    """the kernel variant table of a build of the library, in table order: a list of dicts with the keys VARIANT_FIELDS
+    (include/fibhip.h fibhip_variant_info).  `L`: another loaded build (br.specialised_library), default the stock one.
+    Needs no device."""
+    L = L or lib()
+    L = getattr(L, '_L', L)                             # (a ModuleLibrary: the table of the stock library under it)
+    out = (C.c_int * len(VARIANT_FIELDS))()
+    rows = []
+    for i in range(check(L.fibhip_variant_count(), L)):
+        check(L.fibhip_variant_info(i, out), L)
+        rows.append(dict(zip(VARIANT_FIELDS, [int(x) for x in out])))
+    return rows
 
 
 COURT_INTER_KEYS = ('d_infinity', 'tau_d', 'f_infinity', 'tau_f', 'tau_w', 'w_infinity', 'm_inf', 'tau_m', 'h_inf',

@@ -729,6 +729,20 @@ extern "C" int fibhip_plan_tile(fibhip_t h, int *tile_w, int *tile_h, int *rows_
     return 0;
 }
 
+extern "C" int fibhip_variant_count(void) { return g_nvariants; }
+
+extern "C" int fibhip_variant_info(int i, int out[10])
+{
+    if (i < 0 || i >= g_nvariants || !out) return fail(FIBHIP_EINVAL, "variant_info: bad argument");
+    const Variant &v = g_variants[i];
+    out[0] = v.model; out[1] = v.mode; out[2] = v.fast; out[3] = v.phase;
+    out[4] = v.K; out[5] = v.TX; out[6] = v.TY; out[7] = v.NT;
+    // (the rows of g_variants carry their kind in how they list NT — see V4 / S4 / W4 — Variant::kind is a module's)
+    out[8] = v.NT > 0 ? MK_TICK : (v.NT > -32 ? MK_STRIP : MK_ROWS);
+    out[9] = v.fn_mt ? 1 : 0;
+    return 0;
+}
+
 extern "C" int fibhip_ticks_per_launch(fibhip_t h)
 {
     if (!h) return fail(FIBHIP_EINVAL, "null handle");

@@ -175,7 +175,8 @@ static int build_plan(fibhip_ctx *h)
 // (576^2: 26.7 us per tick with the 512^2 choice, 18.9 with a taller tile).  The first tick of a handle therefore
 // times every candidate ONCE on the handle's own geometry (its real launch: same buffers, same rows; a candidate
 // writes what the real launch overwrites) and keeps the fastest.  All candidates are bit-identical in their results
-// (tests/test_gpu_parity.py::test_fenton_fusion_depths_bit_identical), so the choice changes speed only — ranks of
+// (tests/test_gpu_variant_table.py runs EVERY row of the table, enumerated through fibhip_variant_info, against the
+// one-sub-step-per-launch kernel), so the choice changes speed only — ranks of
 // a sharded grid may choose differently.  FIBHIP_AUTOTUNE=0, FIBHIP_VARIANT or FIBHIP_K switch it off.
 // Courtemanche on aggregates: which tile shape for the launches of two and of three ticks, on this very geometry
 static int autotune_multi(fibhip_ctx *h)

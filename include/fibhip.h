@@ -282,6 +282,14 @@ int fibhip_launch_plan(fibhip_t h, int *fused_steps, int *launches_per_tick);
 /* ... and the tile of the first launch: width, height, and rows per wave (strip kernels) or -threads per workgroup
  * (flat tile kernels)                                                                                              */
 int fibhip_plan_tile(fibhip_t h, int *tile_w, int *tile_h, int *rows_per_wave);
+/* The table of kernel variants THIS build of the library chooses its plans from (a specialised or a traced-model build
+ * answers for its own table); neither call needs a device or a handle.  fibhip_variant_info fills out[0..9] with
+ * model, mode, fast, phase, K, TX, TY, NT as the table lists them (model: a fibhip_model, 100 = Fenton 4v with the
+ * zero-padded Laplacian, 101 = Courtemanche on aggregates; NT: threads of a flat tile, -rows per wave of a strip kernel,
+ * -(32 + rows per wave) of a rows kernel), then the kernel kind (0 flat tile, 1 strip, 4 rows), then 1 if the row also
+ * exists as a launch that advances several ticks.  The kernels of a run-time module are not part of this table.     */
+int fibhip_variant_count(void);
+int fibhip_variant_info(int i, int out[10]);
 /* Consecutive ticks one launch can cover (1 = every tick is its own launch or launches).  Courtemanche under
  * FIBHIP_FAST on one device returns 3: fibhip_step() accepts ticks and launches them three at a time, temporally
  * blocked; whatever has been accepted but not launched is launched by the next call that observes or changes the
