@@ -51,6 +51,7 @@ struct MtState {
     unsigned *snap_flags_dev;       // device address of snap_flags
     unsigned *host_word;    // page-locked (behind snap_flags), read by tile 0 over PCIe: {launch id << 16 | n}, see ahead_settle
     unsigned ids;           // launch ids cycle through 1 .. ids
+    const Variant *last_v;  // shape of the last multi-tick launch that was not a trial (mt_launch: another shape zeroes the words first)
     unsigned seq;           // id of the last multi-tick launch (the host's word names the launch it is meant for)
     bool inflight;          // a multi-tick launch has been issued since the give-up word was last read
     unsigned wait_ms;       // a tile's bound on its wait for a neighbour (FIBHIP_MT_WAIT_MS, fibhip_set_mt_wait_ms); 0 = 2 s
@@ -85,6 +86,7 @@ struct Ahead {
                             // raw pointer handed out (fibhip_state_ptr) — a caller that can write the state at any time
     int n, used;            // ticks computed ahead of the caller / how many of them fibhip_step has handed out
     unsigned id;            // ... of the launch that ran ahead
+    const Variant *v;       // ... and the shape it runs
     int nxt[FIB_MAXVAR];    // where the state lives once all of them are handed out
     hipEvent_t ev;
     unsigned snap_seq;
@@ -257,6 +259,8 @@ struct fibhip_ctx {
     std::vector<PlanItem> plan_multi[4];    // [T]: the one-launch plan of T ticks, T = 2..multi_max
     int multi_max;          // up to this many consecutive ticks go into one launch (1 = never; CourtAgg: 3)
     launch_fn fused_fn;     // Courtemanche: tick + 'slow' in one launch, or null
+    const Variant *period_v;        // the exchange-period row multi-tick launches run (sched.inc mt_variant) beside `plan`, or null
+    bool period_forced;             // ... because the caller forced it (FIBHIP_VARIANT, FIBHIP_K): it runs EVERY multi-tick launch
     bool tuned;             // the plan has been checked against the other tile shapes on this very geometry (autotune)
     int ncu;                // compute units of the device
     fibhip_module *mod;     // FIBHIP_CUSTOM on a run-time module (fibhip_module_load), or null

@@ -723,9 +723,12 @@ extern "C" int fibhip_plan_tile(fibhip_t h, int *tile_w, int *tile_h, int *rows_
     if (!h) return fail(FIBHIP_EINVAL, "null handle");
     if (h->plan.empty()) return fail(FIBHIP_EINVAL, "no plan");
     const PlanItem &it = (h->multi_max > 1 && !h->plan_multi[h->multi_max].empty()) ? h->plan_multi[h->multi_max][0] : h->plan[0];
-    if (tile_w) *tile_w = it.TX;
-    if (tile_h) *tile_h = it.TY;
-    if (rows_per_wave) *rows_per_wave = it.v ? -it.v->NT : 0;
+    // (the exchange-period row, where the multi-tick launches run one: the tile the handle's ticks are computed in)
+    const Variant *pv = mt_variant(h, true);
+    if (!(pv && pv->period)) pv = nullptr;
+    if (tile_w) *tile_w = pv ? pv->TX : it.TX;
+    if (tile_h) *tile_h = pv ? pv->TY : it.TY;
+    if (rows_per_wave) *rows_per_wave = pv ? -pv->NT : (it.v ? -it.v->NT : 0);
     return 0;
 }
 
@@ -739,7 +742,9 @@ extern "C" int fibhip_variant_info(int i, int out[10])
     out[4] = v.K; out[5] = v.TX; out[6] = v.TY; out[7] = v.NT;
     // (the rows of g_variants carry their kind in how they list NT — see V4 / S4 / W4 — Variant::kind is a module's)
     out[8] = v.NT > 0 ? MK_TICK : (v.NT > -32 ? MK_STRIP : MK_ROWS);
-    out[9] = v.fn_mt ? 1 : 0;
+    // (1: a multi-tick launch that exchanges once per tick, K = the tick's sub-steps; an exchange-period row is listed as the
+    // plain strip launch of K sub-steps it also is)
+    out[9] = v.fn_mt && !v.period ? 1 : 0;
     return 0;
 }
 
@@ -834,6 +839,12 @@ extern "C" int fibhip_launch_plan(fibhip_t h, int *fused_steps, int *launches_pe
     }
     if (fused_steps) *fused_steps = h->plan.empty() ? 0 : h->plan[0].K;
     if (launches_per_tick) *launches_per_tick = (int)h->plan.size();
+    // multi-tick launches in exchange periods: (sub-steps of a period, 1) — fibhip_ticks_per_launch still counts ticks
+    if (const Variant *pv = mt_variant(h, true))
+        if (pv->period) {
+            if (fused_steps) *fused_steps = pv->K;
+            if (launches_per_tick) *launches_per_tick = 1;
+        }
     return 0;
 }
 

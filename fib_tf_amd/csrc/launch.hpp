@@ -139,12 +139,15 @@ struct Variant {
     int kind = 0;
     launch_fn fn_mt = nullptr;      // the same shape advancing several ticks per launch (strip_mt_kernel), or null
     hipFunction_t kern_mt = nullptr;        // ... of a run-time module (fn_mt == launch_module, kind MK_STRIP_MT)
+    int period = 0;                 // 1: fn_mt exchanges every K sub-steps with K below the tick's sub-steps (an exchange-period row:
+                                    // strip_kernel.inc PERIODS); fn, the plain launch of K sub-steps, is the rows' own check
 };
 
 // One row of the table: launcher kind L of one policy and phase — and, with MT = 1, the same shape advancing several ticks per
 // launch.  N = threads of a flat tile or rows per wave of a strip; CODE = how the table lists it (Variant::NT).
 #define VROW_MT_0(MODEL, P, MODE, K, TX, TY, N, PH) nullptr
 #define VROW_MT_1(MODEL, P, MODE, K, TX, TY, N, PH) launch_tiles<MK_STRIP_MT, MODEL, P, MODE, K, TX, TY, N, PH>
+#define VROW_MT_2(MODEL, P, MODE, K, TX, TY, N, PH) launch_tiles<MK_STRIP_MT, MODEL, P, MODE, K, TX, TY, N, PH>, nullptr, 1
 #define VROW(L, MT, P, FAST, PH, MODEL, MID, MODE, K, TX, TY, N, CODE)                                                 \
     {MID, MODE, FAST, PH, K, TX, TY, CODE, launch_tiles<L, MODEL, P, MODE, K, TX, TY, N, PH>, nullptr, 0,              \
      VROW_MT_##MT(MODEL, P, MODE, K, TX, TY, N, PH)}
@@ -159,6 +162,9 @@ struct Variant {
 #define S4(MODEL, MID, MODE, K, TX, TY, R) VBOTH(MK_STRIP, 0, MODEL, MID, MODE, K, TX, TY, R, -(R))
 // strip kernels that also exist as multi-tick launches (K = the model's sub-steps per tick)
 #define S4M(MODEL, MID, MODE, K, TX, TY, R) VBOTH(MK_STRIP, 1, MODEL, MID, MODE, K, TX, TY, R, -(R))
+// strip kernels whose multi-tick launch exchanges every K sub-steps, K below the tick's sub-steps (models with UNIFORM_SUBSTEPS):
+// the period decides the rim depth K - 1, the tile width 64 - 2K and how the box's strips land on the four SIMDs
+#define S4P(MODEL, MID, MODE, K, TX, TY, R) VBOTH(MK_STRIP, 2, MODEL, MID, MODE, K, TX, TY, R, -(R))
 // rows kernels (potential in registers, DPP taps) are listed with NT = -(32 + R)
 #define W4(MODEL, MID, MODE, K, TX, TY, R) VBOTH(MK_ROWS, 0, MODEL, MID, MODE, K, TX, TY, R, -(32 + (R)))
 
@@ -192,6 +198,11 @@ static const Variant g_variants[] = {
     S4M(Fenton, FIBHIP_FENTON4V, 0, 10, 44, 36, 4),
     S4M(Fenton, FIBHIP_FENTON4V, 0, 10, 44, 40, 4),
     S4M(Fenton, FIBHIP_FENTON4V, 0, 10, 44, 44, 4),
+    // an exchange period of 6 sub-steps (512^2: 250 tiles of 16 two-row strips; tools/dbg/period_model.py): a candidate of
+    // autotune beside the rows above, never the rule-based plan.  (Measured at 512^2 and not kept, profiles/exchange_period_ab.txt:
+    // K = 8 in 48 x 23, 3 rows per wave — 11.68 against 11.40 us per tick, and two spilled registers with a phase field; K = 7
+    // in 50 x 23, 3 rows per wave, three waves per SIMD — 12.87.)
+    S4P(Fenton, FIBHIP_FENTON4V, 0, 6, 52, 21, 2),
     S4(Fenton, FIBHIP_FENTON4V, 0, 5, 54, 21, 3),
     S4(Fenton, FIBHIP_FENTON4V, 0, 5, 54, 23, 3),
     S4(Fenton, FIBHIP_FENTON4V, 0, 5, 54, 22, 4),

@@ -377,6 +377,10 @@ struct Fenton {
         float cvp, cvn, dvn, cwp, cwn, dwn;
     };
     static constexpr unsigned mask(int) { return 0xFu; }
+    // every sub-step is the same operation (step and stepN ignore their sub-step index): nothing in the arithmetic knows where
+    // a tick ends, so a multi-tick launch may exchange its rims every K < DEFAULT_STEPS sub-steps (strip_kernel.inc, "exchange
+    // periods").  Beeler-Reuter's `skip` schedule and the generated models read the index: they do not declare this.
+    static constexpr bool UNIFORM_SUBSTEPS = true;
 
     template <class P, int MODE>
     static FIB_DEV void step(float (&s)[NVAR], float U0, float lap, const Consts &k, int)

@@ -2,7 +2,8 @@
 // measurement on the handle's own geometry (autotune).
 // (included by fibhip.hip, behind sched.inc: autotune times real launches)
 
-static const Variant *find_variant(const fibhip_ctx *h, int K, const int *want /*TX,TY,NT or null*/, int mode = -1)
+// (`period_ok`: an exchange-period row may be the answer — only where the caller's environment named it, see build_plan)
+static const Variant *find_variant(const fibhip_ctx *h, int K, const int *want /*TX,TY,NT or null*/, int mode = -1, bool period_ok = false)
 {
     const int fast = (h->d.flags & FIBHIP_FAST) ? 1 : 0, phase = h->has_phase ? 1 : 0;
     if (mode < 0) mode = h->mode;
@@ -13,7 +14,7 @@ static const Variant *find_variant(const fibhip_ctx *h, int K, const int *want /
     const int ntab = h->mod ? (int)h->mod->variants.size() : g_nvariants;
     for (int i = 0; i < ntab; ++i) {
         const Variant &v = tab[i];
-        if (v.kind == MK_POINTWISE) continue;
+        if (v.kind == MK_POINTWISE || (v.period && !period_ok)) continue;
         if (v.model != vmodel || v.mode != mode || v.fast != fast || v.phase != phase || v.K != K) continue;
         if (want && (v.TX != want[0] || v.TY != want[1] || v.NT != want[2])) continue;
         return &v;
@@ -26,18 +27,26 @@ static const Variant *find_variant(const fibhip_ctx *h, int K, const int *want /
 static int build_plan(fibhip_ctx *h)
 {
     h->plan.clear();
+    h->period_v = nullptr;
+    h->period_forced = false;
     h->tuned = false;
     h->mt.stale = true;
     int prefK = 0, want[3], nwant = 0;
+    bool env_variant = false, env_k = false;
     if (const char *e = getenv("FIBHIP_VARIANT")) {
         int k = 0;
         if (sscanf(e, "%d,%d,%d,%d", &k, &want[0], &want[1], &want[2]) == 4) {
             prefK = k;
             nwant = 1;
+            env_variant = true;
         }
     }
     if (!prefK)
-        if (const char *e = getenv("FIBHIP_K")) prefK = atoi(e);
+        if (const char *e = getenv("FIBHIP_K")) {
+            prefK = atoi(e);
+            env_k = prefK > 0;
+        }
+    const int envK = (env_variant || env_k) ? prefK : 0;
     if (!prefK) {
         // Measured on MI355X (DESIGN.md §6, tools/sweep.py).  Beeler-Reuter / Courtemanche spend their time
         // in the transcendental pipe (64 / ~70 per cell-step): redundant rim cells cost more than the
@@ -125,13 +134,32 @@ static int build_plan(fibhip_ctx *h)
         const Variant *best = nullptr;
         for (int K = (prefK < rem ? prefK : rem); K >= 1 && !best; --K) {
             if (K > maxghost) continue;
-            best = find_variant(h, K, nwant ? want : nullptr);
+            // (an exchange-period row is taken only where FIBHIP_VARIANT names that very row or FIBHIP_K its K: never by a rule, by
+            // the descent to a shallower K — a tick of 7, 8 or 9 sub-steps, FIBHIP_K=7 — or as the stand-in for a shape that
+            // names no row)
+            best = find_variant(h, K, nwant ? want : nullptr, -1, K == envK);
             if (!best && nwant) best = find_variant(h, K, nullptr);
         }
         if (!best) return fail(FIBHIP_EINVAL, "no kernel variant for model %d mode %d", h->d.model, h->mode);
         h->plan.push_back({best->K, best->fn, best->TY, best->TX, best});
         rem -= best->K;
     }
+    // a forced exchange-period row (FIBHIP_VARIANT, FIBHIP_K): its K sub-steps and the shallower launches that complete the tick
+    // are the plain tick; the multi-tick launches run the row itself, in periods of K (sched.inc mt_variant)
+    if (h->plan[0].v && h->plan[0].v->period) {           // (only ever the row the environment named: find_variant's period_ok)
+        h->period_v = h->plan[0].v;
+        h->period_forced = true;
+    }
+    // FIBHIP_PERIOD_ROW="K,TX,TY,NT": that exchange-period row rides beside the plan as if autotune() had chosen it — the launches
+    // of long declared series only (sched.inc mt_variant) — on any grid (tuning sweeps, and the tests of that path on small grids)
+    if (!h->period_v)
+        if (const char *e = getenv("FIBHIP_PERIOD_ROW")) {
+            int k = 0, w[3];
+            if (sscanf(e, "%d,%d,%d,%d", &k, &w[0], &w[1], &w[2]) == 4) {
+                const Variant *v = find_variant(h, k, w, -1, true);
+                if (v && v->period) h->period_v = v;
+            }
+        }
     // Courtemanche: the reference's driver fires 'slow' right after every 10th tick (court.py:612-617).  When the
     // last tick of a fibhip_step call is still pending at that moment, both run as ONE launch (MODE_FASTSLOW): the
     // 21 arrays are read once instead of twice.  Requirements: a single K=1 launch per tick, no ghost rows, and
@@ -243,18 +271,32 @@ static int autotune(fibhip_ctx *h)
     const Variant *tab = h->mod ? h->mod->variants.data() : g_variants;
     const int ntab = h->mod ? (int)h->mod->variants.size() : g_nvariants;
     std::vector<std::vector<PlanItem>> trials;
+    std::vector<const Variant *> period_of;                       // per trial: the exchange-period row it times, or null
     trials.push_back(heuristic);                                  // the rule-based plan is a candidate like any other
+    period_of.push_back(nullptr);
     for (int i = 0; i < ntab; ++i) {
         const Variant &v = tab[i];
         if (v.kind == MK_POINTWISE) continue;
         if (v.model != h->d.model || v.mode != h->mode || v.fast != fast || v.phase != phase) continue;
         // strip kernels of every fusion depth, and the one-sub-step-per-launch tiles
         const bool strip = v.NT < 0 && v.NT > -32 && v.K >= 2, single = v.NT > 0 && v.K == 1;
+        if (v.period) {
+            if (getenv("FIBHIP_PERIOD_ROW")) continue;            // (the row beside the plan is the caller's choice)
+            // an exchange-period row is a candidate as what it is for: the multi-tick launch, timed like the other rows' (the
+            // trial's plan stays the rule-based one: what a plain tick would run beside it)
+            // (... on grids that fill more than half of the device: what a period buys is the balance of a FULL device's SIMDs and
+            // its rim traffic, measured at 512x512; eight ticks of a handful of tiles time the launch's ends and little else)
+            if (!mt_eligible(h, &v) || 2 * tiles_of(h, v.TX, v.TY) <= h->ncu) continue;
+            trials.push_back(heuristic);
+            period_of.push_back(&v);
+            continue;
+        }
         if (!(strip || single) || h->spt % v.K != 0 || v.K > maxghost) continue;
         if (!heuristic.empty() && heuristic[0].fn == v.fn) continue;
         std::vector<PlanItem> trial;
         for (int n = 0; n < h->spt / v.K; ++n) trial.push_back({v.K, v.fn, v.TY, v.TX, &v});
         trials.push_back(trial);
+        period_of.push_back(nullptr);
     }
     // One tick of a candidate, back to back between one pair of events (the gaps between its launches are part of its
     // cost).  The candidates are timed in ROUNDS — every candidate once per round, the first round a warm-up (code
@@ -268,11 +310,12 @@ static int autotune(fibhip_ctx *h)
             const std::vector<PlanItem> &trial = trials[t];
             h->plan = trial;
             // a shape that will run several ticks per launch is timed as that: AT_MT_TICKS ticks in one launch, per tick
-            const bool as_mt = trial.size() == 1 && mt_eligible(h, trial[0].v);
+            const Variant *mtv = period_of[t] ? period_of[t] : (trial.size() == 1 ? trial[0].v : nullptr);
+            const bool as_mt = mt_eligible(h, mtv);
             HIPCHK(hipEventRecord(h->ev_t0, h->s0));
             int sub = 0;
             if (as_mt) {
-                if (mt_launch(h, trial[0].v, AT_MT_TICKS, false, nullptr)) failed[t] = true;
+                if (mt_launch(h, mtv, AT_MT_TICKS, false, nullptr)) failed[t] = true;
             } else
             for (size_t l = 0; l < trial.size(); ++l) {           // every launch with the rows edges_impl gives it
                 LaunchCtx c;
@@ -292,7 +335,7 @@ static int autotune(fibhip_ctx *h)
                 (void)hipGetLastError();
                 if (getenv("FIBHIP_PRINT_PLAN"))
                     fprintf(stderr, "fibhip: %dx%d model %d: candidate K=%d tile %dx%d could not be launched: %s\n", h->d.height,
-                            h->d.width, h->d.model, trial[0].K, trial[0].TX, trial[0].TY, g_err);
+                            h->d.width, h->d.model, mtv ? mtv->K : trial[0].K, mtv ? mtv->TX : trial[0].TX, mtv ? mtv->TY : trial[0].TY, g_err);
                 if (t == 0) {
                     h->plan = heuristic;
                     return FIBHIP_EHIP;
@@ -313,7 +356,7 @@ static int autotune(fibhip_ctx *h)
                     __atomic_store_n(h->mt.host_give_up(), 0u, __ATOMIC_RELEASE);
                     if (getenv("FIBHIP_PRINT_PLAN"))
                         fprintf(stderr, "fibhip: %dx%d model %d: candidate K=%d tile %dx%d gave up waiting as a multi-tick launch: dropped\n",
-                                h->d.height, h->d.width, h->d.model, trial[0].K, trial[0].TX, trial[0].TY);
+                                h->d.height, h->d.width, h->d.model, mtv->K, mtv->TX, mtv->TY);
                     continue;
                 }
             }
@@ -323,14 +366,29 @@ static int autotune(fibhip_ctx *h)
             if (round > 0 && ms < best_of[t]) best_of[t] = ms;
         }
     }
+    // the fastest plan of whole ticks — and, if it is faster still, the exchange-period row for the multi-tick launches beside it
     std::vector<PlanItem> best_plan = heuristic;
-    float best_ms = 1e30f;
-    for (size_t t = 0; t < trials.size(); ++t)
-        if (!failed[t] && !trials[t].empty() && best_of[t] < best_ms) {
+    float best_ms = 1e30f, best_period_ms = 1e30f;
+    const Variant *best_period = nullptr;
+    for (size_t t = 0; t < trials.size(); ++t) {
+        if (failed[t] || trials[t].empty()) continue;
+        if (period_of[t]) {
+            if (best_of[t] < best_period_ms) {
+                best_period_ms = best_of[t];
+                best_period = period_of[t];
+            }
+        } else if (best_of[t] < best_ms) {
             best_ms = best_of[t];
             best_plan = trials[t];
         }
+    }
     h->plan = best_plan;
+    if (!getenv("FIBHIP_PERIOD_ROW")) h->period_v = best_period_ms < best_ms ? best_period : nullptr;
+    h->period_forced = false;                             // (chosen here, or named by FIBHIP_PERIOD_ROW: long declared series only)
+    if (getenv("FIBHIP_PRINT_PLAN") && h->period_v)
+        fprintf(stderr, "fibhip: %dx%d model %d: several ticks per launch in exchange periods of K=%d sub-steps, tile %dx%d, %d rows per "
+                        "wave, for declared series of %d ticks or more (%.2f us per tick when chosen; everything else runs the plan below)\n",
+                h->d.height, h->d.width, h->d.model, h->period_v->K, h->period_v->TX, h->period_v->TY, -h->period_v->NT, MT_DECLARED_MIN_TICKS, best_period_ms * 1e3f);
     h->mt.stale = true;
     h->launches = launches0;
     if (getenv("FIBHIP_PRINT_PLAN") && !best_plan.empty())

@@ -141,16 +141,48 @@ static int predict_series(const fibhip_ctx *h, bool *repeat)
     return e[-1];
 }
 
+// sub-steps one multi-tick launch of shape `v` advances between two exchanges: the tick's — or, for an exchange-period row
+// (Variant::period), its own K
+static inline bool period_row_ok(const fibhip_ctx *h, const Variant *v)
+{
+#if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
+    // (the model declares its sub-steps alike — the kernel ignores where a tick ends — and the period is shorter than the tick)
+    return !h->mod && h->d.model == FIBHIP_FENTON4V && Fenton::UNIFORM_SUBSTEPS && v->K < h->spt;
+#else
+    return false;
+#endif
+}
+// periods of a launch of T ticks of an exchange-period row, and the sub-steps of the last one (1 .. K)
+static inline int periods_of(const fibhip_ctx *h, const Variant *v, int T, int *last = nullptr)
+{
+    const int S = T * h->spt, P = (S + v->K - 1) / v->K;
+    if (last) *last = S - (P - 1) * v->K;
+    return P;
+}
+
 static bool mt_eligible(const fibhip_ctx *h, const Variant *v)
 {
-    if (h->mt.max <= 1 || !v || !v->fn_mt || v->K != h->spt || h->use_agg) return false;
+    if (h->mt.max <= 1 || !v || !v->fn_mt || h->use_agg) return false;
+    if (v->period ? !period_row_ok(h, v) : v->K != h->spt) return false;
     const long tiles = tiles_of(h, v->TX, v->TY);
     return tiles <= h->ncu && tiles <= MT_MAX_TILES && h->d.device < 16;
 }
 // the shape the handle runs several ticks per launch with, or null (h->obs.on: see "what the recorders ask of the scheduler")
-static const Variant *mt_variant(const fibhip_ctx *h)
+// `long_declared`: the launch belongs to a series the caller has declared, long enough for the declared cap (launch_cap), and
+// carries no read-back
+static const Variant *mt_variant(const fibhip_ctx *h, bool long_declared = false)
 {
-    if (h->obs.on || h->plan.size() != 1 || h->fused_fn || !mt_eligible(h, h->plan[0].v)) return nullptr;
+    if (h->obs.on || h->fused_fn) return nullptr;
+    // An exchange-period row runs multi-tick launches while h->plan stays what a plain tick is made of (a tick on its own, the
+    // replay of recover(), FIBHIP_MT=0): K is no divisor of the tick there.  A row the caller forced runs every multi-tick
+    // launch.  A row autotune() chose runs the launches of long declared series only: measured at 512x512, a launch of ten ticks
+    // that carries a frame pays more for its extra boundaries and its short last period than its sub-steps gain (5000 ticks
+    // with a read-back every 10: 66.50 against 66.11 ms, profiles/exchange_period_ab.txt), and such launches are also the ones
+    // a caller cuts short, which a period row can honour at every K / gcd(K, spt)-th tick only (ahead_settle).
+    if (h->period_v && h->period_forced && mt_eligible(h, h->period_v)) return h->period_v;
+    // (a chosen row rides beside a plan that runs several ticks per launch itself: no such plan, no multi-tick launches at all)
+    if (h->plan.size() != 1 || !mt_eligible(h, h->plan[0].v)) return nullptr;
+    if (h->period_v && long_declared && mt_eligible(h, h->period_v)) return h->period_v;
     return h->plan[0].v;
 }
 
@@ -246,6 +278,8 @@ static inline int launch_cap(const fibhip_ctx *h, bool declared)
 }
 // every pending tick was declared when it was accepted (Series::covered counts from the youngest)
 static inline bool pending_declared(const fibhip_ctx *h) { return h->pending > 0 && h->series.covered >= h->pending; }
+// ... in a declaration long enough for the declared cap: what mt_variant calls `long_declared`
+static inline bool pending_long_declared(const fibhip_ctx *h) { return pending_declared(h) && h->series.expect_long; }
 // ticks of the next multi-tick launch when `waiting` of the pending ticks wait for it
 static inline int next_launch_ticks(const fibhip_ctx *h, int waiting)
 {
@@ -329,6 +363,20 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
         HIPCHK(hipHostGetDevicePointer((void **)&h->mt.snap_flags_dev, h->mt.snap_flags, 0));
         h->mt.host_word = h->mt.snap_flags + MT_HOST_WORD_AT;
     }
+    const bool trial = !commit && !nxt_out;           // (autotune: timed and checked on the spot, never part of the state)
+    // A handle whose chosen exchange-period row runs beside its plan alternates between two tilings.  Tiles store absolute epoch
+    // values and a word nobody wrote for a while is only ever OLDER than wanted, so a stale word makes its reader wait for the
+    // store that is coming anyway — until it is 2^31 boundaries behind, when the wrapping compare reads it as ahead (hours of
+    // nothing but launches of the other shape).  So the tiles' words start equal again whenever the shape changes: queued on the
+    // same stream, and the tiles' words only — the give-up word behind them must stand for the launches queued behind a launch
+    // that gave up.  (autotune's trials alternate shapes eight ticks at a time and zero all words behind the last of them.)
+    if (!trial) {
+        if (h->mt.last_v && h->mt.last_v != v && !h->mt.stale) {
+            HIPCHK(hipMemsetAsync(h->mt.epochs, 0, MtState::words_bytes() - MtState::tail_bytes(), h->s0));
+            h->mt.epoch_base = 0;
+        }
+        h->mt.last_v = v;
+    }
     if (h->mt.stale) {                            // first use, or the tiling may have changed: all words equal again
         HIPCHK(hipMemsetAsync(h->mt.epochs, 0, MtState::words_bytes(), h->s0));
         h->mt.epoch_base = 0;
@@ -346,13 +394,17 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
     h->mt.seq = h->mt.seq % h->mt.ids + 1u;           // 1 .. 65535 (FIBHIP_MT_IDS: a smaller cycle, for the tests)
     // (the host's word keeps naming the last launch it was written for: that id is not given out again while it stands there)
     if (h->mt.host_word && (__atomic_load_n(h->mt.host_word, __ATOMIC_RELAXED) >> 16) == h->mt.seq) h->mt.seq = h->mt.seq % h->mt.ids + 1u;
-    c.mt.ticks_id = (unsigned)T | (h->mt.seq << 16);
+    // (an exchange-period row: the low half counts PERIODS, and the sub-steps of the last one travel in `sub0`, which no model
+    // with uniform sub-steps reads)
+    int last_steps = v->K;
+    const int nbound = v->period ? periods_of(h, v, T, &last_steps) : T;      // passes of the kernel's outer loop
+    if (v->period) c.sub0 = last_steps;
+    c.mt.ticks_id = (unsigned)nbound | (h->mt.seq << 16);
     if (v->kern_mt) module_kernel(c, h, v->kern_mt, MK_STRIP_MT, v);
     c.mt.snap = snap;
     c.mt.snap_flag = h->mt.snap_flags_dev;
     c.mt.snap_seq = h->ahead.snap_seq;
     c.mt.snap_var = (snap_var & 0xFF) | (int)(h->mt.wait_ms << 8);
-    const bool trial = !commit && !nxt_out;           // (autotune: timed and checked on the spot, never part of the state)
     if (!trial) {
         MtRec rec;
         rec.id = h->mt.seq;
@@ -389,7 +441,7 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
         h->n_ticks += T;
     }
     h->mt.inflight = true;
-    h->mt.epoch_base += (unsigned)(T - 1);               // every tile raised its word once per tick boundary
+    h->mt.epoch_base += (unsigned)(nbound - 1);          // every tile raised its word once per tick (period) boundary
     if (commit) memcpy(h->cur, nxt, sizeof nxt);
     if (nxt_out) memcpy(nxt_out, nxt, sizeof nxt);
     // (the sample reads the state and writes the recorder's own buffers only: it may stand behind this unconfirmed launch)
@@ -462,8 +514,9 @@ static int tick_multi(fibhip_t h, int T)
 static int launch_pending(fibhip_t h, int n)
 {
     if (n > 0 && !h->tracing)
-        if (const Variant *v = mt_variant(h)) {
+        if (mt_variant(h)) {
             while (n > 0) {
+                const Variant *v = mt_variant(h, pending_long_declared(h));
                 const int T = next_launch_ticks(h, n);
                 take_pending(h, T);
                 n -= T;
@@ -527,6 +580,7 @@ static int ahead_begin(fibhip_ctx *h, const Variant *v, int L, float *snap = nul
     h->ahead.n = L;
     h->ahead.used = 0;
     h->ahead.id = h->mt.seq;
+    h->ahead.v = v;
     return 0;
 }
 
@@ -573,18 +627,28 @@ static int ahead_settle(fibhip_ctx *h)
     bool kept = false;
     if (h->mt.epochs) {
         // (the word names the launch: earlier launches of this handle may still be queued or running)
-        unsigned word = (h->ahead.id << 16) | (redo > 0 ? (unsigned)redo : MT_CANCEL);
+        unsigned stop_at = redo > 0 ? (unsigned)redo : MT_CANCEL;
+        const Variant *av = h->ahead.v;                 // (the shape THAT launch runs)
+        if (redo > 0 && av && av->period) {
+            // an exchange-period launch counts periods, and holds the state after `redo` ticks only at a boundary that falls on
+            // that tick's end.  Between two boundaries there is nothing to stop at — a period is never shortened on the fly: tiles
+            // that saw the word at different times would disagree — so the launch is cancelled and the ticks handed out are
+            // recomputed from the slab it started from, the way out a stop that came too late takes below.
+            const int sub = redo * h->spt;
+            stop_at = sub % av->K == 0 ? (unsigned)(sub / av->K) : MT_CANCEL;
+        }
+        const bool stop = stop_at != MT_CANCEL;
+        unsigned word = (h->ahead.id << 16) | stop_at;
         // (a plain store: the tiles read this word over PCIe.  A copy through the second stream does not reach a device
         // whose compute units are all taken before the launch has ended: measured at 512x512, 238-387 us)
         __atomic_store_n(h->mt.host_word, word, __ATOMIC_RELEASE);
         h->mt.stale = true;
-        if (redo > 0) {
+        if (stop) {
             HIPCHK(hipMemcpyAsync(h->probe_host + 10, h->mt.stop_count_word(), sizeof(unsigned), hipMemcpyDeviceToHost, h->s0));
             SYNC_S0(h);
             unsigned stopped;
             memcpy(&stopped, h->probe_host + 10, sizeof stopped);
-            const Variant *v = mt_variant(h);
-            kept = (long)stopped == (v ? tiles_of(h, v->TX, v->TY) : -1);
+            kept = (long)stopped == (av ? tiles_of(h, av->TX, av->TY) : -1);
         }
     }
     if (kept) {                                     // the state after `redo` ticks is where the launch wrote it
@@ -786,7 +850,7 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
             L = predict_series(h, &repeats);
         }
         if (nticks < L && may_run_ahead(h, L, repeats, declared, AHEAD_FROM_STEP))
-            if (const Variant *v = mt_variant(h))
+            if (const Variant *v = mt_variant(h, declared && h->series.expect_long))
                 if (int rc = ahead_begin(h, v, L)) return rc;
     }
     int covered = 0;                                   // how many of this call's ticks the declaration covers (its first)
@@ -805,7 +869,7 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
         if (int rc = check_ready(h)) return rc;
         if (!h->tuned)
             if (int rc = autotune(h)) return rc;
-        if (const Variant *v = mt_variant(h)) {
+        if (mt_variant(h)) {
             h->pending += nticks;
             // (a call that goes past the end of its declaration leaves undeclared ticks behind the declared ones: none counts)
             h->series.covered = covered == nticks ? h->series.covered + covered : 0;
@@ -813,6 +877,7 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
             // them) and ends there: between two samples the handle runs the fewest launches `every` allows, whatever the
             // caller's call pattern.  (Without one: mt.cur, as described above.)
             while (h->pending >= (cutting(h) ? imin(sample_room(h), launch_cap(h, pending_declared(h))) : h->mt.cur)) {
+                const Variant *v = mt_variant(h, pending_long_declared(h));
                 const int T = next_launch_ticks(h, h->pending);
                 take_pending(h, T);
                 if (int rc = tick_mt(h, v, T)) return rc;

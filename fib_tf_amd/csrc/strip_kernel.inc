@@ -48,6 +48,15 @@ template <class A>
 struct SameType<A, A> {
     static constexpr bool value = true;
 };
+// M::UNIFORM_SUBSTEPS where a model declares it (models.hpp Fenton): its sub-steps are all the same operation
+template <class M, class = void>
+struct UniformSubsteps {
+    static constexpr int steps = 0;
+};
+template <class M>
+struct UniformSubsteps<M, void_of<decltype(M::UNIFORM_SUBSTEPS)>> {
+    static constexpr int steps = M::UNIFORM_SUBSTEPS ? M::DEFAULT_STEPS : 0;
+};
 template <class M, bool SPARE, class C>
 static FIB_DEV decltype(auto) pinned_for(const C &k)
 {
@@ -90,6 +99,15 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
     constexpr int CX = TX + 2 * (K - 1), CY = TY + 2 * (K - 1);
     static_assert(CX <= 62 && K > 1, "strip_kernel: compute box must fit 62 lanes");
     static_assert(!MT || (CX == 62 && TX >= K && TY >= K), "multi-tick launches: 62-column box, the rim inside the eight neighbours");
+    // Exchange periods.  A model whose sub-steps are all alike (M::UNIFORM_SUBSTEPS) has nothing in its arithmetic that knows
+    // where a tick ends, so a multi-tick launch of it may hand its rims over every K sub-steps with K SMALLER than the tick: a
+    // shallower rim (K - 1), a wider tile (TX = 64 - 2K) and a lower box, which decides how many strips land on each of the four
+    // SIMDs.  Such an instantiation loops over PERIODS where the others loop over ticks: `mt.ticks_id` counts periods, every period
+    // runs K sub-steps except the last, which runs the `sub0` sub-steps that complete the launch's ticks (the step functions
+    // ignore the index sub0 stands for elsewhere), and everything between two periods — parities, epochs, the host's word, the
+    // read-back — is the tick boundary below, word for word.  All of it sits behind `if constexpr (PERIODS)`: the instantiations
+    // with K = the tick's sub-steps compile to the instructions they compiled to before.
+    constexpr bool PERIODS = MT && K < UniformSubsteps<M>::steps;
     constexpr int NW = (CY + R - 1) / R;
     constexpr int LP = 64, LQ = NW * R + 2, NL = LP * LQ;
     constexpr unsigned WMASK = M::mask(MODE);
@@ -291,7 +309,12 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
                 if (own[r]) __hip_atomic_store(mt.snap + off[r], snapl[(c0 + r) * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // write-through
         }
     }
-    if (WHOLE_LOOP && whole) {
+    // a launch's last period is short where the launch's sub-steps are no multiple of K: it runs `sub0` of them (wave-uniform;
+    // once per launch, so it takes the loop with the row bookkeeping whatever the strip).  (A flag, and the bound read from the
+    // kernel's argument where it is needed: a bound kept live across the period cost the 48 x 23 kernel a third spilled register.)
+    [[maybe_unused]] bool short_last = false;
+    if constexpr (PERIODS) short_last = tick + 1 >= (int)(mt.ticks_id & 0xFFFFu) && sub0 < K;
+    if (WHOLE_LOOP && whole && (!PERIODS || !short_last)) {
 #pragma unroll STEP_UNROLL
         for (int st = 0; st < K; ++st) {
             float *B = lds[(st & 1) ^ 1];
@@ -362,6 +385,11 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
         }
         // ---- publish the new potential, then fetch the next sub-step's window ---------------------------
         if (st + 1 < K) {
+            // (a short last period ends here.  The loop keeps its constant trip count: with a bound read at run time the
+            // compiler does not unroll a loop that holds a barrier)
+            if constexpr (PERIODS) {
+                if (short_last && st + 1 >= sub0) break;
+            }
             const unsigned live = ra < rb ? ((1u << rb) - 1u) & ~((1u << ra) - 1u) : 0u;
             const unsigned m = live & pub;
 #pragma unroll

@@ -20,13 +20,21 @@
 //     waiting tile also polls, so the launch drains instead of hanging; the host reports the failure at its next
 //     synchronisation point.  The host only uses this kernel when all tiles can be resident at once (tiles <= CUs)
 //     and never runs two such launches of one process at the same time.
+//   * Exchange periods (strip_kernel.inc PERIODS; launch.hpp S4P rows).  How often tiles exchange is a parameter of the row, not
+//     the tick: a model whose sub-steps are all alike (Fenton: UNIFORM_SUBSTEPS) may run this protocol every K sub-steps with K
+//     below the tick's.  "Tick" in everything above then reads "period": the low half of `ticks_id` counts periods, the epoch
+//     words count periods, the parities alternate per period, the host's word names a period count — the host translates: the
+//     state after n ticks exists inside such a launch only where n ticks end on a period boundary (n * spt a multiple of K); any
+//     other request cancels the launch and its ticks are recomputed from the slab it started from (sched.inc ahead_settle).  A
+//     launch of T ticks runs ceil(T * spt / K) periods, all of K sub-steps but the last, whose sub-steps travel in the kernel's
+//     `sub0` argument.  A period is never shortened on the fly: tiles that saw the host's word at different times would disagree.
 struct MtArgs {
     float *xb;            // exchange buffer
     unsigned *epoch;      // one word per tile, MT_EPOCH_STRIDE words apart
     unsigned *err;        // [0]: a tile gave up waiting; [MT_EPOCH_STRIDE]: the host's word as tile 0 passed it on; [2 * MT_EPOCH_STRIDE]:
                           // tiles that stopped where it said (counted)
     unsigned epoch0;      // value of every epoch word when the launch starts
-    unsigned ticks_id;    // low half: ticks this launch advances; high half: the launch's id, 1 .. 65535 (the host's word names
+    unsigned ticks_id;    // low half: ticks this launch advances (an exchange-period row: periods); high half: the launch's id, 1 .. 65535 (the host's word names
                           // the launch it is meant for).  One word, and the host's word behind the tiles' words of `snap_flag`
                           // instead of a pointer of its own: Beeler-Reuter's kernel spills scalar registers as it is, and three
                           // more kernel arguments cost it 2.5 % (same-box A/B)

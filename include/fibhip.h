@@ -277,7 +277,12 @@ int fibhip_warm(int device);
 #define FIBHIP_COURT_NINTER 32
 int fibhip_court_inter(int device, int n, const float *V, int fast, float *out);
 
-/* introspection for DESIGN/bench: sub-steps fused per launch and launches per tick                      */
+/* introspection for DESIGN/bench: sub-steps fused per launch and launches per tick.  A handle whose multi-tick launches
+ * exchange every K sub-steps with K below the tick's (Fenton 4v, an exchange-period row of the table: FIBHIP_VARIANT or
+ * FIBHIP_K force one for every multi-tick launch) reports (K, 1); fibhip_ticks_per_launch still counts ticks, and
+ * fibhip_plan_tile names that row's tile.  Where the first tick's measurement chose the row (or FIBHIP_PERIOD_ROW named it)
+ * it runs the launches of LONG DECLARED series only (fibhip_expect of 128 ticks or more): both calls then name the shape
+ * of those launches — every other launch of the handle runs the K = the tick's sub-steps plan                          */
 int fibhip_launch_plan(fibhip_t h, int *fused_steps, int *launches_per_tick);
 /* ... and the tile of the first launch: width, height, and rows per wave (strip kernels) or -threads per workgroup
  * (flat tile kernels)                                                                                              */
@@ -287,7 +292,9 @@ int fibhip_plan_tile(fibhip_t h, int *tile_w, int *tile_h, int *rows_per_wave);
  * model, mode, fast, phase, K, TX, TY, NT as the table lists them (model: a fibhip_model, 100 = Fenton 4v with the
  * zero-padded Laplacian, 101 = Courtemanche on aggregates; NT: threads of a flat tile, -rows per wave of a strip kernel,
  * -(32 + rows per wave) of a rows kernel), then the kernel kind (0 flat tile, 1 strip, 4 rows), then 1 if the row also
- * exists as a launch that advances several ticks.  The kernels of a run-time module are not part of this table.     */
+ * exists as a launch that advances several ticks of K sub-steps each (K = the tick's sub-steps; Fenton's row with K = 6 runs
+ * several ticks per launch too, in exchange periods of K sub-steps, and is listed 0: as the plain strip launch of K
+ * sub-steps it also is).  The kernels of a run-time module are not part of this table.                     */
 int fibhip_variant_count(void);
 int fibhip_variant_info(int i, int out[10]);
 /* Consecutive ticks one launch can cover (1 = every tick is its own launch or launches).  Courtemanche under
