@@ -14,6 +14,7 @@ from .court import Courtemanche                 # noqa: F401
 from . import tips                              # noqa: F401  (TipRecorder, link: spiral tips recorded on the device)
 from . import frames                            # noqa: F401  (FrameRecorder: the movie cube recorded on the device)
 from . import stats                             # noqa: F401  (StatsRecorder: tissue statistics recorded on the device)
+from . import spectrum                          # noqa: F401  (SpectrumRecorder: per-cell power spectra and dominant-frequency maps)
 from . import stimulus                          # noqa: F401  (Stimulus, StimulusProgram: pacing protocols run on the device)
 from . import triggers                          # noqa: F401  (Sensor, Trigger, TriggerProgram: triggered stimulation on the device)
 

@@ -18,6 +18,7 @@ FENTON4V, BR, COURT, COURT_US, CUSTOM = 0, 1, 2, 3, 4
 OBS_MAPS = ('first_up', 'last_up', 'prev_up', 'apd', 'count')     # enum fibhip_obs_map, in order
 FRAME_REDUCE = ('point', 'mean')                                  # enum fibhip_frame_reduce, in order
 FRAME_FORMAT = ('float32', 'uint8')                               # enum fibhip_frame_format, in order
+SPECTRUM_MAX_BINS, SPECTRUM_MAX_CHUNK, SPECTRUM_MIN_NFFT, SPECTRUM_MAX_NFFT = 128, 32, 4, 65536
 STAT_KINDS = ('sum', 'min', 'max', 'below', 'above', 'nonfinite')  # enum fibhip_stat_kind, in order
 MAX_STAT_COLS, MAX_STAT_COLS_PER_ARRAY = 64, 8
 STIM_MODES = ('max', 'add')                                       # enum fibhip_stim_mode, in order
@@ -221,6 +222,12 @@ SYMBOLS = {
     'fibhip_stats_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_stats_read': ([_h, C.c_longlong, C.c_longlong, C.POINTER(C.c_double)], C.c_int),
     'fibhip_stats_end': ([_h], C.c_int),
+    'fibhip_spectrum_begin': ([_h, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int], C.c_int),
+    'fibhip_spectrum_count': ([_h, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_spectrum_shape': ([_h, _ip, _ip, _ip], C.c_int),
+    'fibhip_spectrum_read': ([_h, _fp, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_spectrum_peak': ([_h, C.c_int, C.c_int, C.c_int, _ip, _fp, _fp, _fp], C.c_int),
+    'fibhip_spectrum_end': ([_h], C.c_int),
     'fibhip_stim_begin': ([_h, C.c_int, C.POINTER(StimEntry), C.c_int, _fp], C.c_int),
     'fibhip_stim_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_stim_end': ([_h], C.c_int),
@@ -868,6 +875,61 @@ class Stepper:
 
     def frames_end(self):
         self._ck(self._L.fibhip_frames_end(self._h))
+
+    # ---- spectrum recorder (include/fibhip.h fibhip_spectrum_*) ----------------------------------------------------
+    def spectrum_begin(self, var=0, window=None, block=(1, 1), reduce='mean', weight=None, every=1, nfft=128, win=None, tw=None,
+                       bins=(2,), chunk=1):
+        """attaches the spectrum recorder on array `var`: the frame recorder's `window`, `block`, `reduce` and `weight` (levels
+        0 and 1), a sample every `every` ticks, segments of `nfft` samples weighted by `win` [nfft] float32, the twiddle table
+        `tw` [nfft, 2] float32 (cos, -sin of 2 pi m / nfft), the strictly ascending frequency indices `bins` (at most 128, each
+        in [0, nfft / 2]) and `chunk` (1 .. 32, a divisor of nfft): the samples folded by one launch"""
+        wnd = np.ascontiguousarray((0, self.height, 0, self.width) if window is None else window, np.intc).reshape(4)
+        wp = None
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, np.float32)
+            if weight.shape != (self.height, self.width):
+                raise ValueError('spectrum_begin: a weight plane of shape %s on a %d x %d grid' % (weight.shape, self.height, self.width))
+            wp = weight.ctypes.data_as(_fp)
+        win = np.ascontiguousarray(win, np.float32)
+        tw = np.ascontiguousarray(tw, np.float32)
+        if win.shape != (int(nfft),) or tw.shape != (int(nfft), 2):
+            raise ValueError('spectrum_begin: win must be [nfft] and tw [nfft, 2] (got %s and %s for nfft = %d)' % (win.shape, tw.shape, nfft))
+        b = np.ascontiguousarray(bins, np.intc).reshape(-1)
+        self._ck(self._L.fibhip_spectrum_begin(self._h, int(var), wnd.ctypes.data_as(_ip), int(block[0]), int(block[1]),
+                                               FRAME_REDUCE.index(reduce), wp, int(every), int(nfft), win.ctypes.data_as(_fp),
+                                               tw.ctypes.data_as(_fp), int(b.size), b.ctypes.data_as(_ip), int(chunk)))
+
+    def spectrum_count(self):
+        """(samples taken, segments finished) since spectrum_begin (ticks accepted but not launched yet included)"""
+        s, g = C.c_longlong(), C.c_longlong()
+        self._ck(self._L.fibhip_spectrum_count(self._h, C.byref(s), C.byref(g)))
+        return int(s.value), int(g.value)
+
+    def spectrum_shape(self):
+        """(oh, ow, nb) of the attached recorder"""
+        oh, ow, nb = C.c_int(), C.c_int(), C.c_int()
+        self._ck(self._L.fibhip_spectrum_shape(self._h, C.byref(oh), C.byref(ow), C.byref(nb)))
+        return int(oh.value), int(ow.value), int(nb.value)
+
+    def spectrum_read(self):
+        """(P [nb, oh, ow] float32, segments): the power summed over the finished segments; blocks like get_state"""
+        oh, ow, nb = self.spectrum_shape()
+        out = np.empty((nb, oh, ow), np.float32)
+        seg = C.c_longlong()
+        self._ck(self._L.fibhip_spectrum_read(self._h, out.ctypes.data_as(_fp), C.byref(seg)))
+        return out, int(seg.value)
+
+    def spectrum_peak(self, a, b, halfwidth=1):
+        """(kpeak int32, ppeak, pband, pnear float32), each [oh, ow], over the bin positions a <= i <= b"""
+        oh, ow, _ = self.spectrum_shape()
+        kp = np.empty((oh, ow), np.int32)
+        pp, pb, pn = (np.empty((oh, ow), np.float32) for _ in range(3))
+        self._ck(self._L.fibhip_spectrum_peak(self._h, int(a), int(b), int(halfwidth), kp.ctypes.data_as(_ip), pp.ctypes.data_as(_fp),
+                                              pb.ctypes.data_as(_fp), pn.ctypes.data_as(_fp)))
+        return kp, pp, pb, pn
+
+    def spectrum_end(self):
+        self._ck(self._L.fibhip_spectrum_end(self._h))
 
     # ---- statistics recorder (include/fibhip.h fibhip_stats_*) ----------------------------------------------------
     def stats_begin(self, cols, weight=None, mask=None, every=1, capacity=1):

@@ -182,6 +182,28 @@ struct StRec {
     double *trace;          // device: [cap][ncols]
 };
 
+// spectrum recorder (fibhip_spectrum_begin): the fifth sampler — no launch spans a sample tick (sample_room), and the hook on
+// the plain and the multi-tick commit path (spectrum_advance) enqueues spectrum_sample_kernel behind the launch that ends one
+// and, behind the sample that fills the ring, spectrum_fold_kernel.  It ACCUMULATES: both kernels read the give-up word first,
+// and everything about its progress follows from `k` alone — samples k / every, the ring slot and the segment position of a
+// sample, the folds issued samples / chunk, the segments samples / nfft — so a rewind of `k` leaves nothing behind
+struct SpRec {
+    bool on;
+    int var, every;
+    int r0, c0, oh, ow, by, bx;     // the window's first cell, the plane's shape in pixels, the block
+    int reduce;                     // FIBHIP_FRAME_POINT / _MEAN
+    int nfft, nb, chunk;
+    long long k;            // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
+    float *w;               // device: the weight plane [H][W], or null
+    float *win;             // device: [nfft]
+    float *tw;              // device: [nfft][2]
+    int *bins;              // device: [nb]
+    float *ring;            // device: [chunk][oh][ow]
+    float *acc;             // device: Re | Im | P, each [nb][oh][ow]
+    float *maps;            // device: kpeak (int32) | ppeak | pband | pnear, each [oh][ow]
+    size_t npix() const { return (size_t)oh * (size_t)ow; }
+};
+
 // stimulus program (fibhip_stim_begin): the actuator beside the recorders — no launch spans an event tick (stim_room, a term of
 // sample_room), and the hook on the plain and the multi-tick commit path (stim_advance) enqueues stim_kernel behind the launch
 // that ends one, behind the samples of that tick
@@ -287,6 +309,7 @@ struct fibhip_ctx {
     TipRec tip;
     FrRec fr;
     StRec st;
+    SpRec sp;
     StimRec stim;
     TrigRec trig;
     std::vector<TraceRec> trace;

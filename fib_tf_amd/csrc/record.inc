@@ -1,6 +1,6 @@
-// record.inc — the five recorders that run on the device while a model runs: the per-cell activation maps
+// record.inc — the six recorders that run on the device while a model runs: the per-cell activation maps
 // (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
-// (fibhip_frames_*) and the tissue statistics (fibhip_stats_*) — and the two hooks that write the state: the stimulus program
+// (fibhip_frames_*), the tissue statistics (fibhip_stats_*) and the per-cell power spectra (fibhip_spectrum_*) — and the two hooks that write the state: the stimulus program
 // (fibhip_stim_*) and the trigger program (fibhip_trig_*), which senses, decides and fires on the device.  Each is a hook behind a committed launch plus its entry points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
 // (included by fibhip.hip, behind sched.inc)
 
@@ -235,6 +235,81 @@ static void stats_free(fibhip_ctx *h)
     h->st.part = nullptr;
     h->st.trace = nullptr;
     h->st.on = false;
+}
+
+static_assert(SPEC_MAX_BINS == FIBHIP_SPECTRUM_MAX_BINS && SPEC_MAX_CHUNK == FIBHIP_SPECTRUM_MAX_CHUNK &&
+                  FIBHIP_SPECTRUM_MAX_NFFT / 2 * (long long)(FIBHIP_SPECTRUM_MAX_NFFT - 1) <= 0xFFFFFFFFll,
+              "the spectrum kernels' constants follow include/fibhip.h; spectrum_fold_kernel's k * j fits 32 bits unsigned");
+typedef void (*spec_fold_fn)(const float *, float *, float *, float *, const float *, const float2 *, const int *, size_t, int, int, int, int,
+                             const unsigned *);
+template <int... C>
+static spec_fold_fn spec_fold_pick(int chunk, std::integer_sequence<int, C...>)
+{
+    static const spec_fold_fn table[] = {spectrum_fold_kernel<C + 1>...};      // chunk = 1 .. SPEC_MAX_CHUNK
+    return table[chunk - 1];
+}
+// The spectrum recorder's hook behind a launch of `ticks` ticks, the frame recorder's step for step: at a sample tick
+// spectrum_sample_kernel writes the pixel plane into slot s mod chunk of the ring, and behind the sample that fills the ring
+// spectrum_fold_kernel folds the chunk.  Slot, segment position and whether the chunk ends a segment are kernel arguments
+// computed from the host's counter.  `behind_mt`: as for stim_advance — both kernels are handed the give-up word and write
+// nothing once a launch in front of them gave up (the fold accumulates, and a void sample must not overwrite a slot whose fold
+// was skipped: record_kernels.inc); recover() rewinds the counter and the replay comes through here again.
+static int spectrum_advance(fibhip_ctx *h, int ticks, bool behind_mt)
+{
+    SpRec &r = h->sp;
+    r.k += ticks;
+    if (r.k % r.every) return 0;
+    const long long s = r.k / r.every - 1;
+    const unsigned *give_up = behind_mt && h->mt.epochs ? h->mt.give_up_word() : nullptr;
+    const size_t npix = r.npix();
+    SpecSampleArgs a;
+    a.x = h->slab[h->cur[r.var]] + (size_t)r.var * h->vstride;
+    a.w = r.w;
+    a.out = r.ring + (size_t)(s % r.chunk) * npix;
+    a.pitch = h->pitch;
+    a.wpitch = h->d.width;
+    a.r0 = r.r0; a.c0 = r.c0; a.oh = r.oh; a.ow = r.ow; a.by = r.by; a.bx = r.bx;
+    a.give_up = give_up;
+    const bool mean = r.reduce == FIBHIP_FRAME_MEAN;
+    const bool vec = r.by == 1 && r.bx == 1 && h->pitch == h->d.width && h->d.width % 4 == 0 && r.c0 % 4 == 0 && r.ow % 4 == 0 &&
+                     ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.w) | reinterpret_cast<uintptr_t>(a.out)) & 15u) == 0;
+    {
+        const size_t threads = (size_t)r.oh * (size_t)(vec ? r.ow / 4 : r.ow);
+        const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+        if (int rc = trace_open(h, h->s0, "spectrum_sample_kernel", 0, 0, 0, 0, 1)) return rc;
+        if (vec) hipLaunchKernelGGL((spectrum_sample_kernel<false, true>), grid, block, 0, h->s0, a);
+        else if (mean) hipLaunchKernelGGL((spectrum_sample_kernel<true, false>), grid, block, 0, h->s0, a);
+        else hipLaunchKernelGGL((spectrum_sample_kernel<false, false>), grid, block, 0, h->s0, a);
+        HIPCHK(hipGetLastError());
+        if (int rc = trace_close(h, h->s0)) return rc;
+        h->launches++;
+    }
+    if ((s + 1) % r.chunk) return 0;
+    const int j0 = (int)((s + 1 - r.chunk) % r.nfft);                // the segment position of ring slot 0 (a chunk never straddles a segment)
+    const size_t plane = (size_t)r.nb * npix;
+    if (int rc = trace_open(h, h->s0, "spectrum_fold_kernel", 0, 0, 0, 0, 1)) return rc;
+    hipLaunchKernelGGL(spec_fold_pick(r.chunk, std::make_integer_sequence<int, SPEC_MAX_CHUNK>()), dim3((unsigned)((npix + 255) / 256)), dim3(256),
+                       0, h->s0, (const float *)r.ring, r.acc, r.acc + plane, r.acc + 2 * plane, (const float *)r.win,
+                       reinterpret_cast<const float2 *>(r.tw), (const int *)r.bins, npix, r.nfft, r.nb, j0, j0 + r.chunk == r.nfft ? 1 : 0, give_up);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    return 0;
+}
+
+static void spectrum_free(fibhip_ctx *h)
+{
+    SpRec &r = h->sp;
+    if (r.w) hipFree(r.w);
+    if (r.win) hipFree(r.win);
+    if (r.tw) hipFree(r.tw);
+    if (r.bins) hipFree(r.bins);
+    if (r.ring) hipFree(r.ring);
+    if (r.acc) hipFree(r.acc);
+    if (r.maps) hipFree(r.maps);
+    r.w = r.win = r.tw = r.ring = r.acc = r.maps = nullptr;
+    r.bins = nullptr;
+    r.on = false;
 }
 
 // What the stimulus program and the trigger program share.  stim_entry_from: one stimulus {var, mode, shape, rectangle, v, floor,
@@ -984,6 +1059,149 @@ extern "C" int fibhip_stats_end(fibhip_t h)
     FLUSH(h);                                          // the ticks accepted while attached are sampled
     SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
     stats_free(h);
+    return 0;
+}
+
+// ---- spectrum recorder --------------------------------------------------------------------------------------------------
+extern "C" int fibhip_spectrum_begin(fibhip_t h, int var, const int *window, int by, int bx, int reduce, const float *weight, int every,
+                                     int nfft, const float *win, const float *tw, int nb, const int *bins, int chunk)
+{
+    NEED(h);
+    if (!window || !win || !tw || !bins) return fail(FIBHIP_EINVAL, "spectrum_begin: null argument");
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "spectrum_begin: bad var %d", var);
+    const int r0 = window[0], r1 = window[1], c0 = window[2], c1 = window[3];
+    if (r0 < 0 || r1 > h->d.height || c0 < 0 || c1 > h->d.width || r0 >= r1 || c0 >= c1)
+        return fail(FIBHIP_EINVAL, "spectrum_begin: the window rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", r0, r1,
+                    c0, c1, h->d.height, h->d.width);
+    if (by < 1 || by > FIBHIP_MAX_FRAME_BLOCK || bx < 1 || bx > FIBHIP_MAX_FRAME_BLOCK)
+        return fail(FIBHIP_EINVAL, "spectrum_begin: a block is 1 .. %d cells each way (got %d x %d)", FIBHIP_MAX_FRAME_BLOCK, by, bx);
+    const int oh = (r1 - r0) / by, ow = (c1 - c0) / bx;
+    if (oh < 1 || ow < 1)
+        return fail(FIBHIP_EINVAL, "spectrum_begin: a window of %d x %d cells holds no block of %d x %d", r1 - r0, c1 - c0, by, bx);
+    if (reduce != FIBHIP_FRAME_POINT && reduce != FIBHIP_FRAME_MEAN) return fail(FIBHIP_EINVAL, "spectrum_begin: bad reduction %d", reduce);
+    if (every < 1) return fail(FIBHIP_EINVAL, "spectrum_begin: every must be >= 1 (got %d)", every);
+    if (nfft < FIBHIP_SPECTRUM_MIN_NFFT || nfft > FIBHIP_SPECTRUM_MAX_NFFT)
+        return fail(FIBHIP_EINVAL, "spectrum_begin: nfft must be %d .. %d (got %d)", FIBHIP_SPECTRUM_MIN_NFFT, FIBHIP_SPECTRUM_MAX_NFFT, nfft);
+    if (chunk < 1 || chunk > FIBHIP_SPECTRUM_MAX_CHUNK || nfft % chunk)
+        return fail(FIBHIP_EINVAL, "spectrum_begin: chunk must be 1 .. %d and divide nfft = %d (got %d)", FIBHIP_SPECTRUM_MAX_CHUNK, nfft, chunk);
+    if (nb < 1 || nb > FIBHIP_SPECTRUM_MAX_BINS) return fail(FIBHIP_EINVAL, "spectrum_begin: 1 .. %d bins (got %d)", FIBHIP_SPECTRUM_MAX_BINS, nb);
+    for (int i = 0; i < nb; ++i) {
+        if (bins[i] < 0 || bins[i] > nfft / 2)
+            return fail(FIBHIP_EINVAL, "spectrum_begin: bin %d names frequency index %d outside [0, nfft / 2 = %d]", i, bins[i], nfft / 2);
+        if (i > 0 && bins[i] <= bins[i - 1]) return fail(FIBHIP_EINVAL, "spectrum_begin: the bins must be strictly ascending (bin %d)", i);
+    }
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "spectrum_begin: not on a row block (a handle with ghost rows)");
+    if (h->pitch != h->d.width) return fail(FIBHIP_EINVAL, "spectrum_begin: not on a row-interleaved slab");
+    if (h->sp.on) return fail(FIBHIP_EINVAL, "spectrum_begin: a recorder is attached already (fibhip_spectrum_end first)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "spectrum_begin inside an open tick");
+    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick 0 is defined (the rule of fibhip_electrode_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    spectrum_free(h);
+    SpRec &r = h->sp;
+    const size_t npix = (size_t)oh * (size_t)ow;
+    bool ok = hipMalloc((void **)&r.ring, (size_t)chunk * npix * sizeof(float)) == hipSuccess;
+    ok = ok && hipMalloc((void **)&r.acc, 3 * (size_t)nb * npix * sizeof(float)) == hipSuccess;
+    ok = ok && hipMalloc((void **)&r.maps, 4 * npix * sizeof(float)) == hipSuccess;
+    ok = ok && hipMalloc((void **)&r.win, (size_t)nfft * sizeof(float)) == hipSuccess;
+    ok = ok && hipMalloc((void **)&r.tw, 2 * (size_t)nfft * sizeof(float)) == hipSuccess;
+    ok = ok && hipMalloc((void **)&r.bins, (size_t)nb * sizeof(int)) == hipSuccess;
+    if (ok && weight) ok = hipMalloc((void **)&r.w, h->cells * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        spectrum_free(h);
+        return fail(FIBHIP_ENOMEM, "spectrum_begin: hipMalloc failed (%d bins and %d ring planes of %d x %d pixels)", nb, chunk, oh, ow);
+    }
+    HIPCHK(hipMemsetAsync(r.acc, 0, 3 * (size_t)nb * npix * sizeof(float), h->s0));        // Re = Im = P = +0
+    HIPCHK(hipMemcpyAsync(r.win, win, (size_t)nfft * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemcpyAsync(r.tw, tw, 2 * (size_t)nfft * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemcpyAsync(r.bins, bins, (size_t)nb * sizeof(int), hipMemcpyHostToDevice, h->s0));
+    if (weight) HIPCHK(hipMemcpyAsync(r.w, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(wait_stream(h->s0));                        // the caller's tables are free again
+    r.on = true;
+    r.var = var;
+    r.every = every;
+    r.r0 = r0; r.c0 = c0; r.oh = oh; r.ow = ow; r.by = by; r.bx = bx;
+    r.reduce = reduce;
+    r.nfft = nfft; r.nb = nb; r.chunk = chunk;
+    r.k = 0;                                           // sample s follows tick (s + 1) * every, ticks counted from 1 here
+    return 0;
+}
+
+extern "C" int fibhip_spectrum_count(fibhip_t h, long long *samples, long long *segments)
+{
+    NEED(h);
+    if (!h->sp.on) return fail(FIBHIP_EINVAL, "spectrum_count: no recorder attached (fibhip_spectrum_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    const long long n = (h->sp.k + h->pending) / h->sp.every;        // (ticks accepted but not launched yet are sampled when they are)
+    if (samples) *samples = n;
+    if (segments) *segments = n / h->sp.nfft;
+    return 0;
+}
+
+extern "C" int fibhip_spectrum_shape(fibhip_t h, int *oh, int *ow, int *nb)
+{
+    if (!h) return fail(FIBHIP_EINVAL, "null handle");
+    if (!h->sp.on) return fail(FIBHIP_EINVAL, "spectrum_shape: no recorder attached (fibhip_spectrum_begin)");
+    if (oh) *oh = h->sp.oh;
+    if (ow) *ow = h->sp.ow;
+    if (nb) *nb = h->sp.nb;
+    return 0;
+}
+
+extern "C" int fibhip_spectrum_read(fibhip_t h, float *P, long long *segments)
+{
+    NEED(h);
+    if (!h->sp.on) return fail(FIBHIP_EINVAL, "spectrum_read: no recorder attached (fibhip_spectrum_begin)");
+    FLUSH(h);
+    const SpRec &r = h->sp;
+    const size_t plane = (size_t)r.nb * r.npix();
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->journal.n_fallbacks;
+        if (P) HIPCHK(hipMemcpyAsync(P, r.acc + 2 * plane, plane * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        SYNC_S0(h);
+        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and folded again, copy again)
+    }
+    if (segments) *segments = r.k / r.every / r.nfft;
+    return 0;
+}
+
+extern "C" int fibhip_spectrum_peak(fibhip_t h, int a, int b, int halfwidth, int *kpeak, float *ppeak, float *pband, float *pnear)
+{
+    NEED(h);
+    if (!h->sp.on) return fail(FIBHIP_EINVAL, "spectrum_peak: no recorder attached (fibhip_spectrum_begin)");
+    const SpRec &r = h->sp;
+    if (a < 0 || b < a || b >= r.nb) return fail(FIBHIP_EINVAL, "spectrum_peak: the band is bin positions 0 <= a <= b < %d (got %d, %d)", r.nb, a, b);
+    if (halfwidth < 0) return fail(FIBHIP_EINVAL, "spectrum_peak: halfwidth must be >= 0 (got %d)", halfwidth);
+    FLUSH(h);
+    const size_t npix = r.npix(), plane = (size_t)r.nb * npix;
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->journal.n_fallbacks;
+        const int have = r.k / r.every / r.nfft > 0 ? 1 : 0;
+        if (int rc = trace_open(h, h->s0, "spectrum_peak_kernel", 0, 0, 0, 0, 1)) return rc;
+        hipLaunchKernelGGL(spectrum_peak_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->s0, (const float *)(r.acc + 2 * plane), npix, a,
+                           b, halfwidth, have, reinterpret_cast<int *>(r.maps), r.maps + npix, r.maps + 2 * npix, r.maps + 3 * npix);
+        HIPCHK(hipGetLastError());
+        if (int rc = trace_close(h, h->s0)) return rc;
+        h->launches++;
+        if (kpeak) HIPCHK(hipMemcpyAsync(kpeak, r.maps, npix * sizeof(int), hipMemcpyDeviceToHost, h->s0));
+        if (ppeak) HIPCHK(hipMemcpyAsync(ppeak, r.maps + npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        if (pband) HIPCHK(hipMemcpyAsync(pband, r.maps + 2 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        if (pnear) HIPCHK(hipMemcpyAsync(pnear, r.maps + 3 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        SYNC_S0(h);
+        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front had given up: recovered and folded again, the maps again)
+    }
+    return 0;
+}
+
+extern "C" int fibhip_spectrum_end(fibhip_t h)
+{
+    NEED(h);
+    if (!h->sp.on) return 0;
+    FLUSH(h);                                          // the ticks accepted while attached are sampled
+    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
+    spectrum_free(h);
     return 0;
 }
 

@@ -1,4 +1,4 @@
-// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame and statistics recorders, and the
+// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame, statistics and spectrum recorders, and the
 // plain copy whose shape they take (the bandwidth yardstick).  (included by kernels.hpp; the host side is record.inc)
 
 // ---- activation recorder (fibhip_observe_begin): per-cell event maps, updated after every observed tick ----------------
@@ -903,4 +903,159 @@ __global__ void __launch_bounds__(256) stim_gated_kernel(StimArgs a, const unsig
             d.x[at] = x[0];
         }
     }
+}
+
+// ---- spectrum recorder (fibhip_spectrum_begin): a per-pixel Welch periodogram folded while the run goes on --------------------
+// Three kernels.  spectrum_sample_kernel writes the pixel plane of a sample tick — the frame recorder's pixel at lo = 0,
+// span = 1, float32 — into slot s mod chunk of a ring of `chunk` planes; spectrum_fold_kernel, behind the sample that fills the
+// ring, adds the ring's samples to the running DFT sums Re / Im of the recorded bins and, when the chunk ends a segment, the
+// segment's power to P; spectrum_peak_kernel makes the four peak maps from P on demand.  Planes are [nb][oh * ow], consecutive
+// lanes take consecutive pixels; no LDS, no atomics.
+// Both the sample and the fold read the give-up word of the multi-tick launches first (`give_up`, null behind plain ticks:
+// stim_kernel's note) and write NOTHING when it is raised.  The fold because it accumulates: a fold replayed by recover() must
+// not find its samples folded already.  The sample because the ring is shorter than what may be queued behind an unconfirmed
+// launch: a sample of a void slab, taken behind a launch that gave up, would overwrite a slot whose good sample — older than
+// that launch, so never replayed — has not been folded yet (its fold, gated, did nothing).  That is also why the sample is a
+// sibling of frame_kernel and not frame_kernel itself, whose code stays as it is.
+struct SpecSampleArgs {
+    const float *x;         // the watched array (its first row), `pitch` floats between rows
+    const float *w;         // the weight plane [H][W] (wpitch floats between rows), or null
+    float *out;             // the ring slot: [oh][ow]
+    int pitch, wpitch;
+    int r0, c0, oh, ow, by, bx;
+    const unsigned *give_up;
+};
+
+// One pixel per thread, frame_kernel's scalar path at lo = 0, span = 1 (the subtraction and the division are kept: a pixel is
+// the frame recorder's bit for bit); VEC (planar slab, full resolution, every row of the window 16-byte aligned in the array,
+// the weight plane and the slot): four consecutive pixels per thread, one 16-byte load each and one 16-byte store (a block of
+// one cell: MEAN divides by 1.0f, which changes nothing).
+template <bool MEAN, bool VEC>
+__global__ void __launch_bounds__(256) spectrum_sample_kernel(SpecSampleArgs a)
+{
+    if (a.give_up && *a.give_up != 0u) return;                        // (wave-uniform: one scalar load)
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {                                                        // by == bx == 1
+        const size_t ow4 = (size_t)a.ow / 4;
+        if (t >= (size_t)a.oh * ow4) return;
+        const size_t oy = t / ow4, g = t % ow4;
+        const size_t row = (size_t)a.r0 + oy, col = (size_t)a.c0 + 4 * g;
+        const fib_v4f v = *reinterpret_cast<const fib_v4f *>(a.x + row * (size_t)a.pitch + col);
+        fib_v4f p;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) p[e] = frame_cell(v[e], 0.f, 1.f);
+        if (a.w) {
+            const fib_v4f wv = *reinterpret_cast<const fib_v4f *>(a.w + row * (size_t)a.wpitch + col);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) p[e] = p[e] * wv[e];
+        }
+        *reinterpret_cast<fib_v4f *>(a.out + oy * (size_t)a.ow + 4 * g) = p;
+    } else {
+        if (t >= (size_t)a.oh * (size_t)a.ow) return;
+        const size_t oy = t / (size_t)a.ow, ox = t % (size_t)a.ow;
+        const size_t row0 = (size_t)a.r0 + oy * (size_t)a.by, col0 = (size_t)a.c0 + ox * (size_t)a.bx;
+        float pix = 0.f;
+        if (!MEAN) {
+            pix = frame_cell(a.x[row0 * (size_t)a.pitch + col0], 0.f, 1.f);
+            if (a.w) pix = pix * a.w[row0 * (size_t)a.wpitch + col0];
+        } else {
+            const float n_cells = (float)(a.by * a.bx);
+            for (int dy = 0; dy < a.by; ++dy) {
+                const size_t xr = (row0 + (size_t)dy) * (size_t)a.pitch + col0, wr = (row0 + (size_t)dy) * (size_t)a.wpitch + col0;
+                float rs = 0.f;
+                for (int dx = 0; dx < a.bx; ++dx) {
+                    float y = frame_cell(a.x[xr + (size_t)dx], 0.f, 1.f);
+                    if (a.w) y = y * a.w[wr + (size_t)dx];
+                    rs = dx == 0 ? y : rs + y;
+                }
+                pix = dy == 0 ? rs : pix + rs;
+            }
+            pix = pix / n_cells;
+        }
+        a.out[t] = pix;
+    }
+}
+
+// The fold of one chunk: ring slot c holds the sample at segment position j0 + c.  A thread owns one pixel: it reads the pixel's
+// CHUNK ring values once and forms y = x * win[j] once (CHUNK registers, statically indexed: CHUNK is a template parameter),
+// then walks the bins with Re and Im in registers:  Re = Re + y * tw[m][0], Im = Im + y * tw[m][1], m = (k * j) mod N, samples
+// ascending, every operation rounded on its own (-ffp-contract=off).  j, k, m, the window entry and the twiddle pair depend on
+// kernel arguments and loop counters alone: wave-uniform, scalar loads into scalar registers — never a per-lane gather.  m is
+// carried, not divided for: one modulus per bin, then m += k, minus N on overflow (k <= N / 2 <= 32768 and j < N <= 65536: k * j
+// fits 32 bits unsigned).
+// A chunk that starts a segment (j0 == 0) starts Re and Im at +0 without reading them; one that ends a segment (`seg_end`) adds
+// (Re * Re) + (Im * Im) to P and stores +0.  Traffic per pixel: CHUNK * 4 + nb * 16 bytes, plus 8 per bin at a segment end.
+#define SPEC_MAX_BINS 128
+#define SPEC_MAX_CHUNK 32
+template <int CHUNK>
+__global__ void __launch_bounds__(256)
+spectrum_fold_kernel(const float *__restrict__ ring /* [CHUNK][npix] */, float *__restrict__ re_p, float *__restrict__ im_p,
+                     float *__restrict__ P /* [nb][npix] each */, const float *__restrict__ win /* [N] */,
+                     const float2 *__restrict__ tw /* [N] */, const int *__restrict__ bins /* [nb] */, size_t npix, int N, int nb, int j0,
+                     int seg_end, const unsigned *give_up)
+{
+    if (give_up && *give_up != 0u) return;                            // (wave-uniform: one scalar load)
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= npix) return;
+    float y[CHUNK];
+#pragma unroll
+    for (int c = 0; c < CHUNK; ++c) y[c] = ring[(size_t)c * npix + t] * win[j0 + c];
+    const bool fresh = j0 == 0;
+    for (int i = 0; i < nb; ++i) {
+        const unsigned k = (unsigned)bins[i];
+        unsigned m = k * (unsigned)j0 % (unsigned)N;                   // (k <= 32768, j0 < 65536: the product fits 32 bits unsigned)
+        const size_t at = (size_t)i * npix + t;
+        float re = 0.f, im = 0.f;
+        if (!fresh) {
+            re = re_p[at];
+            im = im_p[at];
+        }
+#pragma unroll
+        for (int c = 0; c < CHUNK; ++c) {
+            const float2 w = tw[m];
+            re = re + y[c] * w.x;
+            im = im + y[c] * w.y;
+            m += k;
+            if (m >= (unsigned)N) m -= (unsigned)N;
+        }
+        if (seg_end) {
+            P[at] = P[at] + ((re * re) + (im * im));
+            re = 0.f;
+            im = 0.f;
+        }
+        re_p[at] = re;
+        im_p[at] = im;
+    }
+}
+
+// The peak maps over the bin positions a <= i <= b, one pixel per thread, one pass over P for kpeak, ppeak and pband and a
+// second one over the at most 2 * halfwidth + 1 positions around the peak for pnear (include/fibhip.h has the definition).
+__global__ void __launch_bounds__(256) spectrum_peak_kernel(const float *__restrict__ P, size_t npix, int a, int b, int halfwidth, int have,
+                                                            int *__restrict__ kpeak, float *__restrict__ ppeak, float *__restrict__ pband,
+                                                            float *__restrict__ pnear)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= npix) return;
+    int kp = -1;
+    float best = __builtin_nanf(""), band = 0.f;
+    for (int i = a; i <= b; ++i) {
+        const float p = P[(size_t)i * npix + t];
+        band = i == a ? p : band + p;
+        if (have && (kp < 0 ? p == p : p > best)) {
+            best = p;
+            kp = i;
+        }
+    }
+    float near = __builtin_nanf("");
+    if (kp >= 0) {
+        const int lo = kp - halfwidth > a ? kp - halfwidth : a, hi = kp + halfwidth < b ? kp + halfwidth : b;
+        for (int i = lo; i <= hi; ++i) {
+            const float p = P[(size_t)i * npix + t];
+            near = i == lo ? p : near + p;
+        }
+    }
+    kpeak[t] = kp;
+    ppeak[t] = best;
+    pband[t] = band;
+    pnear[t] = near;
 }

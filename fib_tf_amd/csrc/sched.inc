@@ -48,12 +48,16 @@ static int recover(fibhip_ctx *h, unsigned id)
     h->journal.n_replayed += lost;
     // the samples queued behind the lost launches were taken from a void slab: the replay below (tick_now -> commit_impl)
     // takes them again, into the same slots — the slot is the host's tick counter, so that counter goes back first.  (Every
-    // journal record is younger than the recorder: electrode_begin, tips_begin, frames_begin and stats_begin confirm, and so
+    // journal record is younger than the recorder: electrode_begin, tips_begin, frames_begin, stats_begin and spectrum_begin confirm, and so
     // empty the journal, before they attach.)
     if (h->el.on) h->el.k -= lost;
     if (h->tip.on) h->tip.k -= lost;
     if (h->fr.on) h->fr.k -= lost;
     if (h->st.on) h->st.k -= lost;
+    // ... and the spectrum recorder, the one recorder that accumulates: the samples and the folds queued behind the lost launches
+    // wrote nothing (both kernels leave when they find the give-up word raised), and how far it has sampled and folded follows
+    // from this counter alone — the replay takes the lost samples again and issues the lost folds again, in order
+    if (h->sp.on) h->sp.k -= lost;
     // ... and the stimuli queued behind them wrote nothing (stim_kernel leaves when it finds the give-up word raised): the replay
     // applies the events of the replayed ticks again, and no others — the events of older ticks stand in the restored state
     if (h->stim.on) {
@@ -103,8 +107,8 @@ static int sync_s0(fibhip_ctx *h)
 // traced tick is a plain launch) — and inside the scheduler tick_mt for a launch of one tick and fibhip_step in front of its
 // plain launches.  The entry points that only READ synchronise behind their copy (sync_s0) and take the copy again when a
 // recovery happened in between: fibhip_get_state, fibhip_get_state_direct (both branches of ahead_read_back hand the frame
-// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read, fibhip_frames_read, fibhip_stats_read; fibhip_observe_begin,
-// fibhip_electrode_begin / _end, fibhip_tips_begin / _end, fibhip_frames_begin / _end and fibhip_stats_begin / _end synchronise
+// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read, fibhip_frames_read, fibhip_stats_read, fibhip_spectrum_read / _peak; fibhip_observe_begin,
+// fibhip_electrode_begin / _end, fibhip_tips_begin / _end, fibhip_frames_begin / _end, fibhip_stats_begin / _end and fibhip_spectrum_begin / _end synchronise
 // outright.
 static int confirm(fibhip_ctx *h)
 {
@@ -191,7 +195,9 @@ static const Variant *mt_variant(const fibhip_ctx *h, bool long_declared = false
 //  * activation recorder (h->obs.on): it observes every tick through commit_impl, so nothing fuses ticks — no multi-tick
 //    launches (mt_variant, above, is null: hence no run-ahead and no launched series either), one tick per plain launch (multi_cap);
 //  * the samplers — electrode recorder (h->el.on), tip recorder (h->tip.on), frame recorder (h->fr.on; its counter starts
-//    at every - first, so that its first sample may come early) and statistics recorder (h->st.on), each with a stride of its own: no launch
+//    at every - first, so that its first sample may come early), statistics recorder (h->st.on) and spectrum recorder (h->sp.on; it
+//    never fills up, so it has no term in sampler_full; its sample and its fold stand behind a multi-tick launch unconfirmed and
+//    read the give-up word first, like the stimulus), each with a stride of its own: no launch
 //    spans a sample tick of either (sample_room, the minimum over the attached ones, bounds next_launch_ticks and multi_cap);
 //    nothing runs ahead (may_run_ahead: a launch that runs ahead is handed out tick by tick and may be stopped or recomputed,
 //    so a sample cannot be queued behind it, DESIGN.md section 11); a sample of a SLOW Courtemanche array is taken before
@@ -206,7 +212,7 @@ static const Variant *mt_variant(const fibhip_ctx *h, bool long_declared = false
 //    sample_room, so launches are cut at its samples and nothing runs ahead), whose sample also WRITES the state: sense, decide
 //    and the gated apply come behind the programmed stimuli of the tick, unconfirmed like them (the gated apply reads the
 //    give-up word first); every sample tick comes before the 'slow' behind it (slow_sample_due), whatever arrays it names.
-static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on || h->fr.on || h->st.on || h->trig.on; }
+static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on || h->fr.on || h->st.on || h->sp.on || h->trig.on; }
 // ticks up to and including the next sample tick of one sampler (INT_MAX: not attached)
 static inline int room_of(bool on, int every, long long k) { return on ? every - (int)(k % every) : INT_MAX; }
 // Is entry `e` due right after the n-th tick since attach (n >= 1)?  The events of an entry follow the ticks number
@@ -259,7 +265,7 @@ static inline int sample_room(const fibhip_ctx *h)
 {
     return imin(imin(imin(room_of(h->el.on, h->el.every, h->el.k), room_of(h->tip.on, h->tip.every, h->tip.k)),
                      imin(room_of(h->fr.on, h->fr.every, h->fr.k), room_of(h->st.on, h->st.every, h->st.k))),
-                imin(stim_room(h), room_of(h->trig.on, h->trig.every, h->trig.k)));
+                imin(imin(stim_room(h), room_of(h->trig.on, h->trig.every, h->trig.k)), room_of(h->sp.on, h->sp.every, h->sp.k)));
 }
 // launches are cut at ticks still to come: a launch goes out when the ticks up to the next cut are waiting (fibhip_step)
 static inline bool cutting(const fibhip_ctx *h) { return sampling(h) || stim_room(h) != INT_MAX; }
@@ -304,6 +310,7 @@ static inline bool slow_sample_due(const fibhip_ctx *h)
     if (h->el.on && (h->el.k + h->pending) % h->el.every == 0 && slow(h->el.var)) return true;
     if (h->tip.on && (h->tip.k + h->pending) % h->tip.every == 0 && (slow(h->tip.var) || slow(h->tip.var2))) return true;
     if (h->fr.on && (h->fr.k + h->pending) % h->fr.every == 0 && slow(h->fr.var)) return true;
+    if (h->sp.on && (h->sp.k + h->pending) % h->sp.every == 0 && slow(h->sp.var)) return true;
     if (h->st.on && (h->st.k + h->pending) % h->st.every == 0)
         for (int a = 0; a < h->st.narr; ++a)
             if (slow(h->st.vars[a])) return true;
@@ -453,6 +460,10 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
         if (int rc = frames_advance(h, T)) return rc;
     if (commit && h->st.on)
         if (int rc = stats_advance(h, T)) return rc;
+    // (the spectrum recorder's sample and fold write its own buffers only, but the fold accumulates and the ring is short: both
+    // leave without writing when this launch or one in front of it gave up, and the replay issues them again)
+    if (commit && h->sp.on)
+        if (int rc = spectrum_advance(h, T, true)) return rc;
     // (the stimulus WRITES the state, the slab this launch wrote; it leaves without writing when this launch or one in front
     // of it gave up — so the state the first such launch started from stays intact, as behind a multi-tick launch)
     if (commit && h->stim.on)

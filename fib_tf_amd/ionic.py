@@ -293,6 +293,26 @@ class IonicModel:
             ensure()
         return StatsRecorder(self, columns, every=every, weight=weight, mask=mask, capacity=capacity)
 
+    def record_spectrum(self, every=10, nfft=128, fmin=None, fmax=None, bins=None, window='hann', chunk=None, var=0, block=(1, 1),
+                        reduce='mean', region=None, weight=None):
+        """attaches a spectrum recorder (fib_tf_amd/spectrum.py) to this model's handle: every `every` ticks a pixel plane of
+        state array `var` — the rows and columns `region` = (r0, r1, c0, c1), a `block` = (by, bx) of cells per pixel reduced by
+        `reduce` ('mean' or 'point'), times `weight` ('phase', None or an [height, width] array) — is folded on the device into
+        a per-pixel Welch periodogram: segments of `nfft` samples (no overlap, no detrending) under `window` ('hann': periodic
+        Hann, 'rect', or an array of nfft numbers), at the frequency indices `bins` (at most 128; default: those between `fmin`
+        and `fmax` in Hz, from index 2 — a constant leaks into indices 0 and 1 under the Hann window — to nfft / 2).  `chunk`
+        (a divisor of nfft, at most 32; default: the largest up to 16) is how many samples one fold launch takes and changes
+        no result.  `power()`, `dominant_frequency()` and `peak_maps()` read the maps; nothing else leaves the device.  Call
+        after define(); single device only (row blocks raise NotImplementedError)."""
+        from .spectrum import SpectrumRecorder
+        if not self.defined:
+            raise AssertionError('record_spectrum should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return SpectrumRecorder(self, every=every, nfft=nfft, fmin=fmin, fmax=fmax, bins=bins, window=window, chunk=chunk, var=var,
+                                block=block, reduce=reduce, region=region, weight=weight)
+
     def program_stimuli(self, stimuli):
         """attaches a stimulus program (fib_tf_amd/stimulus.py) to this model's handle: a list of `Stimulus` entries — a site of
         any shape, a value, the tick (or millisecond) of its first event, a period, a count, a hold, 'max' or 'add', any state

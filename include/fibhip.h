@@ -526,6 +526,54 @@ int fibhip_stats_count(fibhip_t h, long long *samples);
 int fibhip_stats_read(fibhip_t h, long long first, long long count, double *dst /* [count][ncols] */);
 int fibhip_stats_end(fibhip_t h);
 
+/* Spectrum recorder: per-cell power spectra (a Welch periodogram) folded on the device while the run goes on, and the
+ * dominant-frequency maps made from them — the sixth recorder and the fifth sampler.  All device arithmetic is float32, every
+ * operation rounded on its own (no contraction), in the order written; no transcendental is evaluated on the device.
+ * Parameters: the watched array `var`; a window rows [r0, r1) x columns [c0, c1), a block (by, bx), each 1 ..
+ * FIBHIP_MAX_FRAME_BLOCK, and a reduction POINT or MEAN — exactly the frame recorder's, with its pixel definition, its
+ * summation order and oh, ow as there, at the fixed levels lo = 0, span = 1: a pixel is the array's own value or block mean —;
+ * an optional weight plane; every >= 1: sample s follows tick (s + 1) * every, ticks counted from 1 at spectrum_begin;
+ * nfft = N, FIBHIP_SPECTRUM_MIN_NFFT .. FIBHIP_SPECTRUM_MAX_NFFT, the segment length in samples; win[N] float32 and tw[N][2]
+ * float32, supplied by the caller (the Python layer fills tw[m] with cos(2 pi m / N) and -sin(2 pi m / N), computed in float64
+ * and then rounded); bins[nb], nb = 1 .. FIBHIP_SPECTRUM_MAX_BINS strictly ascending integers in [0, N / 2]; chunk,
+ * 1 .. FIBHIP_SPECTRUM_MAX_CHUNK with N % chunk == 0.
+ * Fold.  Sample s has position j = s mod N in its segment and pixel value x.  y = x * win[j].  For every bin i with frequency
+ * index k = bins[i], m = (k * j) mod N in integers, and  Re_i = Re_i + y * tw[m][0],  Im_i = Im_i + y * tw[m][1].  Samples are
+ * folded in ascending s; Re and Im start every segment at +0.
+ * Segment end.  After the sample with j = N - 1:  P_i = P_i + ((Re_i * Re_i) + (Im_i * Im_i)), then Re_i = Im_i = +0, then
+ * segments += 1.  P starts at +0 at spectrum_begin.  No overlap, no detrending (with the periodic Hann window a constant leaks
+ * into bins 0 and +-1 only).  The samples of an unfinished segment are part of nothing that can be read.
+ * The result is a pure function of the sampled states: it does not depend on `chunk` (how many samples one fold launch takes)
+ * or on the launch plan.
+ * Peak maps over the bin POSITIONS a <= i <= b (0 <= a <= b < nb), halfwidth >= 0, each [oh][ow]:
+ *   kpeak (int32)  walk i = a .. b: the first P_i that is a number (P_i == P_i) is taken, after that every P_i strictly greater
+ *                  (>) than the one held; kpeak is the position held at the end — the largest P, the lowest position on a tie.
+ *                  -1 when segments == 0 or no P_i is a number
+ *   ppeak          P at that position; NaN where kpeak = -1
+ *   pband          the float32 sum of P_i, i = a .. b ascending, starting from its first term
+ *   pnear          the same sum over max(a, kpeak - halfwidth) .. min(b, kpeak + halfwidth); NaN where kpeak = -1
+ * It may be attached beside every other recorder and both stimulus programs (on a shared tick its sample is taken before that
+ * tick's stimuli); not on a handle with ghost rows or a row-interleaved slab; one at a time.  While attached nothing runs
+ * ahead and no launch spans a sample tick.
+ *   fibhip_spectrum_begin  validates, flushes, synchronises and confirms pending work, copies the tables and attaches
+ *   fibhip_spectrum_count  samples taken and segments finished (ticks accepted but not launched yet included); either may be NULL
+ *   fibhip_spectrum_shape  oh, ow and nb of the attached recorder
+ *   fibhip_spectrum_read   the raw P as [nb][oh][ow] float32 and the segment count; flushes and blocks like get_state
+ *   fibhip_spectrum_peak   the four maps (any may be NULL); flushes and blocks like get_state
+ *   fibhip_spectrum_end    detaches and frees (no recorder attached: nothing); fibhip_destroy does the same                  */
+#define FIBHIP_SPECTRUM_MAX_BINS 128
+#define FIBHIP_SPECTRUM_MAX_CHUNK 32
+#define FIBHIP_SPECTRUM_MIN_NFFT 4
+#define FIBHIP_SPECTRUM_MAX_NFFT 65536
+int fibhip_spectrum_begin(fibhip_t h, int var, const int *window /* r0, r1, c0, c1 */, int by, int bx, int reduce,
+                          const float *weight /* [H*W] or NULL */, int every, int nfft, const float *win /* [nfft] */,
+                          const float *tw /* [nfft][2] */, int nb, const int *bins /* [nb] */, int chunk);
+int fibhip_spectrum_count(fibhip_t h, long long *samples, long long *segments);
+int fibhip_spectrum_shape(fibhip_t h, int *oh, int *ow, int *nb);
+int fibhip_spectrum_read(fibhip_t h, float *P /* [nb][oh][ow] */, long long *segments);
+int fibhip_spectrum_peak(fibhip_t h, int a, int b, int halfwidth, int *kpeak, float *ppeak, float *pband, float *pnear /* [oh][ow] each */);
+int fibhip_spectrum_end(fibhip_t h);
+
 /* Stimulus program: stimuli applied on the device at programmed ticks, from sites of any shape, without a call per stimulus
  * (the reference's only stimulus is add_pace_op / fire_op, fired from the caller's loop body: `if i == s2: fire_op('s2')`;
  * fibhip_pace stands in for it and stays as it is).  A program is 1 .. FIBHIP_MAX_STIM_ENTRIES entries
