@@ -130,12 +130,20 @@ template <class F> FIB_DEV float vzip(float a, float b, F f) { return f(a, b); }
 // constant, or the per-cell 1/(4ϕ) prepared once): q = RN(a*rc); r = a - q*c (exact, one FMA);
 // RN(q + r*rc) is the correctly rounded quotient RN(a/c) (Markstein's theorem) — bit-identical to
 // IEEE division at 3 instructions instead of the ~11 of the generic expansion.  Checked exhaustively
-// over all 2^23 significands for every constant of the three models (tools/ubench/divtest.c);
-// it can differ only when a/c is subnormal (by at most one subnormal ulp).
+// over all 2^23 significands for every constant of the three models (tools/ubench/divtest.c).
+// The proof needs r exact: r is a multiple of ulp(q)*ulp(c), which float32 holds only while that is >= 2^-149, i.e. for
+// |a| >= 2^-102 whatever c is.  Below that r is rounded and the quotient can be one ulp off, although it is a normal
+// number down to |a/c| = 2^-126 (c = -6.8: 1 % of the arguments with |a| in [2^-123, 2^-120]); a subnormal quotient can be
+// one subnormal ulp off as well.  The models' arguments are millivolts and gate values, far above that.  Generated code
+// divides whatever a user's model holds and takes the four-argument form below, which scales a tiny argument first.
+// Outside the finite range ("op contract"): a = +-inf gives NaN (r = -inf*c + inf) where IEEE division gives
+// +-inf, so does a quotient that overflows; a = -0 with c > 0 gives +0.
 // exp and expm1 for the rounding-faithful policy, branch-free.
 //   exp:   v_exp_f32 on x*log2(e) and ONE correction step for the rounding of that product (log2(e) in two terms):
 //          7 instructions against ocml's 18; <= 1 ulp + the instruction's own error (measured on the device,
-//          tools/ubench/acc_rf.hip).  Results below 2^-126 flush to zero.
+//          tools/ubench/acc_rf.hip).  Results below 2^-126 flush to zero.  Outside the finite range ("op
+//          contract"): x > 88.72, +inf and NaN give exp(88.72); x = -inf and finite x < -FLT_MAX/log2(e) = -2.36e38, whose
+//          product x*log2(e) overflows, give NaN (0 * inf in the correction step), not 0.
 //   expm1: no transcendental instruction at all: x = n ln2 + r, expm1(x) = 2^n expm1(r) + (2^n - 1) with the degree-7
 //          Taylor form on |r| <= 0.35; 17 instructions against ocml's 31, <= 0.9 ulp for x < 0 — the only sign a positive
 //          time constant gives rush_larsen — and <= 1.7 ulp for x > 0.
@@ -164,8 +172,9 @@ static FIB_DEV float expm1_rf(float x)
     const float s = __builtin_ldexpf(1.0f, (int)n);
     return __builtin_fmaf(s, q, s - 1.0f);
 }
-// tanh for the rounding-faithful policy: branch-free, <= 1.5 ulp of the true tanh over the whole float32 range,
-// measured on the device (tools/ubench/acc_rf.hip: 22 M arguments per sign; glibc's tanhf: 2.2 ulp, the float32 tanh
+// tanh for the rounding-faithful policy: branch-free, <= 1.6 ulp of the true tanh over the whole float32 range (worst
+// measured on the device: 1.504 ulp at |x| = 0.62927, just above the switch between the two forms; held by
+// tests/test_gpu_traced_ops.py; tools/ubench/acc_rf.hip: 22 M arguments per sign; glibc's tanhf: 2.2 ulp, the float32 tanh
 // TensorFlow's CPU kernels use is a rational approximation of a few ulp too) at ~23 instructions and two
 // transcendental issues, where ocml's tanhf runs both of its divergent branches at ~4x that.
 //   |x| < 0.625:  x + x*z*P(z), z = x^2              (Cephes tanhf's polynomial)
@@ -196,7 +205,8 @@ static FIB_DEV float tanh_rf(float x)
 // relative accuracy a small t had — so tanh's polynomial branch for small arguments (there for the RELATIVE accuracy of tanh
 // alone) and the select between the two branches are dead weight here: 13 instructions instead of 25.  Measured on the device
 // against double precision (tools/ubench/acc_rf.hip, 22 M arguments per sign): see profiles/r04_accuracy_one_plus_tanh.txt —
-// the error of the sum is within that of 1.0f + tanh_rf(x), whose tanh is itself within 1.5 ulp.
+// worst 3.1 x 2^-24 against 1.95 x 2^-24 for 1.0f + tanh_rf(x): NOT the same float32 function as that sum (the two agree for
+// 54-75 % of the arguments), but below the 2^-23 rounding of the state it is added into.
 static FIB_DEV float one_plus_tanh_rf(float x)
 {
     const float y = 2.0f * __builtin_amdgcn_fmed3f(x, -50.0f, 10.0f);   // 1 + tanh rounds to 0 / 2 beyond; keeps e finite and > 0 paths exact
@@ -219,6 +229,7 @@ static FIB_DEV float one_plus_tanh_rf(float x)
 // forms (profiles/r04_fewer_instructions.txt).  (Measured and NOT taken: the twelve sums by Horner's rule, x as one multiply-add —
 // 13 instructions fewer, but the ascending sums are what the reference computes and its rounding errors are what parity is
 // measured against: 4-10 x the distance from the golden trajectories)
+struct any_range {};                              // tag: divc for arguments of any magnitude (generated code)
 struct Exact {
     // a*b + c: the reference rounds the product and the sum separately
     template <class T, class B, class C>
@@ -230,6 +241,20 @@ struct Exact {
         const T q = a * rc;
         const T r = vfma(-q, c, a);
         return vfma(r, rc, q);
+    }
+    // generated code (traced models), 2^-32 <= |c| <= 2^32: the same three instructions, an argument below 2^-60 scaled by
+    // 2^64 first so that the residual stays exact: RN(a/c) wherever that is a normal number, within one subnormal ulp below
+    // (the scaling back rounds a second time there); the same bits as the form above for |a| >= 2^-60
+    template <class T>
+    static FIB_DEV T divc(const T &a, float c, float rc, any_range)
+    {
+        return vmap(a, [c, rc](float x) {
+            const bool tiny = __builtin_fabsf(x) < 0x1p-60f;
+            const float xs = x * (tiny ? 0x1p64f : 1.0f);
+            const float q = xs * rc;
+            const float r = __builtin_fmaf(-q, c, xs);
+            return __builtin_fmaf(r, rc, q) * (tiny ? 0x1p-64f : 1.0f);
+        });
     }
     template <class T>
     static FIB_DEV T tanhv(const T &a) { return vmap(a, [](float x) { return tanh_rf(x); }); }
@@ -261,6 +286,8 @@ struct Fast {
     template <class T> static FIB_DEV T mad3(const T &a, const T &b, const T &c) { return vfma(a, b, c); }
     template <class T>
     static FIB_DEV T divc(const T &a, float, float rc) { return a * rc; }
+    template <class T>
+    static FIB_DEV T divc(const T &a, float, float rc, any_range) { return a * rc; }
     template <class T>
     static FIB_DEV T tanhv(const T &a)
     {   // 1 - 2/(exp(2a)+1), operation-major over the R cells
@@ -299,13 +326,16 @@ struct Fast {
     template <class T> static FIB_DEV T expm1(const T &a) { return exp(a) - 1.0f; }
     template <class T> static FIB_DEV T log(const T &a) { return vmap(a, [](float x) { return __logf(x); }); }
     template <class T> static FIB_DEV T divk(const T &a, float c) { return a * (1.0f / c); }
-    // expm1 for arbitrary user expressions: exp(x)-1 loses everything for |x| << 1, so small arguments take
-    // the cubic Taylor form (relative error < 1e-7 below 0.03)
+    // expm1 for arbitrary user expressions: exp(x)-1 loses everything for |x| << 1, so small arguments take the Taylor
+    // form x + x^2 (1/2 + x/6 + x^2/24), the last step one multiply-add: relative error < 1e-7 below 0.03 (truncation
+    // x^4/120 <= 7e-9, the last rounding 6e-8, what the polynomial's own roundings add is below 0.03 * 2e-7).  (The cubic
+    // x (1 + x/2 + x^2/6) that stood here was 1.1e-6 off at 0.03: its x^4/24 term alone.)
     template <class T> static FIB_DEV T expm1g(const T &a)
     {
         return vmap(a, [](float x) {
             const float big = __expf(x) - 1.0f;
-            const float small = x * __builtin_fmaf(x, __builtin_fmaf(x, 0.16666667f, 0.5f), 1.0f);
+            const float p = __builtin_fmaf(x, __builtin_fmaf(x, 0.041666668f, 0.16666667f), 0.5f);
+            const float small = __builtin_fmaf(x * x, p, x);
             return fabsf(x) < 0.03f ? small : big;
         });
     }

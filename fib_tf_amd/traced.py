@@ -549,9 +549,11 @@ class _Emitter:
             r = self.stmt(special if special else '%s %s %s' % (self.ref(a[0]), _BINOPS[op], self.ref(a[1])))
         elif op == 'div':
             if not isinstance(a[1], Tensor):
-                if divc_is_exact(a[1]):                     # x / c through RN(1/c): 3 instructions, bit-identical
+                # x / c through RN(1/c): 3 instructions (+ the scaling of a tiny x: a user's data may be of any magnitude,
+                # csrc/models.hpp Exact::divc), bit-identical; |c| within 2^+-32 so that the scaled quotient stays finite
+                if 2.0 ** -32 <= abs(a[1]) <= 2.0 ** 32 and divc_is_exact(a[1]):
                     rc = float(np.float32(1.0) / np.float32(a[1]))
-                    r = self.stmt('P::divc(%s, %s, %s)' % (self.ref(a[0]), _lit(a[1]), _lit(rc)))
+                    r = self.stmt('P::divc(%s, %s, %s, any_range())' % (self.ref(a[0]), _lit(a[1]), _lit(rc)))
                 else:
                     r = self.stmt('P::divk(%s, %s)' % (self.ref(a[0]), _lit(a[1])))
             else:
