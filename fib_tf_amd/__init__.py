@@ -15,7 +15,8 @@ from . import tips                              # noqa: F401  (TipRecorder, link
 from . import frames                            # noqa: F401  (FrameRecorder: the movie cube recorded on the device)
 from . import stats                             # noqa: F401  (StatsRecorder: tissue statistics recorded on the device)
 from . import spectrum                          # noqa: F401  (SpectrumRecorder: per-cell power spectra and dominant-frequency maps)
-from . import stimulus                          # noqa: F401  (Stimulus, StimulusProgram: pacing protocols run on the device)
+from . import beats                             # noqa: F401  (BeatRecorder: per-cell beat history, restitution and alternans maps)
+from . import stimulus                        # noqa: F401  (Stimulus, StimulusProgram: pacing protocols run on the device)
 from . import triggers                          # noqa: F401  (Sensor, Trigger, TriggerProgram: triggered stimulation on the device)
 
 __all__ = ['IonicModel', 'Fenton4v', 'BeelerReuter', 'Courtemanche']

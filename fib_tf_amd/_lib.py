@@ -19,6 +19,7 @@ OBS_MAPS = ('first_up', 'last_up', 'prev_up', 'apd', 'count')     # enum fibhip_
 FRAME_REDUCE = ('point', 'mean')                                  # enum fibhip_frame_reduce, in order
 FRAME_FORMAT = ('float32', 'uint8')                               # enum fibhip_frame_format, in order
 SPECTRUM_MAX_BINS, SPECTRUM_MAX_CHUNK, SPECTRUM_MIN_NFFT, SPECTRUM_MAX_NFFT = 128, 32, 4, 65536
+BEATS_MAX_DEPTH = 16
 STAT_KINDS = ('sum', 'min', 'max', 'below', 'above', 'nonfinite')  # enum fibhip_stat_kind, in order
 MAX_STAT_COLS, MAX_STAT_COLS_PER_ARRAY = 64, 8
 STIM_MODES = ('max', 'add')                                       # enum fibhip_stim_mode, in order
@@ -228,6 +229,12 @@ SYMBOLS = {
     'fibhip_spectrum_read': ([_h, _fp, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_spectrum_peak': ([_h, C.c_int, C.c_int, C.c_int, _ip, _fp, _fp, _fp], C.c_int),
     'fibhip_spectrum_end': ([_h], C.c_int),
+    'fibhip_beats_begin': ([_h, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_float, C.c_float, C.c_int], C.c_int),
+    'fibhip_beats_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_beats_shape': ([_h, _ip, _ip, _ip], C.c_int),
+    'fibhip_beats_read': ([_h, _fp, _fp, _fp, _ip, _fp], C.c_int),
+    'fibhip_beats_summary': ([_h, C.c_int, _ip, _fp, _fp, _fp], C.c_int),
+    'fibhip_beats_end': ([_h], C.c_int),
     'fibhip_stim_begin': ([_h, C.c_int, C.POINTER(StimEntry), C.c_int, _fp], C.c_int),
     'fibhip_stim_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_stim_end': ([_h], C.c_int),
@@ -930,6 +937,56 @@ class Stepper:
 
     def spectrum_end(self):
         self._ck(self._L.fibhip_spectrum_end(self._h))
+
+    # ---- beat recorder (include/fibhip.h fibhip_beats_*) -----------------------------------------------------------
+    def beats_begin(self, var=0, window=None, block=(1, 1), reduce='mean', weight=None, every=1, up=0.5, down=0.1, depth=8):
+        """attaches the beat recorder on array `var`: the frame recorder's `window`, `block`, `reduce` and `weight` (levels 0
+        and 1), a sample every `every` ticks, the levels `down` <= `up` and a ring of `depth` (1 .. 16) beats per pixel"""
+        wnd = np.ascontiguousarray((0, self.height, 0, self.width) if window is None else window, np.intc).reshape(4)
+        wp = None
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, np.float32)
+            if weight.shape != (self.height, self.width):
+                raise ValueError('beats_begin: a weight plane of shape %s on a %d x %d grid' % (weight.shape, self.height, self.width))
+            wp = weight.ctypes.data_as(_fp)
+        self._ck(self._L.fibhip_beats_begin(self._h, int(var), wnd.ctypes.data_as(_ip), int(block[0]), int(block[1]),
+                                            FRAME_REDUCE.index(reduce), wp, int(every), float(np.float32(up)), float(np.float32(down)),
+                                            int(depth)))
+
+    def beats_count(self):
+        """samples taken since beats_begin (ticks accepted but not launched yet included)"""
+        s = C.c_longlong()
+        self._ck(self._L.fibhip_beats_count(self._h, C.byref(s)))
+        return int(s.value)
+
+    def beats_shape(self):
+        """(oh, ow, depth) of the attached recorder"""
+        oh, ow, d = C.c_int(), C.c_int(), C.c_int()
+        self._ck(self._L.fibhip_beats_shape(self._h, C.byref(oh), C.byref(ow), C.byref(d)))
+        return int(oh.value), int(ow.value), int(d.value)
+
+    def beats_read(self):
+        """(t_up, t_down, peak float32 [depth, oh, ow] in SLOT order — beat b in slot b % depth —, count int32 [oh, ow], pk
+        float32 [oh, ow]); blocks like get_state"""
+        oh, ow, d = self.beats_shape()
+        tu, td, pe = (np.empty((d, oh, ow), np.float32) for _ in range(3))
+        n = np.empty((oh, ow), np.int32)
+        pk = np.empty((oh, ow), np.float32)
+        self._ck(self._L.fibhip_beats_read(self._h, tu.ctypes.data_as(_fp), td.ctypes.data_as(_fp), pe.ctypes.data_as(_fp),
+                                           n.ctypes.data_as(_ip), pk.ctypes.data_as(_fp)))
+        return tu, td, pe, n, pk
+
+    def beats_summary(self, last):
+        """(nused int32, apd_mean, cl_mean, apd_alt float32), each [oh, ow], over the newest `last` beats"""
+        oh, ow, _ = self.beats_shape()
+        nu = np.empty((oh, ow), np.int32)
+        am, cm, al = (np.empty((oh, ow), np.float32) for _ in range(3))
+        self._ck(self._L.fibhip_beats_summary(self._h, int(last), nu.ctypes.data_as(_ip), am.ctypes.data_as(_fp), cm.ctypes.data_as(_fp),
+                                              al.ctypes.data_as(_fp)))
+        return nu, am, cm, al
+
+    def beats_end(self):
+        self._ck(self._L.fibhip_beats_end(self._h))
 
     # ---- statistics recorder (include/fibhip.h fibhip_stats_*) ----------------------------------------------------
     def stats_begin(self, cols, weight=None, mask=None, every=1, capacity=1):

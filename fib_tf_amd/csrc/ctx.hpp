@@ -204,6 +204,25 @@ struct SpRec {
     size_t npix() const { return (size_t)oh * (size_t)ow; }
 };
 
+// beat recorder (fibhip_beats_begin): the sixth sampler — no launch spans a sample tick (sample_room), and the hook on the plain
+// and the multi-tick commit path (beats_advance) enqueues beat_kernel behind the launch that ends one.  It ACCUMULATES (the
+// count, the open beat's peak, the ring): the kernel reads the give-up word first, and the sample index — with it t0 — follows
+// from `k` alone, so a rewind of `k` leaves nothing behind
+struct BeatRec {
+    bool on;
+    int var, every;
+    int r0, c0, oh, ow, by, bx;     // the window's first cell, the map's shape in pixels, the block
+    int reduce;                     // FIBHIP_FRAME_POINT / _MEAN
+    float up, down;
+    int depth;
+    long long k;            // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
+    float *w;               // device: the weight plane [H][W], or null
+    float *state;           // device: xp | pk | n (int32), each [oh][ow]
+    float *ring;            // device: t_up | t_down | peak, each [depth][oh][ow]
+    float *maps;            // device: nused (int32) | apd_mean | cl_mean | apd_alt, each [oh][ow]
+    size_t npix() const { return (size_t)oh * (size_t)ow; }
+};
+
 // stimulus program (fibhip_stim_begin): the actuator beside the recorders — no launch spans an event tick (stim_room, a term of
 // sample_room), and the hook on the plain and the multi-tick commit path (stim_advance) enqueues stim_kernel behind the launch
 // that ends one, behind the samples of that tick
@@ -310,6 +329,7 @@ struct fibhip_ctx {
     FrRec fr;
     StRec st;
     SpRec sp;
+    BeatRec bt;
     StimRec stim;
     TrigRec trig;
     std::vector<TraceRec> trace;

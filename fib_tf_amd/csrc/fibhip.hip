@@ -33,7 +33,7 @@ using namespace fib;
 #include "ctx.hpp"          // fibhip_ctx and its parts, NEED / FLUSH / CONFIRM / SYNC_S0, the timeline
 #include "tick.inc"         // one tick: pointer tables, rows, edges / interior / commit
 #include "sched.inc"        // when ticks are launched: deferral, multi-tick launches, run-ahead, journal and recovery, fibhip_step
-#include "record.inc"       // activation, electrode, tip, frame, statistics and spectrum recorders; the stimulus program and the trigger program
+#include "record.inc"       // activation, electrode, tip, frame, statistics, spectrum and beat recorders; the stimulus program and the trigger program
 #include "plan.inc"         // build_plan, autotune
 #include "comm.inc"         // the RCCL halo path and fibhip_halo_plan
 // this file: create / destroy, state get / set, pointwise modes, pace / probe / sync / timing, run-time modules, accessors and
@@ -302,6 +302,7 @@ extern "C" int fibhip_destroy(fibhip_t h)
     frames_free(h);
     stats_free(h);
     spectrum_free(h);
+    beats_free(h);
     stim_free(h);
     trig_free(h);
     if (h->mt.xbuf) hipFree(h->mt.xbuf);

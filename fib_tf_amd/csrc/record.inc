@@ -1,6 +1,6 @@
-// record.inc — the six recorders that run on the device while a model runs: the per-cell activation maps
+// record.inc — the seven recorders that run on the device while a model runs: the per-cell activation maps
 // (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
-// (fibhip_frames_*), the tissue statistics (fibhip_stats_*) and the per-cell power spectra (fibhip_spectrum_*) — and the two hooks that write the state: the stimulus program
+// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell beat history (fibhip_beats_*) — and the two hooks that write the state: the stimulus program
 // (fibhip_stim_*) and the trigger program (fibhip_trig_*), which senses, decides and fires on the device.  Each is a hook behind a committed launch plus its entry points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
 // (included by fibhip.hip, behind sched.inc)
 
@@ -309,6 +309,73 @@ static void spectrum_free(fibhip_ctx *h)
     if (r.maps) hipFree(r.maps);
     r.w = r.win = r.tw = r.ring = r.acc = r.maps = nullptr;
     r.bins = nullptr;
+    r.on = false;
+}
+
+static_assert(BEAT_MAX_DEPTH == FIBHIP_BEATS_MAX_DEPTH, "beat_summary_kernel's walk follows include/fibhip.h");
+// beat_kernel over the recorder's map: `init` — the launch of beats_begin, xp = the pixel of the current state; otherwise sample
+// `s` (0-based), whose t0 and step follow from s and the stride alone
+static int beats_launch(fibhip_ctx *h, bool init, long long s, const unsigned *give_up)
+{
+    BeatRec &r = h->bt;
+    const size_t npix = r.npix();
+    BeatArgs a;
+    a.x = h->slab[h->cur[r.var]] + (size_t)r.var * h->vstride;
+    a.w = r.w;
+    a.xp = r.state;
+    a.pk = r.state + npix;
+    a.n = reinterpret_cast<int *>(r.state + 2 * npix);
+    a.t_up = r.ring;
+    a.t_down = r.ring + (size_t)r.depth * npix;
+    a.peak = r.ring + 2 * (size_t)r.depth * npix;
+    a.pitch = h->pitch;
+    a.wpitch = h->d.width;
+    a.r0 = r.r0; a.c0 = r.c0; a.oh = r.oh; a.ow = r.ow; a.by = r.by; a.bx = r.bx;
+    a.depth = r.depth;
+    a.init = init ? 1 : 0;
+    a.up = r.up;
+    a.down = r.down;
+    a.step = (float)((double)r.every * h->d.dt * h->spt);
+    a.t0 = (float)((double)(s * r.every) * h->d.dt * h->spt);
+    a.give_up = give_up;
+    const bool mean = r.reduce == FIBHIP_FRAME_MEAN;
+    // (the recorder's planes come from hipMalloc and npix is a multiple of 4 here: xp, pk and every row of them are aligned)
+    const bool vec = r.by == 1 && r.bx == 1 && h->pitch == h->d.width && h->d.width % 4 == 0 && r.c0 % 4 == 0 && r.ow % 4 == 0 &&
+                     ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.w) | reinterpret_cast<uintptr_t>(a.xp) |
+                       reinterpret_cast<uintptr_t>(a.pk)) & 15u) == 0;
+    const size_t threads = (size_t)r.oh * (size_t)(vec ? r.ow / 4 : r.ow);
+    const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+    // (the timeline event's K says which path ran: the pixels per thread, 4 on the vector path and 1 on the scalar one)
+    if (int rc = trace_open(h, h->s0, "beat_kernel", vec ? 4 : 1, 0, 0, 0, 1)) return rc;
+    if (vec) hipLaunchKernelGGL((beat_kernel<false, true>), grid, block, 0, h->s0, a);
+    else if (mean) hipLaunchKernelGGL((beat_kernel<true, false>), grid, block, 0, h->s0, a);
+    else hipLaunchKernelGGL((beat_kernel<false, false>), grid, block, 0, h->s0, a);
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    return 0;
+}
+
+// The beat recorder's hook behind a launch of `ticks` ticks, the spectrum recorder's step for step: at a sample tick beat_kernel
+// compares the pixel plane with the previous sample's and records the events.  `behind_mt`: as for spectrum_advance — the kernel
+// is handed the give-up word and writes nothing once a launch in front of it gave up; recover() rewinds the counter and the
+// replay comes through here again, with the same sample index.
+static int beats_advance(fibhip_ctx *h, int ticks, bool behind_mt)
+{
+    BeatRec &r = h->bt;
+    r.k += ticks;
+    if (r.k % r.every) return 0;
+    return beats_launch(h, false, r.k / r.every - 1, behind_mt && h->mt.epochs ? h->mt.give_up_word() : nullptr);
+}
+
+static void beats_free(fibhip_ctx *h)
+{
+    BeatRec &r = h->bt;
+    if (r.w) hipFree(r.w);
+    if (r.state) hipFree(r.state);
+    if (r.ring) hipFree(r.ring);
+    if (r.maps) hipFree(r.maps);
+    r.w = r.state = r.ring = r.maps = nullptr;
     r.on = false;
 }
 
@@ -1202,6 +1269,146 @@ extern "C" int fibhip_spectrum_end(fibhip_t h)
     FLUSH(h);                                          // the ticks accepted while attached are sampled
     SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
     spectrum_free(h);
+    return 0;
+}
+
+// ---- beat recorder ------------------------------------------------------------------------------------------------------
+extern "C" int fibhip_beats_begin(fibhip_t h, int var, const int *window, int by, int bx, int reduce, const float *weight, int every,
+                                  float up, float down, int depth)
+{
+    NEED(h);
+    if (!window) return fail(FIBHIP_EINVAL, "beats_begin: null argument");
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "beats_begin: bad var %d", var);
+    const int r0 = window[0], r1 = window[1], c0 = window[2], c1 = window[3];
+    if (r0 < 0 || r1 > h->d.height || c0 < 0 || c1 > h->d.width || r0 >= r1 || c0 >= c1)
+        return fail(FIBHIP_EINVAL, "beats_begin: the window rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", r0, r1, c0,
+                    c1, h->d.height, h->d.width);
+    if (by < 1 || by > FIBHIP_MAX_FRAME_BLOCK || bx < 1 || bx > FIBHIP_MAX_FRAME_BLOCK)
+        return fail(FIBHIP_EINVAL, "beats_begin: a block is 1 .. %d cells each way (got %d x %d)", FIBHIP_MAX_FRAME_BLOCK, by, bx);
+    const int oh = (r1 - r0) / by, ow = (c1 - c0) / bx;
+    if (oh < 1 || ow < 1)
+        return fail(FIBHIP_EINVAL, "beats_begin: a window of %d x %d cells holds no block of %d x %d", r1 - r0, c1 - c0, by, bx);
+    if (reduce != FIBHIP_FRAME_POINT && reduce != FIBHIP_FRAME_MEAN) return fail(FIBHIP_EINVAL, "beats_begin: bad reduction %d", reduce);
+    if (every < 1) return fail(FIBHIP_EINVAL, "beats_begin: every must be >= 1 (got %d)", every);
+    if (!(down <= up)) return fail(FIBHIP_EINVAL, "beats_begin: the levels must be numbers with down <= up (got down %g, up %g)", (double)down, (double)up);
+    if (depth < 1 || depth > FIBHIP_BEATS_MAX_DEPTH)
+        return fail(FIBHIP_EINVAL, "beats_begin: depth must be 1 .. %d (got %d)", FIBHIP_BEATS_MAX_DEPTH, depth);
+    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "beats_begin: not on a row block (a handle with ghost rows)");
+    if (h->pitch != h->d.width) return fail(FIBHIP_EINVAL, "beats_begin: not on a row-interleaved slab");
+    if (h->bt.on) return fail(FIBHIP_EINVAL, "beats_begin: a recorder is attached already (fibhip_beats_end first)");
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "beats_begin inside an open tick");
+    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick 0 and the first xp are defined (the rule of fibhip_electrode_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    beats_free(h);
+    BeatRec &r = h->bt;
+    const size_t npix = (size_t)oh * (size_t)ow;
+    bool ok = hipMalloc((void **)&r.state, 3 * npix * sizeof(float)) == hipSuccess;
+    ok = ok && hipMalloc((void **)&r.ring, 3 * (size_t)depth * npix * sizeof(float)) == hipSuccess;
+    ok = ok && hipMalloc((void **)&r.maps, 4 * npix * sizeof(float)) == hipSuccess;
+    if (ok && weight) ok = hipMalloc((void **)&r.w, h->cells * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        beats_free(h);
+        return fail(FIBHIP_ENOMEM, "beats_begin: hipMalloc failed (a ring of %d beats of %d x %d pixels)", depth, oh, ow);
+    }
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    unsigned nan_bits;
+    memcpy(&nan_bits, &qnan, sizeof nan_bits);
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(r.state + npix), (int)nan_bits, npix, h->s0));                  // pk = NaN
+    HIPCHK(hipMemsetAsync(r.state + 2 * npix, 0, npix * sizeof(int), h->s0));                                // n = 0
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)r.ring, (int)nan_bits, 3 * (size_t)depth * npix, h->s0));       // t_up = t_down = peak = NaN
+    if (weight) HIPCHK(hipMemcpyAsync(r.w, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    r.var = var;
+    r.every = every;
+    r.r0 = r0; r.c0 = c0; r.oh = oh; r.ow = ow; r.by = by; r.bx = bx;
+    r.reduce = reduce;
+    r.up = up; r.down = down;
+    r.depth = depth;
+    r.k = 0;                                           // sample s follows tick (s + 1) * every, ticks counted from 1 here
+    if (int rc = beats_launch(h, true, 0, nullptr)) {  // xp = the pixel of the current state (confirmed above: nothing to gate on)
+        beats_free(h);
+        return rc;
+    }
+    HIPCHK(wait_stream(h->s0));                        // the caller's weight plane is free again
+    r.on = true;
+    return 0;
+}
+
+extern "C" int fibhip_beats_count(fibhip_t h, long long *samples)
+{
+    NEED(h);
+    if (!h->bt.on) return fail(FIBHIP_EINVAL, "beats_count: no recorder attached (fibhip_beats_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    if (samples) *samples = (h->bt.k + h->pending) / h->bt.every;    // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+
+extern "C" int fibhip_beats_shape(fibhip_t h, int *oh, int *ow, int *depth)
+{
+    if (!h) return fail(FIBHIP_EINVAL, "null handle");
+    if (!h->bt.on) return fail(FIBHIP_EINVAL, "beats_shape: no recorder attached (fibhip_beats_begin)");
+    if (oh) *oh = h->bt.oh;
+    if (ow) *ow = h->bt.ow;
+    if (depth) *depth = h->bt.depth;
+    return 0;
+}
+
+extern "C" int fibhip_beats_read(fibhip_t h, float *t_up, float *t_down, float *peak, int *count, float *pk)
+{
+    NEED(h);
+    if (!h->bt.on) return fail(FIBHIP_EINVAL, "beats_read: no recorder attached (fibhip_beats_begin)");
+    FLUSH(h);
+    const BeatRec &r = h->bt;
+    const size_t npix = r.npix(), plane = (size_t)r.depth * npix;
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->journal.n_fallbacks;
+        if (t_up) HIPCHK(hipMemcpyAsync(t_up, r.ring, plane * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        if (t_down) HIPCHK(hipMemcpyAsync(t_down, r.ring + plane, plane * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        if (peak) HIPCHK(hipMemcpyAsync(peak, r.ring + 2 * plane, plane * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        if (count) HIPCHK(hipMemcpyAsync(count, r.state + 2 * npix, npix * sizeof(int), hipMemcpyDeviceToHost, h->s0));
+        if (pk) HIPCHK(hipMemcpyAsync(pk, r.state + npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        SYNC_S0(h);
+        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and sampled again, copy again)
+    }
+    return 0;
+}
+
+extern "C" int fibhip_beats_summary(fibhip_t h, int last, int *nused, float *apd_mean, float *cl_mean, float *apd_alt)
+{
+    NEED(h);
+    if (!h->bt.on) return fail(FIBHIP_EINVAL, "beats_summary: no recorder attached (fibhip_beats_begin)");
+    const BeatRec &r = h->bt;
+    if (last < 1 || last > r.depth) return fail(FIBHIP_EINVAL, "beats_summary: last must be 1 .. depth = %d (got %d)", r.depth, last);
+    FLUSH(h);
+    const size_t npix = r.npix(), plane = (size_t)r.depth * npix;
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->journal.n_fallbacks;
+        if (int rc = trace_open(h, h->s0, "beat_summary_kernel", 0, 0, 0, 0, 1)) return rc;
+        hipLaunchKernelGGL(beat_summary_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->s0,
+                           reinterpret_cast<const int *>(r.state + 2 * npix), (const float *)r.ring, (const float *)(r.ring + plane), npix, r.depth,
+                           last, reinterpret_cast<int *>(r.maps), r.maps + npix, r.maps + 2 * npix, r.maps + 3 * npix);
+        HIPCHK(hipGetLastError());
+        if (int rc = trace_close(h, h->s0)) return rc;
+        h->launches++;
+        if (nused) HIPCHK(hipMemcpyAsync(nused, r.maps, npix * sizeof(int), hipMemcpyDeviceToHost, h->s0));
+        if (apd_mean) HIPCHK(hipMemcpyAsync(apd_mean, r.maps + npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        if (cl_mean) HIPCHK(hipMemcpyAsync(cl_mean, r.maps + 2 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        if (apd_alt) HIPCHK(hipMemcpyAsync(apd_alt, r.maps + 3 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        SYNC_S0(h);
+        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front had given up: recovered and sampled again, the maps again)
+    }
+    return 0;
+}
+
+extern "C" int fibhip_beats_end(fibhip_t h)
+{
+    NEED(h);
+    if (!h->bt.on) return 0;
+    FLUSH(h);                                          // the ticks accepted while attached are sampled
+    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
+    beats_free(h);
     return 0;
 }
 

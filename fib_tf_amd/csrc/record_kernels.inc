@@ -1,4 +1,4 @@
-// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame, statistics and spectrum recorders, and the
+// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame, statistics, spectrum and beat recorders, and the
 // plain copy whose shape they take (the bandwidth yardstick).  (included by kernels.hpp; the host side is record.inc)
 
 // ---- activation recorder (fibhip_observe_begin): per-cell event maps, updated after every observed tick ----------------
@@ -1058,4 +1058,173 @@ __global__ void __launch_bounds__(256) spectrum_peak_kernel(const float *__restr
     ppeak[t] = best;
     pband[t] = band;
     pnear[t] = near;
+}
+
+// ---- beat recorder (fibhip_beats_begin): a per-pixel history of the last `depth` beats ------------------------------------------
+// Two kernels.  beat_kernel, behind a sample tick, forms the pixel xc — the frame recorder's pixel at lo = 0, span = 1, the one
+// spectrum_sample_kernel takes — and compares it with the pixel of the previous sample, xp (the recorder's own plane):
+//   upstroke   xp < up && xc >= up:                 a beat still open (pk a number) leaves peak[(n - 1) % depth] = pk; then
+//                                                   t = t0 + ((up - xp) / (xc - xp)) * step; slot n % depth gets t_up = t,
+//                                                   t_down = NaN, peak = NaN; pk = xc; n += 1
+//   downstroke xp >= down && xc < down, pk a number: t = t0 + ((xp - down) / (xp - xc)) * step; slot (n - 1) % depth gets
+//                                                   t_down = t, peak = pk; pk = NaN
+//   otherwise, pk a number:                         pk = xc > pk ? xc : pk
+// and then xp = xc.  float32, every operation rounded on its own (-ffp-contract=off, IEEE division); NaN compares false: no
+// event, and pk stays.  The ring planes t_up, t_down, peak are [depth][oh * ow] and touched only where an event happens; the slot
+// is formed per lane inside the event branches.  The steady traffic at full resolution is x read, xp and pk read and written:
+// 20 bytes per pixel.  beat_summary_kernel makes the four summary maps from the ring on demand.  No LDS, no atomics.
+// The recorder accumulates (n, pk, the ring), so beat_kernel reads the give-up word of the multi-tick launches first (`give_up`,
+// null behind plain ticks: stim_kernel's note) and writes NOTHING when it is raised, like spectrum_sample_kernel: recover()
+// rewinds the host's tick counter and the replay takes the lost samples again, in order, from good state.
+#define BEAT_MAX_DEPTH 16
+struct BeatArgs {
+    const float *x;         // the watched array (its first row), `pitch` floats between rows
+    const float *w;         // the weight plane [H][W] (wpitch floats between rows), or null
+    float *xp, *pk;         // [oh * ow] each
+    int *n;                 // [oh * ow]
+    float *t_up, *t_down, *peak;    // [depth][oh * ow] each
+    int pitch, wpitch;
+    int r0, c0, oh, ow, by, bx;
+    int depth;
+    int init;               // 1: the launch of beats_begin — xp = the pixel of the current state, nothing else
+    float up, down, t0, step;
+    const unsigned *give_up;
+};
+
+// the events of pixel i; returns the new pk
+static FIB_DEV float beat_events(float xp, float xc, float pk, size_t i, const BeatArgs &a)
+{
+    const bool open = pk == pk;
+    const size_t npix = (size_t)a.oh * (size_t)a.ow;
+    if (xp < a.up && xc >= a.up) {
+        const int n = a.n[i];
+        if (open) a.peak[(size_t)((n - 1) % a.depth) * npix + i] = pk;        // (open: n >= 1)
+        const float t = a.t0 + ((a.up - xp) / (xc - xp)) * a.step;
+        const size_t at = (size_t)(n % a.depth) * npix + i;
+        a.t_up[at] = t;
+        a.t_down[at] = __builtin_nanf("");
+        a.peak[at] = __builtin_nanf("");
+        a.n[i] = n + 1;
+        return xc;
+    }
+    if (xp >= a.down && xc < a.down && open) {
+        const float t = a.t0 + ((xp - a.down) / (xp - xc)) * a.step;
+        const size_t at = (size_t)((a.n[i] - 1) % a.depth) * npix + i;
+        a.t_down[at] = t;
+        a.peak[at] = pk;
+        return __builtin_nanf("");
+    }
+    if (open) return xc > pk ? xc : pk;
+    return pk;
+}
+
+// One pixel per thread, frame_kernel's scalar path at lo = 0, span = 1 (the subtraction and the division are kept: a pixel is
+// the frame recorder's bit for bit); VEC (planar slab, full resolution, every row of the window 16-byte aligned in the array,
+// the weight plane and the recorder's planes): four consecutive pixels per thread — x, xp and pk one 16-byte load each, xp and
+// pk one 16-byte store each —, the events per lane behind that, as in observe_kernel (a block of one cell: MEAN divides by
+// 1.0f, which changes nothing).
+template <bool MEAN, bool VEC>
+__global__ void __launch_bounds__(256) beat_kernel(BeatArgs a)
+{
+    if (a.give_up && *a.give_up != 0u) return;                        // (wave-uniform: one scalar load)
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {                                                        // by == bx == 1
+        const size_t ow4 = (size_t)a.ow / 4;
+        if (t >= (size_t)a.oh * ow4) return;
+        const size_t oy = t / ow4, g = t % ow4;
+        const size_t row = (size_t)a.r0 + oy, col = (size_t)a.c0 + 4 * g;
+        const fib_v4f v = *reinterpret_cast<const fib_v4f *>(a.x + row * (size_t)a.pitch + col);
+        fib_v4f xc;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xc[e] = frame_cell(v[e], 0.f, 1.f);
+        if (a.w) {
+            const fib_v4f wv = *reinterpret_cast<const fib_v4f *>(a.w + row * (size_t)a.wpitch + col);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xc[e] = xc[e] * wv[e];
+        }
+        const size_t i0 = oy * (size_t)a.ow + 4 * g;
+        if (a.init) {
+            *reinterpret_cast<fib_v4f *>(a.xp + i0) = xc;
+            return;
+        }
+        const fib_v4f xp = *reinterpret_cast<const fib_v4f *>(a.xp + i0);
+        fib_v4f pk = *reinterpret_cast<const fib_v4f *>(a.pk + i0);
+        *reinterpret_cast<fib_v4f *>(a.xp + i0) = xc;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pk[e] = beat_events(xp[e], xc[e], pk[e], i0 + (size_t)e, a);
+        *reinterpret_cast<fib_v4f *>(a.pk + i0) = pk;
+    } else {
+        if (t >= (size_t)a.oh * (size_t)a.ow) return;
+        const size_t oy = t / (size_t)a.ow, ox = t % (size_t)a.ow;
+        const size_t row0 = (size_t)a.r0 + oy * (size_t)a.by, col0 = (size_t)a.c0 + ox * (size_t)a.bx;
+        float xc = 0.f;
+        if (!MEAN) {
+            xc = frame_cell(a.x[row0 * (size_t)a.pitch + col0], 0.f, 1.f);
+            if (a.w) xc = xc * a.w[row0 * (size_t)a.wpitch + col0];
+        } else {
+            const float n_cells = (float)(a.by * a.bx);
+            for (int dy = 0; dy < a.by; ++dy) {
+                const size_t xr = (row0 + (size_t)dy) * (size_t)a.pitch + col0, wr = (row0 + (size_t)dy) * (size_t)a.wpitch + col0;
+                float rs = 0.f;
+                for (int dx = 0; dx < a.bx; ++dx) {
+                    float y = frame_cell(a.x[xr + (size_t)dx], 0.f, 1.f);
+                    if (a.w) y = y * a.w[wr + (size_t)dx];
+                    rs = dx == 0 ? y : rs + y;
+                }
+                xc = dy == 0 ? rs : xc + rs;
+            }
+            xc = xc / n_cells;
+        }
+        if (a.init) {
+            a.xp[t] = xc;
+            return;
+        }
+        const float xp = a.xp[t];
+        a.xp[t] = xc;
+        a.pk[t] = beat_events(xp, xc, a.pk[t], t, a);
+    }
+}
+
+// The summary maps of the newest `last` beats, one pixel per thread (include/fibhip.h has the definition): a walk over the beats
+// b0 .. n - 1 for nused, apd_mean and apd_alt, a second one for cl_mean; at most BEAT_MAX_DEPTH ring entries each.
+__global__ void __launch_bounds__(256)
+beat_summary_kernel(const int *__restrict__ count, const float *__restrict__ t_up, const float *__restrict__ t_down, size_t npix, int depth,
+                    int last, int *__restrict__ nused, float *__restrict__ apd_mean, float *__restrict__ cl_mean, float *__restrict__ apd_alt)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= npix) return;
+    const int n = count[t];
+    const int held = n < depth ? n : depth;
+    int b0 = n - held > n - last ? n - held : n - last;
+    if (b0 < 0) b0 = 0;
+    int used = 0, pairs = 0;
+    float sum = 0.f, alt = 0.f, before = __builtin_nanf("");          // `before`: the APD of beat b - 1 (NaN: none in the walk)
+    for (int b = b0; b < n; ++b) {
+        const size_t at = (size_t)(b % depth) * npix + t;
+        const float apd = t_down[at] - t_up[at];
+        if (apd == apd) {
+            sum = used == 0 ? apd : sum + apd;
+            used++;
+            if (before == before) {
+                const float d = apd - before;
+                const float term = (b & 1) ? d : -d;
+                alt = pairs == 0 ? term : alt + term;
+                pairs++;
+            }
+        }
+        before = apd;
+    }
+    int ncl = 0;
+    float cls = 0.f;
+    for (int b = b0 + 1; b < n; ++b) {
+        const float cl = t_up[(size_t)(b % depth) * npix + t] - t_up[(size_t)((b - 1) % depth) * npix + t];
+        if (cl == cl) {
+            cls = ncl == 0 ? cl : cls + cl;
+            ncl++;
+        }
+    }
+    nused[t] = used;
+    apd_mean[t] = used ? sum / (float)used : __builtin_nanf("");
+    cl_mean[t] = ncl ? cls / (float)ncl : __builtin_nanf("");
+    apd_alt[t] = pairs ? alt / (float)pairs : __builtin_nanf("");
 }

@@ -48,7 +48,7 @@ static int recover(fibhip_ctx *h, unsigned id)
     h->journal.n_replayed += lost;
     // the samples queued behind the lost launches were taken from a void slab: the replay below (tick_now -> commit_impl)
     // takes them again, into the same slots — the slot is the host's tick counter, so that counter goes back first.  (Every
-    // journal record is younger than the recorder: electrode_begin, tips_begin, frames_begin, stats_begin and spectrum_begin confirm, and so
+    // journal record is younger than the recorder: electrode_begin, tips_begin, frames_begin, stats_begin, spectrum_begin and beats_begin confirm, and so
     // empty the journal, before they attach.)
     if (h->el.on) h->el.k -= lost;
     if (h->tip.on) h->tip.k -= lost;
@@ -58,6 +58,9 @@ static int recover(fibhip_ctx *h, unsigned id)
     // wrote nothing (both kernels leave when they find the give-up word raised), and how far it has sampled and folded follows
     // from this counter alone — the replay takes the lost samples again and issues the lost folds again, in order
     if (h->sp.on) h->sp.k -= lost;
+    // ... and the beat recorder, which accumulates too (the count, the open beat's peak, the ring): beat_kernel behind the lost
+    // launches wrote nothing, and the sample index — with it t0 — is a function of this counter alone
+    if (h->bt.on) h->bt.k -= lost;
     // ... and the stimuli queued behind them wrote nothing (stim_kernel leaves when it finds the give-up word raised): the replay
     // applies the events of the replayed ticks again, and no others — the events of older ticks stand in the restored state
     if (h->stim.on) {
@@ -107,8 +110,8 @@ static int sync_s0(fibhip_ctx *h)
 // traced tick is a plain launch) — and inside the scheduler tick_mt for a launch of one tick and fibhip_step in front of its
 // plain launches.  The entry points that only READ synchronise behind their copy (sync_s0) and take the copy again when a
 // recovery happened in between: fibhip_get_state, fibhip_get_state_direct (both branches of ahead_read_back hand the frame
-// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read, fibhip_frames_read, fibhip_stats_read, fibhip_spectrum_read / _peak; fibhip_observe_begin,
-// fibhip_electrode_begin / _end, fibhip_tips_begin / _end, fibhip_frames_begin / _end, fibhip_stats_begin / _end and fibhip_spectrum_begin / _end synchronise
+// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read, fibhip_frames_read, fibhip_stats_read, fibhip_spectrum_read / _peak, fibhip_beats_read / _summary; fibhip_observe_begin,
+// fibhip_electrode_begin / _end, fibhip_tips_begin / _end, fibhip_frames_begin / _end, fibhip_stats_begin / _end, fibhip_spectrum_begin / _end and fibhip_beats_begin / _end synchronise
 // outright.
 static int confirm(fibhip_ctx *h)
 {
@@ -195,9 +198,11 @@ static const Variant *mt_variant(const fibhip_ctx *h, bool long_declared = false
 //  * activation recorder (h->obs.on): it observes every tick through commit_impl, so nothing fuses ticks — no multi-tick
 //    launches (mt_variant, above, is null: hence no run-ahead and no launched series either), one tick per plain launch (multi_cap);
 //  * the samplers — electrode recorder (h->el.on), tip recorder (h->tip.on), frame recorder (h->fr.on; its counter starts
-//    at every - first, so that its first sample may come early), statistics recorder (h->st.on) and spectrum recorder (h->sp.on; it
+//    at every - first, so that its first sample may come early), statistics recorder (h->st.on), spectrum recorder (h->sp.on; it
 //    never fills up, so it has no term in sampler_full; its sample and its fold stand behind a multi-tick launch unconfirmed and
-//    read the give-up word first, like the stimulus), each with a stride of its own: no launch
+//    read the give-up word first, like the stimulus) and beat recorder (h->bt.on; a ring never fills either: no term in
+//    sampler_full; its sample stands behind a multi-tick launch unconfirmed and reads the give-up word first; on a shared tick
+//    it is taken behind the other samplers' and before the stimuli), each with a stride of its own: no launch
 //    spans a sample tick of either (sample_room, the minimum over the attached ones, bounds next_launch_ticks and multi_cap);
 //    nothing runs ahead (may_run_ahead: a launch that runs ahead is handed out tick by tick and may be stopped or recomputed,
 //    so a sample cannot be queued behind it, DESIGN.md section 11); a sample of a SLOW Courtemanche array is taken before
@@ -212,7 +217,7 @@ static const Variant *mt_variant(const fibhip_ctx *h, bool long_declared = false
 //    sample_room, so launches are cut at its samples and nothing runs ahead), whose sample also WRITES the state: sense, decide
 //    and the gated apply come behind the programmed stimuli of the tick, unconfirmed like them (the gated apply reads the
 //    give-up word first); every sample tick comes before the 'slow' behind it (slow_sample_due), whatever arrays it names.
-static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on || h->fr.on || h->st.on || h->sp.on || h->trig.on; }
+static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on || h->fr.on || h->st.on || h->sp.on || h->bt.on || h->trig.on; }
 // ticks up to and including the next sample tick of one sampler (INT_MAX: not attached)
 static inline int room_of(bool on, int every, long long k) { return on ? every - (int)(k % every) : INT_MAX; }
 // Is entry `e` due right after the n-th tick since attach (n >= 1)?  The events of an entry follow the ticks number
@@ -265,7 +270,8 @@ static inline int sample_room(const fibhip_ctx *h)
 {
     return imin(imin(imin(room_of(h->el.on, h->el.every, h->el.k), room_of(h->tip.on, h->tip.every, h->tip.k)),
                      imin(room_of(h->fr.on, h->fr.every, h->fr.k), room_of(h->st.on, h->st.every, h->st.k))),
-                imin(imin(stim_room(h), room_of(h->trig.on, h->trig.every, h->trig.k)), room_of(h->sp.on, h->sp.every, h->sp.k)));
+                imin(imin(stim_room(h), room_of(h->trig.on, h->trig.every, h->trig.k)),
+                     imin(room_of(h->sp.on, h->sp.every, h->sp.k), room_of(h->bt.on, h->bt.every, h->bt.k))));
 }
 // launches are cut at ticks still to come: a launch goes out when the ticks up to the next cut are waiting (fibhip_step)
 static inline bool cutting(const fibhip_ctx *h) { return sampling(h) || stim_room(h) != INT_MAX; }
@@ -311,6 +317,7 @@ static inline bool slow_sample_due(const fibhip_ctx *h)
     if (h->tip.on && (h->tip.k + h->pending) % h->tip.every == 0 && (slow(h->tip.var) || slow(h->tip.var2))) return true;
     if (h->fr.on && (h->fr.k + h->pending) % h->fr.every == 0 && slow(h->fr.var)) return true;
     if (h->sp.on && (h->sp.k + h->pending) % h->sp.every == 0 && slow(h->sp.var)) return true;
+    if (h->bt.on && (h->bt.k + h->pending) % h->bt.every == 0 && slow(h->bt.var)) return true;
     if (h->st.on && (h->st.k + h->pending) % h->st.every == 0)
         for (int a = 0; a < h->st.narr; ++a)
             if (slow(h->st.vars[a])) return true;
@@ -464,6 +471,9 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
     // leave without writing when this launch or one in front of it gave up, and the replay issues them again)
     if (commit && h->sp.on)
         if (int rc = spectrum_advance(h, T, true)) return rc;
+    // (the beat recorder's sample accumulates too: gated in the same way)
+    if (commit && h->bt.on)
+        if (int rc = beats_advance(h, T, true)) return rc;
     // (the stimulus WRITES the state, the slab this launch wrote; it leaves without writing when this launch or one in front
     // of it gave up — so the state the first such launch started from stays intact, as behind a multi-tick launch)
     if (commit && h->stim.on)

@@ -10,6 +10,7 @@ static int tips_advance(fibhip_ctx *h, int ticks);
 static int frames_advance(fibhip_ctx *h, int ticks);
 static int stats_advance(fibhip_ctx *h, int ticks);
 static int spectrum_advance(fibhip_ctx *h, int ticks, bool behind_mt);
+static int beats_advance(fibhip_ctx *h, int ticks, bool behind_mt);
 static int stim_advance(fibhip_ctx *h, int ticks, bool behind_mt);       // ... and the stimulus program's, behind them
 static int trig_advance(fibhip_ctx *h, int ticks, bool behind_mt);       // ... and the trigger program's, last: it senses what the stimulus left
 
@@ -288,6 +289,8 @@ static int commit_impl(fibhip_t h)
         if (int rc = stats_advance(h, ticks)) return rc;
     if (h->sp.on)
         if (int rc = spectrum_advance(h, ticks, false)) return rc;
+    if (h->bt.on)
+        if (int rc = beats_advance(h, ticks, false)) return rc;
     // the stimulus comes last: the recorders saw the state as the tick left it, the stimulus belongs to the next tick
     // (a plain tick never stands behind an unconfirmed multi-tick launch — tick_mt, fibhip_step and recover() confirm first — so
     // its stimulus has no give-up word to look at)

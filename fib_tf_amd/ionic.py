@@ -313,6 +313,25 @@ class IonicModel:
         return SpectrumRecorder(self, every=every, nfft=nfft, fmin=fmin, fmax=fmax, bins=bins, window=window, chunk=chunk, var=var,
                                 block=block, reduce=reduce, region=region, weight=weight)
 
+    def record_beats(self, every=10, depth=8, up=None, down=None, var=0, region=None, block=(1, 1), reduce='mean', weight=None):
+        """attaches a beat recorder (fib_tf_amd/beats.py) to this model's handle: every `every` ticks a pixel plane of state
+        array `var` — the rows and columns `region` = (r0, r1, c0, c1), a `block` = (by, bx) of cells per pixel reduced by
+        `reduce` ('mean' or 'point'), times `weight` ('phase', None or an [height, width] array) — is compared on the device
+        with the plane of the previous sample, and every pixel keeps its last `depth` (1 .. 16) beats: the time of the
+        upstroke through `up`, of the downstroke through `down` (default: 50 % and 10 % of [min_v, max_v], the activation
+        recorder's levels, for var = 0) and the peak in between.  `beats()`, `apd()`, `di()`, `cl()` and `restitution()` read
+        the ring, `summary(last)` the maps the device makes of it (mean APD and cycle length, signed alternans amplitude).
+        Between two samples the handle keeps its multi-tick launches.  Call after define(); single device only (row blocks
+        raise NotImplementedError)."""
+        from .beats import BeatRecorder
+        if not self.defined:
+            raise AssertionError('record_beats should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return BeatRecorder(self, every=every, depth=depth, up=up, down=down, var=var, region=region, block=block, reduce=reduce,
+                            weight=weight)
+
     def program_stimuli(self, stimuli):
         """attaches a stimulus program (fib_tf_amd/stimulus.py) to this model's handle: a list of `Stimulus` entries — a site of
         any shape, a value, the tick (or millisecond) of its first event, a period, a count, a hold, 'max' or 'add', any state

@@ -574,6 +574,60 @@ int fibhip_spectrum_read(fibhip_t h, float *P /* [nb][oh][ow] */, long long *seg
 int fibhip_spectrum_peak(fibhip_t h, int a, int b, int halfwidth, int *kpeak, float *ppeak, float *pband, float *pnear /* [oh][ow] each */);
 int fibhip_spectrum_end(fibhip_t h);
 
+/* Beat recorder: a per-cell history of the last `depth` beats — upstroke time, downstroke time and peak of each — kept on the
+ * device while the run goes on, and the summary maps made from it (APD, cycle length, alternans): the seventh recorder and the
+ * sixth sampler.  All device arithmetic is float32, every operation rounded on its own (no contraction), in the order written;
+ * division is IEEE — the activation recorder's contract.
+ * Parameters: the watched array `var`; a window rows [r0, r1) x columns [c0, c1), a block (by, bx), each 1 ..
+ * FIBHIP_MAX_FRAME_BLOCK, a reduction POINT or MEAN and an optional weight plane — exactly the frame recorder's, with its pixel
+ * definition, its summation order and oh, ow as there, at the fixed levels lo = 0, span = 1 (the spectrum recorder's pixel);
+ * every >= 1; two levels down <= up; depth = 1 .. FIBHIP_BEATS_MAX_DEPTH.
+ * Samples.  Sample s (0-based) follows tick (s + 1) * every, ticks counted from 1 at beats_begin.  With dt and steps_per_tick
+ * the handle's:  step = (float)((double)every * dt * steps_per_tick),  t0 = (float)((double)(s * every) * dt * steps_per_tick);
+ * at every = 1 these are the activation recorder's `tick` and `t0`.  Times are milliseconds since beats_begin.
+ * State per pixel: xp, the pixel at the previous sample (at beats_begin: the pixel of the current state); pk, the running peak
+ * of the beat in progress (NaN outside a beat and at beats_begin); n, the int32 count of upstrokes.  The ring: three planes
+ * t_up, t_down, peak, each [depth][oh * ow], all NaN at beats_begin; beat number b lives in slot b mod depth.
+ * Per sample, xc the pixel now:
+ *   1. upstroke, when xp < up && xc >= up:  if pk is a number (a beat was still open) peak[(n - 1) mod depth] = pk, and that
+ *      beat's t_down stays NaN; then t = t0 + ((up - xp) / (xc - xp)) * step; slot n mod depth gets t_up = t, t_down = NaN,
+ *      peak = NaN; pk = xc; n += 1
+ *   2. downstroke, when xp >= down && xc < down and pk is a number:  t = t0 + ((xp - down) / (xp - xc)) * step; slot
+ *      (n - 1) mod depth gets t_down = t, peak = pk; pk = NaN.  (The first downstroke closes the beat: a later dip without an
+ *      upstroke in between finds pk = NaN and records nothing)
+ *   3. otherwise, if pk is a number:  pk = (xc > pk) ? xc : pk
+ *   4. then xp = xc
+ * NaN compares false: a NaN sample is no event and leaves pk alone.  With down <= up cases 1 and 2 exclude each other.  What
+ * fibhip_pace, a stimulus or fibhip_set_state writes between two samples belongs to the next sample.
+ * Summary maps over the newest `last` beats (1 .. depth), each [oh][ow].  For a pixel with count n the walk is the beats
+ * b = max(0, n - min(n, depth), n - last) .. n - 1, ascending, with apd_b = t_down_b - t_up_b:
+ *   nused (int32)  the beats of the walk whose apd_b is a number
+ *   apd_mean       the float32 sum of those apd_b, ascending, starting from its first term, divided by (float)nused
+ *   cl_mean        the same over cl_b = t_up_b - t_up_(b-1) for the pairs (b - 1, b) both in the walk: the terms that are
+ *                  numbers, summed ascending from the first, divided by (float) their number
+ *   apd_alt        over the pairs (b - 1, b) both in the walk whose APDs are both numbers: d = apd_b - apd_(b-1), the term is d
+ *                  for odd b and -d for even b; summed ascending from the first term and divided by (float) the number of
+ *                  pairs.  Its magnitude is the alternans amplitude; a change of its sign across the sheet is discordant alternans
+ * Each map is NaN where it has no term; nused is 0 there.
+ * It may be attached beside every other recorder and both stimulus programs (on a shared tick its sample is taken before that
+ * tick's stimuli); not on a handle with ghost rows or a row-interleaved slab; one at a time.  While attached nothing runs
+ * ahead and no launch spans a sample tick; the result does not depend on the launch plan.
+ *   fibhip_beats_begin    validates, flushes, synchronises and confirms pending work, makes xp from the current state, attaches
+ *   fibhip_beats_count    samples taken (ticks accepted but not launched yet included)
+ *   fibhip_beats_shape    oh, ow and depth of the attached recorder
+ *   fibhip_beats_read     the ring planes in SLOT order, [depth][oh][ow] float32 each, the counts [oh][ow] int32 and the live pk
+ *                         [oh][ow] float32 (any may be NULL); flushes and blocks like get_state
+ *   fibhip_beats_summary  the four maps (any may be NULL); flushes and blocks like get_state
+ *   fibhip_beats_end      detaches and frees (no recorder attached: nothing); fibhip_destroy does the same                   */
+#define FIBHIP_BEATS_MAX_DEPTH 16
+int fibhip_beats_begin(fibhip_t h, int var, const int *window /* r0, r1, c0, c1 */, int by, int bx, int reduce,
+                       const float *weight /* [H*W] or NULL */, int every, float up, float down, int depth);
+int fibhip_beats_count(fibhip_t h, long long *samples);
+int fibhip_beats_shape(fibhip_t h, int *oh, int *ow, int *depth);
+int fibhip_beats_read(fibhip_t h, float *t_up, float *t_down, float *peak /* [depth][oh][ow] each */, int *count, float *pk /* [oh][ow] each */);
+int fibhip_beats_summary(fibhip_t h, int last, int *nused, float *apd_mean, float *cl_mean, float *apd_alt /* [oh][ow] each */);
+int fibhip_beats_end(fibhip_t h);
+
 /* Stimulus program: stimuli applied on the device at programmed ticks, from sites of any shape, without a call per stimulus
  * (the reference's only stimulus is add_pace_op / fire_op, fired from the caller's loop body: `if i == s2: fire_op('s2')`;
  * fibhip_pace stands in for it and stays as it is).  A program is 1 .. FIBHIP_MAX_STIM_ENTRIES entries
