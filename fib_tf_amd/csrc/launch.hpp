@@ -201,7 +201,9 @@ static const Variant g_variants[] = {
     // an exchange period of 6 sub-steps (512^2: 250 tiles of 16 two-row strips; tools/dbg/period_model.py): a candidate of
     // autotune beside the rows above, never the rule-based plan.  (Measured at 512^2 and not kept, profiles/exchange_period_ab.txt:
     // K = 8 in 48 x 23, 3 rows per wave — 11.68 against 11.40 us per tick, and two spilled registers with a phase field; K = 7
-    // in 50 x 23, 3 rows per wave, three waves per SIMD — 12.87.)
+    // in 50 x 23, 3 rows per wave, three waves per SIMD — 12.87.  And profiles/lean_prefix_ab.txt: K = 6 in 52 x 22, sixteen full
+    // strips, 240 tiles, 30 per XCD — 11.28 / 11.44 against 11.13 / 11.13 for 52 x 21 in the same build: the busiest SIMD has
+    // the same 43 row-steps per period, and every tile is on a compute unit of its own either way.)
     S4P(Fenton, FIBHIP_FENTON4V, 0, 6, 52, 21, 2),
     S4(Fenton, FIBHIP_FENTON4V, 0, 5, 54, 21, 3),
     S4(Fenton, FIBHIP_FENTON4V, 0, 5, 54, 23, 3),

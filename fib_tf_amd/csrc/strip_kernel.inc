@@ -284,6 +284,23 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
     constexpr bool WHOLE_LOOP = MT && NV * R <= WHOLE_NVR;
     const bool whole = WHOLE_LOOP && ra_fix == 0 && rb_fix == R && (!top_open || c0 >= K - 1) && (!bot_open || c0 + R <= CY - (K - 1)) &&
                        pub == (1u << R) - 1u && top_r < 0 && bot_r < 0;
+    // A whole PREFIX for the strips of the rim (exchange-period kernels with two-row strips: K = 6, 52 x 21 — strips 1, 2, 13 and
+    // 14 of its 16 are fully live for the first 3, 5, 4 and 2 of a period's 6 sub-steps, and two of them sit on the busiest
+    // SIMD): `n_whole` is the number of leading sub-steps of a full period during which the strip is what `whole` asks for
+    // (`whole` is n_whole == K), and the loop with the row bookkeeping runs those sub-steps as the lean loop does — no live-row
+    // range, no masks, every row published.  A short last period takes the bookkeeping throughout.
+    // The prefix ends on an EVEN sub-step, at the top of a pass of the loop unrolled by two: a strip that changes from lean to
+    // bookkeeping between the two sub-steps of one pass (prefixes of 3 and 5) cost more than the lean sub-step saves — 512 x 512,
+    // µs per tick by HIP events, fast / rounding-faithful: no prefix 11.04 / 15.65, prefixes 3, 5, 4, 2: 11.14 / 15.41, prefixes
+    // 2, 4, 4, 2: 10.84 / 15.15 (profiles/lean_prefix_ab.txt).
+    // (only where the registers are there: the K = 6 kernels sit at 103-107 of 128 with it)
+    constexpr bool LEAN_PREFIX = WHOLE_LOOP && PERIODS && NV * R <= 8;
+    [[maybe_unused]] int n_whole = 0;
+    if constexpr (LEAN_PREFIX) {
+        if (ra_fix == 0 && rb_fix == R && pub == (1u << R) - 1u && top_r < 0 && bot_r < 0)
+            n_whole = min(top_open ? min(K, c0 + 1) : K, bot_open ? CY - R - c0 + 1 : K);
+        if (n_whole < K) n_whole &= ~1;
+    }
     // (the tick loop aligned to 32-256 bytes in the instruction stream: 12.55 +- 0.03 us per tick for every alignment;
     // profiles/r04_ab_kernel_variants.txt)
 #pragma unroll 1
@@ -345,14 +362,21 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
             FIB_STAMP(3 + st);
         }
     } else {
+    [[maybe_unused]] int n_lean = 0;                                // sub-steps of this period that need no bookkeeping (LEAN_PREFIX)
+    if constexpr (LEAN_PREFIX) n_lean = short_last ? 0 : n_whole;
 #pragma unroll STEP_UNROLL
     for (int st = 0; st < K; ++st) {
         float *B = lds[(st & 1) ^ 1];
+        bool lean = false;
+        if constexpr (LEAN_PREFIX) lean = st < n_lean;
         // rows [ra, rb) of this wave's strip are live at this sub-step (wave-uniform): the box loses one ring per
         // sub-step on every side that is not the domain's edge
-        const int ra = top_open ? max(ra_fix, st - c0) : ra_fix;
-        const int rb = bot_open ? min(rb_fix, CY - st - c0) : rb_fix;
-        if (ra == 0 && rb == R) {
+        int ra = 0, rb = R;
+        if (!lean) {
+            ra = top_open ? max(ra_fix, st - c0) : ra_fix;
+            rb = bot_open ? min(rb_fix, CY - st - c0) : rb_fix;
+        }
+        if (lean || (ra == 0 && rb == R)) {
             // ---- whole strip live: one straight-line block.  The R cells of a lane are independent,
             // so the scheduler can interleave their dependency chains; the 3 x (R+2) window is read once.
             float lp[R], cc[R];
@@ -385,6 +409,15 @@ static FIB_DEV void strip_body(const Geo &g, const PtrTab<M::NVAR> &pt, const Ph
         }
         // ---- publish the new potential, then fetch the next sub-step's window ---------------------------
         if (st + 1 < K) {
+            if (lean) {                                             // (never in a short last period)
+#pragma unroll
+                for (int r = 0; r < R; ++r) B[wi + ro(r)] = s[r][0];
+                FIB_WSTAMP(st);
+                __syncthreads();
+                window(B, win);
+                FIB_STAMP(3 + st);
+                continue;
+            }
             // (a short last period ends here.  The loop keeps its constant trip count: with a bound read at run time the
             // compiler does not unroll a loop that holds a barrier)
             if constexpr (PERIODS) {

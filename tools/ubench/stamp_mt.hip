@@ -2,6 +2,8 @@
 // Builds kernels.hpp with -DFIB_STAMPS: s_memtime stamps around every phase of the boundary (kernels.hpp FIB_BSTAMP) and
 // around every sub-step (FIB_STAMP), last tick / last boundary of the launch kept; means over all tiles per wave position.
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize stamp_mt.hip -o stamp_mt ; ./stamp_mt [ticks]
+// The K = 6 exchange-period kernel (profiles/stamps_k6_substeps.txt): -DSTAMP_K=6 -DSTAMP_TX=52 -DSTAMP_TY=21 -DSTAMP_R=2; [ticks]
+// then counts periods, all of them whole.
 #define FIB_STAMPS 1
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -14,7 +16,14 @@ using namespace fib;
 int main(int argc, char **argv)
 {
     const int T = argc > 1 ? atoi(argv[1]) : 8;
-    constexpr int K = 10, TX = 44, TY = 25, R = 3, H = 512, W = 512;
+#ifndef STAMP_K
+#define STAMP_K 10
+#define STAMP_TX 44
+#define STAMP_TY 25
+#define STAMP_R 3
+#endif
+    constexpr int K = STAMP_K, TX = STAMP_TX, TY = STAMP_TY, R = STAMP_R, H = 512, W = 512;
+    constexpr int SUB0 = K < 10 ? K : 0;                      // (an exchange-period kernel: the sub-steps of its last period)
     const size_t n = (size_t)H * W;
     float *buf, *xb;
     unsigned *ep;
@@ -44,13 +53,14 @@ int main(int argc, char **argv)
     for (int rep = 0; rep < 5; ++rep) {
         MtArgs mt{xb, ep, ep + 1024 * 64, epoch0, (unsigned)T | ((unsigned)rep + 1u) << 16, nullptr, hostw_dev, 0, (int)(1526u << 8)};
         hipEventRecord(e0, 0);
-        hipLaunchKernelGGL((strip_mt_kernel<Fenton, Fast, 0, K, TX, TY, R, true>), dim3(grid), dim3(64 * NW), 0, 0, g, pt, ph, k, 0, mt);
+        hipLaunchKernelGGL((strip_mt_kernel<Fenton, Fast, 0, K, TX, TY, R, true>), dim3(grid), dim3(64 * NW), 0, 0, g, pt, ph, k, SUB0, mt);
         hipEventRecord(e1, 0);
         hipEventSynchronize(e1);
         hipEventElapsedTime(&ms, e0, e1);
         epoch0 += T - 1;
     }
-    printf("strip_mt_kernel<Fenton, Fast, K=10, 44x25, R=3>, %d ticks per launch: %.2f us per launch, %.2f us per tick (stamped build)\n", T, ms * 1e3, ms * 1e3 / T);
+    printf("strip_mt_kernel<Fenton, Fast, K=%d, %dx%d, R=%d>, %d %s per launch: %.2f us per launch, %.2f us per tick (stamped build)\n", K, TX, TY, R, T,
+           K < 10 ? "periods" : "ticks", ms * 1e3, ms * 1e3 / (T * K / 10.0));
     std::vector<unsigned long long> st(4096 * 16), bs(4096 * 16);
     hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(fib_stamps), st.size() * 8);
     hipMemcpyFromSymbol(bs.data(), HIP_SYMBOL(fib_bstamps), bs.size() * 8);
