@@ -253,7 +253,7 @@ DEPS = [SRC, HDR] + [os.path.join(HERE, "csrc", f) for f in ("kernels.hpp", "ste
                                                              "strip_kernel.inc", "rows_kernel.inc", "pointwise.inc", "record_kernels.inc",
                                                              "models.hpp", "fenton_step.inc", "br_step.inc",
                                                              "court_step.inc", "court_inter.inc", "host_util.hpp", "launch.hpp",
-                                                             "ctx.hpp", "tick.inc", "sched.inc", "record.inc", "plan.inc", "comm.inc",
+                                                             "ctx.hpp", "sampler.hpp", "recorders.hpp", "tick.inc", "sched.inc", "record.inc", "plan.inc", "comm.inc",
                                                              "unit.inc")]
 
 

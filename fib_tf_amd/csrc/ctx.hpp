@@ -1,5 +1,6 @@
 // ctx.hpp — the handle behind fibhip_t: what it owns, grouped by who changes it, and the few helpers every file reads it with.
 #pragma once
+#include "sampler.hpp"
 
 constexpr int MT_MAX_TICKS = 32;          // default bound on the ticks of one launch of a predicted or undeclared series
 constexpr int MT_MAX_TICKS_DECLARED = 256;      // ... of a launch whose ticks the caller has all DECLARED (fibhip_expect): the smallest setting
@@ -112,6 +113,10 @@ struct Journal {
 };
 
 // ---- the recorders (record.inc) ----------------------------------------------------------------------------------------
+// Every recorder but the activation recorder and the stimulus program is a Sampler (sampler.hpp): `on`, `every`, `k` — the ticks
+// LAUNCHED since it was attached, which recover() rewinds by the ticks it replays — and `cap`.  recorders.hpp lists them in hook
+// order; what they ask of the scheduler is stated in sched.inc.
+
 // activation recorder (fibhip_observe_begin): while `on`, commit_impl enqueues observe_kernel behind every tick
 struct ObsRec {
     bool on;
@@ -120,13 +125,9 @@ struct ObsRec {
     float *buf;             // 6 planes of `cells` (W-pitched): Vp | first_up | last_up | prev_up | apd | count (int32)
     long long k;            // observed ticks since the recorder was attached
 };
-// electrode recorder (fibhip_electrode_begin): while `on`, no launch spans a sample tick (sample_room) and the hooks on the
-// plain and the multi-tick commit path (electrode_advance) enqueue electrode_kernel behind the launch that ends one
-struct ElRec {
-    bool on;
-    int var, n, every;
-    long long cap;          // samples the trace holds
-    long long k;            // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
+// electrode recorder (fibhip_electrode_begin): electrode_kernel behind the launch that ends a sample tick
+struct ElRec : Sampler {
+    int var, n;
     int nchunks, ncomb;     // workgroups of electrode_kernel / of electrode_combine_kernel (0: no electrode has several chunks)
     ElChunk *chunks;        // device: the chunk table
     ElComb *comb;           // device: the electrodes of several chunks
@@ -134,44 +135,37 @@ struct ElRec {
     float *part;            // device: one partial per chunk of such electrodes
     float *trace;           // device: [cap][n]
 };
-// tip recorder (fibhip_tips_begin): a sampler like the electrode recorder — no launch spans a sample tick (sample_room), and
-// the hook on the plain and the multi-tick commit path (tips_advance) enqueues tip_kernel behind the launch that ends one
-struct TipRec {
-    bool on;
-    int var, var2, every, max_tips;
+// tip recorder (fibhip_tips_begin): tip_kernel behind the launch that ends a sample tick
+struct TipRec : Sampler {
+    int var, var2, max_tips;
     float a0, b0;
-    long long cap;          // samples the lists hold
-    long long k;            // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
     unsigned char *mask;    // device: [H][W], or null (every plaquette counts)
     int *counts;            // device: [cap][3] = n_pos, n_neg, stored
     int *records;           // device: [cap][max_tips][4] = row, col, charge, 0
 };
 
-// frame recorder (fibhip_frames_begin): the third sampler — no launch spans a sample tick (sample_room), and the hook on the
-// plain and the multi-tick commit path (frames_advance) enqueues frame_kernel behind the launch that ends one
-struct FrRec {
-    bool on;
-    int var, every;
-    int r0, c0, oh, ow, by, bx;     // the window's first cell, the frame's shape in pixels, the block
-    int reduce, format;             // FIBHIP_FRAME_POINT / _MEAN, FIBHIP_FRAME_F32 / _U8
-    float lo, span;
-    long long cap;          // frames the cube holds
-    long long k;            // every - first + the ticks LAUNCHED since the recorder was attached: a sample is due at every multiple
-                            // of `every`, as for the other samplers (recover() rewinds it by the ticks it replays)
-    float *w;               // device: the weight plane [H][W], or null
-    unsigned char *cube;    // device: [cap][oh][ow] float32 or uint8
-    size_t frame_bytes() const { return (size_t)oh * (size_t)ow * (format == FIBHIP_FRAME_U8 ? 1u : 4u); }
+// the pixel plane the frame, spectrum and beat recorders sample: a window of the grid cut into blocks, one pixel per block
+struct Window {
+    int r0, c0, oh, ow, by, bx;     // the window's first cell, the plane's shape in pixels, the block
+    int reduce;                     // FIBHIP_FRAME_POINT / _MEAN
+    float *w;                       // device: the weight plane [H][W], or null
+    size_t npix() const { return (size_t)oh * (size_t)ow; }
 };
 
-// statistics recorder (fibhip_stats_begin): the fourth sampler — no launch spans a sample tick (sample_room), and the hook on
-// the plain and the multi-tick commit path (stats_advance) enqueues stats_kernel and stats_combine_kernel behind the launch
-// that ends one
-struct StRec {
-    bool on;
-    int ncols, narr, every;
-    int vars[FIB_MAXVAR];   // the distinct arrays the columns name, in order of first appearance (slow_sample_due)
-    long long cap;          // samples the trace holds
-    long long k;            // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
+// frame recorder (fibhip_frames_begin): frame_kernel behind the launch that ends a sample tick.  Its counter starts at
+// every - first, so that its first sample may come early
+struct FrRec : Sampler, Window {
+    int var;
+    int format;             // FIBHIP_FRAME_F32 / _U8
+    float lo, span;
+    unsigned char *cube;    // device: [cap][oh][ow] float32 or uint8
+    size_t frame_bytes() const { return npix() * (format == FIBHIP_FRAME_U8 ? 1u : 4u); }
+};
+
+// statistics recorder (fibhip_stats_begin): stats_kernel and stats_combine_kernel behind the launch that ends a sample tick
+struct StRec : Sampler {
+    int ncols, narr;
+    int vars[FIB_MAXVAR];   // the distinct arrays the columns name, in order of first appearance
     int nchunks;            // chunks of one array: stats_kernel's grid is (nchunks, narr)
     StChunk *chunks;        // device: the chunk table
     StArr *arrs;            // device: the columns of every array
@@ -182,50 +176,36 @@ struct StRec {
     double *trace;          // device: [cap][ncols]
 };
 
-// spectrum recorder (fibhip_spectrum_begin): the fifth sampler — no launch spans a sample tick (sample_room), and the hook on
-// the plain and the multi-tick commit path (spectrum_advance) enqueues spectrum_sample_kernel behind the launch that ends one
-// and, behind the sample that fills the ring, spectrum_fold_kernel.  It ACCUMULATES: both kernels read the give-up word first,
-// and everything about its progress follows from `k` alone — samples k / every, the ring slot and the segment position of a
-// sample, the folds issued samples / chunk, the segments samples / nfft — so a rewind of `k` leaves nothing behind
-struct SpRec {
-    bool on;
-    int var, every;
-    int r0, c0, oh, ow, by, bx;     // the window's first cell, the plane's shape in pixels, the block
-    int reduce;                     // FIBHIP_FRAME_POINT / _MEAN
+// spectrum recorder (fibhip_spectrum_begin): spectrum_sample_kernel behind the launch that ends a sample tick and, behind the
+// sample that fills the ring, spectrum_fold_kernel.  It ACCUMULATES: both kernels read the give-up word first, and everything
+// about its progress follows from `k` alone — samples k / every, the ring slot and the segment position of a sample, the folds
+// issued samples / chunk, the segments samples / nfft — so a rewind of `k` leaves nothing behind.  It never fills up
+struct SpRec : Sampler, Window {
+    int var;
     int nfft, nb, chunk;
-    long long k;            // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
-    float *w;               // device: the weight plane [H][W], or null
     float *win;             // device: [nfft]
     float *tw;              // device: [nfft][2]
     int *bins;              // device: [nb]
     float *ring;            // device: [chunk][oh][ow]
     float *acc;             // device: Re | Im | P, each [nb][oh][ow]
     float *maps;            // device: kpeak (int32) | ppeak | pband | pnear, each [oh][ow]
-    size_t npix() const { return (size_t)oh * (size_t)ow; }
 };
 
-// beat recorder (fibhip_beats_begin): the sixth sampler — no launch spans a sample tick (sample_room), and the hook on the plain
-// and the multi-tick commit path (beats_advance) enqueues beat_kernel behind the launch that ends one.  It ACCUMULATES (the
-// count, the open beat's peak, the ring): the kernel reads the give-up word first, and the sample index — with it t0 — follows
-// from `k` alone, so a rewind of `k` leaves nothing behind
-struct BeatRec {
-    bool on;
-    int var, every;
-    int r0, c0, oh, ow, by, bx;     // the window's first cell, the map's shape in pixels, the block
-    int reduce;                     // FIBHIP_FRAME_POINT / _MEAN
+// beat recorder (fibhip_beats_begin): beat_kernel behind the launch that ends a sample tick.  It ACCUMULATES (the count, the
+// open beat's peak, the ring): the kernel reads the give-up word first, and the sample index — with it t0 — follows from `k`
+// alone, so a rewind of `k` leaves nothing behind.  A ring never fills up
+struct BeatRec : Sampler, Window {
+    int var;
     float up, down;
     int depth;
-    long long k;            // ticks LAUNCHED since the recorder was attached (recover() rewinds it by the ticks it replays)
-    float *w;               // device: the weight plane [H][W], or null
     float *state;           // device: xp | pk | n (int32), each [oh][ow]
     float *ring;            // device: t_up | t_down | peak, each [depth][oh][ow]
     float *maps;            // device: nused (int32) | apd_mean | cl_mean | apd_alt, each [oh][ow]
-    size_t npix() const { return (size_t)oh * (size_t)ow; }
 };
 
-// stimulus program (fibhip_stim_begin): the actuator beside the recorders — no launch spans an event tick (stim_room, a term of
-// sample_room), and the hook on the plain and the multi-tick commit path (stim_advance) enqueues stim_kernel behind the launch
-// that ends one, behind the samples of that tick
+// stimulus program (fibhip_stim_begin): the actuator beside the recorders, driven by its events and not by a stride — no launch
+// spans an event tick (stim_room, a term of sample_room), and stim_kernel goes behind the launch that ends one, behind the
+// samples of that tick
 struct StimEntry {
     int var, mode;
     long long first, period, count, hold;   // fibhip_stim_entry's, validated
@@ -244,15 +224,11 @@ struct StimRec {
     float *planes;          // device: the planes, [nplanes][H][W], or null
 };
 
-// trigger program (fibhip_trig_begin): the closed loop — a sampler (no launch spans a sample tick: sample_room) whose hook on the
-// plain and the multi-tick commit path (trig_advance, behind stim_advance) enqueues sense_kernel, trigger_kernel and the gated
-// apply behind the launch that ends a sample tick.  The automaton's state IS the log on the device: row s follows from row
-// s - 1 and the state alone, and the host knows only the slot (k / every)
-struct TrigRec {
-    bool on;
-    int nsensors, nrules, every;
-    long long cap;          // samples the log holds
-    long long k;            // ticks LAUNCHED since the program was attached (recover() rewinds it by the ticks it replays)
+// trigger program (fibhip_trig_begin): the closed loop — a sampler whose hook (behind the stimulus program's) enqueues
+// sense_kernel, trigger_kernel and the gated apply behind the launch that ends a sample tick.  The automaton's state IS the log
+// on the device: row s follows from row s - 1 and the state alone, and the host knows only the slot
+struct TrigRec : Sampler {
+    int nsensors, nrules;
     bool cut_vec;           // the item tables' [1] entries may be used (pitch == W, W a multiple of 4)
     int max_chunks[2];      // sense_kernel's grid.x, scalar / VEC
     std::vector<StimEntry> stims;   // rule r's stimulus (first / period / count / hold unused: the automaton times it)

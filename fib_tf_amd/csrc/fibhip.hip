@@ -31,6 +31,7 @@ using namespace fib;
 #include "host_util.hpp"    // fail, HIPCHK, the spin-waits
 #include "launch.hpp"       // LaunchCtx, the launchers, the variant table
 #include "ctx.hpp"          // fibhip_ctx and its parts, NEED / FLUSH / CONFIRM / SYNC_S0, the timeline
+#include "recorders.hpp"    // the table of the hooks behind a committed launch, in hook order
 #include "tick.inc"         // one tick: pointer tables, rows, edges / interior / commit
 #include "sched.inc"        // when ticks are launched: deferral, multi-tick launches, run-ahead, journal and recovery, fibhip_step
 #include "record.inc"       // activation, electrode, tip, frame, statistics, spectrum and beat recorders; the stimulus program and the trigger program
@@ -297,14 +298,7 @@ extern "C" int fibhip_destroy(fibhip_t h)
     if (h->phi_dev) hipFree(h->phi_dev);
     if (h->agg) hipFree(h->agg);
     if (h->obs.buf) hipFree(h->obs.buf);
-    electrode_free(h);
-    tips_free(h);
-    frames_free(h);
-    stats_free(h);
-    spectrum_free(h);
-    beats_free(h);
-    stim_free(h);
-    trig_free(h);
+    recorders_free(h);
     if (h->mt.xbuf) hipFree(h->mt.xbuf);
     if (h->mt.epochs) hipFree(h->mt.epochs);
     for (auto &r : h->trace) {

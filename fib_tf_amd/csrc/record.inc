@@ -1,14 +1,151 @@
-// record.inc — the seven recorders that run on the device while a model runs: the per-cell activation maps
+// record.inc — what runs on the device behind the ticks while a model runs.  Seven recorders: the per-cell activation maps
 // (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
-// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell beat history (fibhip_beats_*) — and the two hooks that write the state: the stimulus program
-// (fibhip_stim_*) and the trigger program (fibhip_trig_*), which senses, decides and fires on the device.  Each is a hook behind a committed launch plus its entry points; what they ask of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
+// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell
+// beat history (fibhip_beats_*); and the two hooks that write the state: the stimulus program (fibhip_stim_*) and the trigger
+// program (fibhip_trig_*), which senses, decides and fires on the device.
+// The file has three parts: the helpers every recorder shares; the hooks — per recorder its _advance (behind a launch that the
+// handle's state has moved with) and its _free, the two functions its row of RECORDERS (recorders.hpp) names —; and the entry
+// points.  Every hook but the activation recorder's (it sees every tick) and the stimulus program's (event-driven: its own k and
+// next) counts with a Sampler (sampler.hpp) and computes the slot it writes from that counter alone, so a replay (sched.inc recover()) writes the same slots again.  What the recorders ask
+// of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
 // (included by fibhip.hip, behind sched.inc)
 
+// ---- helpers ------------------------------------------------------------------------------------------------------------
+// where array `var` of the state lives now
+static inline float *array_of(const fibhip_ctx *h, int var) { return h->slab[h->cur[var]] + (size_t)var * h->vstride; }
+// does `var` name an array Courtemanche's 'slow' assigns (one the aggregates are formed from)?
+static inline bool slow_array(int var)
+{
+#if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
+    return !((Courtemanche::FAST_MASK >> var) & 1u);
+#else
+    return false;
+#endif
+}
+// the word the kernels of a hook behind an unconfirmed multi-tick launch read first (null: nothing to gate on)
+static inline const unsigned *give_up_of(const fibhip_ctx *h, bool behind_mt) { return behind_mt && h->mt.epochs ? h->mt.give_up_word() : nullptr; }
+static inline unsigned qnan_bits()
+{
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    unsigned bits;
+    memcpy(&bits, &qnan, sizeof bits);
+    return bits;
+}
+template <class T>
+static inline void dev_free(T *&p)
+{
+    if (p) hipFree(p);
+    p = nullptr;
+}
+// one kernel on s0 as one event `name` of the timeline; `launch` is the hipLaunchKernelGGL
+template <class F>
+static int launch_traced(fibhip_ctx *h, const char *name, int K, F launch)
+{
+    if (int rc = trace_open(h, h->s0, name, K, 0, 0, 0, 1)) return rc;
+    launch();
+    HIPCHK(hipGetLastError());
+    if (int rc = trace_close(h, h->s0)) return rc;
+    h->launches++;
+    return 0;
+}
+static inline dim3 blocks_of(size_t threads) { return dim3((unsigned)((threads + 255) / 256)); }
+
+// what no recorder attaches to: a row block, an open tick
+static int attach_refusals(const fibhip_ctx *h, const char *who)
+{
+    if (is_shard(h)) return fail(FIBHIP_EINVAL, "%s: not on a row block (a handle with ghost rows)", who);
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "%s inside an open tick", who);
+    return 0;
+}
+// "<prefix>rows [r0, r1) x columns [c0, c1) is empty or outside the H x W grid"; the prefix is printf's
+static int rect_check(const fibhip_ctx *h, int r0, int r1, int c0, int c1, const char *prefix, ...)
+{
+    const int H = h->d.height, W = h->d.width;
+    if (r0 >= 0 && r1 <= H && c0 >= 0 && c1 <= W && r0 < r1 && c0 < c1) return 0;
+    char who[128];
+    va_list ap;
+    va_start(ap, prefix);
+    vsnprintf(who, sizeof who, prefix, ap);
+    va_end(ap);
+    return fail(FIBHIP_EINVAL, "%srows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", who, r0, r1, c0, c1, H, W);
+}
+// the pixel plane of the frame, spectrum and beat recorders from the caller's window, block and reduction
+static int window_from(const fibhip_ctx *h, const char *who, const int *window, int by, int bx, int reduce, Window &out)
+{
+    const int r0 = window[0], r1 = window[1], c0 = window[2], c1 = window[3];
+    if (int rc = rect_check(h, r0, r1, c0, c1, "%s: the window ", who)) return rc;
+    if (by < 1 || by > FIBHIP_MAX_FRAME_BLOCK || bx < 1 || bx > FIBHIP_MAX_FRAME_BLOCK)
+        return fail(FIBHIP_EINVAL, "%s: a block is 1 .. %d cells each way (got %d x %d)", who, FIBHIP_MAX_FRAME_BLOCK, by, bx);
+    const int oh = (r1 - r0) / by, ow = (c1 - c0) / bx;
+    if (oh < 1 || ow < 1) return fail(FIBHIP_EINVAL, "%s: a window of %d x %d cells holds no block of %d x %d", who, r1 - r0, c1 - c0, by, bx);
+    if (reduce != FIBHIP_FRAME_POINT && reduce != FIBHIP_FRAME_MEAN) return fail(FIBHIP_EINVAL, "%s: bad reduction %d", who, reduce);
+    out.r0 = r0; out.c0 = c0; out.oh = oh; out.ow = ow; out.by = by; out.bx = bx;
+    out.reduce = reduce;
+    out.w = nullptr;
+    return 0;
+}
+// every row of the window starts 16-byte aligned in the array `x` and in the weight plane, and four pixels are four cells or
+// whole blocks of them: what the three pixel kernels' vector paths share (each adds the alignment of what it writes)
+static inline bool window_vec_ok(const fibhip_ctx *h, const Window &p, const float *x)
+{
+    return h->pitch == h->d.width && h->d.width % 4 == 0 && p.c0 % 4 == 0 && p.ow % 4 == 0 &&
+           ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(p.w)) & 15u) == 0;
+}
+// the window's part of FrameArgs, SpecSampleArgs and BeatArgs
+template <class Args>
+static inline void window_fill(const fibhip_ctx *h, const Window &p, int var, Args &a)
+{
+    a.x = array_of(h, var);
+    a.w = p.w;
+    a.pitch = h->pitch;
+    a.wpitch = h->d.width;
+    a.r0 = p.r0; a.c0 = p.c0; a.oh = p.oh; a.ow = p.ow; a.by = p.by; a.bx = p.bx;
+}
+// "[first, first + count) of `taken`": the range a _read may ask for (`what`: "samples", "frames")
+static int range_check(const char *who, const char *what, long long first, long long count, long long taken)
+{
+    if (first < 0 || count < 0 || first + count > taken)
+        return fail(FIBHIP_EINVAL, "%s: %s [%lld, %lld) of %lld taken", who, what, first, first + count, taken);
+    return 0;
+}
+// A read-back: `copies` enqueues it on s0 (launches and asynchronous copies; it returns a status), then the stream is waited
+// for.  If that wait found a launch in front of the copies that had given up, the state was recovered and the lost samples
+// were taken again: the copies are enqueued once more
+template <class F>
+static int read_confirmed(fibhip_ctx *h, F copies)
+{
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long fb0 = h->journal.n_fallbacks;
+        if (int rc = copies()) return rc;
+        SYNC_S0(h);
+        if (h->journal.n_fallbacks == fb0) break;
+    }
+    return 0;
+}
+// every _end: nothing to do unless attached; else the ticks accepted while attached are sampled (their events applied), and
+// confirmed, so that no replay is left that would want the recorder; then its buffers go
+static int detach(fibhip_ctx *h, bool on, recorder_free_fn *release)
+{
+    if (!on) return 0;
+    FLUSH(h);
+    SYNC_S0(h);
+    release(h);
+    return 0;
+}
+// the four maps of a _peak or a _summary, `npix` 4-byte values each, to the destinations that are not null
+static int copy_maps(fibhip_ctx *h, const float *maps, size_t npix, void *const dst[4])
+{
+    for (int i = 0; i < 4; ++i)
+        if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], maps + (size_t)i * npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+    return 0;
+}
+
+// ---- the hooks ----------------------------------------------------------------------------------------------------------
 // the activation recorder's update for the tick just committed (observed tick k = obs_k), on s0 behind it
 static int observe_enqueue(fibhip_ctx *h)
 {
     const size_t n = h->cells;
-    const float *pot = h->slab[h->cur[h->obs.var]] + (size_t)h->obs.var * h->vstride;
+    const float *pot = array_of(h, h->obs.var);
     ObsMaps m;
     m.first = h->obs.buf + n;
     m.last = h->obs.buf + 2 * n;
@@ -20,167 +157,125 @@ static int observe_enqueue(fibhip_ctx *h)
     const bool vec = h->pitch == h->d.width && (reinterpret_cast<uintptr_t>(pot) & 15u) == 0;
     const size_t threads = vec ? n / 4 + n % 4 : n;
     const Geo g = base_geo(h);
-    if (int rc = trace_open(h, h->s0, "observe_kernel", 0, 0, 0, 0, 1)) return rc;
-    if (vec)
-        hipLaunchKernelGGL(observe_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->s0, g, pot, h->obs.buf, m,
-                           h->obs.up, h->obs.down, t0, tick);
-    else
-        hipLaunchKernelGGL(observe_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->s0, g, pot, h->obs.buf, m,
-                           h->obs.up, h->obs.down, t0, tick);
-    HIPCHK(hipGetLastError());
-    if (int rc = trace_close(h, h->s0)) return rc;
-    h->launches++;
+    const dim3 grid = blocks_of(threads);
+    if (int rc = launch_traced(h, "observe_kernel", 0, [&] {
+            if (vec) hipLaunchKernelGGL(observe_kernel<true>, grid, dim3(256), 0, h->s0, g, pot, h->obs.buf, m, h->obs.up, h->obs.down, t0, tick);
+            else hipLaunchKernelGGL(observe_kernel<false>, grid, dim3(256), 0, h->s0, g, pot, h->obs.buf, m, h->obs.up, h->obs.down, t0, tick);
+        }))
+        return rc;
     h->obs.k++;
     return 0;
 }
 
-// The electrode recorder's hook behind a launch of `ticks` ticks (plain: commit_impl; multi-tick: mt_launch).  No launch
-// spans a sample tick (sample_room), so a sample is due exactly when the counter lands on a multiple of `every`; it is enqueued
-// on s0 behind that launch and reads the state the handle has just moved to.  The slot is a kernel argument computed from the
-// host's counter, never a pointer kept on the device: a replay (recover()) writes the same slots again.
-static int electrode_advance(fibhip_ctx *h, int ticks)
+// The electrode recorder's hook behind a launch of `ticks` ticks (plain: commit_impl; multi-tick: mt_launch).  A sample that is
+// due is enqueued on s0 behind that launch and reads the state the handle has just moved to.  The slot is a kernel argument
+// computed from the host's counter, never a pointer kept on the device: a replay (recover()) writes the same slots again.
+static int electrode_advance(fibhip_ctx *h, int ticks, bool)
 {
-    h->el.k += ticks;
-    if (h->el.k % h->el.every) return 0;
-    const long long s = h->el.k / h->el.every - 1;
-    if (s >= h->el.cap) return fail(FIBHIP_EINVAL, "electrode recorder: trace full");      // (fibhip_step refuses before this)
-    const float *x = h->slab[h->cur[h->el.var]] + (size_t)h->el.var * h->vstride;
-    float *row = h->el.trace + (size_t)s * h->el.n;
-    if (int rc = trace_open(h, h->s0, "electrode_kernel", 0, 0, 0, 0, 1)) return rc;
-    hipLaunchKernelGGL(electrode_kernel, dim3((unsigned)h->el.nchunks), dim3(EL_THREADS), 0, h->s0, x, h->pitch, h->el.chunks, h->el.w,
-                       row, h->el.part);
-    HIPCHK(hipGetLastError());
-    if (int rc = trace_close(h, h->s0)) return rc;
-    h->launches++;
-    if (h->el.ncomb) {
-        if (int rc = trace_open(h, h->s0, "electrode_combine_kernel", 0, 0, 0, 0, 1)) return rc;
-        hipLaunchKernelGGL(electrode_combine_kernel, dim3((unsigned)h->el.ncomb), dim3(256), 0, h->s0, h->el.comb, h->el.part, row);
-        HIPCHK(hipGetLastError());
-        if (int rc = trace_close(h, h->s0)) return rc;
-        h->launches++;
-    }
-    return 0;
+    ElRec &r = h->el;
+    long long s;
+    if (!r.advance(ticks, &s)) return 0;
+    if (s >= r.cap) return fail(FIBHIP_EINVAL, "electrode recorder: trace full");              // (fibhip_step refuses before this)
+    const float *x = array_of(h, r.var);
+    float *row = r.trace + (size_t)s * r.n;
+    if (int rc = launch_traced(h, "electrode_kernel", 0, [&] {
+            hipLaunchKernelGGL(electrode_kernel, dim3((unsigned)r.nchunks), dim3(EL_THREADS), 0, h->s0, x, h->pitch, r.chunks, r.w, row, r.part);
+        }))
+        return rc;
+    if (!r.ncomb) return 0;
+    return launch_traced(h, "electrode_combine_kernel", 0,
+                         [&] { hipLaunchKernelGGL(electrode_combine_kernel, dim3((unsigned)r.ncomb), dim3(256), 0, h->s0, r.comb, r.part, row); });
 }
-
 static void electrode_free(fibhip_ctx *h)
 {
-    if (h->el.chunks) hipFree(h->el.chunks);
-    if (h->el.comb) hipFree(h->el.comb);
-    if (h->el.w) hipFree(h->el.w);
-    if (h->el.part) hipFree(h->el.part);
-    if (h->el.trace) hipFree(h->el.trace);
-    h->el.chunks = nullptr;
-    h->el.comb = nullptr;
-    h->el.w = h->el.part = h->el.trace = nullptr;
+    dev_free(h->el.chunks);
+    dev_free(h->el.comb);
+    dev_free(h->el.w);
+    dev_free(h->el.part);
+    dev_free(h->el.trace);
     h->el.on = false;
 }
 
-// The tip recorder's hook, the electrode recorder's step for step: at a sample tick the sample's three counters are zeroed and
-// tip_kernel is enqueued behind them on s0.  Slot and counters are addressed from the host's counter, so a replay zeroes and
-// fills the same slot again; records beyond `stored` are never looked at, so the list itself is not cleared.
-static int tips_advance(fibhip_ctx *h, int ticks)
+// The tip recorder's hook: at a sample tick the sample's three counters are zeroed and tip_kernel is enqueued behind them on
+// s0.  Slot and counters are addressed from the host's counter, so a replay zeroes and fills the same slot again; records
+// beyond `stored` are never looked at, so the list itself is not cleared.
+static int tips_advance(fibhip_ctx *h, int ticks, bool)
 {
-    h->tip.k += ticks;
-    if (h->tip.k % h->tip.every) return 0;
-    const long long s = h->tip.k / h->tip.every - 1;
-    if (s >= h->tip.cap) return fail(FIBHIP_EINVAL, "tip recorder: trace full");               // (fibhip_step refuses before this)
-    const float *a = h->slab[h->cur[h->tip.var]] + (size_t)h->tip.var * h->vstride;
-    const float *b = h->slab[h->cur[h->tip.var2]] + (size_t)h->tip.var2 * h->vstride;
-    int *cnt = h->tip.counts + 3 * (size_t)s;
-    int4 *rec = reinterpret_cast<int4 *>(h->tip.records) + (size_t)s * (size_t)h->tip.max_tips;
+    TipRec &r = h->tip;
+    long long s;
+    if (!r.advance(ticks, &s)) return 0;
+    if (s >= r.cap) return fail(FIBHIP_EINVAL, "tip recorder: trace full");                    // (fibhip_step refuses before this)
+    const float *a = array_of(h, r.var), *b = array_of(h, r.var2);
+    int *cnt = r.counts + 3 * (size_t)s;
+    int4 *rec = reinterpret_cast<int4 *>(r.records) + (size_t)s * (size_t)r.max_tips;
     const Geo g = base_geo(h);
     const bool vec = h->pitch == g.W && g.W % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
-    const size_t threads = (size_t)(g.H - 1) * (size_t)(vec ? g.W / 4 : g.W - 1);
+    const dim3 grid = blocks_of((size_t)(g.H - 1) * (size_t)(vec ? g.W / 4 : g.W - 1));
     HIPCHK(hipMemsetAsync(cnt, 0, 3 * sizeof(int), h->s0));
-    if (int rc = trace_open(h, h->s0, "tip_kernel", 0, 0, 0, 0, 1)) return rc;
-    if (vec)
-        hipLaunchKernelGGL(tip_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->s0, g, a, b, h->tip.a0, h->tip.b0,
-                           h->tip.mask, cnt, rec, h->tip.max_tips);
-    else
-        hipLaunchKernelGGL(tip_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->s0, g, a, b, h->tip.a0, h->tip.b0,
-                           h->tip.mask, cnt, rec, h->tip.max_tips);
-    HIPCHK(hipGetLastError());
-    if (int rc = trace_close(h, h->s0)) return rc;
-    h->launches++;
-    return 0;
+    return launch_traced(h, "tip_kernel", 0, [&] {
+        if (vec) hipLaunchKernelGGL(tip_kernel<true>, grid, dim3(256), 0, h->s0, g, a, b, r.a0, r.b0, r.mask, cnt, rec, r.max_tips);
+        else hipLaunchKernelGGL(tip_kernel<false>, grid, dim3(256), 0, h->s0, g, a, b, r.a0, r.b0, r.mask, cnt, rec, r.max_tips);
+    });
 }
-
 static void tips_free(fibhip_ctx *h)
 {
-    if (h->tip.mask) hipFree(h->tip.mask);
-    if (h->tip.counts) hipFree(h->tip.counts);
-    if (h->tip.records) hipFree(h->tip.records);
-    h->tip.mask = nullptr;
-    h->tip.counts = h->tip.records = nullptr;
+    dev_free(h->tip.mask);
+    dev_free(h->tip.counts);
+    dev_free(h->tip.records);
     h->tip.on = false;
 }
 
-// The frame recorder's hook, the tip recorder's step for step.  Its counter started at every - first (fibhip_frames_begin), so
-// a sample is due when it lands on a multiple of `every`, like the others'; the frame's slot in the cube is a kernel argument
-// computed from that counter, so a replay fills the same slot again.
+// The frame recorder's hook.  Its counter started at every - first (fibhip_frames_begin), so a sample is due when it lands on a
+// multiple of `every`, like the others'; the frame's slot in the cube is a kernel argument computed from that counter, so a
+// replay fills the same slot again.
 template <bool U8, bool MEAN>
 static void frame_launch(const FrameArgs &a, bool vec, size_t threads, hipStream_t st)
 {
-    const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+    const dim3 grid = blocks_of(threads), block(256);
     if (vec) hipLaunchKernelGGL((frame_kernel<U8, MEAN, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((frame_kernel<U8, MEAN, false>), grid, block, 0, st, a);
 }
 
-static int frames_advance(fibhip_ctx *h, int ticks)
+static int frames_advance(fibhip_ctx *h, int ticks, bool)
 {
     FrRec &f = h->fr;
-    f.k += ticks;
-    if (f.k % f.every) return 0;
-    const long long s = f.k / f.every - 1;
+    long long s;
+    if (!f.advance(ticks, &s)) return 0;
     if (s >= f.cap) return fail(FIBHIP_EINVAL, "frame recorder: trace full");                 // (fibhip_step refuses before this)
     FrameArgs a;
-    a.x = h->slab[h->cur[f.var]] + (size_t)f.var * h->vstride;
-    a.w = f.w;
+    window_fill(h, f, f.var, a);
     a.out = f.cube + (size_t)s * f.frame_bytes();
-    a.pitch = h->pitch;
-    a.wpitch = h->d.width;
-    a.r0 = f.r0; a.c0 = f.c0; a.oh = f.oh; a.ow = f.ow; a.by = f.by; a.bx = f.bx;
     a.lo = f.lo; a.span = f.span;
-    // every row of the window starts 16-byte aligned in the array and in the weight plane, and so does every row of the frame
-    // (four pixels are 16 bytes of a float32 frame and 4 bytes of an 8-bit one)
+    // ... and so does every row of the frame (four pixels are 16 bytes of a float32 frame and 4 bytes of an 8-bit one)
     const bool u8 = f.format == FIBHIP_FRAME_U8, mean = f.reduce == FIBHIP_FRAME_MEAN;
-    const bool vec = h->pitch == h->d.width && h->d.width % 4 == 0 && f.c0 % 4 == 0 && f.ow % 4 == 0 &&
-                     ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.w)) & 15u) == 0 &&
-                     (reinterpret_cast<uintptr_t>(a.out) & (u8 ? 3u : 15u)) == 0;
+    const bool vec = window_vec_ok(h, f, a.x) && (reinterpret_cast<uintptr_t>(a.out) & (u8 ? 3u : 15u)) == 0;
     const size_t threads = (size_t)f.oh * (size_t)(vec ? f.ow / 4 : f.ow);
-    if (int rc = trace_open(h, h->s0, "frame_kernel", 0, 0, 0, 0, 1)) return rc;
-    if (u8 && mean) frame_launch<true, true>(a, vec, threads, h->s0);
-    else if (u8) frame_launch<true, false>(a, vec, threads, h->s0);
-    else if (mean) frame_launch<false, true>(a, vec, threads, h->s0);
-    else frame_launch<false, false>(a, vec, threads, h->s0);
-    HIPCHK(hipGetLastError());
-    if (int rc = trace_close(h, h->s0)) return rc;
-    h->launches++;
-    return 0;
+    return launch_traced(h, "frame_kernel", 0, [&] {
+        if (u8 && mean) frame_launch<true, true>(a, vec, threads, h->s0);
+        else if (u8) frame_launch<true, false>(a, vec, threads, h->s0);
+        else if (mean) frame_launch<false, true>(a, vec, threads, h->s0);
+        else frame_launch<false, false>(a, vec, threads, h->s0);
+    });
 }
-
 static void frames_free(fibhip_ctx *h)
 {
-    if (h->fr.w) hipFree(h->fr.w);
-    if (h->fr.cube) hipFree(h->fr.cube);
-    h->fr.w = nullptr;
-    h->fr.cube = nullptr;
+    dev_free(h->fr.w);
+    dev_free(h->fr.cube);
     h->fr.on = false;
 }
 
 static_assert(ST_SLOTS == FIBHIP_MAX_STAT_COLS_PER_ARRAY && (int)ST_KINDS == (int)FIBHIP_STAT_NONFINITE + 1 && (int)ST_SUM == (int)FIBHIP_STAT_SUM &&
                   (int)ST_BELOW == (int)FIBHIP_STAT_BELOW && ST_MAX_CHUNKS == 4 * 64 && ST_MIN_CHUNK % 4 == 0,
               "stats_kernel's constants follow include/fibhip.h; stats_combine_kernel folds four chunks per lane of one wave");
-// The statistics recorder's hook, the electrode recorder's step for step: at a sample tick stats_kernel is enqueued on s0 behind
-// the launch that ended there (one partial per column and chunk), and stats_combine_kernel behind it (the sample's row).  The
-// row's slot is a kernel argument computed from the host's counter, so a replay (recover()) writes the same slot again; the
-// partials are rewritten whole by every sample.
-static int stats_advance(fibhip_ctx *h, int ticks)
+// The statistics recorder's hook: at a sample tick stats_kernel is enqueued on s0 behind the launch that ended there (one
+// partial per column and chunk), and stats_combine_kernel behind it (the sample's row).  The row's slot is a kernel argument
+// computed from the host's counter, so a replay (recover()) writes the same slot again; the partials are rewritten whole by
+// every sample.
+static int stats_advance(fibhip_ctx *h, int ticks, bool)
 {
     StRec &r = h->st;
-    r.k += ticks;
-    if (r.k % r.every) return 0;
-    const long long s = r.k / r.every - 1;
+    long long s;
+    if (!r.advance(ticks, &s)) return 0;
     if (s >= r.cap) return fail(FIBHIP_EINVAL, "statistics recorder: trace full");             // (fibhip_step refuses before this)
     StArgs a;
     a.slab0 = h->slab[0];
@@ -190,7 +285,7 @@ static int stats_advance(fibhip_ctx *h, int ticks)
     for (int i = 0; i < r.narr; ++i) {
         const int v = r.vars[i];
         if (h->cur[v]) a.cur_mask |= 1u << v;
-        align |= reinterpret_cast<uintptr_t>(h->slab[h->cur[v]] + (size_t)v * h->vstride);
+        align |= reinterpret_cast<uintptr_t>(array_of(h, v));
     }
     a.W = h->d.width;
     a.pitch = h->pitch;
@@ -204,36 +299,24 @@ static int stats_advance(fibhip_ctx *h, int ticks)
     // (the chunk table was cut for the vector path exactly when pitch == W and W % 4 == 0; the pointers are looked at here)
     const bool vec = h->pitch == h->d.width && h->d.width % 4 == 0 && (align & 15u) == 0;
     const dim3 grid((unsigned)r.nchunks, (unsigned)r.narr);
-    if (int rc = trace_open(h, h->s0, "stats_kernel", 0, 0, 0, 0, 1)) return rc;
-    if (vec) hipLaunchKernelGGL(stats_kernel<true>, grid, dim3(ST_THREADS), 0, h->s0, a);
-    else hipLaunchKernelGGL(stats_kernel<false>, grid, dim3(ST_THREADS), 0, h->s0, a);
-    HIPCHK(hipGetLastError());
-    if (int rc = trace_close(h, h->s0)) return rc;
-    h->launches++;
-    if (int rc = trace_open(h, h->s0, "stats_combine_kernel", 0, 0, 0, 0, 1)) return rc;
-    hipLaunchKernelGGL(stats_combine_kernel, dim3(1), dim3(256), 0, h->s0, r.cols, r.ncols, r.part, r.nchunks, r.trace + (size_t)s * r.ncols);
-    HIPCHK(hipGetLastError());
-    if (int rc = trace_close(h, h->s0)) return rc;
-    h->launches++;
-    return 0;
+    if (int rc = launch_traced(h, "stats_kernel", 0, [&] {
+            if (vec) hipLaunchKernelGGL(stats_kernel<true>, grid, dim3(ST_THREADS), 0, h->s0, a);
+            else hipLaunchKernelGGL(stats_kernel<false>, grid, dim3(ST_THREADS), 0, h->s0, a);
+        }))
+        return rc;
+    return launch_traced(h, "stats_combine_kernel", 0, [&] {
+        hipLaunchKernelGGL(stats_combine_kernel, dim3(1), dim3(256), 0, h->s0, r.cols, r.ncols, r.part, r.nchunks, r.trace + (size_t)s * r.ncols);
+    });
 }
-
 static void stats_free(fibhip_ctx *h)
 {
-    if (h->st.chunks) hipFree(h->st.chunks);
-    if (h->st.arrs) hipFree(h->st.arrs);
-    if (h->st.cols) hipFree(h->st.cols);
-    if (h->st.w) hipFree(h->st.w);
-    if (h->st.mask) hipFree(h->st.mask);
-    if (h->st.part) hipFree(h->st.part);
-    if (h->st.trace) hipFree(h->st.trace);
-    h->st.chunks = nullptr;
-    h->st.arrs = nullptr;
-    h->st.cols = nullptr;
-    h->st.w = nullptr;
-    h->st.mask = nullptr;
-    h->st.part = nullptr;
-    h->st.trace = nullptr;
+    dev_free(h->st.chunks);
+    dev_free(h->st.arrs);
+    dev_free(h->st.cols);
+    dev_free(h->st.w);
+    dev_free(h->st.mask);
+    dev_free(h->st.part);
+    dev_free(h->st.trace);
     h->st.on = false;
 }
 
@@ -248,67 +331,51 @@ static spec_fold_fn spec_fold_pick(int chunk, std::integer_sequence<int, C...>)
     static const spec_fold_fn table[] = {spectrum_fold_kernel<C + 1>...};      // chunk = 1 .. SPEC_MAX_CHUNK
     return table[chunk - 1];
 }
-// The spectrum recorder's hook behind a launch of `ticks` ticks, the frame recorder's step for step: at a sample tick
-// spectrum_sample_kernel writes the pixel plane into slot s mod chunk of the ring, and behind the sample that fills the ring
-// spectrum_fold_kernel folds the chunk.  Slot, segment position and whether the chunk ends a segment are kernel arguments
-// computed from the host's counter.  `behind_mt`: as for stim_advance — both kernels are handed the give-up word and write
-// nothing once a launch in front of them gave up (the fold accumulates, and a void sample must not overwrite a slot whose fold
-// was skipped: record_kernels.inc); recover() rewinds the counter and the replay comes through here again.
+// The spectrum recorder's hook behind a launch of `ticks` ticks: at a sample tick spectrum_sample_kernel writes the pixel plane
+// into slot s mod chunk of the ring, and behind the sample that fills the ring spectrum_fold_kernel folds the chunk.  Slot,
+// segment position and whether the chunk ends a segment are kernel arguments computed from the host's counter.  `behind_mt`: as
+// for stim_advance — both kernels are handed the give-up word and write nothing once a launch in front of them gave up (the
+// fold accumulates, and a void sample must not overwrite a slot whose fold was skipped: record_kernels.inc); recover() rewinds
+// the counter and the replay comes through here again.
 static int spectrum_advance(fibhip_ctx *h, int ticks, bool behind_mt)
 {
     SpRec &r = h->sp;
-    r.k += ticks;
-    if (r.k % r.every) return 0;
-    const long long s = r.k / r.every - 1;
-    const unsigned *give_up = behind_mt && h->mt.epochs ? h->mt.give_up_word() : nullptr;
+    long long s;
+    if (!r.advance(ticks, &s)) return 0;
+    const unsigned *give_up = give_up_of(h, behind_mt);
     const size_t npix = r.npix();
     SpecSampleArgs a;
-    a.x = h->slab[h->cur[r.var]] + (size_t)r.var * h->vstride;
-    a.w = r.w;
+    window_fill(h, r, r.var, a);
     a.out = r.ring + (size_t)(s % r.chunk) * npix;
-    a.pitch = h->pitch;
-    a.wpitch = h->d.width;
-    a.r0 = r.r0; a.c0 = r.c0; a.oh = r.oh; a.ow = r.ow; a.by = r.by; a.bx = r.bx;
     a.give_up = give_up;
     const bool mean = r.reduce == FIBHIP_FRAME_MEAN;
-    const bool vec = r.by == 1 && r.bx == 1 && h->pitch == h->d.width && h->d.width % 4 == 0 && r.c0 % 4 == 0 && r.ow % 4 == 0 &&
-                     ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.w) | reinterpret_cast<uintptr_t>(a.out)) & 15u) == 0;
-    {
-        const size_t threads = (size_t)r.oh * (size_t)(vec ? r.ow / 4 : r.ow);
-        const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-        if (int rc = trace_open(h, h->s0, "spectrum_sample_kernel", 0, 0, 0, 0, 1)) return rc;
-        if (vec) hipLaunchKernelGGL((spectrum_sample_kernel<false, true>), grid, block, 0, h->s0, a);
-        else if (mean) hipLaunchKernelGGL((spectrum_sample_kernel<true, false>), grid, block, 0, h->s0, a);
-        else hipLaunchKernelGGL((spectrum_sample_kernel<false, false>), grid, block, 0, h->s0, a);
-        HIPCHK(hipGetLastError());
-        if (int rc = trace_close(h, h->s0)) return rc;
-        h->launches++;
-    }
+    const bool vec = r.by == 1 && r.bx == 1 && window_vec_ok(h, r, a.x) && (reinterpret_cast<uintptr_t>(a.out) & 15u) == 0;
+    const dim3 grid = blocks_of((size_t)r.oh * (size_t)(vec ? r.ow / 4 : r.ow)), block(256);
+    if (int rc = launch_traced(h, "spectrum_sample_kernel", 0, [&] {
+            if (vec) hipLaunchKernelGGL((spectrum_sample_kernel<false, true>), grid, block, 0, h->s0, a);
+            else if (mean) hipLaunchKernelGGL((spectrum_sample_kernel<true, false>), grid, block, 0, h->s0, a);
+            else hipLaunchKernelGGL((spectrum_sample_kernel<false, false>), grid, block, 0, h->s0, a);
+        }))
+        return rc;
     if ((s + 1) % r.chunk) return 0;
     const int j0 = (int)((s + 1 - r.chunk) % r.nfft);                // the segment position of ring slot 0 (a chunk never straddles a segment)
     const size_t plane = (size_t)r.nb * npix;
-    if (int rc = trace_open(h, h->s0, "spectrum_fold_kernel", 0, 0, 0, 0, 1)) return rc;
-    hipLaunchKernelGGL(spec_fold_pick(r.chunk, std::make_integer_sequence<int, SPEC_MAX_CHUNK>()), dim3((unsigned)((npix + 255) / 256)), dim3(256),
-                       0, h->s0, (const float *)r.ring, r.acc, r.acc + plane, r.acc + 2 * plane, (const float *)r.win,
-                       reinterpret_cast<const float2 *>(r.tw), (const int *)r.bins, npix, r.nfft, r.nb, j0, j0 + r.chunk == r.nfft ? 1 : 0, give_up);
-    HIPCHK(hipGetLastError());
-    if (int rc = trace_close(h, h->s0)) return rc;
-    h->launches++;
-    return 0;
+    return launch_traced(h, "spectrum_fold_kernel", 0, [&] {
+        hipLaunchKernelGGL(spec_fold_pick(r.chunk, std::make_integer_sequence<int, SPEC_MAX_CHUNK>()), blocks_of(npix), block, 0, h->s0,
+                           (const float *)r.ring, r.acc, r.acc + plane, r.acc + 2 * plane, (const float *)r.win,
+                           reinterpret_cast<const float2 *>(r.tw), (const int *)r.bins, npix, r.nfft, r.nb, j0, j0 + r.chunk == r.nfft ? 1 : 0, give_up);
+    });
 }
-
 static void spectrum_free(fibhip_ctx *h)
 {
     SpRec &r = h->sp;
-    if (r.w) hipFree(r.w);
-    if (r.win) hipFree(r.win);
-    if (r.tw) hipFree(r.tw);
-    if (r.bins) hipFree(r.bins);
-    if (r.ring) hipFree(r.ring);
-    if (r.acc) hipFree(r.acc);
-    if (r.maps) hipFree(r.maps);
-    r.w = r.win = r.tw = r.ring = r.acc = r.maps = nullptr;
-    r.bins = nullptr;
+    dev_free(r.w);
+    dev_free(r.win);
+    dev_free(r.tw);
+    dev_free(r.bins);
+    dev_free(r.ring);
+    dev_free(r.acc);
+    dev_free(r.maps);
     r.on = false;
 }
 
@@ -320,17 +387,13 @@ static int beats_launch(fibhip_ctx *h, bool init, long long s, const unsigned *g
     BeatRec &r = h->bt;
     const size_t npix = r.npix();
     BeatArgs a;
-    a.x = h->slab[h->cur[r.var]] + (size_t)r.var * h->vstride;
-    a.w = r.w;
+    window_fill(h, r, r.var, a);
     a.xp = r.state;
     a.pk = r.state + npix;
     a.n = reinterpret_cast<int *>(r.state + 2 * npix);
     a.t_up = r.ring;
     a.t_down = r.ring + (size_t)r.depth * npix;
     a.peak = r.ring + 2 * (size_t)r.depth * npix;
-    a.pitch = h->pitch;
-    a.wpitch = h->d.width;
-    a.r0 = r.r0; a.c0 = r.c0; a.oh = r.oh; a.ow = r.ow; a.by = r.by; a.bx = r.bx;
     a.depth = r.depth;
     a.init = init ? 1 : 0;
     a.up = r.up;
@@ -340,42 +403,33 @@ static int beats_launch(fibhip_ctx *h, bool init, long long s, const unsigned *g
     a.give_up = give_up;
     const bool mean = r.reduce == FIBHIP_FRAME_MEAN;
     // (the recorder's planes come from hipMalloc and npix is a multiple of 4 here: xp, pk and every row of them are aligned)
-    const bool vec = r.by == 1 && r.bx == 1 && h->pitch == h->d.width && h->d.width % 4 == 0 && r.c0 % 4 == 0 && r.ow % 4 == 0 &&
-                     ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.w) | reinterpret_cast<uintptr_t>(a.xp) |
-                       reinterpret_cast<uintptr_t>(a.pk)) & 15u) == 0;
-    const size_t threads = (size_t)r.oh * (size_t)(vec ? r.ow / 4 : r.ow);
-    const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+    const bool vec = r.by == 1 && r.bx == 1 && window_vec_ok(h, r, a.x) &&
+                     ((reinterpret_cast<uintptr_t>(a.xp) | reinterpret_cast<uintptr_t>(a.pk)) & 15u) == 0;
+    const dim3 grid = blocks_of((size_t)r.oh * (size_t)(vec ? r.ow / 4 : r.ow)), block(256);
     // (the timeline event's K says which path ran: the pixels per thread, 4 on the vector path and 1 on the scalar one)
-    if (int rc = trace_open(h, h->s0, "beat_kernel", vec ? 4 : 1, 0, 0, 0, 1)) return rc;
-    if (vec) hipLaunchKernelGGL((beat_kernel<false, true>), grid, block, 0, h->s0, a);
-    else if (mean) hipLaunchKernelGGL((beat_kernel<true, false>), grid, block, 0, h->s0, a);
-    else hipLaunchKernelGGL((beat_kernel<false, false>), grid, block, 0, h->s0, a);
-    HIPCHK(hipGetLastError());
-    if (int rc = trace_close(h, h->s0)) return rc;
-    h->launches++;
-    return 0;
+    return launch_traced(h, "beat_kernel", vec ? 4 : 1, [&] {
+        if (vec) hipLaunchKernelGGL((beat_kernel<false, true>), grid, block, 0, h->s0, a);
+        else if (mean) hipLaunchKernelGGL((beat_kernel<true, false>), grid, block, 0, h->s0, a);
+        else hipLaunchKernelGGL((beat_kernel<false, false>), grid, block, 0, h->s0, a);
+    });
 }
 
-// The beat recorder's hook behind a launch of `ticks` ticks, the spectrum recorder's step for step: at a sample tick beat_kernel
-// compares the pixel plane with the previous sample's and records the events.  `behind_mt`: as for spectrum_advance — the kernel
-// is handed the give-up word and writes nothing once a launch in front of it gave up; recover() rewinds the counter and the
-// replay comes through here again, with the same sample index.
+// The beat recorder's hook behind a launch of `ticks` ticks: at a sample tick beat_kernel compares the pixel plane with the
+// previous sample's and records the events.  `behind_mt`: as for spectrum_advance — the kernel is handed the give-up word and
+// writes nothing once a launch in front of it gave up; recover() rewinds the counter and the replay comes through here again,
+// with the same sample index.
 static int beats_advance(fibhip_ctx *h, int ticks, bool behind_mt)
 {
-    BeatRec &r = h->bt;
-    r.k += ticks;
-    if (r.k % r.every) return 0;
-    return beats_launch(h, false, r.k / r.every - 1, behind_mt && h->mt.epochs ? h->mt.give_up_word() : nullptr);
+    long long s;
+    return h->bt.advance(ticks, &s) ? beats_launch(h, false, s, give_up_of(h, behind_mt)) : 0;
 }
-
 static void beats_free(fibhip_ctx *h)
 {
     BeatRec &r = h->bt;
-    if (r.w) hipFree(r.w);
-    if (r.state) hipFree(r.state);
-    if (r.ring) hipFree(r.ring);
-    if (r.maps) hipFree(r.maps);
-    r.w = r.state = r.ring = r.maps = nullptr;
+    dev_free(r.w);
+    dev_free(r.state);
+    dev_free(r.ring);
+    dev_free(r.maps);
     r.on = false;
 }
 
@@ -394,9 +448,7 @@ static int stim_entry_from(const fibhip_ctx *h, const char *who, const char *wha
     e.var = var; e.mode = mode;
     const float untouched = mode == FIBHIP_STIM_MAX ? ninf : 0.f;
     if (shape == FIBHIP_STIM_RECT) {
-        if (r0 < 0 || r1 > H || c0 < 0 || c1 > W || r0 >= r1 || c0 >= c1)
-            return fail(FIBHIP_EINVAL, "%s: %s %d: rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", who, what, i, r0, r1, c0,
-                        c1, H, W);
+        if (int rc = rect_check(h, r0, r1, c0, c1, "%s: %s %d: ", who, what, i)) return rc;
         if (!std::isfinite(v)) return fail(FIBHIP_EINVAL, "%s: %s %d: v must be finite (got %g)", who, what, i, v);
         if (!(std::isfinite(floor) || (mode == FIBHIP_STIM_MAX && floor == ninf)))
             return fail(FIBHIP_EINVAL, "%s: %s %d: floor must be finite%s (got %g)", who, what, i, mode == FIBHIP_STIM_MAX ? " or -inf" : "", floor);
@@ -420,19 +472,52 @@ static int stim_entry_from(const fibhip_ctx *h, const char *who, const char *wha
         if (b_r0 >= b_r1) b_r0 = b_r1 = b_c0 = b_c1 = 0;
         e.b_r0 = b_r0; e.b_r1 = b_r1; e.b_c0 = b_c0; e.b_c1 = b_c1;
     }
-#if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
-    e.slow = h->d.model == FIBHIP_COURT && !((Courtemanche::FAST_MASK >> var) & 1u);
-#endif
+    e.slow = h->d.model == FIBHIP_COURT && slow_array(var);
     return 0;
 }
 static void stim_due_fill(const fibhip_ctx *h, const StimEntry &e, float *planes, StimDue &d)
 {
-    d.x = h->slab[h->cur[e.var]] + (size_t)e.var * h->vstride;
+    d.x = array_of(h, e.var);
     d.plane = e.plane >= 0 ? planes + (size_t)e.plane * h->cells : nullptr;
     d.mode = e.mode;
     d.b_r0 = e.b_r0; d.b_r1 = e.b_r1; d.b_c0 = e.b_c0; d.b_c1 = e.b_c1;
     d.r0 = e.r0; d.r1 = e.r1; d.c0 = e.c0; d.c1 = e.c1;
     d.v = e.v; d.floor = e.floor;
+}
+// The StimArgs of one launch of stim_kernel or stim_gated_kernel.  stim_args_add: entry `e` becomes a.e[i], its visit box joins
+// the launch's and its pointers join `align`.  stim_args_finish: the launch visits the union of the boxes — false: planes that
+// leave every cell untouched, nothing to visit —, four cells per thread (`vec`) where the slab allows it
+static void stim_args_begin(StimArgs &a)
+{
+    memset(&a, 0, sizeof a);
+    a.r0 = a.c0 = INT_MAX;
+}
+static StimDue &stim_args_add(const fibhip_ctx *h, const StimEntry &e, float *planes, StimArgs &a, size_t i, uintptr_t &align)
+{
+    StimDue &d = a.e[i];
+    stim_due_fill(h, e, planes, d);
+    align |= reinterpret_cast<uintptr_t>(d.x) | reinterpret_cast<uintptr_t>(d.plane);
+    if (e.b_r0 < e.b_r1) {
+        a.r0 = imin(a.r0, e.b_r0); a.r1 = imax(a.r1, e.b_r1);
+        a.c0 = imin(a.c0, e.b_c0); a.c1 = imax(a.c1, e.b_c1);
+    }
+    return d;
+}
+static bool stim_args_finish(const fibhip_ctx *h, StimArgs &a, int n, uintptr_t align, bool behind_mt, bool &vec, dim3 &grid)
+{
+    if (a.r0 >= a.r1) return false;
+    const int W = h->d.width;
+    a.n = n;
+    a.W = W;
+    a.pitch = h->pitch;
+    a.give_up = give_up_of(h, behind_mt);
+    vec = h->pitch == W && W % 4 == 0 && (align & 15u) == 0;
+    if (vec) {
+        a.c0 = a.c0 / 4 * 4;
+        a.c1 = (a.c1 + 3) / 4 * 4;                                  // (<= W: W is a multiple of 4)
+    }
+    grid = blocks_of((size_t)(a.r1 - a.r0) * (size_t)((a.c1 - a.c0) / (vec ? 4 : 1)));
+    return true;
 }
 
 static_assert(STIM_MAX_DUE <= FIBHIP_MAX_STIM_ENTRIES && (int)STIM_MAX == (int)FIBHIP_STIM_MAX && (int)STIM_ADD == (int)FIBHIP_STIM_ADD,
@@ -458,52 +543,32 @@ static int stim_advance(fibhip_ctx *h, int ticks, bool behind_mt)
     r.next = stim_next(r);
     if (due.empty()) return 0;
     std::stable_sort(due.begin(), due.end(), [](const StimEntry *a, const StimEntry *b) { return a->var < b->var; });
-    const int W = h->d.width;
     for (size_t first = 0; first < due.size(); first += STIM_MAX_DUE) {
         const size_t n = due.size() - first < (size_t)STIM_MAX_DUE ? due.size() - first : (size_t)STIM_MAX_DUE;
         StimArgs a;
-        memset(&a, 0, sizeof a);
-        a.r0 = a.c0 = INT_MAX;
+        stim_args_begin(a);
         uintptr_t align = 0;
         for (size_t i = 0; i < n; ++i) {
             const StimEntry &e = *due[first + i];
-            StimDue &d = a.e[i];
-            stim_due_fill(h, e, r.planes, d);
+            StimDue &d = stim_args_add(h, e, r.planes, a, i, align);
             d.load = i == 0 || due[first + i - 1]->var != e.var;
             d.store = i + 1 == n || due[first + i + 1]->var != e.var;
-            align |= reinterpret_cast<uintptr_t>(d.x) | reinterpret_cast<uintptr_t>(d.plane);
-            if (e.b_r0 < e.b_r1) {
-                a.r0 = imin(a.r0, e.b_r0); a.r1 = imax(a.r1, e.b_r1);
-                a.c0 = imin(a.c0, e.b_c0); a.c1 = imax(a.c1, e.b_c1);
-            }
             if (e.slow && h->use_agg) h->agg_dirty = true;          // as fibhip_set_state: the next tick forms the aggregates afresh
         }
-        if (a.r0 >= a.r1) continue;                                 // (planes that leave every cell untouched: nothing to visit)
-        a.n = (int)n;
-        a.W = W;
-        a.pitch = h->pitch;
-        a.give_up = behind_mt && h->mt.epochs ? h->mt.give_up_word() : nullptr;
-        const bool vec = h->pitch == W && W % 4 == 0 && (align & 15u) == 0;
-        if (vec) {
-            a.c0 = a.c0 / 4 * 4;
-            a.c1 = (a.c1 + 3) / 4 * 4;                              // (<= W: W is a multiple of 4)
-        }
-        const size_t threads = (size_t)(a.r1 - a.r0) * (size_t)((a.c1 - a.c0) / (vec ? 4 : 1));
-        const dim3 grid((unsigned)((threads + 255) / 256));
-        if (int rc = trace_open(h, h->s0, "stim_kernel", 0, 0, 0, 0, 1)) return rc;
-        if (vec) hipLaunchKernelGGL(stim_kernel<true>, grid, dim3(256), 0, h->s0, a);
-        else hipLaunchKernelGGL(stim_kernel<false>, grid, dim3(256), 0, h->s0, a);
-        HIPCHK(hipGetLastError());
-        if (int rc = trace_close(h, h->s0)) return rc;
-        h->launches++;
+        bool vec;
+        dim3 grid;
+        if (!stim_args_finish(h, a, (int)n, align, behind_mt, vec, grid)) continue;
+        if (int rc = launch_traced(h, "stim_kernel", 0, [&] {
+                if (vec) hipLaunchKernelGGL(stim_kernel<true>, grid, dim3(256), 0, h->s0, a);
+                else hipLaunchKernelGGL(stim_kernel<false>, grid, dim3(256), 0, h->s0, a);
+            }))
+            return rc;
     }
     return 0;
 }
-
 static void stim_free(fibhip_ctx *h)
 {
-    if (h->stim.planes) hipFree(h->stim.planes);
-    h->stim.planes = nullptr;
+    dev_free(h->stim.planes);
     h->stim.entries.clear();
     h->stim.on = false;
 }
@@ -521,11 +586,9 @@ static_assert(TRIG_MAX == FIBHIP_MAX_TRIG_SENSORS && TRIG_MAX == FIBHIP_MAX_TRIG
 static int trig_advance(fibhip_ctx *h, int ticks, bool behind_mt)
 {
     TrigRec &r = h->trig;
-    r.k += ticks;
-    if (r.k % r.every) return 0;
-    const long long s = r.k / r.every - 1;
+    long long s;
+    if (!r.advance(ticks, &s)) return 0;
     if (s >= r.cap) return fail(FIBHIP_EINVAL, "trigger program: log full");                    // (fibhip_step refuses before this)
-    const int W = h->d.width;
     SenseArgs a;
     a.slab0 = h->slab[0];
     a.slab1 = h->slab[1];
@@ -534,9 +597,9 @@ static int trig_advance(fibhip_ctx *h, int ticks, bool behind_mt)
     for (int i = 0; i < r.nsensors; ++i) {
         const int v = r.vars[i];
         if (h->cur[v]) a.cur_mask |= 1u << v;
-        align |= reinterpret_cast<uintptr_t>(h->slab[h->cur[v]] + (size_t)v * h->vstride);
+        align |= reinterpret_cast<uintptr_t>(array_of(h, v));
     }
-    a.W = W;
+    a.W = h->d.width;
     a.pitch = h->pitch;
     a.vstride = h->vstride;
     a.cells = h->cells;
@@ -544,79 +607,49 @@ static int trig_advance(fibhip_ctx *h, int ticks, bool behind_mt)
     a.masks = r.masks;
     a.part = r.part;
     const bool vec = r.cut_vec && (align & 15u) == 0;
-    {
-        const dim3 grid((unsigned)r.max_chunks[vec], (unsigned)r.nsensors);
-        if (int rc = trace_open(h, h->s0, vec ? "sense_kernel<true>" : "sense_kernel<false>", 0, 0, 0, 0, 1)) return rc;
-        if (vec) hipLaunchKernelGGL(sense_kernel<true>, grid, dim3(SENSE_THREADS), 0, h->s0, a);
-        else hipLaunchKernelGGL(sense_kernel<false>, grid, dim3(SENSE_THREADS), 0, h->s0, a);
-        HIPCHK(hipGetLastError());
-        if (int rc = trace_close(h, h->s0)) return rc;
-        h->launches++;
-    }
-    if (int rc = trace_open(h, h->s0, "trigger_kernel", 0, 0, 0, 0, 1)) return rc;
-    hipLaunchKernelGGL(trigger_kernel, dim3(1), dim3(256), 0, h->s0, r.sites, r.nsensors, vec ? 1 : 0, r.part, r.rules, r.nrules, r.rows, r.fire, (int)s);
-    HIPCHK(hipGetLastError());
-    if (int rc = trace_close(h, h->s0)) return rc;
-    h->launches++;
+    const dim3 sgrid((unsigned)r.max_chunks[vec], (unsigned)r.nsensors);
+    if (int rc = launch_traced(h, vec ? "sense_kernel<true>" : "sense_kernel<false>", 0, [&] {
+            if (vec) hipLaunchKernelGGL(sense_kernel<true>, sgrid, dim3(SENSE_THREADS), 0, h->s0, a);
+            else hipLaunchKernelGGL(sense_kernel<false>, sgrid, dim3(SENSE_THREADS), 0, h->s0, a);
+        }))
+        return rc;
+    if (int rc = launch_traced(h, "trigger_kernel", 0, [&] {
+            hipLaunchKernelGGL(trigger_kernel, dim3(1), dim3(256), 0, h->s0, r.sites, r.nsensors, vec ? 1 : 0, r.part, r.rules, r.nrules, r.rows,
+                               r.fire, (int)s);
+        }))
+        return rc;
     // the gated apply: the union of the rules' visit boxes, every sample (its workgroups leave after two scalar loads when no
     // rule fires)
     StimArgs g;
-    memset(&g, 0, sizeof g);
-    g.r0 = g.c0 = INT_MAX;
+    stim_args_begin(g);
     uintptr_t galign = 0;
     for (int i = 0; i < r.nrules; ++i) {
-        const StimEntry &e = r.stims[i];
-        StimDue &d = g.e[i];
-        stim_due_fill(h, e, r.planes, d);
+        StimDue &d = stim_args_add(h, r.stims[i], r.planes, g, (size_t)i, galign);
         d.load = d.store = 1;
-        galign |= reinterpret_cast<uintptr_t>(d.x) | reinterpret_cast<uintptr_t>(d.plane);
-        if (e.b_r0 < e.b_r1) {
-            g.r0 = imin(g.r0, e.b_r0); g.r1 = imax(g.r1, e.b_r1);
-            g.c0 = imin(g.c0, e.b_c0); g.c1 = imax(g.c1, e.b_c1);
-        }
     }
-    if (g.r0 >= g.r1) return 0;                                     // (planes that leave every cell untouched: nothing to visit)
-    g.n = r.nrules;
-    g.W = W;
-    g.pitch = h->pitch;
-    g.give_up = behind_mt && h->mt.epochs ? h->mt.give_up_word() : nullptr;
-    const bool gvec = h->pitch == W && W % 4 == 0 && (galign & 15u) == 0;
-    if (gvec) {
-        g.c0 = g.c0 / 4 * 4;
-        g.c1 = (g.c1 + 3) / 4 * 4;                                  // (<= W: W is a multiple of 4)
-    }
-    const size_t threads = (size_t)(g.r1 - g.r0) * (size_t)((g.c1 - g.c0) / (gvec ? 4 : 1));
-    const dim3 grid((unsigned)((threads + 255) / 256));
-    if (int rc = trace_open(h, h->s0, gvec ? "stim_gated_kernel<true>" : "stim_gated_kernel<false>", 0, 0, 0, 0, 1)) return rc;
-    if (gvec) hipLaunchKernelGGL(stim_gated_kernel<true>, grid, dim3(256), 0, h->s0, g, (const unsigned *)(r.fire + s));
-    else hipLaunchKernelGGL(stim_gated_kernel<false>, grid, dim3(256), 0, h->s0, g, (const unsigned *)(r.fire + s));
-    HIPCHK(hipGetLastError());
-    if (int rc = trace_close(h, h->s0)) return rc;
-    h->launches++;
-    return 0;
+    bool gvec;
+    dim3 grid;
+    if (!stim_args_finish(h, g, r.nrules, galign, behind_mt, gvec, grid)) return 0;
+    return launch_traced(h, gvec ? "stim_gated_kernel<true>" : "stim_gated_kernel<false>", 0, [&] {
+        if (gvec) hipLaunchKernelGGL(stim_gated_kernel<true>, grid, dim3(256), 0, h->s0, g, (const unsigned *)(r.fire + s));
+        else hipLaunchKernelGGL(stim_gated_kernel<false>, grid, dim3(256), 0, h->s0, g, (const unsigned *)(r.fire + s));
+    });
 }
-
 static void trig_free(fibhip_ctx *h)
 {
     TrigRec &r = h->trig;
-    if (r.sites) hipFree(r.sites);
-    if (r.rules) hipFree(r.rules);
-    if (r.masks) hipFree(r.masks);
-    if (r.planes) hipFree(r.planes);
-    if (r.part) hipFree(r.part);
-    if (r.rows) hipFree(r.rows);
-    if (r.fire) hipFree(r.fire);
-    r.sites = nullptr;
-    r.rules = nullptr;
-    r.masks = nullptr;
-    r.planes = nullptr;
-    r.part = nullptr;
-    r.rows = nullptr;
-    r.fire = nullptr;
+    dev_free(r.sites);
+    dev_free(r.rules);
+    dev_free(r.masks);
+    dev_free(r.planes);
+    dev_free(r.part);
+    dev_free(r.rows);
+    dev_free(r.fire);
     r.stims.clear();
     r.on = false;
 }
 
+// ---- the entry points ---------------------------------------------------------------------------------------------------
 // ---- activation recorder ------------------------------------------------------------------------------------------------
 extern "C" int fibhip_observe_begin(fibhip_t h, int var, float up, float down)
 {
@@ -624,21 +657,16 @@ extern "C" int fibhip_observe_begin(fibhip_t h, int var, float up, float down)
     if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "observe_begin: bad var %d", var);
     if (std::isnan(up) || std::isnan(down) || down > up)
         return fail(FIBHIP_EINVAL, "observe_begin: thresholds must be numbers with down <= up (got up %g, down %g)", up, down);
-    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "observe_begin: not on a row block (a handle with ghost rows)");
-    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "observe_begin inside an open tick");
+    if (int rc = attach_refusals(h, "observe_begin")) return rc;
     // everything accepted so far runs unobserved and is confirmed: a multi-tick launch that gave up is recovered HERE, before
     // Vp is copied (the recorder must not start from the slab such a launch left void)
     FLUSH(h);
     SYNC_S0(h);
     const size_t n = h->cells;
     if (!h->obs.buf) HIPCHK(hipMalloc((void **)&h->obs.buf, 6 * n * sizeof(float)));
-    HIPCHK(hipMemcpy2DAsync(h->obs.buf, (size_t)h->d.width * sizeof(float), h->slab[h->cur[var]] + (size_t)var * h->vstride,
-                            (size_t)h->pitch * sizeof(float), (size_t)h->d.width * sizeof(float), (size_t)h->d.height,
-                            hipMemcpyDeviceToDevice, h->s0));
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    unsigned nan_bits;
-    memcpy(&nan_bits, &qnan, sizeof nan_bits);
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(h->obs.buf + n), (int)nan_bits, 4 * n, h->s0));   // first | last | prev | apd
+    HIPCHK(hipMemcpy2DAsync(h->obs.buf, (size_t)h->d.width * sizeof(float), array_of(h, var), (size_t)h->pitch * sizeof(float),
+                            (size_t)h->d.width * sizeof(float), (size_t)h->d.height, hipMemcpyDeviceToDevice, h->s0));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(h->obs.buf + n), (int)qnan_bits(), 4 * n, h->s0));   // first | last | prev | apd
     HIPCHK(hipMemsetAsync(h->obs.buf + 5 * n, 0, n * sizeof(int), h->s0));                      // count
     h->obs.on = true;
     h->obs.var = var;
@@ -692,8 +720,7 @@ extern "C" int fibhip_electrode_begin(fibhip_t h, int var, int n, const int *rec
     if (every < 1) return fail(FIBHIP_EINVAL, "electrode_begin: every must be >= 1 (got %d)", every);
     if (capacity < 1 || capacity > (long long)(SIZE_MAX / sizeof(float) / (size_t)n))
         return fail(FIBHIP_EINVAL, "electrode_begin: bad capacity %lld", capacity);
-    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "electrode_begin: not on a row block (a handle with ghost rows)");
-    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "electrode_begin inside an open tick");
+    if (int rc = attach_refusals(h, "electrode_begin")) return rc;
     // the chunk table: one chunk per patch of up to EL_CHUNK cells, larger patches in at most 256 equal chunks
     std::vector<ElChunk> chunks;
     std::vector<ElComb> combs;
@@ -701,9 +728,7 @@ extern "C" int fibhip_electrode_begin(fibhip_t h, int var, int n, const int *rec
     int nparts = 0;
     for (int e = 0; e < n; ++e) {
         const int r0 = rects[4 * e], r1 = rects[4 * e + 1], c0 = rects[4 * e + 2], c1 = rects[4 * e + 3];
-        if (r0 < 0 || r1 > h->d.height || c0 < 0 || c1 > h->d.width || r0 >= r1 || c0 >= c1)
-            return fail(FIBHIP_EINVAL, "electrode_begin: electrode %d: rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid",
-                        e, r0, r1, c0, c1, h->d.height, h->d.width);
+        if (int rc = rect_check(h, r0, r1, c0, c1, "electrode_begin: electrode %d: ", e)) return rc;
         const size_t m = (size_t)(r1 - r0) * (size_t)(c1 - c0);
         if (woff + m > 0x7FFFFFFFu) return fail(FIBHIP_EINVAL, "electrode_begin: more than 2^31 - 1 weights");
         for (size_t i = 0; i < m; ++i)
@@ -748,11 +773,10 @@ extern "C" int fibhip_electrode_begin(fibhip_t h, int var, int n, const int *rec
     HIPCHK(hipMemsetAsync(h->el.trace, 0, (size_t)capacity * (size_t)n * sizeof(float), h->s0));
     HIPCHK(wait_stream(h->s0));                        // `chunks`, `combs` and the caller's arrays are free again
     h->el.on = true;
+    h->el.start(every, capacity);
+    h->el.before_slow = slow_array(var);
     h->el.var = var;
     h->el.n = n;
-    h->el.every = every;
-    h->el.cap = capacity;
-    h->el.k = 0;
     h->el.nchunks = (int)chunks.size();
     h->el.ncomb = (int)combs.size();
     return 0;
@@ -764,7 +788,7 @@ extern "C" int fibhip_electrode_count(fibhip_t h, long long *samples)
     if (!samples) return fail(FIBHIP_EINVAL, "electrode_count: null argument");
     if (!h->el.on) return fail(FIBHIP_EINVAL, "electrode_count: no recorder attached (fibhip_electrode_begin)");
     SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = (h->el.k + h->pending) / h->el.every;   // (ticks accepted but not launched yet are sampled when they are)
+    *samples = h->el.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
     return 0;
 }
 
@@ -773,28 +797,19 @@ extern "C" int fibhip_electrode_read(fibhip_t h, long long first, long long coun
     NEED(h);
     if (!h->el.on) return fail(FIBHIP_EINVAL, "electrode_read: no recorder attached (fibhip_electrode_begin)");
     FLUSH(h);
-    const long long taken = h->el.k / h->el.every;
-    if (first < 0 || count < 0 || first + count > taken)
-        return fail(FIBHIP_EINVAL, "electrode_read: samples [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (int rc = range_check("electrode_read", "samples", first, count, h->el.taken())) return rc;
     if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "electrode_read: null destination");
-    for (int pass = 0; pass < 2; ++pass) {
-        const long long fb0 = h->journal.n_fallbacks;
+    return read_confirmed(h, [&] {
         if (count > 0)
             HIPCHK(hipMemcpyAsync(dst, h->el.trace + (size_t)first * h->el.n, (size_t)count * h->el.n * sizeof(float), hipMemcpyDeviceToHost, h->s0));
-        SYNC_S0(h);
-        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and re-sampled, copy again)
-    }
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" int fibhip_electrode_end(fibhip_t h)
 {
     NEED(h);
-    if (!h->el.on) return 0;
-    FLUSH(h);                                          // the ticks accepted while attached are sampled
-    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
-    electrode_free(h);
-    return 0;
+    return detach(h, h->el.on, electrode_free);
 }
 
 // ---- tip recorder -------------------------------------------------------------------------------------------------------
@@ -809,8 +824,7 @@ extern "C" int fibhip_tips_begin(fibhip_t h, int var, int var2, float a0, float 
     if (max_tips < 1 || max_tips > FIBHIP_MAX_TIPS) return fail(FIBHIP_EINVAL, "tips_begin: 1 .. %d tips per sample (got %d)", FIBHIP_MAX_TIPS, max_tips);
     if (capacity < 1 || capacity > (long long)(SIZE_MAX / (4 * sizeof(int)) / (size_t)max_tips))
         return fail(FIBHIP_EINVAL, "tips_begin: bad capacity %lld", capacity);
-    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "tips_begin: not on a row block (a handle with ghost rows)");
-    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "tips_begin inside an open tick");
+    if (int rc = attach_refusals(h, "tips_begin")) return rc;
     if (h->d.height < 2 || h->d.width < 2) return fail(FIBHIP_EINVAL, "tips_begin: a %d x %d grid has no plaquette", h->d.height, h->d.width);
     // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
     // tick k = 0 is defined (the rule of fibhip_electrode_begin)
@@ -829,14 +843,13 @@ extern "C" int fibhip_tips_begin(fibhip_t h, int var, int var2, float a0, float 
     HIPCHK(hipMemsetAsync(h->tip.counts, 0, (size_t)capacity * 3 * sizeof(int), h->s0));
     HIPCHK(wait_stream(h->s0));                        // the caller's mask is free again
     h->tip.on = true;
+    h->tip.start(every, capacity);
+    h->tip.before_slow = slow_array(var) || slow_array(var2);
     h->tip.var = var;
     h->tip.var2 = var2;
     h->tip.a0 = a0;
     h->tip.b0 = b0;
-    h->tip.every = every;
     h->tip.max_tips = max_tips;
-    h->tip.cap = capacity;
-    h->tip.k = 0;
     return 0;
 }
 
@@ -846,7 +859,7 @@ extern "C" int fibhip_tips_count(fibhip_t h, long long *samples)
     if (!samples) return fail(FIBHIP_EINVAL, "tips_count: null argument");
     if (!h->tip.on) return fail(FIBHIP_EINVAL, "tips_count: no recorder attached (fibhip_tips_begin)");
     SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = (h->tip.k + h->pending) / h->tip.every; // (ticks accepted but not launched yet are sampled when they are)
+    *samples = h->tip.taken_with(h->pending);          // (ticks accepted but not launched yet are sampled when they are)
     return 0;
 }
 
@@ -855,33 +868,24 @@ extern "C" int fibhip_tips_read(fibhip_t h, long long first, long long count, in
     NEED(h);
     if (!h->tip.on) return fail(FIBHIP_EINVAL, "tips_read: no recorder attached (fibhip_tips_begin)");
     FLUSH(h);
-    const long long taken = h->tip.k / h->tip.every;
-    if (first < 0 || count < 0 || first + count > taken)
-        return fail(FIBHIP_EINVAL, "tips_read: samples [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (int rc = range_check("tips_read", "samples", first, count, h->tip.taken())) return rc;
     if (count > 0 && !counts) return fail(FIBHIP_EINVAL, "tips_read: null destination");
     const size_t per = (size_t)h->tip.max_tips * 4;
-    for (int pass = 0; pass < 2; ++pass) {
-        const long long fb0 = h->journal.n_fallbacks;
+    return read_confirmed(h, [&] {
         if (count > 0) {
             HIPCHK(hipMemcpyAsync(counts, h->tip.counts + 3 * (size_t)first, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost, h->s0));
             if (records)
                 HIPCHK(hipMemcpyAsync(records, h->tip.records + (size_t)first * per, (size_t)count * per * sizeof(int), hipMemcpyDeviceToHost,
                                       h->s0));
         }
-        SYNC_S0(h);
-        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and re-sampled, copy again)
-    }
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" int fibhip_tips_end(fibhip_t h)
 {
     NEED(h);
-    if (!h->tip.on) return 0;
-    FLUSH(h);                                          // the ticks accepted while attached are sampled
-    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
-    tips_free(h);
-    return 0;
+    return detach(h, h->tip.on, tips_free);
 }
 
 // ---- frame recorder -----------------------------------------------------------------------------------------------------
@@ -891,16 +895,9 @@ extern "C" int fibhip_frames_begin(fibhip_t h, int var, const int *window, int b
     NEED(h);
     if (!window) return fail(FIBHIP_EINVAL, "frames_begin: null window");
     if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "frames_begin: bad var %d", var);
-    const int r0 = window[0], r1 = window[1], c0 = window[2], c1 = window[3];
-    if (r0 < 0 || r1 > h->d.height || c0 < 0 || c1 > h->d.width || r0 >= r1 || c0 >= c1)
-        return fail(FIBHIP_EINVAL, "frames_begin: the window rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", r0, r1,
-                    c0, c1, h->d.height, h->d.width);
-    if (by < 1 || by > FIBHIP_MAX_FRAME_BLOCK || bx < 1 || bx > FIBHIP_MAX_FRAME_BLOCK)
-        return fail(FIBHIP_EINVAL, "frames_begin: a block is 1 .. %d cells each way (got %d x %d)", FIBHIP_MAX_FRAME_BLOCK, by, bx);
-    const int oh = (r1 - r0) / by, ow = (c1 - c0) / bx;
-    if (oh < 1 || ow < 1)
-        return fail(FIBHIP_EINVAL, "frames_begin: a window of %d x %d cells holds no block of %d x %d", r1 - r0, c1 - c0, by, bx);
-    if (reduce != FIBHIP_FRAME_POINT && reduce != FIBHIP_FRAME_MEAN) return fail(FIBHIP_EINVAL, "frames_begin: bad reduction %d", reduce);
+    Window px;
+    if (int rc = window_from(h, "frames_begin", window, by, bx, reduce, px)) return rc;
+    const int oh = px.oh, ow = px.ow;
     if (format != FIBHIP_FRAME_F32 && format != FIBHIP_FRAME_U8) return fail(FIBHIP_EINVAL, "frames_begin: bad format %d", format);
     if (std::isnan(lo)) return fail(FIBHIP_EINVAL, "frames_begin: the level lo must be a number");
     if (!std::isfinite(span) || span == 0.f) return fail(FIBHIP_EINVAL, "frames_begin: span must be finite and not zero (got %g)", span);
@@ -908,13 +905,13 @@ extern "C" int fibhip_frames_begin(fibhip_t h, int var, const int *window, int b
     if (first < 1 || first > every) return fail(FIBHIP_EINVAL, "frames_begin: first must be 1 .. every = %d (got %d)", every, first);
     const size_t per = (size_t)oh * (size_t)ow * (format == FIBHIP_FRAME_U8 ? 1u : 4u);
     if (capacity < 1 || capacity > (long long)(SIZE_MAX / 2 / per)) return fail(FIBHIP_EINVAL, "frames_begin: bad capacity %lld", capacity);
-    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "frames_begin: not on a row block (a handle with ghost rows)");
-    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "frames_begin inside an open tick");
+    if (int rc = attach_refusals(h, "frames_begin")) return rc;
     // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
     // tick 0 is defined (the rule of fibhip_electrode_begin)
     FLUSH(h);
     SYNC_S0(h);
     frames_free(h);
+    static_cast<Window &>(h->fr) = px;
     bool ok = hipMalloc((void **)&h->fr.cube, (size_t)capacity * per) == hipSuccess;
     if (ok && weight) ok = hipMalloc((void **)&h->fr.w, h->cells * sizeof(float)) == hipSuccess;
     if (!ok) {
@@ -927,15 +924,12 @@ extern "C" int fibhip_frames_begin(fibhip_t h, int var, const int *window, int b
         HIPCHK(wait_stream(h->s0));                    // the caller's plane is free again
     }
     h->fr.on = true;
+    h->fr.start(every, capacity, every - first);       // sample s follows tick first + s * every, ticks counted from 1 here
+    h->fr.before_slow = slow_array(var);
     h->fr.var = var;
-    h->fr.every = every;
-    h->fr.r0 = r0; h->fr.c0 = c0; h->fr.oh = oh; h->fr.ow = ow; h->fr.by = by; h->fr.bx = bx;
-    h->fr.reduce = reduce;
     h->fr.format = format;
     h->fr.lo = lo;
     h->fr.span = span;
-    h->fr.cap = capacity;
-    h->fr.k = every - first;                           // sample s follows tick first + s * every, ticks counted from 1 here
     return 0;
 }
 
@@ -945,7 +939,7 @@ extern "C" int fibhip_frames_count(fibhip_t h, long long *samples)
     if (!samples) return fail(FIBHIP_EINVAL, "frames_count: null argument");
     if (!h->fr.on) return fail(FIBHIP_EINVAL, "frames_count: no recorder attached (fibhip_frames_begin)");
     SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = (h->fr.k + h->pending) / h->fr.every;   // (ticks accepted but not launched yet are sampled when they are)
+    *samples = h->fr.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
     return 0;
 }
 
@@ -964,28 +958,19 @@ extern "C" int fibhip_frames_read(fibhip_t h, long long first, long long count, 
     NEED(h);
     if (!h->fr.on) return fail(FIBHIP_EINVAL, "frames_read: no recorder attached (fibhip_frames_begin)");
     FLUSH(h);
-    const long long taken = h->fr.k / h->fr.every;
-    if (first < 0 || count < 0 || first + count > taken)
-        return fail(FIBHIP_EINVAL, "frames_read: frames [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (int rc = range_check("frames_read", "frames", first, count, h->fr.taken())) return rc;
     if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "frames_read: null destination");
     const size_t per = h->fr.frame_bytes();
-    for (int pass = 0; pass < 2; ++pass) {
-        const long long fb0 = h->journal.n_fallbacks;
+    return read_confirmed(h, [&] {
         if (count > 0) HIPCHK(hipMemcpyAsync(dst, h->fr.cube + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost, h->s0));
-        SYNC_S0(h);
-        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and re-sampled, copy again)
-    }
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" int fibhip_frames_end(fibhip_t h)
 {
     NEED(h);
-    if (!h->fr.on) return 0;
-    FLUSH(h);                                          // the ticks accepted while attached are sampled
-    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
-    frames_free(h);
-    return 0;
+    return detach(h, h->fr.on, frames_free);
 }
 
 // ---- statistics recorder ------------------------------------------------------------------------------------------------
@@ -1032,8 +1017,7 @@ extern "C" int fibhip_stats_begin(fibhip_t h, int ncols, const fibhip_stat_col *
             if (!std::isfinite(weight[i]))
                 return fail(FIBHIP_EINVAL, "stats_begin: the weight plane has a value that is not finite (row %zu, column %zu)",
                             i / (size_t)h->d.width, i % (size_t)h->d.width);
-    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "stats_begin: not on a row block (a handle with ghost rows)");
-    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "stats_begin inside an open tick");
+    if (int rc = attach_refusals(h, "stats_begin")) return rc;
     if (h->st.on) return fail(FIBHIP_EINVAL, "stats_begin: a recorder is attached already (fibhip_stats_end first)");
     // stats_kernel counts cells in 32 bits, and a thread looks up to one batch beyond its chunk's end before it drops the cell
     if (h->cells > (size_t)UINT_MAX - 4u * ST_VBATCH * ST_THREADS)
@@ -1079,12 +1063,14 @@ extern "C" int fibhip_stats_begin(fibhip_t h, int ncols, const fibhip_stat_col *
     HIPCHK(hipMemsetAsync(r.trace, 0, (size_t)capacity * (size_t)ncols * sizeof(double), h->s0));
     HIPCHK(wait_stream(h->s0));                        // the tables and the caller's planes are free again
     r.on = true;
+    r.start(every, capacity);
     r.ncols = ncols;
     r.narr = (int)arrs.size();
-    for (int a = 0; a < r.narr; ++a) r.vars[a] = arrs[a].var;
-    r.every = every;
-    r.cap = capacity;
-    r.k = 0;
+    r.before_slow = false;
+    for (int a = 0; a < r.narr; ++a) {
+        r.vars[a] = arrs[a].var;
+        r.before_slow |= slow_array(r.vars[a]);
+    }
     r.nchunks = (int)chunks.size();
     return 0;
 }
@@ -1095,7 +1081,7 @@ extern "C" int fibhip_stats_count(fibhip_t h, long long *samples)
     if (!samples) return fail(FIBHIP_EINVAL, "stats_count: null argument");
     if (!h->st.on) return fail(FIBHIP_EINVAL, "stats_count: no recorder attached (fibhip_stats_begin)");
     SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = (h->st.k + h->pending) / h->st.every;   // (ticks accepted but not launched yet are sampled when they are)
+    *samples = h->st.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
     return 0;
 }
 
@@ -1104,29 +1090,20 @@ extern "C" int fibhip_stats_read(fibhip_t h, long long first, long long count, d
     NEED(h);
     if (!h->st.on) return fail(FIBHIP_EINVAL, "stats_read: no recorder attached (fibhip_stats_begin)");
     FLUSH(h);
-    const long long taken = h->st.k / h->st.every;
-    if (first < 0 || count < 0 || first + count > taken)
-        return fail(FIBHIP_EINVAL, "stats_read: samples [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (int rc = range_check("stats_read", "samples", first, count, h->st.taken())) return rc;
     if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "stats_read: null destination");
-    for (int pass = 0; pass < 2; ++pass) {
-        const long long fb0 = h->journal.n_fallbacks;
+    return read_confirmed(h, [&] {
         if (count > 0)
             HIPCHK(hipMemcpyAsync(dst, h->st.trace + (size_t)first * h->st.ncols, (size_t)count * h->st.ncols * sizeof(double),
                                   hipMemcpyDeviceToHost, h->s0));
-        SYNC_S0(h);
-        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and re-sampled, copy again)
-    }
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" int fibhip_stats_end(fibhip_t h)
 {
     NEED(h);
-    if (!h->st.on) return 0;
-    FLUSH(h);                                          // the ticks accepted while attached are sampled
-    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
-    stats_free(h);
-    return 0;
+    return detach(h, h->st.on, stats_free);
 }
 
 // ---- spectrum recorder --------------------------------------------------------------------------------------------------
@@ -1136,16 +1113,9 @@ extern "C" int fibhip_spectrum_begin(fibhip_t h, int var, const int *window, int
     NEED(h);
     if (!window || !win || !tw || !bins) return fail(FIBHIP_EINVAL, "spectrum_begin: null argument");
     if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "spectrum_begin: bad var %d", var);
-    const int r0 = window[0], r1 = window[1], c0 = window[2], c1 = window[3];
-    if (r0 < 0 || r1 > h->d.height || c0 < 0 || c1 > h->d.width || r0 >= r1 || c0 >= c1)
-        return fail(FIBHIP_EINVAL, "spectrum_begin: the window rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", r0, r1,
-                    c0, c1, h->d.height, h->d.width);
-    if (by < 1 || by > FIBHIP_MAX_FRAME_BLOCK || bx < 1 || bx > FIBHIP_MAX_FRAME_BLOCK)
-        return fail(FIBHIP_EINVAL, "spectrum_begin: a block is 1 .. %d cells each way (got %d x %d)", FIBHIP_MAX_FRAME_BLOCK, by, bx);
-    const int oh = (r1 - r0) / by, ow = (c1 - c0) / bx;
-    if (oh < 1 || ow < 1)
-        return fail(FIBHIP_EINVAL, "spectrum_begin: a window of %d x %d cells holds no block of %d x %d", r1 - r0, c1 - c0, by, bx);
-    if (reduce != FIBHIP_FRAME_POINT && reduce != FIBHIP_FRAME_MEAN) return fail(FIBHIP_EINVAL, "spectrum_begin: bad reduction %d", reduce);
+    Window px;
+    if (int rc = window_from(h, "spectrum_begin", window, by, bx, reduce, px)) return rc;
+    const int oh = px.oh, ow = px.ow;
     if (every < 1) return fail(FIBHIP_EINVAL, "spectrum_begin: every must be >= 1 (got %d)", every);
     if (nfft < FIBHIP_SPECTRUM_MIN_NFFT || nfft > FIBHIP_SPECTRUM_MAX_NFFT)
         return fail(FIBHIP_EINVAL, "spectrum_begin: nfft must be %d .. %d (got %d)", FIBHIP_SPECTRUM_MIN_NFFT, FIBHIP_SPECTRUM_MAX_NFFT, nfft);
@@ -1157,17 +1127,17 @@ extern "C" int fibhip_spectrum_begin(fibhip_t h, int var, const int *window, int
             return fail(FIBHIP_EINVAL, "spectrum_begin: bin %d names frequency index %d outside [0, nfft / 2 = %d]", i, bins[i], nfft / 2);
         if (i > 0 && bins[i] <= bins[i - 1]) return fail(FIBHIP_EINVAL, "spectrum_begin: the bins must be strictly ascending (bin %d)", i);
     }
-    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "spectrum_begin: not on a row block (a handle with ghost rows)");
+    if (int rc = attach_refusals(h, "spectrum_begin")) return rc;
     if (h->pitch != h->d.width) return fail(FIBHIP_EINVAL, "spectrum_begin: not on a row-interleaved slab");
     if (h->sp.on) return fail(FIBHIP_EINVAL, "spectrum_begin: a recorder is attached already (fibhip_spectrum_end first)");
-    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "spectrum_begin inside an open tick");
     // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
     // tick 0 is defined (the rule of fibhip_electrode_begin)
     FLUSH(h);
     SYNC_S0(h);
     spectrum_free(h);
     SpRec &r = h->sp;
-    const size_t npix = (size_t)oh * (size_t)ow;
+    static_cast<Window &>(r) = px;
+    const size_t npix = px.npix();
     bool ok = hipMalloc((void **)&r.ring, (size_t)chunk * npix * sizeof(float)) == hipSuccess;
     ok = ok && hipMalloc((void **)&r.acc, 3 * (size_t)nb * npix * sizeof(float)) == hipSuccess;
     ok = ok && hipMalloc((void **)&r.maps, 4 * npix * sizeof(float)) == hipSuccess;
@@ -1187,12 +1157,10 @@ extern "C" int fibhip_spectrum_begin(fibhip_t h, int var, const int *window, int
     if (weight) HIPCHK(hipMemcpyAsync(r.w, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
     HIPCHK(wait_stream(h->s0));                        // the caller's tables are free again
     r.on = true;
+    r.start(every, LLONG_MAX);                         // sample s follows tick (s + 1) * every, ticks counted from 1 here
+    r.before_slow = slow_array(var);
     r.var = var;
-    r.every = every;
-    r.r0 = r0; r.c0 = c0; r.oh = oh; r.ow = ow; r.by = by; r.bx = bx;
-    r.reduce = reduce;
     r.nfft = nfft; r.nb = nb; r.chunk = chunk;
-    r.k = 0;                                           // sample s follows tick (s + 1) * every, ticks counted from 1 here
     return 0;
 }
 
@@ -1201,7 +1169,7 @@ extern "C" int fibhip_spectrum_count(fibhip_t h, long long *samples, long long *
     NEED(h);
     if (!h->sp.on) return fail(FIBHIP_EINVAL, "spectrum_count: no recorder attached (fibhip_spectrum_begin)");
     SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    const long long n = (h->sp.k + h->pending) / h->sp.every;        // (ticks accepted but not launched yet are sampled when they are)
+    const long long n = h->sp.taken_with(h->pending);                // (ticks accepted but not launched yet are sampled when they are)
     if (samples) *samples = n;
     if (segments) *segments = n / h->sp.nfft;
     return 0;
@@ -1224,13 +1192,12 @@ extern "C" int fibhip_spectrum_read(fibhip_t h, float *P, long long *segments)
     FLUSH(h);
     const SpRec &r = h->sp;
     const size_t plane = (size_t)r.nb * r.npix();
-    for (int pass = 0; pass < 2; ++pass) {
-        const long long fb0 = h->journal.n_fallbacks;
-        if (P) HIPCHK(hipMemcpyAsync(P, r.acc + 2 * plane, plane * sizeof(float), hipMemcpyDeviceToHost, h->s0));
-        SYNC_S0(h);
-        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and folded again, copy again)
-    }
-    if (segments) *segments = r.k / r.every / r.nfft;
+    if (int rc = read_confirmed(h, [&] {
+            if (P) HIPCHK(hipMemcpyAsync(P, r.acc + 2 * plane, plane * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+            return 0;
+        }))
+        return rc;
+    if (segments) *segments = r.taken() / r.nfft;
     return 0;
 }
 
@@ -1243,33 +1210,22 @@ extern "C" int fibhip_spectrum_peak(fibhip_t h, int a, int b, int halfwidth, int
     if (halfwidth < 0) return fail(FIBHIP_EINVAL, "spectrum_peak: halfwidth must be >= 0 (got %d)", halfwidth);
     FLUSH(h);
     const size_t npix = r.npix(), plane = (size_t)r.nb * npix;
-    for (int pass = 0; pass < 2; ++pass) {
-        const long long fb0 = h->journal.n_fallbacks;
-        const int have = r.k / r.every / r.nfft > 0 ? 1 : 0;
-        if (int rc = trace_open(h, h->s0, "spectrum_peak_kernel", 0, 0, 0, 0, 1)) return rc;
-        hipLaunchKernelGGL(spectrum_peak_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->s0, (const float *)(r.acc + 2 * plane), npix, a,
-                           b, halfwidth, have, reinterpret_cast<int *>(r.maps), r.maps + npix, r.maps + 2 * npix, r.maps + 3 * npix);
-        HIPCHK(hipGetLastError());
-        if (int rc = trace_close(h, h->s0)) return rc;
-        h->launches++;
-        if (kpeak) HIPCHK(hipMemcpyAsync(kpeak, r.maps, npix * sizeof(int), hipMemcpyDeviceToHost, h->s0));
-        if (ppeak) HIPCHK(hipMemcpyAsync(ppeak, r.maps + npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
-        if (pband) HIPCHK(hipMemcpyAsync(pband, r.maps + 2 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
-        if (pnear) HIPCHK(hipMemcpyAsync(pnear, r.maps + 3 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
-        SYNC_S0(h);
-        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front had given up: recovered and folded again, the maps again)
-    }
-    return 0;
+    void *const dst[4] = {kpeak, ppeak, pband, pnear};
+    return read_confirmed(h, [&] {
+        const int have = r.taken() / r.nfft > 0 ? 1 : 0;
+        if (int rc = launch_traced(h, "spectrum_peak_kernel", 0, [&] {
+                hipLaunchKernelGGL(spectrum_peak_kernel, blocks_of(npix), dim3(256), 0, h->s0, (const float *)(r.acc + 2 * plane), npix, a, b,
+                                   halfwidth, have, reinterpret_cast<int *>(r.maps), r.maps + npix, r.maps + 2 * npix, r.maps + 3 * npix);
+            }))
+            return rc;
+        return copy_maps(h, r.maps, npix, dst);
+    });
 }
 
 extern "C" int fibhip_spectrum_end(fibhip_t h)
 {
     NEED(h);
-    if (!h->sp.on) return 0;
-    FLUSH(h);                                          // the ticks accepted while attached are sampled
-    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
-    spectrum_free(h);
-    return 0;
+    return detach(h, h->sp.on, spectrum_free);
 }
 
 // ---- beat recorder ------------------------------------------------------------------------------------------------------
@@ -1279,31 +1235,24 @@ extern "C" int fibhip_beats_begin(fibhip_t h, int var, const int *window, int by
     NEED(h);
     if (!window) return fail(FIBHIP_EINVAL, "beats_begin: null argument");
     if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "beats_begin: bad var %d", var);
-    const int r0 = window[0], r1 = window[1], c0 = window[2], c1 = window[3];
-    if (r0 < 0 || r1 > h->d.height || c0 < 0 || c1 > h->d.width || r0 >= r1 || c0 >= c1)
-        return fail(FIBHIP_EINVAL, "beats_begin: the window rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", r0, r1, c0,
-                    c1, h->d.height, h->d.width);
-    if (by < 1 || by > FIBHIP_MAX_FRAME_BLOCK || bx < 1 || bx > FIBHIP_MAX_FRAME_BLOCK)
-        return fail(FIBHIP_EINVAL, "beats_begin: a block is 1 .. %d cells each way (got %d x %d)", FIBHIP_MAX_FRAME_BLOCK, by, bx);
-    const int oh = (r1 - r0) / by, ow = (c1 - c0) / bx;
-    if (oh < 1 || ow < 1)
-        return fail(FIBHIP_EINVAL, "beats_begin: a window of %d x %d cells holds no block of %d x %d", r1 - r0, c1 - c0, by, bx);
-    if (reduce != FIBHIP_FRAME_POINT && reduce != FIBHIP_FRAME_MEAN) return fail(FIBHIP_EINVAL, "beats_begin: bad reduction %d", reduce);
+    Window px;
+    if (int rc = window_from(h, "beats_begin", window, by, bx, reduce, px)) return rc;
+    const int oh = px.oh, ow = px.ow;
     if (every < 1) return fail(FIBHIP_EINVAL, "beats_begin: every must be >= 1 (got %d)", every);
     if (!(down <= up)) return fail(FIBHIP_EINVAL, "beats_begin: the levels must be numbers with down <= up (got down %g, up %g)", (double)down, (double)up);
     if (depth < 1 || depth > FIBHIP_BEATS_MAX_DEPTH)
         return fail(FIBHIP_EINVAL, "beats_begin: depth must be 1 .. %d (got %d)", FIBHIP_BEATS_MAX_DEPTH, depth);
-    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "beats_begin: not on a row block (a handle with ghost rows)");
+    if (int rc = attach_refusals(h, "beats_begin")) return rc;
     if (h->pitch != h->d.width) return fail(FIBHIP_EINVAL, "beats_begin: not on a row-interleaved slab");
     if (h->bt.on) return fail(FIBHIP_EINVAL, "beats_begin: a recorder is attached already (fibhip_beats_end first)");
-    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "beats_begin inside an open tick");
     // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
     // tick 0 and the first xp are defined (the rule of fibhip_electrode_begin)
     FLUSH(h);
     SYNC_S0(h);
     beats_free(h);
     BeatRec &r = h->bt;
-    const size_t npix = (size_t)oh * (size_t)ow;
+    static_cast<Window &>(r) = px;
+    const size_t npix = px.npix();
     bool ok = hipMalloc((void **)&r.state, 3 * npix * sizeof(float)) == hipSuccess;
     ok = ok && hipMalloc((void **)&r.ring, 3 * (size_t)depth * npix * sizeof(float)) == hipSuccess;
     ok = ok && hipMalloc((void **)&r.maps, 4 * npix * sizeof(float)) == hipSuccess;
@@ -1313,20 +1262,15 @@ extern "C" int fibhip_beats_begin(fibhip_t h, int var, const int *window, int by
         beats_free(h);
         return fail(FIBHIP_ENOMEM, "beats_begin: hipMalloc failed (a ring of %d beats of %d x %d pixels)", depth, oh, ow);
     }
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    unsigned nan_bits;
-    memcpy(&nan_bits, &qnan, sizeof nan_bits);
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(r.state + npix), (int)nan_bits, npix, h->s0));                  // pk = NaN
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(r.state + npix), (int)qnan_bits(), npix, h->s0));               // pk = NaN
     HIPCHK(hipMemsetAsync(r.state + 2 * npix, 0, npix * sizeof(int), h->s0));                                // n = 0
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)r.ring, (int)nan_bits, 3 * (size_t)depth * npix, h->s0));       // t_up = t_down = peak = NaN
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)r.ring, (int)qnan_bits(), 3 * (size_t)depth * npix, h->s0));    // t_up = t_down = peak = NaN
     if (weight) HIPCHK(hipMemcpyAsync(r.w, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    r.start(every, LLONG_MAX);                         // sample s follows tick (s + 1) * every, ticks counted from 1 here
+    r.before_slow = slow_array(var);
     r.var = var;
-    r.every = every;
-    r.r0 = r0; r.c0 = c0; r.oh = oh; r.ow = ow; r.by = by; r.bx = bx;
-    r.reduce = reduce;
     r.up = up; r.down = down;
     r.depth = depth;
-    r.k = 0;                                           // sample s follows tick (s + 1) * every, ticks counted from 1 here
     if (int rc = beats_launch(h, true, 0, nullptr)) {  // xp = the pixel of the current state (confirmed above: nothing to gate on)
         beats_free(h);
         return rc;
@@ -1341,7 +1285,7 @@ extern "C" int fibhip_beats_count(fibhip_t h, long long *samples)
     NEED(h);
     if (!h->bt.on) return fail(FIBHIP_EINVAL, "beats_count: no recorder attached (fibhip_beats_begin)");
     SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    if (samples) *samples = (h->bt.k + h->pending) / h->bt.every;    // (ticks accepted but not launched yet are sampled when they are)
+    if (samples) *samples = h->bt.taken_with(h->pending);            // (ticks accepted but not launched yet are sampled when they are)
     return 0;
 }
 
@@ -1362,17 +1306,14 @@ extern "C" int fibhip_beats_read(fibhip_t h, float *t_up, float *t_down, float *
     FLUSH(h);
     const BeatRec &r = h->bt;
     const size_t npix = r.npix(), plane = (size_t)r.depth * npix;
-    for (int pass = 0; pass < 2; ++pass) {
-        const long long fb0 = h->journal.n_fallbacks;
+    return read_confirmed(h, [&] {
         if (t_up) HIPCHK(hipMemcpyAsync(t_up, r.ring, plane * sizeof(float), hipMemcpyDeviceToHost, h->s0));
         if (t_down) HIPCHK(hipMemcpyAsync(t_down, r.ring + plane, plane * sizeof(float), hipMemcpyDeviceToHost, h->s0));
         if (peak) HIPCHK(hipMemcpyAsync(peak, r.ring + 2 * plane, plane * sizeof(float), hipMemcpyDeviceToHost, h->s0));
         if (count) HIPCHK(hipMemcpyAsync(count, r.state + 2 * npix, npix * sizeof(int), hipMemcpyDeviceToHost, h->s0));
         if (pk) HIPCHK(hipMemcpyAsync(pk, r.state + npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
-        SYNC_S0(h);
-        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered and sampled again, copy again)
-    }
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" int fibhip_beats_summary(fibhip_t h, int last, int *nused, float *apd_mean, float *cl_mean, float *apd_alt)
@@ -1383,33 +1324,22 @@ extern "C" int fibhip_beats_summary(fibhip_t h, int last, int *nused, float *apd
     if (last < 1 || last > r.depth) return fail(FIBHIP_EINVAL, "beats_summary: last must be 1 .. depth = %d (got %d)", r.depth, last);
     FLUSH(h);
     const size_t npix = r.npix(), plane = (size_t)r.depth * npix;
-    for (int pass = 0; pass < 2; ++pass) {
-        const long long fb0 = h->journal.n_fallbacks;
-        if (int rc = trace_open(h, h->s0, "beat_summary_kernel", 0, 0, 0, 0, 1)) return rc;
-        hipLaunchKernelGGL(beat_summary_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->s0,
-                           reinterpret_cast<const int *>(r.state + 2 * npix), (const float *)r.ring, (const float *)(r.ring + plane), npix, r.depth,
-                           last, reinterpret_cast<int *>(r.maps), r.maps + npix, r.maps + 2 * npix, r.maps + 3 * npix);
-        HIPCHK(hipGetLastError());
-        if (int rc = trace_close(h, h->s0)) return rc;
-        h->launches++;
-        if (nused) HIPCHK(hipMemcpyAsync(nused, r.maps, npix * sizeof(int), hipMemcpyDeviceToHost, h->s0));
-        if (apd_mean) HIPCHK(hipMemcpyAsync(apd_mean, r.maps + npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
-        if (cl_mean) HIPCHK(hipMemcpyAsync(cl_mean, r.maps + 2 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
-        if (apd_alt) HIPCHK(hipMemcpyAsync(apd_alt, r.maps + 3 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, h->s0));
-        SYNC_S0(h);
-        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front had given up: recovered and sampled again, the maps again)
-    }
-    return 0;
+    void *const dst[4] = {nused, apd_mean, cl_mean, apd_alt};
+    return read_confirmed(h, [&] {
+        if (int rc = launch_traced(h, "beat_summary_kernel", 0, [&] {
+                hipLaunchKernelGGL(beat_summary_kernel, blocks_of(npix), dim3(256), 0, h->s0, reinterpret_cast<const int *>(r.state + 2 * npix),
+                                   (const float *)r.ring, (const float *)(r.ring + plane), npix, r.depth, last, reinterpret_cast<int *>(r.maps),
+                                   r.maps + npix, r.maps + 2 * npix, r.maps + 3 * npix);
+            }))
+            return rc;
+        return copy_maps(h, r.maps, npix, dst);
+    });
 }
 
 extern "C" int fibhip_beats_end(fibhip_t h)
 {
     NEED(h);
-    if (!h->bt.on) return 0;
-    FLUSH(h);                                          // the ticks accepted while attached are sampled
-    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the recorder
-    beats_free(h);
-    return 0;
+    return detach(h, h->bt.on, beats_free);
 }
 
 // ---- stimulus program ---------------------------------------------------------------------------------------------------
@@ -1435,8 +1365,7 @@ extern "C" int fibhip_stim_begin(fibhip_t h, int n, const fibhip_stim_entry *ent
             return rc;
         list.push_back(e);
     }
-    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "stim_begin: not on a row block (a handle with ghost rows)");
-    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "stim_begin inside an open tick");
+    if (int rc = attach_refusals(h, "stim_begin")) return rc;
     if (h->stim.on) return fail(FIBHIP_EINVAL, "stim_begin: a program is attached already (fibhip_stim_end first)");
     // everything accepted so far runs unstimulated and is confirmed: a multi-tick launch that gave up is recovered HERE, before
     // tick k = 0 is defined (the rule of fibhip_electrode_begin)
@@ -1475,11 +1404,7 @@ extern "C" int fibhip_stim_count(fibhip_t h, long long *applied)
 extern "C" int fibhip_stim_end(fibhip_t h)
 {
     NEED(h);
-    if (!h->stim.on) return 0;
-    FLUSH(h);                                          // the events of the ticks accepted while attached are applied
-    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the program
-    stim_free(h);
-    return 0;
+    return detach(h, h->stim.on, stim_free);
 }
 
 // ---- trigger program ----------------------------------------------------------------------------------------------------
@@ -1508,9 +1433,7 @@ extern "C" int fibhip_trig_begin(fibhip_t h, int nsensors, const fibhip_trig_sen
         if (std::isnan(q.level)) return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: the level must be a number", i);
         long long cells_of_site = 0;
         if (q.site == FIBHIP_TRIG_RECT) {
-            if (q.r0 < 0 || q.r1 > H || q.c0 < 0 || q.c1 > W || q.r0 >= q.r1 || q.c0 >= q.c1)
-                return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", i, q.r0,
-                            q.r1, q.c0, q.c1, H, W);
+            if (int rc = rect_check(h, q.r0, q.r1, q.c0, q.c1, "trig_begin: sensor %d: ", i)) return rc;
             d.r0 = q.r0; d.r1 = q.r1; d.c0 = q.c0; d.c1 = q.c1;
             d.mask = -1;
             cells_of_site = (long long)(q.r1 - q.r0) * (q.c1 - q.c0);
@@ -1581,8 +1504,7 @@ extern "C" int fibhip_trig_begin(fibhip_t h, int nsensors, const fibhip_trig_sen
 #endif
         stims.push_back(e);
     }
-    if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "trig_begin: not on a row block (a handle with ghost rows)");
-    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "trig_begin inside an open tick");
+    if (int rc = attach_refusals(h, "trig_begin")) return rc;
     if (h->trig.on) return fail(FIBHIP_EINVAL, "trig_begin: a program is attached already (fibhip_trig_end first)");
     // everything accepted so far runs unsensed and is confirmed: a multi-tick launch that gave up is recovered HERE, before
     // sample 0 is defined (the rule of fibhip_electrode_begin) — every journal record is younger than the program
@@ -1611,11 +1533,10 @@ extern "C" int fibhip_trig_begin(fibhip_t h, int nsensors, const fibhip_trig_sen
     HIPCHK(hipMemsetAsync(r.fire, 0, (size_t)capacity * sizeof(unsigned), h->s0));
     HIPCHK(wait_stream(h->s0));                        // the tables and the caller's masks and planes are free again
     r.on = true;
+    r.start(every, capacity);
+    r.before_slow = true;                              // tick, sense / stimulus, slow: whatever arrays it names
     r.nsensors = nsensors;
     r.nrules = nrules;
-    r.every = every;
-    r.cap = capacity;
-    r.k = 0;
     r.cut_vec = cut_vec;
     r.max_chunks[0] = max_chunks[0];
     r.max_chunks[1] = max_chunks[1];
@@ -1630,7 +1551,7 @@ extern "C" int fibhip_trig_count(fibhip_t h, long long *samples)
     if (!samples) return fail(FIBHIP_EINVAL, "trig_count: null argument");
     if (!h->trig.on) return fail(FIBHIP_EINVAL, "trig_count: no program attached (fibhip_trig_begin)");
     SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = (h->trig.k + h->pending) / h->trig.every;   // (ticks accepted but not launched yet are sampled when they are)
+    *samples = h->trig.taken_with(h->pending);         // (ticks accepted but not launched yet are sampled when they are)
     return 0;
 }
 
@@ -1639,27 +1560,18 @@ extern "C" int fibhip_trig_read(fibhip_t h, long long first, long long count, in
     NEED(h);
     if (!h->trig.on) return fail(FIBHIP_EINVAL, "trig_read: no program attached (fibhip_trig_begin)");
     FLUSH(h);
-    const long long taken = h->trig.k / h->trig.every;
-    if (first < 0 || count < 0 || first + count > taken)
-        return fail(FIBHIP_EINVAL, "trig_read: samples [%lld, %lld) of %lld taken", first, first + count, taken);
+    if (int rc = range_check("trig_read", "samples", first, count, h->trig.taken())) return rc;
     if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "trig_read: null destination");
     const size_t row = (size_t)h->trig.nrules * TRIG_ROW;
-    for (int pass = 0; pass < 2; ++pass) {
-        const long long fb0 = h->journal.n_fallbacks;
+    return read_confirmed(h, [&] {
         if (count > 0)
             HIPCHK(hipMemcpyAsync(dst, h->trig.rows + (size_t)first * row, (size_t)count * row * sizeof(int), hipMemcpyDeviceToHost, h->s0));
-        SYNC_S0(h);
-        if (h->journal.n_fallbacks == fb0) break;           // (a launch in front of the copy had given up: recovered, the rows rewritten, copy again)
-    }
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" int fibhip_trig_end(fibhip_t h)
 {
     NEED(h);
-    if (!h->trig.on) return 0;
-    FLUSH(h);                                          // the ticks accepted while attached are sensed, their stimuli applied
-    SYNC_S0(h);                                        // ... and confirmed, so that no replay is left that would want the program
-    trig_free(h);
-    return 0;
+    return detach(h, h->trig.on, trig_free);
 }

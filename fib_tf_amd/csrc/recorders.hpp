@@ -1,0 +1,98 @@
+// recorders.hpp — the ONE list of the hooks that stand behind a committed launch (record.inc), in hook order.  Whatever
+// enumerates recorders walks this table: the hooks behind a plain tick and behind a multi-tick launch (recorders_advance), what
+// they ask of the scheduler (sched.inc: sampling, sample_room, slow_sample_due, sampler_full), the rewind of a recovery
+// (recorders_rewind) and the release of their buffers (recorders_free).  A new recorder is one row here.  The table is a
+// constant: the loops over it unroll, the offsets fold and the hooks are called directly — nothing on fibhip_step's per-call path
+// goes through a pointer.
+// (included by fibhip.hip between ctx.hpp and tick.inc; the functions the rows name are record.inc's)
+#pragma once
+
+typedef int recorder_advance_fn(fibhip_ctx *h, int ticks, bool behind_mt);
+typedef void recorder_free_fn(fibhip_ctx *h);
+struct Recorder {
+    const char *noun;                   // what sampler_full calls it
+    size_t sampler;                     // where its Sampler lives in the handle; NO_SAMPLER: the stimulus program, driven by events
+    recorder_advance_fn *advance;       // the hook behind a launch of `ticks` ticks
+    recorder_free_fn *release;          // frees its device buffers and detaches it
+};
+constexpr size_t NO_SAMPLER = ~(size_t)0;
+
+static recorder_advance_fn electrode_advance, tips_advance, frames_advance, stats_advance, spectrum_advance, beats_advance, stim_advance, trig_advance;
+static recorder_free_fn electrode_free, tips_free, frames_free, stats_free, spectrum_free, beats_free, stim_free, trig_free;
+static long long stim_next(const StimRec &r);                   // sched.inc
+
+// (`on` is the Sampler's first member; the handle holds vectors, which is all that makes offsetof conditionally supported here)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+#define SAMPLER_AT(member) offsetof(fibhip_ctx, member.on)
+// The ORDER is the order of the launches behind a tick and is load-bearing: the samplers see the state as the tick left it; the
+// stimulus belongs to the next tick and comes behind them; the trigger program senses what the stimulus left and fires last.
+// Behind a multi-tick launch every hook stands UNCONFIRMED (behind_mt), and a recovery rewinds every counter by the ticks it
+// replays — the slot is the host's counter, so the replay fills the same slots again.  Why each row may be rewound:
+static constexpr Recorder RECORDERS[] = {
+    // these four read the state and rewrite whole slots of their own buffers: a sample taken from a void slab is overwritten
+    {"electrode", SAMPLER_AT(el), electrode_advance, electrode_free},
+    {"tip", SAMPLER_AT(tip), tips_advance, tips_free},
+    {"frame", SAMPLER_AT(fr), frames_advance, frames_free},
+    {"statistics", SAMPLER_AT(st), stats_advance, stats_free},
+    // these two ACCUMULATE (the fold and the short ring; the count, the open beat's peak, the ring): their kernels read the
+    // give-up word first and write nothing once a launch in front of them gave up, and how far they have come follows from the
+    // counter alone — the replay takes the lost samples and issues the lost folds again, in order.  Neither ever fills up
+    {"spectrum", SAMPLER_AT(sp), spectrum_advance, spectrum_free},
+    {"beat", SAMPLER_AT(bt), beats_advance, beats_free},
+    // it WRITES the state, the slab the launch wrote: stim_kernel reads the give-up word first, so the state the first lost
+    // launch started from stays intact; the replay applies the events of the replayed ticks again, and no others — the events
+    // of older ticks stand in the restored state.  Its rewind recomputes `next` (recorders_rewind)
+    {"stimulus", NO_SAMPLER, stim_advance, stim_free},
+    // its automaton's state is the log itself, row s a pure function of row s - 1 and the state.  The rows the lost samples
+    // wrote were made from a void slab, and the gated apply behind them wrote nothing (it reads the give-up word first).  The
+    // replay rewrites those rows IN ORDER, each from a predecessor that is older than the lost launch (good: trig_begin
+    // confirms before it attaches) or has just been rewritten: no detection lost, none doubled, and a delay or a train that
+    // straddles the lost launch goes on as in the untouched run
+    {"trigger", SAMPLER_AT(trig), trig_advance, trig_free},
+};
+#undef SAMPLER_AT
+#pragma clang diagnostic pop
+
+static inline Sampler *sampler_of(fibhip_ctx *h, const Recorder &r)
+{
+    return r.sampler == NO_SAMPLER ? nullptr : reinterpret_cast<Sampler *>(reinterpret_cast<char *>(h) + r.sampler);
+}
+static inline const Sampler *sampler_of(const fibhip_ctx *h, const Recorder &r) { return sampler_of(const_cast<fibhip_ctx *>(h), r); }
+static inline bool attached(const fibhip_ctx *h, const Recorder &r)
+{
+    const Sampler *s = sampler_of(h, r);
+    return s ? s->on : h->stim.on;
+}
+
+// the hooks behind a launch of `ticks` ticks the handle's state has moved with.  `behind_mt`: that launch is a multi-tick launch
+// nobody may have confirmed — the hooks that accumulate or write the state hand their kernels the give-up word then.  A plain
+// tick never stands behind an unconfirmed multi-tick launch (tick_mt, fibhip_step and recover() confirm first)
+static int recorders_advance(fibhip_ctx *h, int ticks, bool behind_mt)
+{
+    for (const Recorder &r : RECORDERS)
+        if (attached(h, r))
+            if (int rc = r.advance(h, ticks, behind_mt)) return rc;
+    return 0;
+}
+
+// recover(): the samples and stimuli queued behind the lost launches were taken from, or kept off, a void slab; the replay
+// (tick_now -> commit_impl) comes through the hooks again.  (Every journal record is younger than every recorder: each _begin
+// confirms, and so empties the journal, before it attaches.)
+static void recorders_rewind(fibhip_ctx *h, int lost)
+{
+    for (const Recorder &r : RECORDERS) {
+        if (!attached(h, r)) continue;
+        if (Sampler *s = sampler_of(h, r)) {
+            s->rewind(lost);
+        } else {
+            h->stim.k -= lost;
+            h->stim.next = stim_next(h->stim);
+        }
+    }
+}
+
+static void recorders_free(fibhip_ctx *h)
+{
+    for (const Recorder &r : RECORDERS) r.release(h);
+}

@@ -17,7 +17,6 @@
 // bit-identical by construction — the ticks the handle's state had already moved past.  (The replay stays one launch per tick
 // however long the lost launches were: the fallback leaves no multi-tick launch to replay with, mt.max is 1 from here on.
 // Its cost is bounded by what the journal holds, MT_MAX_TICKS_IN_FLIGHT ticks and one launch: journal_bound.)
-static long long stim_next(const StimRec &r);                     // (below, with the scheduler's other questions to the program)
 static int recover(fibhip_ctx *h, unsigned id)
 {
     size_t i = 0;
@@ -47,33 +46,9 @@ static int recover(fibhip_ctx *h, unsigned id)
     h->journal.n_fallbacks++;
     h->journal.n_replayed += lost;
     // the samples queued behind the lost launches were taken from a void slab: the replay below (tick_now -> commit_impl)
-    // takes them again, into the same slots — the slot is the host's tick counter, so that counter goes back first.  (Every
-    // journal record is younger than the recorder: electrode_begin, tips_begin, frames_begin, stats_begin, spectrum_begin and beats_begin confirm, and so
-    // empty the journal, before they attach.)
-    if (h->el.on) h->el.k -= lost;
-    if (h->tip.on) h->tip.k -= lost;
-    if (h->fr.on) h->fr.k -= lost;
-    if (h->st.on) h->st.k -= lost;
-    // ... and the spectrum recorder, the one recorder that accumulates: the samples and the folds queued behind the lost launches
-    // wrote nothing (both kernels leave when they find the give-up word raised), and how far it has sampled and folded follows
-    // from this counter alone — the replay takes the lost samples again and issues the lost folds again, in order
-    if (h->sp.on) h->sp.k -= lost;
-    // ... and the beat recorder, which accumulates too (the count, the open beat's peak, the ring): beat_kernel behind the lost
-    // launches wrote nothing, and the sample index — with it t0 — is a function of this counter alone
-    if (h->bt.on) h->bt.k -= lost;
-    // ... and the stimuli queued behind them wrote nothing (stim_kernel leaves when it finds the give-up word raised): the replay
-    // applies the events of the replayed ticks again, and no others — the events of older ticks stand in the restored state
-    if (h->stim.on) {
-        h->stim.k -= lost;
-        h->stim.next = stim_next(h->stim);
-    }
-    // ... and the trigger program: its automaton's state is the log itself, row s a pure function of row s - 1 and the state.
-    // The rows the lost samples wrote were made from a void slab, and the gated apply behind them wrote nothing (it reads the
-    // give-up word first).  The counter goes back, and the replay rewrites those rows IN ORDER, each from a predecessor that is
-    // older than the lost launch (good: trig_begin confirms before it attaches, and every row older than the journal's first
-    // record was made behind a launch that ended well) or has just been rewritten.  So a detection is never lost and never
-    // doubled, and a delay or a train that straddles the lost launch goes on as in the untouched run (DESIGN.md section 16).
-    if (h->trig.on) h->trig.k -= lost;
+    // takes them again, into the same slots — the slot is the host's tick counter, so every counter goes back first
+    // (recorders.hpp says, row by row, why that is all it takes)
+    recorders_rewind(h, lost);
     h->journal.recovering = true;
     int rc = 0;
     for (int t = 0; t < lost && rc == 0; ++t) rc = tick_now(h);
@@ -197,29 +172,31 @@ static const Variant *mt_variant(const fibhip_ctx *h, bool long_declared = false
 // Every constraint an attached recorder (record.inc) puts on the launches is stated HERE and nowhere else:
 //  * activation recorder (h->obs.on): it observes every tick through commit_impl, so nothing fuses ticks — no multi-tick
 //    launches (mt_variant, above, is null: hence no run-ahead and no launched series either), one tick per plain launch (multi_cap);
-//  * the samplers — electrode recorder (h->el.on), tip recorder (h->tip.on), frame recorder (h->fr.on; its counter starts
-//    at every - first, so that its first sample may come early), statistics recorder (h->st.on), spectrum recorder (h->sp.on; it
-//    never fills up, so it has no term in sampler_full; its sample and its fold stand behind a multi-tick launch unconfirmed and
-//    read the give-up word first, like the stimulus) and beat recorder (h->bt.on; a ring never fills either: no term in
-//    sampler_full; its sample stands behind a multi-tick launch unconfirmed and reads the give-up word first; on a shared tick
-//    it is taken behind the other samplers' and before the stimuli), each with a stride of its own: no launch
-//    spans a sample tick of either (sample_room, the minimum over the attached ones, bounds next_launch_ticks and multi_cap);
+//  * the samplers — every row of RECORDERS (recorders.hpp) that has a Sampler, each with a stride of its own: no launch spans
+//    a sample tick of any of them (sample_room, the minimum over the attached ones, bounds next_launch_ticks and multi_cap);
 //    nothing runs ahead (may_run_ahead: a launch that runs ahead is handed out tick by tick and may be stopped or recomputed,
-//    so a sample cannot be queued behind it, DESIGN.md section 11); a sample of a SLOW Courtemanche array is taken before
-//    'slow' rides on its tick (slow_sample_due);
-//  * the stimulus program (h->stim.on), the one hook that WRITES the state: no launch spans an event tick (stim_room, one more
+//    so a sample cannot be queued behind it, DESIGN.md section 11); a sample of a SLOW Courtemanche array — the Sampler's
+//    before_slow, set at attach — is taken before 'slow' rides on its tick (slow_sample_due); one that has no slot left refuses further
+//    ticks (sampler_full; the spectrum and the beat recorder never fill up, their cap is LLONG_MAX).  On a shared tick the
+//    samples go out in the table's order, behind a multi-tick launch unconfirmed (recorders_advance);
+//  * the stimulus program (h->stim.on), the one row without a Sampler and the one hook that WRITES the state on the host's
+//    word: no launch spans an event tick (stim_room, one more
 //    term of sample_room), and while events are still to come a launch goes out when the ticks up to the next one are waiting
 //    (cutting); nothing runs ahead while a program is attached (may_run_ahead: a stimulus cannot be queued behind a launch that
 //    may be stopped or recomputed); a tick with an event due is never fused with the 'slow' behind it, whatever array the event
 //    names — the stimulus comes right after its tick (slow_sample_due).  The stimulus is queued behind its launch WITHOUT
 //    confirming it: stim_kernel writes nothing once a launch in front of it gave up (the rule above confirm());
-//  * the trigger program (h->trig.on): a sampler with a stride of its own like the four above (a term of sampling and
-//    sample_room, so launches are cut at its samples and nothing runs ahead), whose sample also WRITES the state: sense, decide
-//    and the gated apply come behind the programmed stimuli of the tick, unconfirmed like them (the gated apply reads the
-//    give-up word first); every sample tick comes before the 'slow' behind it (slow_sample_due), whatever arrays it names.
-static inline bool sampling(const fibhip_ctx *h) { return h->el.on || h->tip.on || h->fr.on || h->st.on || h->sp.on || h->bt.on || h->trig.on; }
-// ticks up to and including the next sample tick of one sampler (INT_MAX: not attached)
-static inline int room_of(bool on, int every, long long k) { return on ? every - (int)(k % every) : INT_MAX; }
+//  * the trigger program, the last row: a sampler like the others (launches are cut at its samples and nothing runs ahead)
+//    whose sample also WRITES the state: sense, decide and the gated apply come behind the programmed stimuli of the tick,
+//    unconfirmed like them (the gated apply reads the give-up word first); every sample tick comes before the 'slow' behind it
+//    (its before_slow is always true), whatever arrays it names.
+// (sample_room and cutting are on fibhip_step's per-call path: they read the Samplers through the rows' offsets and call nothing)
+static inline bool sampling(const fibhip_ctx *h)
+{
+    for (const Recorder &r : RECORDERS)
+        if (r.sampler != NO_SAMPLER && sampler_of(h, r)->on) return true;
+    return false;
+}
 // Is entry `e` due right after the n-th tick since attach (n >= 1)?  The events of an entry follow the ticks number
 // first + 1 + j * period + d, j = 0 .. count - 1 (count == 0: without end), d = 0 .. hold - 1 (include/fibhip.h).
 static inline bool stim_due(const StimEntry &e, long long n)
@@ -268,10 +245,10 @@ static inline int stim_room(const fibhip_ctx *h)
 // ... and of any attached sampler, and of the stimulus program: no launch may span one
 static inline int sample_room(const fibhip_ctx *h)
 {
-    return imin(imin(imin(room_of(h->el.on, h->el.every, h->el.k), room_of(h->tip.on, h->tip.every, h->tip.k)),
-                     imin(room_of(h->fr.on, h->fr.every, h->fr.k), room_of(h->st.on, h->st.every, h->st.k))),
-                imin(imin(stim_room(h), room_of(h->trig.on, h->trig.every, h->trig.k)),
-                     imin(room_of(h->sp.on, h->sp.every, h->sp.k), room_of(h->bt.on, h->bt.every, h->bt.k))));
+    int room = stim_room(h);
+    for (const Recorder &r : RECORDERS)
+        if (r.sampler != NO_SAMPLER) room = imin(room, sampler_of(h, r)->room());
+    return room;
 }
 // launches are cut at ticks still to come: a launch goes out when the ticks up to the next cut are waiting (fibhip_step)
 static inline bool cutting(const fibhip_ctx *h) { return sampling(h) || stim_room(h) != INT_MAX; }
@@ -310,17 +287,11 @@ static inline bool slow_sample_due(const fibhip_ctx *h)
 #if !defined(FIB_CUSTOM_ONLY) && !defined(FIB_ONLY_BR)
     // (a stimulus due after the last pending tick comes before 'slow' too, whatever array it names)
     if (h->stim.on && h->stim.k + h->pending == h->stim.next) return true;
-    // (... and so does a sample of the trigger program: tick, sense / stimulus, slow)
-    if (h->trig.on && (h->trig.k + h->pending) % h->trig.every == 0) return true;
-    auto slow = [](int var) { return !((Courtemanche::FAST_MASK >> var) & 1u); };
-    if (h->el.on && (h->el.k + h->pending) % h->el.every == 0 && slow(h->el.var)) return true;
-    if (h->tip.on && (h->tip.k + h->pending) % h->tip.every == 0 && (slow(h->tip.var) || slow(h->tip.var2))) return true;
-    if (h->fr.on && (h->fr.k + h->pending) % h->fr.every == 0 && slow(h->fr.var)) return true;
-    if (h->sp.on && (h->sp.k + h->pending) % h->sp.every == 0 && slow(h->sp.var)) return true;
-    if (h->bt.on && (h->bt.k + h->pending) % h->bt.every == 0 && slow(h->bt.var)) return true;
-    if (h->st.on && (h->st.k + h->pending) % h->st.every == 0)
-        for (int a = 0; a < h->st.narr; ++a)
-            if (slow(h->st.vars[a])) return true;
+    // (... and so does a sample of the trigger program — tick, sense / stimulus, slow — and a sample that reads a slow array)
+    for (const Recorder &r : RECORDERS) {
+        const Sampler *s = sampler_of(h, r);
+        if (s && s->on && s->before_slow && s->due_after(h->pending)) return true;
+    }
     return false;
 #else
     return false;
@@ -330,15 +301,13 @@ static inline bool slow_sample_due(const fibhip_ctx *h)
 // it holds
 static inline const char *sampler_full(const fibhip_ctx *h, int more, long long *cap = nullptr)
 {
-    const struct { bool on; long long k; int every; long long cap; const char *name; } s[] = {
-        {h->el.on, h->el.k, h->el.every, h->el.cap, "electrode"}, {h->tip.on, h->tip.k, h->tip.every, h->tip.cap, "tip"},
-        {h->fr.on, h->fr.k, h->fr.every, h->fr.cap, "frame"}, {h->st.on, h->st.k, h->st.every, h->st.cap, "statistics"},
-        {h->trig.on, h->trig.k, h->trig.every, h->trig.cap, "trigger"}};
-    for (const auto &r : s)
-        if (r.on && (r.k + more) / r.every > r.cap) {
-            if (cap) *cap = r.cap;
-            return r.name;
+    for (const Recorder &r : RECORDERS) {
+        const Sampler *s = sampler_of(h, r);
+        if (s && s->on && s->full_after(more)) {
+            if (cap) *cap = s->cap;
+            return r.noun;
         }
+    }
     return nullptr;
 }
 
@@ -458,29 +427,9 @@ static int mt_launch(fibhip_t h, const Variant *v, int T, bool commit, int *nxt_
     h->mt.epoch_base += (unsigned)(nbound - 1);          // every tile raised its word once per tick (period) boundary
     if (commit) memcpy(h->cur, nxt, sizeof nxt);
     if (nxt_out) memcpy(nxt_out, nxt, sizeof nxt);
-    // (the sample reads the state and writes the recorder's own buffers only: it may stand behind this unconfirmed launch)
-    if (commit && h->el.on)
-        if (int rc = electrode_advance(h, T)) return rc;
-    if (commit && h->tip.on)
-        if (int rc = tips_advance(h, T)) return rc;
-    if (commit && h->fr.on)
-        if (int rc = frames_advance(h, T)) return rc;
-    if (commit && h->st.on)
-        if (int rc = stats_advance(h, T)) return rc;
-    // (the spectrum recorder's sample and fold write its own buffers only, but the fold accumulates and the ring is short: both
-    // leave without writing when this launch or one in front of it gave up, and the replay issues them again)
-    if (commit && h->sp.on)
-        if (int rc = spectrum_advance(h, T, true)) return rc;
-    // (the beat recorder's sample accumulates too: gated in the same way)
-    if (commit && h->bt.on)
-        if (int rc = beats_advance(h, T, true)) return rc;
-    // (the stimulus WRITES the state, the slab this launch wrote; it leaves without writing when this launch or one in front
-    // of it gave up — so the state the first such launch started from stays intact, as behind a multi-tick launch)
-    if (commit && h->stim.on)
-        if (int rc = stim_advance(h, T, true)) return rc;
-    // (... and so does the trigger program's gated apply; its rows are rewritten by the replay)
-    if (commit && h->trig.on) return trig_advance(h, T, true);
-    return 0;
+    // (the hooks stand behind this launch unconfirmed: a sample reads the state and writes the recorder's own buffers only, and
+    // whatever accumulates or writes the state leaves without writing when this launch or one in front of it gave up)
+    return commit ? recorders_advance(h, T, true) : 0;
 }
 
 // A caller that never synchronises must not grow the journal without bound: every 256 multi-tick launches, or

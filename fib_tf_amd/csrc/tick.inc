@@ -3,16 +3,7 @@
 // (included by fibhip.hip)
 
 static int autotune(fibhip_ctx *h);                               // plan.inc: the first tick of a handle chooses its plan
-// the recorders' hooks behind a committed tick (record.inc)
-static int observe_enqueue(fibhip_ctx *h);
-static int electrode_advance(fibhip_ctx *h, int ticks);
-static int tips_advance(fibhip_ctx *h, int ticks);
-static int frames_advance(fibhip_ctx *h, int ticks);
-static int stats_advance(fibhip_ctx *h, int ticks);
-static int spectrum_advance(fibhip_ctx *h, int ticks, bool behind_mt);
-static int beats_advance(fibhip_ctx *h, int ticks, bool behind_mt);
-static int stim_advance(fibhip_ctx *h, int ticks, bool behind_mt);       // ... and the stimulus program's, behind them
-static int trig_advance(fibhip_ctx *h, int ticks, bool behind_mt);       // ... and the trigger program's, last: it senses what the stimulus left
+static int observe_enqueue(fibhip_ctx *h);                       // record.inc: the activation recorder's hook behind a committed tick
 
 // ------------------------------------------------------------------------------------------
 // stepping
@@ -279,26 +270,8 @@ static int commit_impl(fibhip_t h)
     // the recorder sees every tick on its own: while it is attached nothing fuses ticks (multi_cap, mt_variant), span is 1
     if (h->obs.on)
         if (int rc = observe_enqueue(h)) return rc;
-    if (h->el.on)
-        if (int rc = electrode_advance(h, ticks)) return rc;
-    if (h->tip.on)
-        if (int rc = tips_advance(h, ticks)) return rc;
-    if (h->fr.on)
-        if (int rc = frames_advance(h, ticks)) return rc;
-    if (h->st.on)
-        if (int rc = stats_advance(h, ticks)) return rc;
-    if (h->sp.on)
-        if (int rc = spectrum_advance(h, ticks, false)) return rc;
-    if (h->bt.on)
-        if (int rc = beats_advance(h, ticks, false)) return rc;
-    // the stimulus comes last: the recorders saw the state as the tick left it, the stimulus belongs to the next tick
-    // (a plain tick never stands behind an unconfirmed multi-tick launch — tick_mt, fibhip_step and recover() confirm first — so
-    // its stimulus has no give-up word to look at)
-    if (h->stim.on)
-        if (int rc = stim_advance(h, ticks, false)) return rc;
-    // ... and the trigger program after that: its sensors see this tick's programmed stimulus, its own stimuli follow
-    if (h->trig.on) return trig_advance(h, ticks, false);
-    return 0;
+    // ... then the hooks of recorders.hpp, in its order (a plain tick stands behind a confirmed stream: no give-up word to look at)
+    return recorders_advance(h, ticks, false);
 }
 
 static int tick_now(fibhip_t h)
