@@ -22,6 +22,7 @@ SPECTRUM_MAX_BINS, SPECTRUM_MAX_CHUNK, SPECTRUM_MIN_NFFT, SPECTRUM_MAX_NFFT = 12
 BEATS_MAX_DEPTH = 16
 STAT_KINDS = ('sum', 'min', 'max', 'below', 'above', 'nonfinite')  # enum fibhip_stat_kind, in order
 MAX_STAT_COLS, MAX_STAT_COLS_PER_ARRAY = 64, 8
+MAX_LEADS, MAX_LEAD_TABLES = 64, 4
 STIM_MODES = ('max', 'add')                                       # enum fibhip_stim_mode, in order
 STIM_SHAPES = ('rect', 'plane')                                   # enum fibhip_stim_shape, in order
 MAX_STIM_ENTRIES, MAX_STIM_PLANES = 64, 8
@@ -223,6 +224,10 @@ SYMBOLS = {
     'fibhip_stats_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_stats_read': ([_h, C.c_longlong, C.c_longlong, C.POINTER(C.c_double)], C.c_int),
     'fibhip_stats_end': ([_h], C.c_int),
+    'fibhip_leads_begin': ([_h, C.c_int, C.c_int, _ip, C.c_int, _fp, _fp, C.c_int, C.c_longlong], C.c_int),
+    'fibhip_leads_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_leads_read': ([_h, C.c_longlong, C.c_longlong, C.POINTER(C.c_double)], C.c_int),
+    'fibhip_leads_end': ([_h], C.c_int),
     'fibhip_spectrum_begin': ([_h, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int], C.c_int),
     'fibhip_spectrum_count': ([_h, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_spectrum_shape': ([_h, _ip, _ip, _ip], C.c_int),
@@ -1029,6 +1034,43 @@ class Stepper:
 
     def stats_end(self):
         self._ck(self._L.fibhip_stats_end(self._h))
+
+    # ---- lead recorder (include/fibhip.h fibhip_leads_*) ----------------------------------------------------------
+    def leads_begin(self, pos, tables, weight=None, var=0, every=1, capacity=1):
+        """attaches the lead recorder: `pos` is a list of (row, col, table), `tables` a float32 [ntables, height, width] array
+        of lead-field tables, `weight` an [height, width] float32 plane or None (weight 1); one row of float64, one value per
+        lead, every `every` ticks, `capacity` rows at the most"""
+        pos = np.ascontiguousarray(pos, np.int32).reshape(-1, 3)
+        tables = np.ascontiguousarray(tables, np.float32)
+        if tables.ndim != 3 or tables.shape[1:] != (self.height, self.width):
+            raise ValueError('leads_begin: tables of shape %s on a %d x %d grid' % (tables.shape, self.height, self.width))
+        wp = None
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, np.float32)
+            if weight.shape != (self.height, self.width):
+                raise ValueError('leads_begin: a weight plane of shape %s on a %d x %d grid' % (weight.shape, self.height, self.width))
+            wp = weight.ctypes.data_as(_fp)
+        self._ck(self._L.fibhip_leads_begin(self._h, int(var), len(pos), pos.ctypes.data_as(_ip), len(tables), tables.ctypes.data_as(_fp), wp,
+                                            int(every), int(capacity)))
+        self._ld_n = len(pos)
+
+    def leads_count(self):
+        """samples taken since leads_begin (ticks accepted but not launched yet included)"""
+        k = C.c_longlong()
+        self._ck(self._L.fibhip_leads_count(self._h, C.byref(k)))
+        return int(k.value)
+
+    def leads_read(self, first=0, count=None):
+        """samples [first, first + count) as a float64 [count, nleads] array (count=None: all taken so far); blocks like
+        get_state, detaches nothing"""
+        if count is None:
+            count = self.leads_count() - int(first)
+        out = np.empty((max(int(count), 0), getattr(self, '_ld_n', 0)), np.float64)
+        self._ck(self._L.fibhip_leads_read(self._h, int(first), int(count), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def leads_end(self):
+        self._ck(self._L.fibhip_leads_end(self._h))
 
     # ---- stimulus program (include/fibhip.h fibhip_stim_*) --------------------------------------------------------
     def stim_begin(self, entries, planes=None):

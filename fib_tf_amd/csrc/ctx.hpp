@@ -176,6 +176,18 @@ struct StRec : Sampler {
     double *trace;          // device: [cap][ncols]
 };
 
+// lead recorder (fibhip_leads_begin): lead_kernel and lead_combine_kernel behind the launch that ends a sample tick.  Both rewrite
+// whole slots (the partials, the sample's row) from the state alone
+struct LeadRec : Sampler {
+    int var, n;
+    int tiles_x, tiles_y;   // lead_kernel's grid, from H and W alone
+    int *pos;               // device: [n][4] = row, col, table, 0
+    float *tables;          // device: [ntables][H][W]
+    float *weight;          // device: the weight plane [H][W], or null (weight 1)
+    double *part;           // device: [n][tiles_x * tiles_y], one partial per (lead, tile)
+    double *rows;           // device: [cap][n]
+};
+
 // spectrum recorder (fibhip_spectrum_begin): spectrum_sample_kernel behind the launch that ends a sample tick and, behind the
 // sample that fills the ring, spectrum_fold_kernel.  It ACCUMULATES: both kernels read the give-up word first, and everything
 // about its progress follows from `k` alone — samples k / every, the ring slot and the segment position of a sample, the folds
@@ -304,6 +316,7 @@ struct fibhip_ctx {
     TipRec tip;
     FrRec fr;
     StRec st;
+    LeadRec ld;
     SpRec sp;
     BeatRec bt;
     StimRec stim;

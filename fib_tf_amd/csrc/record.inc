@@ -1,6 +1,6 @@
-// record.inc — what runs on the device behind the ticks while a model runs.  Seven recorders: the per-cell activation maps
+// record.inc — what runs on the device behind the ticks while a model runs.  Eight recorders: the per-cell activation maps
 // (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
-// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell
+// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the unipolar electrograms (fibhip_leads_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell
 // beat history (fibhip_beats_*); and the two hooks that write the state: the stimulus program (fibhip_stim_*) and the trigger
 // program (fibhip_trig_*), which senses, decides and fires on the device.
 // The file has three parts: the helpers every recorder shares; the hooks — per recorder its _advance (behind a launch that the
@@ -318,6 +318,45 @@ static void stats_free(fibhip_ctx *h)
     dev_free(h->st.part);
     dev_free(h->st.trace);
     h->st.on = false;
+}
+
+static_assert(LD_MAX == FIBHIP_MAX_LEADS && LD_MAX % LD_GROUP == 0 && LD_THREADS == 256 && LD_TY % (LD_THREADS / 64) == 0,
+              "lead_kernel's constants follow include/fibhip.h; four waves, each LD_CPT rows of the tile");
+// The lead recorder's hook: at a sample tick lead_kernel is enqueued on s0 behind the launch that ended there (one partial per
+// lead and tile) and lead_combine_kernel behind it (the sample's row).  The row's slot is a kernel argument computed from the
+// host's counter, so a replay (recover()) writes the same slot again; the partials are rewritten whole by every sample.
+static int leads_advance(fibhip_ctx *h, int ticks, bool)
+{
+    LeadRec &r = h->ld;
+    long long s;
+    if (!r.advance(ticks, &s)) return 0;
+    if (s >= r.cap) return fail(FIBHIP_EINVAL, "lead recorder: trace full");                   // (fibhip_step refuses before this)
+    LeadArgs a;
+    a.x = array_of(h, r.var);
+    a.w = r.weight;
+    a.dpy = h->has_phase ? h->phase3 : nullptr;
+    a.dpx = h->has_phase ? h->phase3 + h->cells : nullptr;
+    a.q4 = h->has_phase ? h->phase3 + 2 * h->cells : nullptr;
+    a.r4 = h->has_phase ? h->phase3 + 3 * h->cells : nullptr;
+    a.pos = r.pos;
+    a.tables = r.tables;
+    a.part = r.part;
+    a.H = h->d.height; a.W = h->d.width; a.pitch = h->pitch; a.n = r.n;
+    const dim3 grid((unsigned)r.tiles_x, (unsigned)r.tiles_y);
+    if (int rc = launch_traced(h, "lead_kernel", 0, [&] { hipLaunchKernelGGL(lead_kernel, grid, dim3(LD_THREADS), 0, h->s0, a); })) return rc;
+    double *row = r.rows + (size_t)s * (size_t)r.n;
+    return launch_traced(h, "lead_combine_kernel", 0, [&] {
+        hipLaunchKernelGGL(lead_combine_kernel, dim3((unsigned)r.n), dim3(256), 0, h->s0, (const double *)r.part, r.tiles_x * r.tiles_y, row);
+    });
+}
+static void leads_free(fibhip_ctx *h)
+{
+    dev_free(h->ld.pos);
+    dev_free(h->ld.tables);
+    dev_free(h->ld.weight);
+    dev_free(h->ld.part);
+    dev_free(h->ld.rows);
+    h->ld.on = false;
 }
 
 static_assert(SPEC_MAX_BINS == FIBHIP_SPECTRUM_MAX_BINS && SPEC_MAX_CHUNK == FIBHIP_SPECTRUM_MAX_CHUNK &&
@@ -1104,6 +1143,112 @@ extern "C" int fibhip_stats_end(fibhip_t h)
 {
     NEED(h);
     return detach(h, h->st.on, stats_free);
+}
+
+// ---- lead recorder ------------------------------------------------------------------------------------------------------
+// does the handle's diffusion term use the zero-padded convolution Laplacian (fenton_simple.py)?
+static inline bool zero_padded(const fibhip_ctx *h)
+{
+    if (h->d.flags & FIBHIP_ZEROPAD) return true;
+#ifdef FIB_CUSTOM_MODEL_INC
+    if (h->d.model == FIBHIP_CUSTOM && !h->mod && ZeroPadOf<Custom>::value) return true;
+#endif
+    return false;
+}
+
+extern "C" int fibhip_leads_begin(fibhip_t h, int var, int n, const int *pos, int ntables, const float *tables, const float *weight, int every,
+                                  long long capacity)
+{
+    NEED(h);
+    if (!pos || !tables) return fail(FIBHIP_EINVAL, "leads_begin: null argument");
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "leads_begin: bad var %d", var);
+    if (n < 1 || n > FIBHIP_MAX_LEADS) return fail(FIBHIP_EINVAL, "leads_begin: 1 .. %d leads (got %d)", FIBHIP_MAX_LEADS, n);
+    if (ntables < 1 || ntables > FIBHIP_MAX_LEAD_TABLES)
+        return fail(FIBHIP_EINVAL, "leads_begin: 1 .. %d lead-field tables (got %d)", FIBHIP_MAX_LEAD_TABLES, ntables);
+    if (every < 1) return fail(FIBHIP_EINVAL, "leads_begin: every must be >= 1 (got %d)", every);
+    if (capacity < 1 || capacity > (long long)(SIZE_MAX / sizeof(double) / (size_t)n)) return fail(FIBHIP_EINVAL, "leads_begin: bad capacity %lld", capacity);
+    const int H = h->d.height, W = h->d.width;
+    if (H < 3 || W < 3) return fail(FIBHIP_EINVAL, "leads_begin: a %d x %d grid has no interior cell", H, W);
+    if (zero_padded(h))
+        return fail(FIBHIP_EINVAL, "leads_begin: not on a model with the zero-padded Laplacian (FIBHIP_ZEROPAD): its diffusion term is not this source");
+    std::vector<int> table(4 * (size_t)n);
+    for (int e = 0; e < n; ++e) {
+        const int r = pos[3 * e], c = pos[3 * e + 1], t = pos[3 * e + 2];
+        if (r < 0 || r >= H || c < 0 || c >= W) return fail(FIBHIP_EINVAL, "leads_begin: lead %d: cell (%d, %d) is outside the %d x %d grid", e, r, c, H, W);
+        if (t < 0 || t >= ntables) return fail(FIBHIP_EINVAL, "leads_begin: lead %d: table %d of %d", e, t, ntables);
+        table[4 * e] = r; table[4 * e + 1] = c; table[4 * e + 2] = t; table[4 * e + 3] = 0;
+    }
+    for (int t = 0; t < ntables; ++t)
+        for (size_t i = 0; i < h->cells; ++i)
+            if (!std::isfinite(tables[(size_t)t * h->cells + i]))
+                return fail(FIBHIP_EINVAL, "leads_begin: table %d has a value that is not finite (row %zu, column %zu)", t, i / (size_t)W, i % (size_t)W);
+    if (weight)
+        for (size_t i = 0; i < h->cells; ++i)
+            if (!std::isfinite(weight[i]))
+                return fail(FIBHIP_EINVAL, "leads_begin: the weight plane has a value that is not finite (row %zu, column %zu)", i / (size_t)W,
+                            i % (size_t)W);
+    if (int rc = attach_refusals(h, "leads_begin")) return rc;
+    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    leads_free(h);
+    LeadRec &r = h->ld;
+    const int tiles_x = (W + LD_TX - 1) / LD_TX, tiles_y = (H + LD_TY - 1) / LD_TY;
+    const size_t ntiles = (size_t)tiles_x * (size_t)tiles_y;
+    bool ok = hipMalloc((void **)&r.pos, table.size() * sizeof(int)) == hipSuccess &&
+              hipMalloc((void **)&r.tables, (size_t)ntables * h->cells * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&r.part, (size_t)n * ntiles * sizeof(double)) == hipSuccess &&
+              hipMalloc((void **)&r.rows, (size_t)capacity * (size_t)n * sizeof(double)) == hipSuccess;
+    if (ok && weight) ok = hipMalloc((void **)&r.weight, h->cells * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        leads_free(h);
+        return fail(FIBHIP_ENOMEM, "leads_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d leads, %d tables)", capacity, n, ntables);
+    }
+    HIPCHK(hipMemcpyAsync(r.pos, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemcpyAsync(r.tables, tables, (size_t)ntables * h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    if (weight) HIPCHK(hipMemcpyAsync(r.weight, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemsetAsync(r.rows, 0, (size_t)capacity * (size_t)n * sizeof(double), h->s0));
+    HIPCHK(wait_stream(h->s0));                        // `table` and the caller's arrays are free again
+    r.on = true;
+    r.start(every, capacity);
+    r.before_slow = slow_array(var);
+    r.var = var;
+    r.n = n;
+    r.tiles_x = tiles_x;
+    r.tiles_y = tiles_y;
+    return 0;
+}
+
+extern "C" int fibhip_leads_count(fibhip_t h, long long *samples)
+{
+    NEED(h);
+    if (!samples) return fail(FIBHIP_EINVAL, "leads_count: null argument");
+    if (!h->ld.on) return fail(FIBHIP_EINVAL, "leads_count: no recorder attached (fibhip_leads_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    *samples = h->ld.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+
+extern "C" int fibhip_leads_read(fibhip_t h, long long first, long long count, double *dst)
+{
+    NEED(h);
+    if (!h->ld.on) return fail(FIBHIP_EINVAL, "leads_read: no recorder attached (fibhip_leads_begin)");
+    FLUSH(h);
+    if (int rc = range_check("leads_read", "samples", first, count, h->ld.taken())) return rc;
+    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "leads_read: null destination");
+    return read_confirmed(h, [&] {
+        if (count > 0)
+            HIPCHK(hipMemcpyAsync(dst, h->ld.rows + (size_t)first * h->ld.n, (size_t)count * h->ld.n * sizeof(double), hipMemcpyDeviceToHost, h->s0));
+        return 0;
+    });
+}
+
+extern "C" int fibhip_leads_end(fibhip_t h)
+{
+    NEED(h);
+    return detach(h, h->ld.on, leads_free);
 }
 
 // ---- spectrum recorder --------------------------------------------------------------------------------------------------

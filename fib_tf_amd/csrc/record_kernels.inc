@@ -1,4 +1,4 @@
-// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame, statistics, spectrum and beat recorders, and the
+// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame, statistics, spectrum, beat and lead recorders, and the
 // plain copy whose shape they take (the bandwidth yardstick).  (included by kernels.hpp; the host side is record.inc)
 
 // ---- activation recorder (fibhip_observe_begin): per-cell event maps, updated after every observed tick ----------------
@@ -1227,4 +1227,154 @@ beat_summary_kernel(const int *__restrict__ count, const float *__restrict__ t_u
     apd_mean[t] = used ? sum / (float)used : __builtin_nanf("");
     cl_mean[t] = ncl ? cls / (float)ncl : __builtin_nanf("");
     apd_alt[t] = pairs ? alt / (float)pairs : __builtin_nanf("");
+}
+
+// ---- lead recorder (fibhip_leads_begin): unipolar electrograms, the membrane current seen through a lead field ---------------
+// The SOURCE at an interior cell (1 <= r <= H - 2, 1 <= c <= W - 2) of the watched array X is the stand-alone laplace() of
+// the boundary-enforced array: stencil9 over taps read at (clamp(r + dr, 1, H - 2), clamp(c + dc, 1, W - 2)) — tick_kernel's
+// rule —, plus phase_term<Exact> from the prepared dpy, dpx, q4, r4 where the handle has a phase field.  Always the exact form,
+// whatever the handle's policy, float32, every operation rounded on its own (-ffp-contract=off).  q = w * S is one more float32
+// product (no plane: q = S); the outer ring of the grid holds ghost copies and contributes nothing.  Lead e sits at cell (re, ce)
+// and names a table T: its weight of cell (r, c) is T[|r - re|][|c - ce|], its term (double)T * (double)q — exact, the product
+// of two float32 — and its sample the float64 sum of the terms, every addition rounded on its own (no fma), in an order fixed
+// by H and W alone:
+//   lead_kernel, grid (ceil(W / LD_TX), ceil(H / LD_TY)), LD_THREADS threads: a workgroup stages its tile of X with a one-cell
+//   ring in LDS through the clamp (consecutive lanes, consecutive words: conflict-free for all nine taps) and lane l of wave v
+//   forms q ONCE for the cells (row v + 4j, column l) of the tile, j = 0 .. LD_CPT - 1, in registers.  Then the leads in groups
+//   of LD_GROUP: the group's float64 accumulators are addressed by fully unrolled loops only (a run-time index would put them
+//   in scratch: frame_kernel's note), a lead's cell and table are wave-uniform (scalar loads), the group's table loads are
+//   issued together in front of its arithmetic (a slot beyond the last lead repeats the last lead and is dropped), and a
+//   wave's table loads for one row of cells are consecutive addresses, ascending or descending.  A thread adds its cells in the
+//   order of j; then six shuffle levels in each wave (lead_group_sum: the group's eight sums as one butterfly, a fixed tree per
+//   lead), the wave sums through LDS, (w0 + w1) + (w2 + w3) by one thread
+//   per lead, and ONE plain 64-bit store per (lead, tile) into part[lead][tile].  X, the weight plane and the phase arrays are
+//   read once per sample however many leads there are.
+//   lead_combine_kernel, one workgroup per lead, a second launch on the same stream: thread t adds the tiles t, t + 256, ...
+//   in that order (any tile count), then the same wave and workgroup tree, and writes the lead's entry of the sample's row.
+// A cell outside the interior adds the term +0.0 (its table address is clamped into the table).  No atomics of any kind.
+#define LD_TX 64
+#define LD_TY 16
+#define LD_THREADS 256
+#define LD_CPT (LD_TY / (LD_THREADS / 64))      // cells per thread
+#define LD_GROUP 8
+#define LD_MAX 64               // leads (FIBHIP_MAX_LEADS)
+struct LeadArgs {
+    const float *x;             // the watched array (its first row), `pitch` floats between rows
+    const float *w;             // the weight plane [H][W], or null
+    const float *dpy, *dpx, *q4, *r4;   // the prepared phase arrays [H][W], or all null: no phase field
+    const int *pos;             // [n][4] = row, col, table, 0
+    const float *tables;        // [ntables][H][W]
+    double *part;               // [n][tiles]
+    int H, W, pitch, n;
+};
+
+static FIB_DEV double lead_wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
+    return v;
+}
+
+// The LD_GROUP = 8 sums of a group over the 64 lanes of a wave as ONE butterfly: at the levels 32, 16 and 8 a lane hands the half
+// of its values its partner keeps to that partner (lane ^ level) and adds what it receives to the half it keeps — 4, 2 and 1
+// shuffles instead of 8 each —, after which it holds one value, that of slot 4 * bit 5 + 2 * bit 4 + bit 3 of its lane number
+// (returned); the levels 4, 2 and 1 finish that one.  Which value a lane keeps is a select, never a run-time index.  Every
+// slot's sum is the same tree — pairs 32 apart, then 16, 8, 4, 2, 1 — and IEEE addition commutes, so a lead's sum does not
+// depend on the slot it has in its group: its bits are those of the six plain levels over (lane, lane ^ level).  The sum is
+// left in acc[0] of the lanes that hold the slot.
+static FIB_DEV int lead_group_sum(double (&acc)[LD_GROUP], int lane)
+{
+    static_assert(LD_GROUP == 8, "three halving levels");
+    const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double keep = b5 ? acc[i + 4] : acc[i], send = b5 ? acc[i] : acc[i + 4];
+        acc[i] = keep + __shfl_xor(send, 32, 64);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const double keep = b4 ? acc[i + 2] : acc[i], send = b4 ? acc[i] : acc[i + 2];
+        acc[i] = keep + __shfl_xor(send, 16, 64);
+    }
+    {
+        const double keep = b3 ? acc[1] : acc[0], send = b3 ? acc[0] : acc[1];
+        acc[0] = keep + __shfl_xor(send, 8, 64);
+    }
+#pragma unroll
+    for (int off = 4; off > 0; off >>= 1) acc[0] = acc[0] + __shfl_xor(acc[0], off, 64);
+    return (b5 ? 4 : 0) + (b4 ? 2 : 0) + (b3 ? 1 : 0);
+}
+
+__global__ void __launch_bounds__(LD_THREADS) lead_kernel(LeadArgs a)
+{
+    constexpr int LP = LD_TX + 2, LQ = LD_TY + 2, NW = LD_THREADS / 64;
+    __shared__ float tile[LQ * LP];
+    __shared__ double wres[NW][LD_MAX];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x0 = (int)blockIdx.x * LD_TX, y0 = (int)blockIdx.y * LD_TY;
+    const int H = a.H, W = a.W;
+    for (int i = tid; i < LQ * LP; i += LD_THREADS) {
+        const int ly = i / LP, lx = i - ly * LP;
+        const int yy = clampi(y0 - 1 + ly, 1, H - 2), xx = clampi(x0 - 1 + lx, 1, W - 2);
+        tile[i] = a.x[(size_t)yy * (size_t)a.pitch + (size_t)xx];
+    }
+    __syncthreads();
+    const int c = x0 + lane;
+    const int ca = min(c, W - 1);                                    // (the column a table address is formed from)
+    float q[LD_CPT];
+    int ra[LD_CPT];
+#pragma unroll
+    for (int j = 0; j < LD_CPT; ++j) {
+        const int ly = wave + NW * j, r = y0 + ly;
+        ra[j] = min(r, H - 1);
+        q[j] = 0.f;
+        if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
+            const float *t = tile + (ly + 1) * LP + lane + 1;
+            const float N = t[-LP], S = t[LP], Wv = t[-1], E = t[1];
+            float s = stencil9(N, S, Wv, E, t[-LP - 1], t[LP - 1], t[-LP + 1], t[LP + 1], t[0]);
+            const size_t o = (size_t)r * (size_t)W + (size_t)c;
+            if (a.dpy) s = s + phase_term<Exact>(N, S, Wv, E, a.dpy[o], a.dpx[o], a.q4[o], a.r4[o]);
+            q[j] = a.w ? a.w[o] * s : s;
+        }
+    }
+    const size_t cells = (size_t)H * (size_t)W;
+    for (int g0 = 0; g0 < a.n; g0 += LD_GROUP) {
+        // all of the group's table loads first, with no branch between them, so that they are in flight together; a slot beyond
+        // the last lead repeats the last lead (the same addresses once more) and its sum is dropped
+        float k[LD_GROUP][LD_CPT];
+#pragma unroll
+        for (int e = 0; e < LD_GROUP; ++e) {
+            const int *__restrict__ p = a.pos + 4 * min(g0 + e, a.n - 1);
+            const int re = p[0], ce = p[1];
+            const float *__restrict__ T = a.tables + (size_t)p[2] * cells + (size_t)__builtin_abs(ca - ce);
+#pragma unroll
+            for (int j = 0; j < LD_CPT; ++j) k[e][j] = T[(size_t)__builtin_abs(ra[j] - re) * (size_t)W];
+        }
+        double acc[LD_GROUP];
+#pragma unroll
+        for (int e = 0; e < LD_GROUP; ++e) {
+            acc[e] = 0.0;
+#pragma unroll
+            for (int j = 0; j < LD_CPT; ++j) acc[e] = acc[e] + (double)k[e][j] * (double)q[j];
+        }
+        const int e = lead_group_sum(acc, lane);
+        if ((lane & 7) == 0 && g0 + e < a.n) wres[wave][g0 + e] = acc[0];
+    }
+    __syncthreads();
+    if (tid < a.n) {
+        const double v = (wres[0][tid] + wres[1][tid]) + (wres[2][tid] + wres[3][tid]);
+        a.part[(size_t)tid * ((size_t)gridDim.x * gridDim.y) + ((size_t)blockIdx.y * gridDim.x + blockIdx.x)] = v;
+    }
+}
+
+__global__ void __launch_bounds__(256) lead_combine_kernel(const double *__restrict__ part, int ntiles, double *__restrict__ row)
+{
+    __shared__ double wres[4];
+    const double *__restrict__ p = part + (size_t)blockIdx.x * (size_t)ntiles;
+    double v = 0.0;
+    for (int t = (int)threadIdx.x; t < ntiles; t += 256) v = v + p[t];
+    v = lead_wave_sum(v);
+    if ((threadIdx.x & 63u) == 0) wres[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) row[blockIdx.x] = (wres[0] + wres[1]) + (wres[2] + wres[3]);
 }

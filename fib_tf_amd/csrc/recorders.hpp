@@ -17,8 +17,8 @@ struct Recorder {
 };
 constexpr size_t NO_SAMPLER = ~(size_t)0;
 
-static recorder_advance_fn electrode_advance, tips_advance, frames_advance, stats_advance, spectrum_advance, beats_advance, stim_advance, trig_advance;
-static recorder_free_fn electrode_free, tips_free, frames_free, stats_free, spectrum_free, beats_free, stim_free, trig_free;
+static recorder_advance_fn electrode_advance, tips_advance, frames_advance, stats_advance, leads_advance, spectrum_advance, beats_advance, stim_advance, trig_advance;
+static recorder_free_fn electrode_free, tips_free, frames_free, stats_free, leads_free, spectrum_free, beats_free, stim_free, trig_free;
 static long long stim_next(const StimRec &r);                   // sched.inc
 
 // (`on` is the Sampler's first member; the handle holds vectors, which is all that makes offsetof conditionally supported here)
@@ -35,6 +35,11 @@ static constexpr Recorder RECORDERS[] = {
     {"tip", SAMPLER_AT(tip), tips_advance, tips_free},
     {"frame", SAMPLER_AT(fr), frames_advance, frames_free},
     {"statistics", SAMPLER_AT(st), stats_advance, stats_free},
+    // ... and so does the lead recorder, a fifth of that kind: lead_kernel reads the state, the phase arrays and the recorder's
+    // own constant tables and writes every partial of its (lead, tile) slots whole; lead_combine_kernel writes the sample's row
+    // whole from those partials.  Nothing is accumulated across samples and the slot follows from the counter, so a sample taken
+    // from a void slab is overwritten, partials and row, when the replay takes it again
+    {"lead", SAMPLER_AT(ld), leads_advance, leads_free},
     // these two ACCUMULATE (the fold and the short ring; the count, the open beat's peak, the ring): their kernels read the
     // give-up word first and write nothing once a launch in front of them gave up, and how far they have come follows from the
     // counter alone — the replay takes the lost samples and issues the lost folds again, in order.  Neither ever fills up

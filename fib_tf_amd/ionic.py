@@ -293,6 +293,24 @@ class IonicModel:
             ensure()
         return StatsRecorder(self, columns, every=every, weight=weight, mask=mask, capacity=capacity)
 
+    def record_leads(self, positions, tables, table_of=None, every=1, weight='phase', var=0, capacity=None):
+        """attaches a lead recorder (fib_tf_amd/leads.py) to this model's handle: every `every` ticks the unipolar electrogram of
+        every electrode of `positions` — a list of up to 64 integer cells (row, col) — is formed on the device and kept there
+        until `traces()` / `raw()` read it: the float64 sum over the interior cells of K_e * (w * laplace(X)), with X the state
+        array `var` behind enforce_boundary, laplace the model's own (9-point Laplacian plus the phase-field term, always in the
+        exact form), `weight` w ('phase': the model's phase field if it has one; None: 1; or an [height, width] array) and
+        K_e(r, c) = T[|r - row_e|][|c - col_e|] the electrode's lead field.  `tables` is one table [height, width] or up to 4
+        of them (`leads.point_table` makes a point electrode's); with several, `table_of` names one per electrode.  Default
+        capacity: the samples of a whole run of `duration`.  Call after define(); single device only (row blocks raise
+        NotImplementedError); a model with the zero-padded Laplacian is refused."""
+        from .leads import LeadRecorder
+        if not self.defined:
+            raise AssertionError('record_leads should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return LeadRecorder(self, positions, tables, table_of=table_of, every=every, weight=weight, var=var, capacity=capacity)
+
     def record_spectrum(self, every=10, nfft=128, fmin=None, fmax=None, bins=None, window='hann', chunk=None, var=0, block=(1, 1),
                         reduce='mean', region=None, weight=None):
         """attaches a spectrum recorder (fib_tf_amd/spectrum.py) to this model's handle: every `every` ticks a pixel plane of

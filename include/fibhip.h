@@ -526,6 +526,40 @@ int fibhip_stats_count(fibhip_t h, long long *samples);
 int fibhip_stats_read(fibhip_t h, long long first, long long count, double *dst /* [count][ncols] */);
 int fibhip_stats_end(fibhip_t h);
 
+/* Lead recorder: unipolar electrograms.  An extracellular electrode sees the transmembrane current of every cell through a lead
+ * field; the recorder forms that current from the watched array on the device every `every` ticks and appends one float64 per
+ * lead to a trace that stays on the device until it is read.  With X the array `var` on the height x width grid, one sample is
+ * (restated in NumPy in tests/lead_ref.py):
+ *     source  on the interior cells 1 <= r <= height - 2, 1 <= c <= width - 2 only (the outer ring holds ghost copies and
+ *             contributes nothing): S = the 9-point Laplacian in the reference's order over taps read at
+ *             X[clamp(r + dr, 1, height - 2)][clamp(c + dc, 1, width - 2)], plus the phase-field term with the correctly
+ *             rounded quotient where the handle has a phase field — laplace(enforce_boundary(X)) of the stand-alone array ops,
+ *             always in the exact form, whatever the handle's arithmetic policy; float32, every operation rounded on its own.
+ *     weight  q = w * S, one float32 product rounded on its own; w is the caller's plane [height*width], or 1 without one.
+ *     lead    lead e sits at the cell (row_e, col_e) and names one of the ntables lead-field tables T, each float32
+ *             [height][width]: K_e(r, c) = T[|r - row_e|][|c - col_e|].  Its term of a cell is (double)K_e * (double)q, exact;
+ *             its value the float64 sum of the terms over the interior cells, every addition rounded on its own (no fma), in an
+ *             order fixed by height and width alone — not by the number of leads, the stride, the launch plan or the run.
+ *             Against the exact sum of the n terms: |value - sum| <= n * 2^-53 / (1 - n * 2^-53) * sum |term|.
+ * A NaN in the interior makes every lead NaN.  The sample ticks, the capacity rule ("trace full"), the launches and the 'slow'
+ * rule are those of the statistics recorder; the recorder may be attached beside every other recorder, each with its own stride.
+ * Refused with FIBHIP_EINVAL, the message naming the offender: var out of range, n outside 1 .. FIBHIP_MAX_LEADS, ntables
+ * outside 1 .. FIBHIP_MAX_LEAD_TABLES, a lead outside the grid or naming a table that is not there, a table or weight value that
+ * is not finite, every < 1, capacity < 1, a grid smaller than 3 x 3, a handle with the zero-padded Laplacian (FIBHIP_ZEROPAD: its
+ * diffusion term is not this source), inside an open tick, a row block (a handle with ghost rows).
+ *   fibhip_leads_begin  flushes, synchronises and confirms pending work, copies positions, tables and the plane and attaches
+ *   fibhip_leads_count  samples taken so far (ticks accepted but not launched yet included)
+ *   fibhip_leads_read   samples [first, first + count) as [count][n] float64; flushes and blocks like get_state; does not detach
+ *                       and does not reset the sample index
+ *   fibhip_leads_end    detaches and frees the trace (no recorder attached: nothing); fibhip_destroy does the same             */
+#define FIBHIP_MAX_LEADS 64
+#define FIBHIP_MAX_LEAD_TABLES 4
+int fibhip_leads_begin(fibhip_t h, int var, int n, const int *pos /* [n][3] = row, col, table */, int ntables,
+                       const float *tables /* [ntables][H*W] */, const float *weight /* [H*W] or NULL */, int every, long long capacity);
+int fibhip_leads_count(fibhip_t h, long long *samples);
+int fibhip_leads_read(fibhip_t h, long long first, long long count, double *dst /* [count][n] */);
+int fibhip_leads_end(fibhip_t h);
+
 /* Spectrum recorder: per-cell power spectra (a Welch periodogram) folded on the device while the run goes on, and the
  * dominant-frequency maps made from them — the sixth recorder and the fifth sampler.  All device arithmetic is float32, every
  * operation rounded on its own (no contraction), in the order written; no transcendental is evaluated on the device.
