@@ -17,6 +17,7 @@ from . import stats                             # noqa: F401  (StatsRecorder: ti
 from . import spectrum                          # noqa: F401  (SpectrumRecorder: per-cell power spectra and dominant-frequency maps)
 from . import beats                             # noqa: F401  (BeatRecorder: per-cell beat history, restitution and alternans maps)
 from . import leads                             # noqa: F401  (LeadRecorder: unipolar electrograms from the membrane current)
+from . import waves                             # noqa: F401  (WaveRecorder: excited domains labelled and counted on the device)
 from . import stimulus                        # noqa: F401  (Stimulus, StimulusProgram: pacing protocols run on the device)
 from . import triggers                          # noqa: F401  (Sensor, Trigger, TriggerProgram: triggered stimulation on the device)
 

@@ -23,6 +23,11 @@ BEATS_MAX_DEPTH = 16
 STAT_KINDS = ('sum', 'min', 'max', 'below', 'above', 'nonfinite')  # enum fibhip_stat_kind, in order
 MAX_STAT_COLS, MAX_STAT_COLS_PER_ARRAY = 64, 8
 MAX_LEADS, MAX_LEAD_TABLES = 64, 4
+WAVE_KINDS = ('above', 'below')                                   # enum fibhip_wave_kind, in order
+MAX_WAVES = 65536
+# struct fibhip_wave_record (40 bytes)
+WAVE_RECORD_DTYPE = np.dtype([('seed', np.int32), ('area', np.int32), ('sum_r', np.int64), ('sum_c', np.int64),
+                              ('r0', np.int32), ('r1', np.int32), ('c0', np.int32), ('c1', np.int32)])
 STIM_MODES = ('max', 'add')                                       # enum fibhip_stim_mode, in order
 STIM_SHAPES = ('rect', 'plane')                                   # enum fibhip_stim_shape, in order
 MAX_STIM_ENTRIES, MAX_STIM_PLANES = 64, 8
@@ -228,6 +233,12 @@ SYMBOLS = {
     'fibhip_leads_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_leads_read': ([_h, C.c_longlong, C.c_longlong, C.POINTER(C.c_double)], C.c_int),
     'fibhip_leads_end': ([_h], C.c_int),
+    'fibhip_waves_begin': ([_h, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
+                            C.c_longlong], C.c_int),
+    'fibhip_waves_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_waves_read': ([_h, C.c_longlong, C.c_longlong, _ip, C.c_void_p], C.c_int),
+    'fibhip_waves_labels': ([_h, _ip], C.c_int),
+    'fibhip_waves_end': ([_h], C.c_int),
     'fibhip_spectrum_begin': ([_h, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int], C.c_int),
     'fibhip_spectrum_count': ([_h, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_spectrum_shape': ([_h, _ip, _ip, _ip], C.c_int),
@@ -1071,6 +1082,50 @@ class Stepper:
 
     def leads_end(self):
         self._ck(self._L.fibhip_leads_end(self._h))
+
+    # ---- wave recorder (include/fibhip.h fibhip_waves_*) ----------------------------------------------------------
+    def waves_begin(self, var=0, kind=0, level=0.0, var2=-1, kind2=0, level2=0.0, conn=4, mask=None, max_waves=256, every=1, capacity=1):
+        """attaches (or re-attaches, with empty lists) the wave recorder: a cell is set where `mask` ([height, width], or None:
+        everywhere) is non-zero and array `var` is above (`kind` 0) or below (1) `level`, and array `var2` (-1: none) meets
+        (`kind2`, `level2`) too; the connected components under `conn` = 4 or 8 are the waves; one sample every `every` ticks,
+        `capacity` samples of up to `max_waves` records at the most"""
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.shape != (self.height, self.width):
+                raise ValueError('waves_begin: a mask of shape %s on a %d x %d grid' % (mask.shape, self.height, self.width))
+            mp = mask.ctypes.data_as(C.POINTER(C.c_ubyte))
+        self._ck(self._L.fibhip_waves_begin(self._h, int(var), int(kind), float(level), int(var2), int(kind2), float(level2), int(conn), mp,
+                                            int(max_waves), int(every), int(capacity)))
+        self._wave_max = int(max_waves)
+
+    def waves_count(self):
+        """samples taken since waves_begin (ticks accepted but not launched yet included)"""
+        k = C.c_longlong()
+        self._ck(self._L.fibhip_waves_count(self._h, C.byref(k)))
+        return int(k.value)
+
+    def waves_read(self, first=0, count=None, records=True):
+        """samples [first, first + count) (count=None: all taken so far) as (counts, records): counts int32 [count, 3] = n,
+        stored, cells; records WAVE_RECORD_DTYPE [count, max_waves], of which the first `stored` of each sample are valid, in
+        no fixed order (records=False: None).  Blocks like get_state, detaches nothing"""
+        if count is None:
+            count = self.waves_count() - int(first)
+        n = max(int(count), 0)
+        counts = np.zeros((n, 3), np.int32)
+        recs = np.zeros((n, getattr(self, '_wave_max', 0)), WAVE_RECORD_DTYPE) if records else None
+        self._ck(self._L.fibhip_waves_read(self._h, int(first), int(count), counts.ctypes.data_as(_ip),
+                                           recs.ctypes.data_as(C.c_void_p) if records else None))
+        return counts, recs
+
+    def waves_labels(self):
+        """the label plane of the latest sample: int32 [height, width], the seed of the cell's wave or -1"""
+        out = np.empty((self.height, self.width), np.int32)
+        self._ck(self._L.fibhip_waves_labels(self._h, out.ctypes.data_as(_ip)))
+        return out
+
+    def waves_end(self):
+        self._ck(self._L.fibhip_waves_end(self._h))
 
     # ---- stimulus program (include/fibhip.h fibhip_stim_*) --------------------------------------------------------
     def stim_begin(self, entries, planes=None):

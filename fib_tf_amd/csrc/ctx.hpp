@@ -188,6 +188,19 @@ struct LeadRec : Sampler {
     double *rows;           // device: [cap][n]
 };
 
+// wave recorder (fibhip_waves_begin): wave_label_kernel, wave_merge_kernel, wave_root_kernel and wave_reduce_kernel behind the
+// launch that ends a sample tick.  The two planes are scratch that every sample rewrites before it reads them; the sample's
+// counts are zeroed and its records written whole
+struct WaveRec : Sampler {
+    int var, var2, kind, kind2, conn, max_waves;
+    float level, level2;
+    unsigned char *mask;    // device: [H][W], or null (every cell counts)
+    int *labels;            // device: [H][W], the label plane of the latest sample
+    int *slots;             // device: [H][W], a root's slot in its sample's records
+    int *counts;            // device: [cap][3] = n, stored, cells
+    WaveRecord *records;    // device: [cap][max_waves]
+};
+
 // spectrum recorder (fibhip_spectrum_begin): spectrum_sample_kernel behind the launch that ends a sample tick and, behind the
 // sample that fills the ring, spectrum_fold_kernel.  It ACCUMULATES: both kernels read the give-up word first, and everything
 // about its progress follows from `k` alone — samples k / every, the ring slot and the segment position of a sample, the folds
@@ -317,6 +330,7 @@ struct fibhip_ctx {
     FrRec fr;
     StRec st;
     LeadRec ld;
+    WaveRec wv;
     SpRec sp;
     BeatRec bt;
     StimRec stim;

@@ -34,7 +34,7 @@ using namespace fib;
 #include "recorders.hpp"    // the table of the hooks behind a committed launch, in hook order
 #include "tick.inc"         // one tick: pointer tables, rows, edges / interior / commit
 #include "sched.inc"        // when ticks are launched: deferral, multi-tick launches, run-ahead, journal and recovery, fibhip_step
-#include "record.inc"       // activation, electrode, tip, frame, statistics, lead, spectrum and beat recorders; the stimulus program and the trigger program
+#include "record.inc"       // activation, electrode, tip, frame, statistics, lead, wave, spectrum and beat recorders; the stimulus program and the trigger program
 #include "plan.inc"         // build_plan, autotune
 #include "comm.inc"         // the RCCL halo path and fibhip_halo_plan
 // this file: create / destroy, state get / set, pointwise modes, pace / probe / sync / timing, run-time modules, accessors and

@@ -1,6 +1,6 @@
-// record.inc — what runs on the device behind the ticks while a model runs.  Eight recorders: the per-cell activation maps
+// record.inc — what runs on the device behind the ticks while a model runs.  Nine recorders: the per-cell activation maps
 // (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
-// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the unipolar electrograms (fibhip_leads_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell
+// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the unipolar electrograms (fibhip_leads_*), the excited domains (fibhip_waves_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell
 // beat history (fibhip_beats_*); and the two hooks that write the state: the stimulus program (fibhip_stim_*) and the trigger
 // program (fibhip_trig_*), which senses, decides and fires on the device.
 // The file has three parts: the helpers every recorder shares; the hooks — per recorder its _advance (behind a launch that the
@@ -357,6 +357,62 @@ static void leads_free(fibhip_ctx *h)
     dev_free(h->ld.part);
     dev_free(h->ld.rows);
     h->ld.on = false;
+}
+
+static_assert(sizeof(WaveRecord) == sizeof(fibhip_wave_record) && offsetof(WaveRecord, sum_r) == offsetof(fibhip_wave_record, sum_r) &&
+                  offsetof(WaveRecord, r0) == offsetof(fibhip_wave_record, r0) && sizeof(WaveRecord) == 40 && WV_THREADS == 256 &&
+                  WV_TX == 64 && WV_TY % (WV_THREADS / 64) == 0,
+              "the wave kernels' record is include/fibhip.h's; a tile row is one wave, four waves share the rows of a tile");
+// The wave recorder's hook: at a sample tick the sample's three counts are zeroed and the four kernels are enqueued behind them
+// on s0 (the merge only where the grid has more than one tile).  Counts and records are addressed from the host's counter, so a
+// replay zeroes and fills the same slot again; the two planes belong to whichever sample is the latest.
+static int waves_advance(fibhip_ctx *h, int ticks, bool)
+{
+    WaveRec &r = h->wv;
+    long long s;
+    if (!r.advance(ticks, &s)) return 0;
+    if (s >= r.cap) return fail(FIBHIP_EINVAL, "wave recorder: trace full");                   // (fibhip_step refuses before this)
+    const int H = h->d.height, W = h->d.width, ncells = (int)h->cells;
+    int *cnt = r.counts + 3 * (size_t)s;
+    WaveRecord *rec = r.records + (size_t)s * (size_t)r.max_waves;
+    WaveArgs a;
+    a.x = array_of(h, r.var);
+    a.x2 = r.var2 >= 0 ? array_of(h, r.var2) : nullptr;
+    a.mask = r.mask;
+    a.labels = r.labels;
+    a.cnt = cnt;
+    a.H = H; a.W = W; a.pitch = h->pitch;
+    a.kind = r.kind; a.kind2 = r.kind2; a.conn = r.conn;
+    a.level = r.level; a.level2 = r.level2;
+    const size_t tiles = (size_t)((W + WV_TX - 1) / WV_TX) * (size_t)((H + WV_TY - 1) / WV_TY);
+    const int nbr = (H - 1) / WV_TY, nbc = (W - 1) / WV_TX;
+    const size_t border = (size_t)nbr * (size_t)W + (size_t)nbc * (size_t)H;
+    const dim3 cells = blocks_of(h->cells);
+    HIPCHK(hipMemsetAsync(cnt, 0, 3 * sizeof(int), h->s0));
+    if (int rc = launch_traced(h, "wave_label_kernel", 0,
+                               [&] { hipLaunchKernelGGL(wave_label_kernel, dim3((unsigned)tiles), dim3(WV_THREADS), 0, h->s0, a); }))
+        return rc;
+    if (border)
+        if (int rc = launch_traced(h, "wave_merge_kernel", 0, [&] {
+                hipLaunchKernelGGL(wave_merge_kernel, blocks_of(border), dim3(256), 0, h->s0, r.labels, H, W, r.conn, nbr, nbc);
+            }))
+            return rc;
+    if (int rc = launch_traced(h, "wave_root_kernel", 0, [&] {
+            hipLaunchKernelGGL(wave_root_kernel, cells, dim3(256), 0, h->s0, r.labels, r.slots, ncells, cnt, rec, r.max_waves);
+        }))
+        return rc;
+    return launch_traced(h, "wave_reduce_kernel", 0, [&] {
+        hipLaunchKernelGGL(wave_reduce_kernel, blocks_of((h->cells + WV_RED_CPT - 1) / WV_RED_CPT), dim3(256), 0, h->s0, (const int *)r.labels, (const int *)r.slots, ncells, W, rec, r.max_waves);
+    });
+}
+static void waves_free(fibhip_ctx *h)
+{
+    dev_free(h->wv.mask);
+    dev_free(h->wv.labels);
+    dev_free(h->wv.slots);
+    dev_free(h->wv.counts);
+    dev_free(h->wv.records);
+    h->wv.on = false;
 }
 
 static_assert(SPEC_MAX_BINS == FIBHIP_SPECTRUM_MAX_BINS && SPEC_MAX_CHUNK == FIBHIP_SPECTRUM_MAX_CHUNK &&
@@ -1249,6 +1305,105 @@ extern "C" int fibhip_leads_end(fibhip_t h)
 {
     NEED(h);
     return detach(h, h->ld.on, leads_free);
+}
+
+// ---- wave recorder ------------------------------------------------------------------------------------------------------
+extern "C" int fibhip_waves_begin(fibhip_t h, int var, int kind, float level, int var2, int kind2, float level2, int conn,
+                                  const unsigned char *mask, int max_waves, int every, long long capacity)
+{
+    NEED(h);
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "waves_begin: bad var %d", var);
+    if (var2 < -1 || var2 >= h->nvar) return fail(FIBHIP_EINVAL, "waves_begin: bad var2 %d (-1: none)", var2);
+    if (kind != FIBHIP_WAVE_ABOVE && kind != FIBHIP_WAVE_BELOW) return fail(FIBHIP_EINVAL, "waves_begin: bad kind %d", kind);
+    if (!std::isfinite(level)) return fail(FIBHIP_EINVAL, "waves_begin: the level must be finite");
+    if (var2 >= 0) {
+        if (kind2 != FIBHIP_WAVE_ABOVE && kind2 != FIBHIP_WAVE_BELOW) return fail(FIBHIP_EINVAL, "waves_begin: bad kind2 %d", kind2);
+        if (!std::isfinite(level2)) return fail(FIBHIP_EINVAL, "waves_begin: level2 must be finite");
+    }
+    if (conn != 4 && conn != 8) return fail(FIBHIP_EINVAL, "waves_begin: conn is 4 or 8 (got %d)", conn);
+    if (max_waves < 1 || max_waves > FIBHIP_MAX_WAVES)
+        return fail(FIBHIP_EINVAL, "waves_begin: 1 .. %d waves per sample (got %d)", FIBHIP_MAX_WAVES, max_waves);
+    if (every < 1) return fail(FIBHIP_EINVAL, "waves_begin: every must be >= 1 (got %d)", every);
+    if (capacity < 1 || capacity > (long long)(SIZE_MAX / sizeof(WaveRecord) / (size_t)max_waves))
+        return fail(FIBHIP_EINVAL, "waves_begin: bad capacity %lld", capacity);
+    if (int rc = attach_refusals(h, "waves_begin")) return rc;
+    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    waves_free(h);
+    WaveRec &r = h->wv;
+    bool ok = hipMalloc((void **)&r.counts, (size_t)capacity * 3 * sizeof(int)) == hipSuccess &&
+              hipMalloc((void **)&r.records, (size_t)capacity * (size_t)max_waves * sizeof(WaveRecord)) == hipSuccess &&
+              hipMalloc((void **)&r.labels, h->cells * sizeof(int)) == hipSuccess &&
+              hipMalloc((void **)&r.slots, h->cells * sizeof(int)) == hipSuccess;
+    if (ok && mask) ok = hipMalloc((void **)&r.mask, h->cells) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        waves_free(h);
+        return fail(FIBHIP_ENOMEM, "waves_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d waves)", capacity, max_waves);
+    }
+    if (mask) HIPCHK(hipMemcpyAsync(r.mask, mask, h->cells, hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemsetAsync(r.counts, 0, (size_t)capacity * 3 * sizeof(int), h->s0));
+    HIPCHK(hipMemsetAsync(r.labels, 0xFF, h->cells * sizeof(int), h->s0));
+    HIPCHK(hipMemsetAsync(r.slots, 0xFF, h->cells * sizeof(int), h->s0));
+    HIPCHK(wait_stream(h->s0));                        // the caller's mask is free again
+    r.on = true;
+    r.start(every, capacity);
+    r.before_slow = slow_array(var) || (var2 >= 0 && slow_array(var2));
+    r.var = var; r.kind = kind; r.level = level;
+    r.var2 = var2; r.kind2 = kind2; r.level2 = level2;
+    r.conn = conn;
+    r.max_waves = max_waves;
+    return 0;
+}
+
+extern "C" int fibhip_waves_count(fibhip_t h, long long *samples)
+{
+    NEED(h);
+    if (!samples) return fail(FIBHIP_EINVAL, "waves_count: null argument");
+    if (!h->wv.on) return fail(FIBHIP_EINVAL, "waves_count: no recorder attached (fibhip_waves_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    *samples = h->wv.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+
+extern "C" int fibhip_waves_read(fibhip_t h, long long first, long long count, int *counts, fibhip_wave_record *records)
+{
+    NEED(h);
+    if (!h->wv.on) return fail(FIBHIP_EINVAL, "waves_read: no recorder attached (fibhip_waves_begin)");
+    FLUSH(h);
+    if (int rc = range_check("waves_read", "samples", first, count, h->wv.taken())) return rc;
+    if (count > 0 && !counts) return fail(FIBHIP_EINVAL, "waves_read: null destination");
+    const size_t per = (size_t)h->wv.max_waves;
+    return read_confirmed(h, [&] {
+        if (count > 0) {
+            HIPCHK(hipMemcpyAsync(counts, h->wv.counts + 3 * (size_t)first, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost, h->s0));
+            if (records)
+                HIPCHK(hipMemcpyAsync(records, h->wv.records + (size_t)first * per, (size_t)count * per * sizeof(WaveRecord),
+                                      hipMemcpyDeviceToHost, h->s0));
+        }
+        return 0;
+    });
+}
+
+extern "C" int fibhip_waves_labels(fibhip_t h, int *dst)
+{
+    NEED(h);
+    if (!h->wv.on) return fail(FIBHIP_EINVAL, "waves_labels: no recorder attached (fibhip_waves_begin)");
+    if (!dst) return fail(FIBHIP_EINVAL, "waves_labels: null destination");
+    FLUSH(h);
+    if (h->wv.taken() < 1) return fail(FIBHIP_EINVAL, "waves_labels: no sample has been taken yet");
+    return read_confirmed(h, [&] {
+        HIPCHK(hipMemcpyAsync(dst, h->wv.labels, h->cells * sizeof(int), hipMemcpyDeviceToHost, h->s0));
+        return 0;
+    });
+}
+
+extern "C" int fibhip_waves_end(fibhip_t h)
+{
+    NEED(h);
+    return detach(h, h->wv.on, waves_free);
 }
 
 // ---- spectrum recorder --------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame, statistics, spectrum, beat and lead recorders, and the
+// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame, statistics, spectrum, beat, lead and wave recorders, and the
 // plain copy whose shape they take (the bandwidth yardstick).  (included by kernels.hpp; the host side is record.inc)
 
 // ---- activation recorder (fibhip_observe_begin): per-cell event maps, updated after every observed tick ----------------
@@ -1377,4 +1377,326 @@ __global__ void __launch_bounds__(256) lead_combine_kernel(const double *__restr
     if ((threadIdx.x & 63u) == 0) wres[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) row[blockIdx.x] = (wres[0] + wres[1]) + (wres[2] + wres[3]);
+}
+
+// ---- wave recorder (fibhip_waves_begin): connected components of the cells that meet a condition -------------------------
+// A cell is SET when its mask byte is non-zero (no mask: every cell) and X > level (kind 0) or X < level (kind 1) holds on the
+// watched array, and on the second array with its own kind and level where there is one: strict float32 compares, a NaN is never
+// set.  Set cells that touch under conn = 4 or 8 form a WAVE; its SEED is the smallest linear index r * W + c among its cells.
+// Four kernels on one stream per sample, behind a 12-byte memset of the sample's counts {n, stored, cells}; everything is integer
+// arithmetic and the only thing the order of arrival decides is the order of the records:
+//   wave_label_kernel  one workgroup per tile of WV_TX x WV_TY cells, lane l of wave v owns the cells (row v + 4j, column l) of the
+//     tile (lead_kernel's ownership), so a tile row is one ballot.  `cells` takes one atomicAdd per wave that has set cells.  In
+//     LDS every set cell starts as the child of the first cell of its horizontal RUN (from the ballot, no union), then the runs
+//     of consecutive rows are united where they touch — one union per contact, not per cell: a cell whose left, upper-left and
+//     upper neighbours are all set leaves its upper contact to its left neighbour — by the lock-free union below on LDS.  Behind
+//     a barrier every cell of the tile inside the grid writes the global label plane: the global linear index of its local
+//     root (local and global order agree inside a tile, so that is the smallest index of its local component), or -1.
+//   wave_merge_kernel  one thread per cell of a tile's top row and per cell of a tile's left column (no tile border: not
+//     launched): a set cell is united with its set neighbours across the border — above, and under conn = 8 above-left and
+//     above-right, for a top row; left, and under conn = 8 above-left and below-left, for a left column; between them these are
+//     all pairs of neighbours in different tiles, the two diagonals across a tile corner included — on the global plane.
+//   wave_root_kernel   one thread per cell: a set cell replaces its label by its root.  A cell that is its own root takes a slot
+//     (one atomicAdd on `n` per wave of the GPU that has roots), writes it into the slot plane — written by roots, read at
+//     roots' entries only — and, if the slot is below max_waves, counts itself in `stored` and initialises its record.
+//   wave_reduce_kernel one thread per cell: a set cell whose root's slot is below max_waves adds itself to that record, area by
+//     a 32-bit atomicAdd, the row and column sums by 64-bit atomicAdds, the box by atomicMin / atomicMax.  Where the contributing
+//     lanes of a wave of the GPU all name ONE slot (inside a large domain: always) they are reduced across the wave first and one
+//     lane issues the seven atomics.
+// The union (wave_unite): find both roots, hang the larger under the smaller with atomicMin, and where the atomicMin met a label
+// that was no longer a root go on from what it returned.  A label never exceeds its cell's index, so every path descends and
+// every loop is bounded by the plane; no kernel waits for another workgroup, and each ends whatever the state holds.  Linear
+// indices are int32 (H * W < 2^31); offsets into the state are size_t.
+#define WV_TX 64
+#define WV_TY 16
+#define WV_THREADS 256
+#define WV_CPT (WV_TY / (WV_THREADS / 64))      // cells per thread
+struct WaveRecord {             // fibhip_wave_record
+    int seed, area;
+    long long sum_r, sum_c;
+    int r0, r1, c0, c1;
+};
+struct WaveArgs {
+    const float *x, *x2;        // the watched arrays (their first rows), `pitch` floats between rows; x2 null: one condition
+    const unsigned char *mask;  // [H][W], or null
+    int *labels;                // [H][W]
+    int *cnt;                   // this sample's {n, stored, cells}
+    int H, W, pitch, kind, kind2, conn;
+    float level, level2;
+};
+
+template <int SCOPE>
+static FIB_DEV int wave_find(const int *L, int i)
+{
+    for (;;) {
+        const int p = __hip_atomic_load(L + i, __ATOMIC_RELAXED, SCOPE);
+        if (p >= i || p < 0) return i;                  // (a root holds its own index; anything else that does not descend ends the walk too)
+        i = p;
+    }
+}
+template <int SCOPE>
+static FIB_DEV void wave_unite(int *L, int a, int b)
+{
+    for (;;) {
+        a = wave_find<SCOPE>(L, a);
+        b = wave_find<SCOPE>(L, b);
+        if (a == b) return;
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, SCOPE);     // b < a: labels only ever descend
+        if (old == a || old < 0) return;
+        a = old;                                        // `a` had been hung elsewhere meanwhile: a + b has dropped, go on from there
+    }
+}
+static FIB_DEV bool wave_cond(float x, int kind, float level) { return kind ? x < level : x > level; }
+
+__global__ void __launch_bounds__(WV_THREADS) wave_label_kernel(WaveArgs a)
+{
+    constexpr int NW = WV_THREADS / 64, WG = __HIP_MEMORY_SCOPE_WORKGROUP;
+    __shared__ int lab[WV_TX * WV_TY];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tiles_x = (a.W + WV_TX - 1) / WV_TX;
+    const int x0 = (int)(blockIdx.x % (unsigned)tiles_x) * WV_TX, y0 = (int)(blockIdx.x / (unsigned)tiles_x) * WV_TY;
+    const int c = x0 + lane;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    bool set[WV_CPT];
+    int total = 0;
+#pragma unroll
+    for (int j = 0; j < WV_CPT; ++j) {
+        const int ly = wave + NW * j, r = y0 + ly;
+        bool s = false;
+        if (r < a.H && c < a.W && (!a.mask || a.mask[(size_t)r * (size_t)a.W + (size_t)c] != 0)) {
+            const size_t o = (size_t)r * (size_t)a.pitch + (size_t)c;
+            s = wave_cond(a.x[o], a.kind, a.level);
+            if (s && a.x2) s = wave_cond(a.x2[o], a.kind2, a.level2);
+        }
+        const unsigned long long m = __ballot(s);
+        total += __popcll(m);
+        const unsigned long long gap = ~m & below;      // the unset cells to the left: the run starts behind the last of them
+        const int start = gap ? 64 - __builtin_clzll(gap) : 0;
+        set[j] = s;
+        lab[ly * WV_TX + lane] = s ? ly * WV_TX + start : -1;
+    }
+    if (total && lane == 0) atomicAdd(&a.cnt[2], total);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < WV_CPT; ++j) {
+        const int ly = wave + NW * j, i = ly * WV_TX + lane;
+        if (!set[j] || ly == 0) continue;
+        // (whether a cell is set never changes: only the labels of set cells move)
+        const bool up = lab[i - WV_TX] >= 0;
+        const bool left = lane > 0 && lab[i - 1] >= 0, upleft = lane > 0 && lab[i - WV_TX - 1] >= 0;
+        const bool upright = lane < WV_TX - 1 && lab[i - WV_TX + 1] >= 0;
+        if (up && !(left && upleft)) wave_unite<WG>(lab, i, i - WV_TX);
+        if (a.conn == 8 && !up) {
+            if (upleft && !left) wave_unite<WG>(lab, i, i - WV_TX - 1);
+            if (upright) wave_unite<WG>(lab, i, i - WV_TX + 1);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < WV_CPT; ++j) {
+        const int ly = wave + NW * j, r = y0 + ly;
+        if (r >= a.H || c >= a.W) continue;
+        int out = -1;
+        if (set[j]) {
+            const int root = wave_find<WG>(lab, ly * WV_TX + lane);
+            out = (y0 + root / WV_TX) * a.W + x0 + root % WV_TX;
+        }
+        a.labels[(size_t)r * (size_t)a.W + (size_t)c] = out;
+    }
+}
+
+// thread t < nbr * W: the cell (16 (t / W + 1), t % W) of a top row; else, with u = t - nbr * W, the cell (u % H, 64 (u / H + 1)) of
+// a left column; nbr = (H - 1) / WV_TY and nbc = (W - 1) / WV_TX border rows and columns.  One union per CONTACT, as inside a
+// tile: where the cell before it along the border lies in the same tile and it and its straight neighbour are set too, that
+// cell (or one before it) has made the contact, and the label kernel has joined both pairs along the border.  At the first cell
+// of a tile nothing is left to others: the cell before it is joined to it by the OTHER border's thread, which may rely on this one.
+// A diagonal is looked at only where the straight neighbour is not set (else it touches the straight neighbour, and whoever
+// owns that pair joins them)
+__global__ void __launch_bounds__(256) wave_merge_kernel(int *__restrict__ labels, int H, int W, int conn, int nbr, int nbc)
+{
+    constexpr int AG = __HIP_MEMORY_SCOPE_AGENT;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long rows = (long long)nbr * W;
+    if (t >= rows + (long long)nbc * H) return;
+    int r, c, dr, dc;                   // the cell; the straight neighbour across the border is (r - dr, c - dc)
+    if (t < rows) {
+        r = ((int)(t / W) + 1) * WV_TY; c = (int)(t % W); dr = 1; dc = 0;
+    } else {
+        const long long u = t - rows;
+        c = ((int)(u / H) + 1) * WV_TX; r = (int)(u % H); dr = 0; dc = 1;
+    }
+    const int i = r * W + c;
+    // (whether a cell is set does not change here: plain loads will do)
+    auto is_set = [&](int rr, int cc) { return rr >= 0 && rr < H && cc >= 0 && cc < W && labels[rr * W + cc] >= 0; };
+    if (!is_set(r, c)) return;
+    const int pr = r - dc, pc = c - dr;                                 // the cell before this one along the border
+    const bool same_tile = dr ? c % WV_TX != 0 : r % WV_TY != 0;        // ... lies in this cell's tile
+    const bool before = same_tile && is_set(pr, pc);
+    if (is_set(r - dr, c - dc)) {
+        if (!(before && is_set(pr - dr, pc - dc))) wave_unite<AG>(labels, i, (r - dr) * W + (c - dc));
+    } else if (conn == 8) {
+        if (!before && is_set(pr - dr, pc - dc)) wave_unite<AG>(labels, i, (pr - dr) * W + (pc - dc));
+        const int fr = r - dr + dc, fc = c - dc + dr;
+        if (is_set(fr, fc)) wave_unite<AG>(labels, i, fr * W + fc);
+    }
+}
+
+__global__ void __launch_bounds__(256) wave_root_kernel(int *__restrict__ labels, int *__restrict__ slots, int ncells,
+                                                        int *__restrict__ cnt, WaveRecord *__restrict__ rec, int max_waves)
+{
+    constexpr int AG = __HIP_MEMORY_SCOPE_AGENT;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int i = (int)t;
+    bool root = false;
+    if (t < ncells) {
+        const int l = labels[i];
+        if (l >= 0) {
+            const int rt = wave_find<AG>(labels, l);
+            root = rt == i;
+            if (rt != l) __hip_atomic_store(labels + i, rt, __ATOMIC_RELAXED, AG);      // (a path through this cell stays a path)
+        }
+    }
+    // every lane of the wave comes here
+    const unsigned long long roots = __ballot(root);
+    if (!roots) return;
+    const int lane = (int)(threadIdx.x & 63u);
+    int base = 0;
+    if (lane == 0) base = atomicAdd(&cnt[0], __popcll(roots));
+    base = __shfl(base, 0, 64);
+    const int slot = base + __popcll(roots & ((1ull << lane) - 1ull));
+    const bool keep = root && slot < max_waves;
+    const unsigned long long kept = __ballot(keep);
+    if (kept && lane == 0) atomicAdd(&cnt[1], __popcll(kept));
+    if (root) slots[i] = slot;
+    if (keep) {
+        WaveRecord w;
+        w.seed = i; w.area = 0;
+        w.sum_r = 0; w.sum_c = 0;
+        w.r0 = 0x7fffffff; w.r1 = -1; w.c0 = 0x7fffffff; w.c1 = -1;
+        rec[slot] = w;
+    }
+}
+
+template <class T, class F>
+static FIB_DEV T wave_all(T v, F f)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = f(v, __shfl_xor(v, off, 64));
+    return v;
+}
+// what a set of cells adds to its wave's record
+struct WaveSum {
+    int area;
+    long long sr, sc;
+    int r0, r1, c0, c1;
+    FIB_DEV void clear()
+    {
+        area = 0; sr = 0; sc = 0;
+        r0 = 0x7fffffff; r1 = -1; c0 = 0x7fffffff; c1 = -1;
+    }
+    FIB_DEV void cell(int r, int c)
+    {
+        area += 1; sr += r; sc += c;
+        r0 = min(r0, r); r1 = max(r1, r); c0 = min(c0, c); c1 = max(c1, c);
+    }
+    FIB_DEV void fold(const WaveSum &o)
+    {
+        area += o.area; sr += o.sr; sc += o.sc;
+        r0 = min(r0, o.r0); r1 = max(r1, o.r1); c0 = min(c0, o.c0); c1 = max(c1, o.c1);
+    }
+    // over the 64 lanes; every lane of the wave must come here
+    FIB_DEV void across_the_wave()
+    {
+        area = wave_all<int>(area, [](int x, int y) { return x + y; });
+        sr = wave_all<long long>(sr, [](long long x, long long y) { return x + y; });
+        sc = wave_all<long long>(sc, [](long long x, long long y) { return x + y; });
+        r0 = wave_all<int>(r0, [](int x, int y) { return min(x, y); });
+        c0 = wave_all<int>(c0, [](int x, int y) { return min(x, y); });
+        r1 = wave_all<int>(r1, [](int x, int y) { return max(x, y); });
+        c1 = wave_all<int>(c1, [](int x, int y) { return max(x, y); });
+    }
+    FIB_DEV void add_to(WaveRecord *w) const
+    {
+        atomicAdd(&w->area, area);
+        atomicAdd(reinterpret_cast<unsigned long long *>(&w->sum_r), (unsigned long long)sr);
+        atomicAdd(reinterpret_cast<unsigned long long *>(&w->sum_c), (unsigned long long)sc);
+        atomicMin(&w->r0, r0);
+        atomicMax(&w->r1, r1);
+        atomicMin(&w->c0, c0);
+        atomicMax(&w->c1, c1);
+    }
+};
+
+// A workgroup takes WV_RED_CPT * 256 consecutive cells, thread t the cells base + 256 j + t: all labels are loaded first, then all
+// slots (two round trips, not 2 * WV_RED_CPT).  While the contributing lanes of a wave all name one slot, and the same slot as
+// before, every lane adds its cells up in registers — nothing crosses lanes; when that ends (another slot, or several in one
+// step) what has run up is folded across the wave and one lane issues its seven atomics, and a step with several slots goes
+// lane by lane.  What is left at the end is folded across the wave, the four waves' sums meet in LDS, and thread 0 folds
+// neighbours of equal slot before it issues the atomics: inside a large domain a workgroup of 4096 cells issues seven.  (One
+// cell per thread and the fold per wave took 197 us at 512^2 on a spiral of 150 000 cells: 17 000 atomics on one cache line.)
+#define WV_RED_CPT 16
+__global__ void __launch_bounds__(256) wave_reduce_kernel(const int *__restrict__ labels, const int *__restrict__ slots, int ncells, int W,
+                                                          WaveRecord *__restrict__ rec, int max_waves)
+{
+    __shared__ int wslot[4];
+    __shared__ WaveSum wsum[4];
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const long long base = (long long)blockIdx.x * (256 * WV_RED_CPT) + threadIdx.x;
+    int slot[WV_RED_CPT];
+#pragma unroll
+    for (int j = 0; j < WV_RED_CPT; ++j) {
+        const long long t = base + 256 * j;
+        slot[j] = t < ncells ? labels[t] : -1;                  // (the root, for now)
+    }
+#pragma unroll
+    for (int j = 0; j < WV_RED_CPT; ++j) {
+        const int s = slot[j] >= 0 ? slots[slot[j]] : -1;
+        slot[j] = s >= 0 && s < max_waves ? s : -1;
+    }
+    int run = -1;                                               // (wave-uniform) the slot the lanes' sums belong to, -1: none
+    WaveSum mine;
+    mine.clear();
+#pragma unroll
+    for (int j = 0; j < WV_RED_CPT; ++j) {
+        const unsigned long long act = __ballot(slot[j] >= 0);
+        if (!act) continue;                                     // (wave-uniform)
+        const int i = (int)(base + 256 * j), r = i / W, c = i - r * W;
+        const int first = __shfl(slot[j], __builtin_ctzll(act), 64);
+        const bool one = __ballot(slot[j] >= 0 && slot[j] != first) == 0;
+        if (!(one && (run < 0 || run == first))) {
+            if (run >= 0) {
+                mine.across_the_wave();
+                if (lane == 0) mine.add_to(rec + run);
+                mine.clear();
+            }
+            run = -1;
+        }
+        if (one) {
+            run = first;
+            if (slot[j] >= 0) mine.cell(r, c);
+        } else if (slot[j] >= 0) {
+            WaveSum w;
+            w.clear();
+            w.cell(r, c);
+            w.add_to(rec + slot[j]);
+        }
+    }
+    mine.across_the_wave();
+    if (lane == 0) {
+        wslot[wave] = run;
+        wsum[wave] = mine;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 0; w < 4; ++w) {
+            if (wslot[w] < 0) continue;
+            if (w + 1 < 4 && wslot[w + 1] == wslot[w]) wsum[w + 1].fold(wsum[w]);
+            else wsum[w].add_to(rec + wslot[w]);
+        }
+    }
 }

@@ -17,8 +17,8 @@ struct Recorder {
 };
 constexpr size_t NO_SAMPLER = ~(size_t)0;
 
-static recorder_advance_fn electrode_advance, tips_advance, frames_advance, stats_advance, leads_advance, spectrum_advance, beats_advance, stim_advance, trig_advance;
-static recorder_free_fn electrode_free, tips_free, frames_free, stats_free, leads_free, spectrum_free, beats_free, stim_free, trig_free;
+static recorder_advance_fn electrode_advance, tips_advance, frames_advance, stats_advance, leads_advance, waves_advance, spectrum_advance, beats_advance, stim_advance, trig_advance;
+static recorder_free_fn electrode_free, tips_free, frames_free, stats_free, leads_free, waves_free, spectrum_free, beats_free, stim_free, trig_free;
 static long long stim_next(const StimRec &r);                   // sched.inc
 
 // (`on` is the Sampler's first member; the handle holds vectors, which is all that makes offsetof conditionally supported here)
@@ -40,6 +40,12 @@ static constexpr Recorder RECORDERS[] = {
     // whole from those partials.  Nothing is accumulated across samples and the slot follows from the counter, so a sample taken
     // from a void slab is overwritten, partials and row, when the replay takes it again
     {"lead", SAMPLER_AT(ld), leads_advance, leads_free},
+    // ... and the wave recorder, a sixth: the label plane and the slot plane are scratch that every sample rewrites before it
+    // reads them (wave_label_kernel writes every label from the state, wave_root_kernel every slot that is read); the sample's
+    // counts are zeroed in front of its kernels and its records initialised and filled whole; the slot follows from the counter.
+    // A sample taken from a void slab is overwritten, counts, records and planes, when the replay takes it again.  No give-up
+    // word is needed: nothing is accumulated across samples, and its kernels end on any state (no loop waits for anything)
+    {"wave", SAMPLER_AT(wv), waves_advance, waves_free},
     // these two ACCUMULATE (the fold and the short ring; the count, the open beat's peak, the ring): their kernels read the
     // give-up word first and write nothing once a launch in front of them gave up, and how far they have come follows from the
     // counter alone — the replay takes the lost samples and issues the lost folds again, in order.  Neither ever fills up

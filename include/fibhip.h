@@ -560,6 +560,51 @@ int fibhip_leads_count(fibhip_t h, long long *samples);
 int fibhip_leads_read(fibhip_t h, long long first, long long count, double *dst /* [count][n] */);
 int fibhip_leads_end(fibhip_t h);
 
+/* Wave recorder: the excited domains of the sheet, labelled and measured on the device.  Every `every` ticks the cells that meet
+ * a condition are grouped into connected components, the WAVES; their number, and per wave its size, centroid sums and bounding
+ * box, are appended to lists that stay on the device until they are read.  Restated in NumPy in tests/wave_ref.py.
+ *     set     the cell (r, c) of the height x width grid is SET when mask[r][c] != 0 (NULL: every cell), the condition holds on
+ *             the array `var` — kind FIBHIP_WAVE_ABOVE: X > level, FIBHIP_WAVE_BELOW: X < level, strict float32 compares, so a
+ *             NaN is never set — and, if var2 >= 0, the condition (kind2, level2) holds on the array `var2` as well (var2 = -1:
+ *             none).
+ *     wave    two set cells are neighbours under conn = 4 (N, S, W, E) or conn = 8 (the diagonals too); a wave is a connected
+ *             component of set cells.  Its SEED is the smallest linear index r * width + c among its cells: the wave's
+ *             identity, a function of the plane alone.
+ *     record  fibhip_wave_record: seed, area (cells), sum_r and sum_c (the 64-bit sums of the rows and the columns of its cells;
+ *             the centroid is sum / area), and the inclusive bounding box r0 <= r <= r1, c0 <= c <= c1.
+ *     counts  per sample int32[3] = n, stored, cells: the number of waves (exact however many there are), the number of
+ *             records written = min(n, max_waves), and the number of set cells (exact).
+ *     records up to max_waves per sample, in the order of arrival (sort by seed).  Where n > max_waves, WHICH waves are stored
+ *             is unspecified (the tip recorder's contract); every stored record is whole and exact and no seed appears twice.
+ *     labels  the int32 plane [height][width] of the LATEST sample: the seed of the cell's wave, -1 for a cell that is not set.
+ * Everything is integer arithmetic on the outcome of the compares: the same on every launch plan, stride and policy.  The sample
+ * ticks, the capacity rule ("trace full"), the launches and the 'slow' rule are those of the tip recorder; the recorder may be
+ * attached beside every other recorder, each with its own stride.
+ * Refused with FIBHIP_EINVAL, the message naming the offender: var out of range, var2 neither -1 nor in range, a kind that is
+ * neither ABOVE nor BELOW, a level that is not finite, conn other than 4 or 8, max_waves outside 1 .. FIBHIP_MAX_WAVES,
+ * every < 1, capacity < 1 or too large, inside an open tick, a row block (a handle with ghost rows).
+ *   fibhip_waves_begin   flushes, synchronises and confirms pending work, copies the mask (or none: NULL) and attaches; again:
+ *                        re-attaches with empty lists
+ *   fibhip_waves_count   samples taken so far (ticks accepted but not launched yet included)
+ *   fibhip_waves_read    samples [first, first + count): counts as [count][3] and (unless NULL) records as [count][max_waves],
+ *                        of which the first `stored` of each sample are valid; flushes and blocks like get_state; does not detach
+ *   fibhip_waves_labels  the label plane of the latest sample taken, confirmed; refused before the first sample
+ *   fibhip_waves_end     detaches and frees (no recorder attached: nothing); fibhip_destroy does the same                      */
+#define FIBHIP_MAX_WAVES 65536
+enum fibhip_wave_kind { FIBHIP_WAVE_ABOVE = 0, FIBHIP_WAVE_BELOW = 1 };
+typedef struct fibhip_wave_record {
+    int seed, area;
+    long long sum_r, sum_c;
+    int r0, r1, c0, c1;
+} fibhip_wave_record;               /* 40 bytes */
+int fibhip_waves_begin(fibhip_t h, int var, int kind, float level, int var2, int kind2, float level2, int conn,
+                       const unsigned char *mask /* [H*W] or NULL */, int max_waves, int every, long long capacity);
+int fibhip_waves_count(fibhip_t h, long long *samples);
+int fibhip_waves_read(fibhip_t h, long long first, long long count, int *counts /* [count][3] */,
+                      fibhip_wave_record *records /* [count][max_waves] or NULL */);
+int fibhip_waves_labels(fibhip_t h, int *dst /* [H*W] */);
+int fibhip_waves_end(fibhip_t h);
+
 /* Spectrum recorder: per-cell power spectra (a Welch periodogram) folded on the device while the run goes on, and the
  * dominant-frequency maps made from them — the sixth recorder and the fifth sampler.  All device arithmetic is float32, every
  * operation rounded on its own (no contraction), in the order written; no transcendental is evaluated on the device.
