@@ -19,6 +19,7 @@ and feeds them back as the variables' current values for the next `define()`
 reference's `add_pace_op` (`ionic.py:125-163`) in the same way.
 
 Usage:  python tests/golden/make_golden.py            (about 2-3 minutes)
+        python tests/golden/make_golden.py timestep   (the ts_*.npz fixtures at other time steps only, seconds)
 """
 import os
 import sys
@@ -93,25 +94,36 @@ def unit_ops():
 # --------------------------------------------------------------------------
 # 2. single-step, branch-covering
 # --------------------------------------------------------------------------
-def fenton_step():
-    rng = np.random.default_rng(1234)
-    H, W = 37, 53
+def fenton_random_state(rng, H, W):
     U = rng.uniform(-0.05, 1.05, (H, W)).astype(f32)
     # exact thresholds: sign()==0 -> Heaviside 0.5 (fenton.py:73-79); strict > (fenton.py:87-88)
     U[3, 3:9] = [0.23, 0.3, 0.146, 0.84, 0.8, 0.0]
     U[0, 7] = 0.23
     U[5, 0] = 0.3
     V, Wg, S = (rng.uniform(0.0, 1.0, (H, W)).astype(f32) for _ in range(3))
+    return U, V, Wg, S
+
+
+def fenton_step_at(dt, diff, hole, state):
+    """one solve() and one differentiate() of `state` = (U, V, W, S) at time step `dt`"""
+    U, V, Wg, S = state
+    H, W = U.shape
+    m = fenton.Fenton4v(cfg(H, W, diff, dt=dt))
+    if hole:
+        m.add_hole_to_phase_field(*hole)
+    U1, V1, W1, S1 = m.solve((T(U), T(V), T(Wg), T(S)))
+    dU, dV, dW, dS = m.differentiate(T(U), T(V), T(Wg), T(S))
+    return dict(diff=diff, dt=dt, phase=(m.phase if hole else np.zeros(0, f32)),
+                U=U, V=V, W=Wg, S=S, U1=U1.a, V1=V1.a, W1=W1.a, S1=S1.a,
+                dU=dU.a, dV=dV.a, dW=dW.a, dS=dS.a)
+
+
+def fenton_step():
+    rng = np.random.default_rng(1234)
+    state = fenton_random_state(rng, 37, 53)
     for diff, hole in ((1.5, True), (0.7, False)):
-        m = fenton.Fenton4v(cfg(H, W, diff))
-        if hole:
-            m.add_hole_to_phase_field(25, 17, 7)
-        U1, V1, W1, S1 = m.solve((T(U), T(V), T(Wg), T(S)))
-        dU, dV, dW, dS = m.differentiate(T(U), T(V), T(Wg), T(S))
         save('fenton_step_%s' % ('phase' if hole else 'nophase'),
-             diff=diff, dt=0.1, phase=(m.phase if hole else np.zeros(0, f32)),
-             U=U, V=V, W=Wg, S=S, U1=U1.a, V1=V1.a, W1=W1.a, S1=S1.a,
-             dU=dU.a, dV=dV.a, dW=dW.a, dS=dS.a)
+             **fenton_step_at(0.1, diff, (25, 17, 7) if hole else None, state))
 
 
 BR_NAMES = ['V', 'C', 'M', 'H', 'J', 'D', 'F', 'XI']
@@ -126,20 +138,25 @@ def br_random_state(rng, H, W):
     return st
 
 
-def br_step():
-    rng = np.random.default_rng(4321)
-    H, W = 37, 53
-    st = br_random_state(rng, H, W)
+def br_step_at(dt, diff, hole, st):
+    """solve(state, n) for n in (1, 5, 0), direct and Chebyshev gates, at time step `dt`"""
+    H, W = st['V'].shape
     out = {k: v for k, v in st.items()}
     for cheby in (False, True):
-        m = br.BeelerReuter(cfg(H, W, 0.809, cheby=cheby))
-        m.add_hole_to_phase_field(25, 17, 7)
+        m = br.BeelerReuter(cfg(H, W, diff, cheby=cheby, dt=dt))
+        m.add_hole_to_phase_field(*hole)
         out['phase'] = m.phase
         for n in (1, 5, 0):
             res = m.solve(tuple(T(st[k]) for k in BR_NAMES), n)
             for k, r in zip(BR_NAMES, res):
                 out['%s1_%s_n%d' % (k, 'cheby' if cheby else 'direct', n)] = r.a
-    save('br_step', diff=0.809, dt=0.1, **out)
+    out.update(diff=diff, dt=dt)
+    return out
+
+
+def br_step():
+    rng = np.random.default_rng(4321)
+    save('br_step', **br_step_at(0.1, 0.809, (25, 17, 7), br_random_state(rng, 37, 53)))
 
 
 class _Term:
@@ -210,27 +227,36 @@ def court_random_state(rng, H, W):
     return st
 
 
-def court_step():
-    rng = np.random.default_rng(999)
-    H, W = 37, 53
-    st = court_random_state(rng, H, W)
+def court_step_at(dt, diff, hole, st):
+    """one solve() of the 21 variables, chronic and not, at time step `dt`"""
+    H, W = st['V'].shape
     out = dict(st)
     with np.errstate(all='ignore'):
         for chronic in (True, False):
-            m = court.Courtemanche(cfg(H, W, 0.809))
+            m = court.Courtemanche(cfg(H, W, diff, dt=dt))
             m.chronic = chronic
-            m.add_hole_to_phase_field(25, 17, 7)
+            m.add_hole_to_phase_field(*hole)
             out['phase'] = m.phase
             res = m.solve({k: T(v) for k, v in st.items()})
             for k in COURT_NAMES:
                 out['%s_1_%s' % (k, 'chronic' if chronic else 'acute')] = res[k].a
+    out.update(diff=diff, dt=dt)
+    return out
+
+
+def court_step():
+    rng = np.random.default_rng(999)
+    H, W = 37, 53
+    st = court_random_state(rng, H, W)
+    out = court_step_at(0.1, 0.809, (25, 17, 7), st)
+    with np.errstate(all='ignore'):
         # calc_inter through the numpy branch at the cross-check voltage of
         # generate_table.cpp:15 (python floats -> float64 arithmetic there)
         m = court.Courtemanche(cfg(H, W, 0.809))
         inter = m.calc_inter(T(st['V']), tf)
         for k, v in inter.items():
             out['inter_' + k] = v.a
-    save('court_step', diff=0.809, dt=0.1, **out)
+    save('court_step', **out)
 
 
 # --------------------------------------------------------------------------
@@ -245,12 +271,12 @@ def current(names):
     return {n: np.array(tf.variable_override[n]) for n in names}
 
 
-def fenton_traj(name, H, W, diff, hole, ticks, snaps, s2=None, cube_every=None):
+def fenton_traj_at(dt, H, W, diff, hole, ticks, snaps, s2=None, cube_every=None):
     tf.variable_override.clear()
-    m = fenton.Fenton4v(cfg(H, W, diff))
+    m = fenton.Fenton4v(cfg(H, W, diff, dt=dt))
     if hole:
         m.add_hole_to_phase_field(*hole)
-    out = {'phase': m.phase if hole else np.zeros(0, f32), 'diff': diff, 'dt': 0.1,
+    out = {'phase': m.phase if hole else np.zeros(0, f32), 'diff': diff, 'dt': dt,
            'hole': np.array(hole if hole else [], f32)}
     cube = []
     for i in range(ticks):
@@ -274,7 +300,11 @@ def fenton_traj(name, H, W, diff, hole, ticks, snaps, s2=None, cube_every=None):
     if cube:
         out['cube'] = np.array(cube, f32)
         out['s2'] = np.array([s2[0], s2[2]], f32)
-    save(name, **out)
+    return out
+
+
+def fenton_traj(name, H, W, diff, hole, ticks, snaps, s2=None, cube_every=None):
+    save(name, **fenton_traj_at(0.1, H, W, diff, hole, ticks, snaps, s2, cube_every))
 
 
 def fenton_simple_traj(name, H, W, diff, steps, snaps, s2_step):
@@ -303,11 +333,11 @@ def fenton_simple_traj(name, H, W, diff, steps, snaps, s2_step):
     save(name, **out)
 
 
-def br_traj(name, H, W, diff, hole, ticks, snaps, cheby, skip, s2=None):
+def br_traj_at(dt, H, W, diff, hole, ticks, snaps, cheby, skip, s2=None):
     tf.variable_override.clear()
-    m = br.BeelerReuter(cfg(H, W, diff, cheby=cheby, skip=skip))
+    m = br.BeelerReuter(cfg(H, W, diff, cheby=cheby, skip=skip, dt=dt))
     m.add_hole_to_phase_field(*hole)
-    out = {'phase': m.phase, 'diff': diff, 'dt': 0.1, 'hole': np.array(hole, f32),
+    out = {'phase': m.phase, 'diff': diff, 'dt': dt, 'hole': np.array(hole, f32),
            'cheby': cheby, 'skip': skip}
     for i in range(ticks):
         m.define()
@@ -324,17 +354,21 @@ def br_traj(name, H, W, diff, hole, ticks, snaps, cheby, skip, s2=None):
                 out['%s_t%d' % (k, i + 1)] = v
     out['snap_ticks'] = np.array(sorted(snaps))
     out['dt_per_step'] = m.dt_per_step
-    save(name, **out)
+    return out
 
 
-def court_traj(name, H, W, diff, holes, ticks, snaps, s2=None):
+def br_traj(name, H, W, diff, hole, ticks, snaps, cheby, skip, s2=None):
+    save(name, **br_traj_at(0.1, H, W, diff, hole, ticks, snaps, cheby, skip, s2))
+
+
+def court_traj_at(dt, H, W, diff, holes, ticks, snaps, s2=None):
     """court.py:615-621 schedule: fast group every tick (ionic.py:203), then the
     caller fires 'slow' when i % 10 == 0 — a second evaluation of solve on the
     post-fast state."""
-    m = court.Courtemanche(cfg(H, W, diff))
+    m = court.Courtemanche(cfg(H, W, diff, dt=dt))
     for h in holes:
         m.add_hole_to_phase_field(*h)
-    out = {'phase': m.phase, 'diff': diff, 'dt': 0.1}
+    out = {'phase': m.phase, 'diff': diff, 'dt': dt}
     state = None
     trend = []
     with np.errstate(all='ignore'):
@@ -368,17 +402,21 @@ def court_traj(name, H, W, diff, holes, ticks, snaps, s2=None):
     out['snap_ticks'] = np.array(sorted(snaps))
     out['trend'] = np.array(trend, f32)
     out['names'] = np.array(names)
-    save(name, **out)
+    return out
 
 
-def court_ultra_traj(name, H, W, diff, holes, ticks, snaps, s2=None, ultra_slow=False):
+def court_traj(name, H, W, diff, holes, ticks, snaps, s2=None):
+    save(name, **court_traj_at(0.1, H, W, diff, holes, ticks, snaps, s2))
+
+
+def court_ultra_traj_at(dt, H, W, diff, holes, ticks, snaps, s2=None, ultra_slow=False):
     """court_ultra.py: every tick assigns all variables with dt (court_ultra.py:107-111,127-128);
     config['ultra_slow'] = False as in its own __main__ (court_ultra.py:543), or True for the
     22-variable model with the `_us_` gate (court_ultra.py:81-82,198-199,221-222,445-450)"""
-    m = court_ultra.Courtemanche(cfg(H, W, diff, ultra_slow=ultra_slow))
+    m = court_ultra.Courtemanche(cfg(H, W, diff, ultra_slow=ultra_slow, dt=dt))
     for h in holes:
         m.add_hole_to_phase_field(*h)
-    out = {'phase': m.phase, 'diff': diff, 'dt': 0.1}
+    out = {'phase': m.phase, 'diff': diff, 'dt': dt}
     state = None
     with np.errstate(all='ignore'):
         for i in range(ticks):
@@ -410,10 +448,119 @@ def court_ultra_traj(name, H, W, diff, holes, ticks, snaps, s2=None, ultra_slow=
         out['us_sweep_V'] = vs
         out['us_sweep_us_infinity'] = np.array(inter['us_infinity'].a)
         out['us_sweep_tau_us'] = np.array(inter['tau_us'].a)
-    save(name, **out)
+    return out
+
+
+def court_ultra_traj(name, H, W, diff, holes, ticks, snaps, s2=None, ultra_slow=False):
+    save(name, **court_ultra_traj_at(0.1, H, W, diff, holes, ticks, snaps, s2, ultra_slow))
+
+
+# --------------------------------------------------------------------------
+# 4. time steps and diffusion coefficients other than 0.1 ms (ts_*.npz)
+# --------------------------------------------------------------------------
+# two steps below 0.1, one above, one without diffusion; 0.02, 0.03, 0.05 and 0.2 have no binary representation, so
+# float(dt) and every double product of dt rounds
+TS_PAIRS = {'fenton': [(0.02, 1.5), (0.05, 3.0), (0.2, 0.7), (0.03, 0.0)],
+            'br': [(0.02, 0.809), (0.05, 1.6), (0.2, 0.4), (0.03, 0.0)],
+            'court': [(0.02, 0.809), (0.05, 1.6), (0.2, 0.4), (0.03, 0.0)]}
+TS_STEP_SHAPE, TS_STEP_HOLE = (24, 40), (20, 12, 4)
+TS_TRAJ_SHAPE, TS_TRAJ_HOLE = (48, 56), (28, 24, 5)
+
+
+def _tagged(out, keys, p):
+    return {'%s_p%d' % (k, p): out[k] for k in keys}
+
+
+def timestep_steps():
+    """one file per model: the seeded input state once, the outputs of solve() per (dt, diff) pair with the suffix
+    `_p<index>`; `dt` and `diff` are the arrays of the pairs.  Outputs that the reference returns bit for bit equal to an
+    array already in the file are not stored twice: Beeler-Reuter's V, C, M, H do not depend on `n` and solve(state, 0)
+    returns the slow gates it was given (checked here; the loader in tests/timestep_cases.py puts them back), and the
+    variables of Courtemanche that `chronic` does not reach are stored for chronic only."""
+    H, W = TS_STEP_SHAPE
+    # Fenton
+    U, V, Wg, S = fenton_random_state(np.random.default_rng(2024), H, W)
+    out = dict(U=U, V=V, W=Wg, S=S)
+    for p, (dt, diff) in enumerate(TS_PAIRS['fenton']):
+        r = fenton_step_at(dt, diff, TS_STEP_HOLE, (U, V, Wg, S))
+        out['phase'] = r['phase']
+        out.update(_tagged(r, ['U1', 'V1', 'W1', 'S1'], p))
+    save('ts_fenton_step', dt=np.array([p[0] for p in TS_PAIRS['fenton']]),
+         diff=np.array([p[1] for p in TS_PAIRS['fenton']]), **out)
+    # Beeler-Reuter
+    st = br_random_state(np.random.default_rng(2025), H, W)
+    # The 0/0 voltages of alpha_m (-47 mV) and alpha_x1 (-23 mV) stay out, with a clearance of 0.5 mV: in
+    # (V + 47) / (1 - exp(-0.1 (V + 47))) one ulp of exp (6e-8) over the denominator 0.1 * d is a relative rate error of
+    # 6e-7 / d at a distance of d mV.  The seeded state had one cell 0.028 mV from -47: there NumPy and libm differ by 2e-5
+    # in alpha_m and by 5.6e-6 .. 1.1e-5 in the new m, every other cell by <= 6e-7.  At d = 0.5 the term is 1.2e-6 of the rate.
+    for s in (-47.0, -23.0):
+        close_by = np.abs(st['V'] - f32(s)) < 0.5
+        st['V'][close_by] = np.where(st['V'][close_by] < s, f32(s - 0.5), f32(s + 0.5))
+    assert not (np.abs(st['V'] + 47.0) < 0.5).any() and not (np.abs(st['V'] + 23.0) < 0.5).any()
+    out = dict(st)
+    for p, (dt, diff) in enumerate(TS_PAIRS['br']):
+        r = br_step_at(dt, diff, TS_STEP_HOLE, st)
+        out['phase'] = r['phase']
+        for tag in ('direct', 'cheby'):
+            for k in BR_NAMES:
+                n1 = r['%s1_%s_n1' % (k, tag)]
+                if k in ('V', 'C', 'M', 'H'):
+                    assert all(np.array_equal(r['%s1_%s_n%d' % (k, tag, n)], n1) for n in (5, 0))
+                    out['%s1_%s_p%d' % (k, tag, p)] = n1
+                else:
+                    assert np.array_equal(r['%s1_%s_n0' % (k, tag)], st[k])
+                    out['%s1_%s_n1_p%d' % (k, tag, p)] = n1
+                    out['%s1_%s_n5_p%d' % (k, tag, p)] = r['%s1_%s_n5' % (k, tag)]
+    save('ts_br_step', dt=np.array([p[0] for p in TS_PAIRS['br']]), diff=np.array([p[1] for p in TS_PAIRS['br']]), **out)
+    # Courtemanche
+    st = court_random_state(np.random.default_rng(2026), H, W)
+    out = dict(st)
+    for p, (dt, diff) in enumerate(TS_PAIRS['court']):
+        r = court_step_at(dt, diff, TS_STEP_HOLE, st)
+        out['phase'] = r['phase']
+        for k in COURT_NAMES:
+            out['%s_1_chronic_p%d' % (k, p)] = r[k + '_1_chronic']
+            if not np.array_equal(r[k + '_1_acute'], r[k + '_1_chronic'], equal_nan=True):
+                out['%s_1_acute_p%d' % (k, p)] = r[k + '_1_acute']
+    save('ts_court_step', dt=np.array([p[0] for p in TS_PAIRS['court']]),
+         diff=np.array([p[1] for p in TS_PAIRS['court']]), **out)
+
+
+def timestep_trajectories():
+    """20 ticks through define() per (dt, diff) pair, snapshots at two ticks: one file per model and pair"""
+    H, W = TS_TRAJ_SHAPE
+    for p, (dt, diff) in enumerate(TS_PAIRS['fenton']):
+        save('ts_fenton_traj_p%d' % p, **fenton_traj_at(dt, H, W, diff, TS_TRAJ_HOLE, 20, {3, 20}))
+    for p, (dt, diff) in enumerate(TS_PAIRS['br']):
+        out = {}
+        for cheby in (False, True):
+            for skip in (False, True):
+                r = br_traj_at(dt, H, W, diff, TS_TRAJ_HOLE, 20, {3, 20}, cheby, skip)
+                tag = ('cheby' if cheby else 'direct') + ('_skip' if skip else '')
+                for k in ('phase', 'diff', 'dt', 'hole', 'snap_ticks', 'dt_per_step'):
+                    out[k] = r[k]
+                for k, v in r.items():
+                    if k.startswith('init_'):
+                        assert k not in out or np.array_equal(out[k], v)
+                        out[k] = v
+                    elif '_t' in k and k.rsplit('_t', 1)[1].isdigit():
+                        out['%s_%s' % (tag, k)] = v
+        save('ts_br_traj_p%d' % p, **out)
+    for p, (dt, diff) in enumerate(TS_PAIRS['court']):
+        # 21 ticks: 'slow' fires at ticks 0, 10 and 20; S2 after tick 12
+        save('ts_court_traj_p%d' % p, **court_traj_at(dt, H, W, diff, [TS_TRAJ_HOLE], 21, {11, 21}, s2=(12, 'luq', 10.0)))
+        save('ts_court_ultra_traj_p%d' % p, **court_ultra_traj_at(dt, H, W, diff, [TS_TRAJ_HOLE], 12, {5, 12}))
+
+
+def timestep():
+    timestep_steps()
+    timestep_trajectories()
 
 
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'timestep':
+        timestep()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == 'court_ultra':
         court_ultra_traj('court_ultra_traj', 48, 56, 1.5, [(28, 24, 5), (28, 24, 22, True)], 120, {1, 10, 60, 120},
                          s2=(50, 'luq', 10.0))
@@ -450,6 +597,7 @@ def main():
     court_ultra_traj('court_ultra_us_traj', 40, 48, 1.5, [(24, 20, 5)], 120, {1, 10, 60, 120},
                      s2=(50, 'luq', 10.0), ultra_slow=True)
     fenton_simple_traj('fenton_simple_traj', 40, 56, 1.5, 300, {1, 2, 10, 100, 200, 300}, 150)
+    timestep()
 
 
 if __name__ == '__main__':

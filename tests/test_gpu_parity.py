@@ -9,6 +9,8 @@ Two arithmetic policies are shipped and BOTH are tested here (config['fast_math'
 Tolerances (float32):
   * pure arithmetic (boundary, Laplacian incl. phase-field term): BIT-EXACT under both policies.
   * one sub-step through tanh/exp/expm1/log: |d| <= 4e-6 * range (exact), 3e-5 * range (fast).
+    At a time step other than 0.1 ms (tests/test_gpu_timestep.py) these are multiplied by max(1, dt / 0.1): the difference
+    between two float32 evaluations of a step is a rate error times dt; a step below 0.1 ms gets no extra room.
   * trajectories, both policies: |d| <= 2e-5 * range at <= 200 sub-steps, 1e-3 * range at 1000
     sub-steps (round-off grows along the upstroke; beyond wave break the dynamics are chaotic).
 `range` is max_v - min_v of the model (1 for Fenton, 120 mV for BR, 150 mV for Courtemanche);

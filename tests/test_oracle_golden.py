@@ -59,7 +59,7 @@ def test_br_step(orc, golden, mode, n):
 SINGULAR = [-10.0001, -10.0, 7.9, -47.13, -14.1, 3.3328, 19.9]
 
 
-def court_envelope_samples(orc, slab, phase, chronic):
+def court_envelope_samples(orc, slab, phase, chronic, dt=0.1, diff=0.809):
     """one Courtemanche step under every combination of exp() moved by -1/0/+1 ulp and all potentials moved by -2 .. +2
     float32 neighbours: what ANY float32 evaluation of the reference's formulas may legitimately return"""
     samples = []
@@ -70,7 +70,7 @@ def court_envelope_samples(orc, slab, phase, chronic):
                 s2 = slab.copy()
                 for _ in range(abs(shift)):
                     s2[0] = np.nextafter(s2[0], np.float32(np.inf if shift > 0 else -np.inf))
-                samples.append(orc.court_step(s2, 0.1, 0.809, phase, chronic).astype(np.float64))
+                samples.append(orc.court_step(s2, dt, diff, phase, chronic).astype(np.float64))
     finally:
         orc.set_exp_ulps(0)
     return np.stack(samples)
@@ -241,6 +241,48 @@ def test_court_ultra_us_trajectory(orc, golden):
     # 1 - tanh(x) cancels for V >> -83 mV: one ulp of tanh is an absolute 6e-8 in alpha_us/3e-5
     assert np.allclose(a, f['us_sweep_us_infinity'], rtol=3e-6, atol=3e-7)
     assert np.allclose(b, f['us_sweep_tau_us'], rtol=3e-6, atol=0)
+
+
+@pytest.fixture(scope='module')
+def timestep_figures(orc, golden):
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import timestep_cases as tc
+    n = orc.num_threads()
+    orc.set_threads(min(n, 2))                          # planes of 960 and 2688 cells: a wide team only waits for itself
+    try:
+        return tc, tc.oracle_figures(orc, golden)
+    finally:
+        orc.set_threads(n)
+
+
+@pytest.mark.parametrize('kind,model', [('step', 'fenton'), ('step', 'br'), ('step', 'court'), ('traj', 'fenton'), ('traj', 'br'),
+                                        ('traj', 'court'), ('traj', 'court_ultra')])     # (court_ultra.py's solve is court.py's)
+@pytest.mark.parametrize('p', range(4))
+def test_oracle_at_other_time_steps(timestep_figures, kind, model, p):
+    """the oracle against the reference's own solve() and define() at (dt, diff) other than (0.1, .): tests/golden/ts_*.npz,
+    under the bounds the device's rounding-faithful policy gets in tests/test_gpu_timestep.py (one sub-step:
+    4e-6 * max(1, dt / 0.1) of range; 20 ticks: 2e-5 of range) — measured here against the reference, so the device's
+    oracle comparisons at these time steps do not rest on the oracle alone"""
+    tc, figs = timestep_figures
+    tc.check(figs['%s %s %s' % (kind, model, tc.pair_id(model.split('_')[0], p))])
+
+
+def test_timestep_fixtures_exact_parts(orc, golden):
+    """arithmetic-only parts of the new fixtures, bit for bit in the oracle at every dt: Fenton's V1 and W1 (no
+    transcendental function on their path), Beeler-Reuter's slow gates under solve(state, 0)"""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import timestep_cases as tc
+    for p in range(tc.NPAIRS):
+        c = tc.fenton_step_case(golden, p)
+        out = orc.fenton_step(np.stack([c[k] for k in 'UVWS']), c['dt'], c['diff'], c['phase'])
+        assert np.array_equal(out[1], c['V1']) and np.array_equal(out[2], c['W1']), p
+        c = tc.br_step_case(golden, p)
+        out = orc.br_step(np.stack([c[k] for k in tc.BR_VARS]), c['dt'], c['diff'], c['phase'], None, 0)
+        for i, k in enumerate(tc.BR_VARS):
+            if k in tc.BR_SLOW:
+                assert np.array_equal(out[i], c[k]), (p, k)
 
 
 def test_fenton_simple_trajectory(orc, golden):

@@ -22,6 +22,11 @@ MODELS = {
 }
 
 
+# (name, dt, diff): the two transcriptions at time steps other than 0.1 ms (tests/test_gpu_timestep.py) — the generator
+# folds dt and diff into the source, so each is a code object of its own
+TIMESTEP_TWINS = (('fv', 0.02, 1.5), ('fv', 0.2, 0.7), ('ev', 0.02, 0.809), ('ev', 0.2, 0.4))
+
+
 def make_model(name, H, W, hole=None, **extra):
     mod, cls, needs_install, dt, diff, _ = MODELS[name]
     if needs_install:
