@@ -28,6 +28,8 @@ MAX_WAVES = 65536
 # struct fibhip_wave_record (40 bytes)
 WAVE_RECORD_DTYPE = np.dtype([('seed', np.int32), ('area', np.int32), ('sum_r', np.int64), ('sum_c', np.int64),
                               ('r0', np.int32), ('r1', np.int32), ('c0', np.int32), ('c1', np.int32)])
+MAX_WAVE_LINKS = 65536
+WAVE_LINK_DTYPE = np.dtype([('prev', np.int32), ('seed', np.int32), ('overlap', np.int32)])      # fibhip_wave_link (12 bytes)
 STIM_MODES = ('max', 'add')                                       # enum fibhip_stim_mode, in order
 STIM_SHAPES = ('rect', 'plane')                                   # enum fibhip_stim_shape, in order
 MAX_STIM_ENTRIES, MAX_STIM_PLANES = 64, 8
@@ -238,6 +240,8 @@ SYMBOLS = {
     'fibhip_waves_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_waves_read': ([_h, C.c_longlong, C.c_longlong, _ip, C.c_void_p], C.c_int),
     'fibhip_waves_labels': ([_h, _ip], C.c_int),
+    'fibhip_waves_links_begin': ([_h, C.c_int], C.c_int),
+    'fibhip_waves_links_read': ([_h, C.c_longlong, C.c_longlong, _ip, C.c_void_p], C.c_int),
     'fibhip_waves_end': ([_h], C.c_int),
     'fibhip_spectrum_begin': ([_h, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int], C.c_int),
     'fibhip_spectrum_count': ([_h, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], C.c_int),
@@ -1098,6 +1102,26 @@ class Stepper:
         self._ck(self._L.fibhip_waves_begin(self._h, int(var), int(kind), float(level), int(var2), int(kind2), float(level2), int(conn), mp,
                                             int(max_waves), int(every), int(capacity)))
         self._wave_max = int(max_waves)
+        self._wave_link_max = 0
+
+    def waves_links_begin(self, max_links=512):
+        """turns links on for the wave recorder just attached (before its first tick): per sample, which waves of the sample
+        before share cells with which waves of this one, up to `max_links` records (prev, seed, overlap)"""
+        self._ck(self._L.fibhip_waves_links_begin(self._h, int(max_links)))
+        self._wave_link_max = int(max_links)
+
+    def waves_links_read(self, first=0, count=None, records=True):
+        """samples [first, first + count) (count=None: all taken so far) as (counts, links): counts int32 [count, 4] = links,
+        stored, cells, lost; links WAVE_LINK_DTYPE [count, max_links], of which the first `stored` of each sample are valid, in
+        no fixed order (records=False: None).  Blocks like waves_read; refused while links are off"""
+        if count is None:
+            count = self.waves_count() - int(first)
+        n = max(int(count), 0)
+        counts = np.zeros((n, 4), np.int32)
+        recs = np.zeros((n, getattr(self, '_wave_link_max', 0)), WAVE_LINK_DTYPE) if records else None
+        self._ck(self._L.fibhip_waves_links_read(self._h, int(first), int(count), counts.ctypes.data_as(_ip),
+                                                 recs.ctypes.data_as(C.c_void_p) if records else None))
+        return counts, recs
 
     def waves_count(self):
         """samples taken since waves_begin (ticks accepted but not launched yet included)"""
@@ -1126,6 +1150,7 @@ class Stepper:
 
     def waves_end(self):
         self._ck(self._L.fibhip_waves_end(self._h))
+        self._wave_link_max = 0
 
     # ---- stimulus program (include/fibhip.h fibhip_stim_*) --------------------------------------------------------
     def stim_begin(self, entries, planes=None):

@@ -199,6 +199,15 @@ struct WaveRec : Sampler {
     int *slots;             // device: [H][W], a root's slot in its sample's records
     int *counts;            // device: [cap][3] = n, stored, cells
     WaveRecord *records;    // device: [cap][max_waves]
+    // links (fibhip_waves_links_begin; max_links = 0: off): `prev` is the ONE thing here that is carried from sample to sample.
+    // The two link kernels read the give-up word first and write nothing once a launch in front of them gave up, so it stays
+    // the label plane of the last good sample until the replay takes the lost samples again, in order
+    int max_links;
+    unsigned link_entries;  // T: the smallest power of two >= 4 * max_links
+    int *prev;              // device: [H][W], the label plane of the sample before (-1 everywhere before the first)
+    unsigned long long *link_table;     // device: T keys (pair + 1; 0: empty), then T int32 cell counts; scratch of one sample
+    int *link_counts;       // device: [cap][4] = links, stored, cells, lost
+    WaveLink *link_records; // device: [cap][max_links]
 };
 
 // spectrum recorder (fibhip_spectrum_begin): spectrum_sample_kernel behind the launch that ends a sample tick and, behind the

@@ -1,6 +1,6 @@
 // record.inc — what runs on the device behind the ticks while a model runs.  Nine recorders: the per-cell activation maps
 // (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
-// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the unipolar electrograms (fibhip_leads_*), the excited domains (fibhip_waves_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell
+// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the unipolar electrograms (fibhip_leads_*), the excited domains and their links from sample to sample (fibhip_waves_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell
 // beat history (fibhip_beats_*); and the two hooks that write the state: the stimulus program (fibhip_stim_*) and the trigger
 // program (fibhip_trig_*), which senses, decides and fires on the device.
 // The file has three parts: the helpers every recorder shares; the hooks — per recorder its _advance (behind a launch that the
@@ -363,10 +363,16 @@ static_assert(sizeof(WaveRecord) == sizeof(fibhip_wave_record) && offsetof(WaveR
                   offsetof(WaveRecord, r0) == offsetof(fibhip_wave_record, r0) && sizeof(WaveRecord) == 40 && WV_THREADS == 256 &&
                   WV_TX == 64 && WV_TY % (WV_THREADS / 64) == 0,
               "the wave kernels' record is include/fibhip.h's; a tile row is one wave, four waves share the rows of a tile");
+static_assert(sizeof(WaveLink) == sizeof(fibhip_wave_link) && sizeof(WaveLink) == 12 && offsetof(WaveLink, seed) == offsetof(fibhip_wave_link, seed) &&
+                  offsetof(WaveLink, overlap) == offsetof(fibhip_wave_link, overlap) && WV_LINK_PROBES == 32 &&
+                  4ll * FIBHIP_MAX_WAVE_LINKS <= 0x40000000ll,
+              "the link kernels' record is include/fibhip.h's; a table of <= 32 entries is covered by one probe sequence; T fits 32 bits");
 // The wave recorder's hook: at a sample tick the sample's three counts are zeroed and the four kernels are enqueued behind them
 // on s0 (the merge only where the grid has more than one tile).  Counts and records are addressed from the host's counter, so a
-// replay zeroes and fills the same slot again; the two planes belong to whichever sample is the latest.
-static int waves_advance(fibhip_ctx *h, int ticks, bool)
+// replay zeroes and fills the same slot again; the two planes belong to whichever sample is the latest.  With links on, a clear
+// of the table and of the sample's link counts and the two link kernels follow on the same stream; those two are gated
+// (`behind_mt`), the four in front of them are not: `labels` stays scratch, `prev` stays the plane of the last good sample.
+static int waves_advance(fibhip_ctx *h, int ticks, bool behind_mt)
 {
     WaveRec &r = h->wv;
     long long s;
@@ -401,12 +407,39 @@ static int waves_advance(fibhip_ctx *h, int ticks, bool)
             hipLaunchKernelGGL(wave_root_kernel, cells, dim3(256), 0, h->s0, r.labels, r.slots, ncells, cnt, rec, r.max_waves);
         }))
         return rc;
-    return launch_traced(h, "wave_reduce_kernel", 0, [&] {
-        hipLaunchKernelGGL(wave_reduce_kernel, blocks_of((h->cells + WV_RED_CPT - 1) / WV_RED_CPT), dim3(256), 0, h->s0, (const int *)r.labels, (const int *)r.slots, ncells, W, rec, r.max_waves);
+    if (int rc = launch_traced(h, "wave_reduce_kernel", 0, [&] {
+            hipLaunchKernelGGL(wave_reduce_kernel, blocks_of((h->cells + WV_RED_CPT - 1) / WV_RED_CPT), dim3(256), 0, h->s0, (const int *)r.labels, (const int *)r.slots, ncells, W, rec, r.max_waves);
+        }))
+        return rc;
+    if (!r.max_links) return 0;
+    // links: the table and the sample's four counts are cleared (the table is scratch; a void sample's counts stay zero until
+    // the replay takes it again), then the two kernels, which look at the give-up word behind an unconfirmed launch
+    const unsigned *give_up = give_up_of(h, behind_mt);
+    const unsigned T = r.link_entries;
+    int *lcnt = r.link_counts + 4 * (size_t)s;
+    WaveLink *lrec = r.link_records + (size_t)s * (size_t)r.max_links;
+    HIPCHK(hipMemsetAsync(r.link_table, 0, (size_t)T * (sizeof(unsigned long long) + sizeof(int)), h->s0));
+    HIPCHK(hipMemsetAsync(lcnt, 0, 4 * sizeof(int), h->s0));
+    if (int rc = launch_traced(h, "wave_link_kernel", 0, [&] {
+            hipLaunchKernelGGL(wave_link_kernel, blocks_of((h->cells + WV_LINK_CPT - 1) / WV_LINK_CPT), dim3(256), 0, h->s0, (const int *)r.labels, r.prev, ncells, r.link_table, T - 1u, lcnt, give_up);
+        }))
+        return rc;
+    return launch_traced(h, "wave_link_pack_kernel", 0, [&] {
+        hipLaunchKernelGGL(wave_link_pack_kernel, blocks_of(T), dim3(256), 0, h->s0, (const unsigned long long *)r.link_table, T, lcnt, lrec, r.max_links, give_up);
     });
+}
+static void wave_links_free(fibhip_ctx *h)
+{
+    dev_free(h->wv.prev);
+    dev_free(h->wv.link_table);
+    dev_free(h->wv.link_counts);
+    dev_free(h->wv.link_records);
+    h->wv.max_links = 0;
+    h->wv.link_entries = 0;
 }
 static void waves_free(fibhip_ctx *h)
 {
+    wave_links_free(h);
     dev_free(h->wv.mask);
     dev_free(h->wv.labels);
     dev_free(h->wv.slots);
@@ -1381,6 +1414,61 @@ extern "C" int fibhip_waves_read(fibhip_t h, long long first, long long count, i
             HIPCHK(hipMemcpyAsync(counts, h->wv.counts + 3 * (size_t)first, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost, h->s0));
             if (records)
                 HIPCHK(hipMemcpyAsync(records, h->wv.records + (size_t)first * per, (size_t)count * per * sizeof(WaveRecord),
+                                      hipMemcpyDeviceToHost, h->s0));
+        }
+        return 0;
+    });
+}
+
+extern "C" int fibhip_waves_links_begin(fibhip_t h, int max_links)
+{
+    NEED(h);
+    WaveRec &r = h->wv;
+    if (!r.on) return fail(FIBHIP_EINVAL, "waves_links_begin: no recorder attached (fibhip_waves_begin)");
+    if (r.max_links) return fail(FIBHIP_EINVAL, "waves_links_begin: links are on already (%d per sample)", r.max_links);
+    if (max_links < 1 || max_links > FIBHIP_MAX_WAVE_LINKS)
+        return fail(FIBHIP_EINVAL, "waves_links_begin: 1 .. %d links per sample (got %d)", FIBHIP_MAX_WAVE_LINKS, max_links);
+    if (r.cap > (long long)(SIZE_MAX / sizeof(WaveLink) / (size_t)max_links))
+        return fail(FIBHIP_EINVAL, "waves_links_begin: %lld samples of %d links do not fit", r.cap, max_links);
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "waves_links_begin inside an open tick");
+    // sample s links to sample s - 1: links start with the recorder or not at all
+    if (r.k != 0 || h->pending != 0)
+        return fail(FIBHIP_EINVAL, "waves_links_begin: the recorder has seen ticks already (%lld launched, %lld pending): call it right behind fibhip_waves_begin",
+                    r.k, (long long)h->pending);
+    SYNC_S0(h);
+    unsigned T = 4;
+    while (T < 4u * (unsigned)max_links) T <<= 1;
+    const bool ok = hipMalloc((void **)&r.prev, h->cells * sizeof(int)) == hipSuccess &&
+                    hipMalloc((void **)&r.link_table, (size_t)T * (sizeof(unsigned long long) + sizeof(int))) == hipSuccess &&
+                    hipMalloc((void **)&r.link_counts, (size_t)r.cap * 4 * sizeof(int)) == hipSuccess &&
+                    hipMalloc((void **)&r.link_records, (size_t)r.cap * (size_t)max_links * sizeof(WaveLink)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        wave_links_free(h);                            // (the wave recorder stays attached, without links)
+        return fail(FIBHIP_ENOMEM, "waves_links_begin: hipMalloc of the link buffers failed (%lld samples of %d links)", r.cap, max_links);
+    }
+    HIPCHK(hipMemsetAsync(r.prev, 0xFF, h->cells * sizeof(int), h->s0));
+    HIPCHK(hipMemsetAsync(r.link_counts, 0, (size_t)r.cap * 4 * sizeof(int), h->s0));
+    HIPCHK(wait_stream(h->s0));
+    r.max_links = max_links;
+    r.link_entries = T;
+    return 0;
+}
+
+extern "C" int fibhip_waves_links_read(fibhip_t h, long long first, long long count, int *counts, fibhip_wave_link *links)
+{
+    NEED(h);
+    if (!h->wv.on) return fail(FIBHIP_EINVAL, "waves_links_read: no recorder attached (fibhip_waves_begin)");
+    if (!h->wv.max_links) return fail(FIBHIP_EINVAL, "waves_links_read: links are off (fibhip_waves_links_begin)");
+    FLUSH(h);
+    if (int rc = range_check("waves_links_read", "samples", first, count, h->wv.taken())) return rc;
+    if (count > 0 && !counts) return fail(FIBHIP_EINVAL, "waves_links_read: null destination");
+    const size_t per = (size_t)h->wv.max_links;
+    return read_confirmed(h, [&] {
+        if (count > 0) {
+            HIPCHK(hipMemcpyAsync(counts, h->wv.link_counts + 4 * (size_t)first, (size_t)count * 4 * sizeof(int), hipMemcpyDeviceToHost, h->s0));
+            if (links)
+                HIPCHK(hipMemcpyAsync(links, h->wv.link_records + (size_t)first * per, (size_t)count * per * sizeof(WaveLink),
                                       hipMemcpyDeviceToHost, h->s0));
         }
         return 0;

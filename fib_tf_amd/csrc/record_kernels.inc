@@ -1700,3 +1700,166 @@ __global__ void __launch_bounds__(256) wave_reduce_kernel(const int *__restrict_
         }
     }
 }
+
+// ---- links (fibhip_waves_links_begin): which wave of the sample before does a wave of this sample share cells with ---------------
+// With L[s] the label plane of sample s, a LINK of sample s >= 1 is a pair (prev, seed) for which some cell c has
+// L[s - 1][c] = prev >= 0 and L[s][c] = seed >= 0; its OVERLAP is the number of such cells.  Two kernels behind the sample's four,
+// behind a memset of the table and of the sample's four counts {links, stored, cells, lost}:
+//   wave_link_kernel       one pass over the cells: a cell that is set in both planes adds itself to its pair's entry of an
+//     open-addressing table in global memory, then prev[c] = labels[c] — by the cell's own thread, the only one that touches it.
+//     A key is the 64-bit pair plus one (0: empty; a memset clears keys and counts at once); an insertion is a relaxed
+//     agent-scope 64-bit compare-exchange on the key, then a 32-bit atomicAdd on the entry's count.  T entries, a power of two;
+//     double hashing: a 64-bit mixer gives the first entry and an ODD step, so T <= 32 entries are all visited within the
+//     WV_LINK_PROBES = 32 probes that bound the walk.  A pair that finds neither itself nor an empty entry within the bound
+//     adds its cells to `lost` and is gone; nothing is ever deleted, so a pair that is in the table is found again by the same
+//     walk and its overlap is exact whatever else was lost.  Contention as in wave_reduce_kernel: while the contributing lanes of a
+//     wave all name one pair they count in registers, the counts are folded across the wave and the four waves' through LDS
+//     (inside a large domain a workgroup of 4096 cells issues ONE insertion); a step with several pairs peels off up to
+//     WV_LINK_PEEL of them, one insertion each by ballot and popcount, and whatever is left goes lane by lane.  `cells` and
+//     `lost` take one atomicAdd per workgroup.
+//   wave_link_pack_kernel  one thread per entry: an occupied entry takes a rank (one atomicAdd on `links` per wave of the GPU, ranks
+//     by ballot: wave_root_kernel's way) and, if that is below max_links, counts itself in `stored` and writes its record.
+// Both read the give-up word first and write NOTHING once it is raised — not prev, not the table, not the slot: prev is carried
+// from sample to sample and has to stay the plane of the last good sample (recorders.hpp).  Integer atomics only, no kernel waits
+// for another workgroup, every loop is bounded by a constant; they end whatever the planes hold.
+#define WV_LINK_PROBES 32
+#define WV_LINK_CPT 16
+#define WV_LINK_PEEL 4
+struct WaveLink {               // fibhip_wave_link
+    int prev, seed, overlap;
+};
+static FIB_DEV unsigned long long wave_link_mix(unsigned long long x)      // (the finaliser of splitmix64)
+{
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+// `n` cells for the pair behind `key` (never 0); -> the cells that found no room (0 or n).  tmask = T - 1, T >= 4
+static FIB_DEV int wave_link_insert(unsigned long long *keys, int *vals, unsigned tmask, unsigned long long key, int n)
+{
+    constexpr int AG = __HIP_MEMORY_SCOPE_AGENT;
+    const unsigned long long h = wave_link_mix(key);
+    unsigned i = (unsigned)h & tmask;
+    const unsigned step = ((unsigned)(h >> 32) | 1u) & tmask;
+    for (int p = 0; p < WV_LINK_PROBES; ++p) {
+        unsigned long long k = __hip_atomic_load(keys + i, __ATOMIC_RELAXED, AG);
+        if (k == 0ull && __hip_atomic_compare_exchange_strong(keys + i, &k, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, AG)) k = key;
+        // (a compare-exchange that failed has left in k what it met)
+        if (k == key) {
+            atomicAdd(vals + i, n);
+            return 0;
+        }
+        i = (i + step) & tmask;
+    }
+    return n;
+}
+
+__global__ void __launch_bounds__(256) wave_link_kernel(const int *__restrict__ labels, int *__restrict__ prev, int ncells,
+                                                        unsigned long long *__restrict__ keys, unsigned tmask, int *__restrict__ cnt,
+                                                        const unsigned *__restrict__ give_up)
+{
+    if (give_up && *give_up != 0u) return;                      // (wave-uniform: one scalar load)
+    __shared__ unsigned long long wkey[4];
+    __shared__ int wn[4], wcells[4], wlost[4];
+    int *vals = reinterpret_cast<int *>(keys + (size_t)tmask + 1);
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const long long base = (long long)blockIdx.x * (256 * WV_LINK_CPT) + threadIdx.x;
+    int now[WV_LINK_CPT], was[WV_LINK_CPT];
+#pragma unroll
+    for (int j = 0; j < WV_LINK_CPT; ++j) {
+        const long long t = base + 256 * j;
+        now[j] = t < ncells ? labels[t] : -1;
+        was[j] = t < ncells ? prev[t] : -1;
+    }
+    unsigned long long key[WV_LINK_CPT];                        // 0: the cell contributes nothing
+#pragma unroll
+    for (int j = 0; j < WV_LINK_CPT; ++j) {
+        const long long t = base + 256 * j;
+        if (t < ncells && now[j] != was[j]) prev[t] = now[j];
+        key[j] = now[j] >= 0 && was[j] >= 0 ? (((unsigned long long)(unsigned)was[j] << 32) | (unsigned long long)(unsigned)now[j]) + 1ull : 0ull;
+    }
+    unsigned long long run = 0ull;                              // (wave-uniform) the pair the lanes' counts belong to, 0: none
+    int mine = 0, cells = 0, lost = 0;
+#pragma unroll
+    for (int j = 0; j < WV_LINK_CPT; ++j) {
+        const bool on = key[j] != 0ull;
+        const unsigned long long act = __ballot(on);
+        if (!act) continue;                                     // (wave-uniform)
+        cells += on ? 1 : 0;
+        const unsigned long long first = __shfl(key[j], __builtin_ctzll(act), 64);
+        const bool one = __ballot(on && key[j] != first) == 0;
+        if (!(one && (run == 0ull || run == first))) {
+            if (run != 0ull) {
+                mine = wave_all<int>(mine, [](int x, int y) { return x + y; });
+                if (lane == 0) lost += wave_link_insert(keys, vals, tmask, run, mine);
+                mine = 0;
+            }
+            run = 0ull;
+        }
+        if (one) {
+            run = first;
+            mine += on ? 1 : 0;
+        } else {
+            unsigned long long rest = act;                      // (wave-uniform, and so is the loop)
+#pragma unroll
+            for (int p = 0; p < WV_LINK_PEEL; ++p) {
+                if (!rest) break;
+                const int leader = __builtin_ctzll(rest);
+                const unsigned long long k = __shfl(key[j], leader, 64);
+                const unsigned long long same = __ballot(on && key[j] == k);
+                if (lane == leader) lost += wave_link_insert(keys, vals, tmask, k, __popcll(same));
+                rest &= ~same;
+            }
+            if ((rest >> lane) & 1ull) lost += wave_link_insert(keys, vals, tmask, key[j], 1);
+        }
+    }
+    mine = wave_all<int>(mine, [](int x, int y) { return x + y; });
+    cells = wave_all<int>(cells, [](int x, int y) { return x + y; });
+    lost = wave_all<int>(lost, [](int x, int y) { return x + y; });
+    if (lane == 0) {
+        wkey[wave] = run;
+        wn[wave] = mine;
+        wcells[wave] = cells;
+        wlost[wave] = lost;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0, l = 0;
+        for (int w = 0; w < 4; ++w) {
+            c += wcells[w];
+            l += wlost[w];
+            if (wkey[w] == 0ull) continue;
+            if (w + 1 < 4 && wkey[w + 1] == wkey[w]) wn[w + 1] += wn[w];
+            else l += wave_link_insert(keys, vals, tmask, wkey[w], wn[w]);
+        }
+        if (c) atomicAdd(&cnt[2], c);
+        if (l) atomicAdd(&cnt[3], l);
+    }
+}
+
+__global__ void __launch_bounds__(256) wave_link_pack_kernel(const unsigned long long *__restrict__ keys, unsigned entries, int *__restrict__ cnt,
+                                                             WaveLink *__restrict__ rec, int max_links, const unsigned *__restrict__ give_up)
+{
+    if (give_up && *give_up != 0u) return;                      // (wave-uniform: one scalar load)
+    const int *vals = reinterpret_cast<const int *>(keys + (size_t)entries);
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;
+    const unsigned long long key = t < entries ? keys[t] : 0ull;
+    // every lane of the wave comes here
+    const unsigned long long full = __ballot(key != 0ull);
+    if (!full) return;
+    const int lane = (int)(threadIdx.x & 63u);
+    int base = 0;
+    if (lane == 0) base = atomicAdd(&cnt[0], __popcll(full));
+    base = __shfl(base, 0, 64);
+    const int rank = base + __popcll(full & ((1ull << lane) - 1ull));
+    const bool keep = key != 0ull && rank < max_links;
+    const unsigned long long kept = __ballot(keep);
+    if (kept && lane == 0) atomicAdd(&cnt[1], __popcll(kept));
+    if (keep) {
+        const unsigned long long pair = key - 1ull;
+        WaveLink w;
+        w.prev = (int)(unsigned)(pair >> 32); w.seed = (int)(unsigned)(pair & 0xffffffffull);
+        w.overlap = vals[t];
+        rec[rank] = w;
+    }
+}

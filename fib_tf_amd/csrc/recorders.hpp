@@ -44,7 +44,14 @@ static constexpr Recorder RECORDERS[] = {
     // reads them (wave_label_kernel writes every label from the state, wave_root_kernel every slot that is read); the sample's
     // counts are zeroed in front of its kernels and its records initialised and filled whole; the slot follows from the counter.
     // A sample taken from a void slab is overwritten, counts, records and planes, when the replay takes it again.  No give-up
-    // word is needed: nothing is accumulated across samples, and its kernels end on any state (no loop waits for anything)
+    // word is needed: nothing is accumulated across samples, and its kernels end on any state (no loop waits for anything).
+    // With LINKS on (fibhip_waves_links_begin) one thing IS carried from sample to sample: `prev`, the label plane of the sample
+    // before.  The row may still be rewound, by the beat recorder's argument below: the two link kernels read the give-up word
+    // first and write nothing once a launch in front of them gave up — not prev, not the table, not the sample's slot — so
+    // however many void samples were queued, prev stays the plane of the last GOOD sample (a double buffer of planes would not
+    // do: several samples can stand unconfirmed); the replay, plain ticks with no word to look at, takes the lost samples again
+    // IN ORDER from that plane, and their slots follow from the counter.  The four kernels in front stay ungated (`labels` is
+    // scratch), and the row keeps its place: the launch order on a shared tick is tested
     {"wave", SAMPLER_AT(wv), waves_advance, waves_free},
     // these two ACCUMULATE (the fold and the short ring; the count, the open beat's peak, the ring): their kernels read the
     // give-up word first and write nothing once a launch in front of them gave up, and how far they have come follows from the

@@ -311,7 +311,8 @@ class IonicModel:
             ensure()
         return LeadRecorder(self, positions, tables, table_of=table_of, every=every, weight=weight, var=var, capacity=capacity)
 
-    def record_waves(self, level=None, kind='above', every=1, conn=4, mask=None, max_waves=256, capacity=None, var=0, also=None):
+    def record_waves(self, level=None, kind='above', every=1, conn=4, mask=None, max_waves=256, capacity=None, var=0, also=None,
+                     links=False, max_links=None):
         """attaches a wave recorder (fib_tf_amd/waves.py) to this model's handle: every `every` ticks the cells of `mask` where
         state array `var` is above (`kind` 'above') or below ('below') `level` — strict float32 compares, a NaN is never set —
         and, with `also` = (array, kind, level), a second array meets its own condition, are grouped on the device into their
@@ -319,7 +320,10 @@ class IonicModel:
         area, centroid sums and bounding box, up to `max_waves` per sample, are kept there until `counts()` / `waves()` read
         them; `labels()` is the label plane of the latest sample.  `level` defaults to the activation recorder's `up` (50 % of
         [min_v, max_v]); `mask` to `phase > 0.5` with the outer ring of the grid, the ghost copies, cleared; arrays are names
-        or indices of VAR_NAMES.  Default capacity: the samples of a whole run of `duration`.  Call after define(); single
+        or indices of VAR_NAMES.  Default capacity: the samples of a whole run of `duration`.  With `links=True` the device
+        also keeps, per sample, which waves of the sample before share cells with which waves of this one and how many — up to
+        `max_links` records (default 2 * max_waves) — for `links()`, `events()` (births, deaths, splits, merges) and `tracks()`;
+        choose `every` so that a wave overlaps itself from one sample to the next.  Call after define(); single
         device only (row blocks raise NotImplementedError)."""
         from .waves import WaveRecorder
         if not self.defined:
@@ -328,7 +332,7 @@ class IonicModel:
         if ensure is not None:
             ensure()
         return WaveRecorder(self, level=level, kind=kind, every=every, conn=conn, mask=mask, max_waves=max_waves, capacity=capacity,
-                            var=var, also=also)
+                            var=var, also=also, links=links, max_links=max_links)
 
     def record_spectrum(self, every=10, nfft=128, fmin=None, fmax=None, bins=None, window='hann', chunk=None, var=0, block=(1, 1),
                         reduce='mean', region=None, weight=None):

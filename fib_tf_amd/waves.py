@@ -6,13 +6,24 @@ has no tip for the tip recorder to find.  `WaveRecorder` has the library label t
 condition every `every` ticks (`wave_label_kernel`, `wave_merge_kernel`, `wave_root_kernel`, `wave_reduce_kernel`) and keeps
 their counts and records on the device until they are read: no read-back and no synchronisation per sample (DESIGN.md section
 21).  The definition is exact (include/fibhip.h, fibhip_waves_*; restated in NumPy in tests/wave_ref.py).  With
-`kind='below'` the same machinery gives the domains of the excitable gap."""
+`kind='below'` the same machinery gives the domains of the excitable gap.
+
+With `links=True` two more kernels (`wave_link_kernel`, `wave_link_pack_kernel`) keep, per sample, the pairs (wave of the sample
+before, wave of this sample) that share cells and how many cells they share: what tells a wave that split from one that died
+while another was born beside it.  `events` and `track` below turn those lists into wavebreak, coalescence, birth and death
+counts and into a genealogy of the waves — plain NumPy on the lists, nothing of the device."""
 import numpy as np
 
-from ._lib import MAX_WAVES, WAVE_KINDS
+from ._lib import MAX_WAVE_LINKS, MAX_WAVES, WAVE_KINDS
 
 WAVE_DTYPE = np.dtype([('t_ms', np.float64), ('seed', np.int32), ('area', np.int32), ('cy', np.float64), ('cx', np.float64),
                        ('r0', np.int32), ('r1', np.int32), ('c0', np.int32), ('c1', np.int32)])
+
+
+LINK_DTYPE = np.dtype([('t_ms', np.float64), ('prev', np.int32), ('seed', np.int32), ('overlap', np.int32)])
+EVENT_DTYPE = np.dtype([('t_ms', np.float64), ('waves', np.int32), ('births', np.int32), ('deaths', np.int32), ('splits', np.int32),
+                        ('merges', np.int32), ('continued', np.int32)])
+POINT_DTYPE = np.dtype([('t_ms', np.float64), ('seed', np.int32), ('area', np.int32), ('cy', np.float64), ('cx', np.float64)])
 
 
 def _array_index(model, var, what):
@@ -64,7 +75,8 @@ class WaveRecorder:
     `dt_per_step * dt` ms.  At most `max_waves` waves are kept per sample (`truncated()` names the samples that had more);
     `counts()` is exact regardless."""
 
-    def __init__(self, model, level=None, kind='above', every=1, conn=4, mask=None, max_waves=256, capacity=None, var=0, also=None):
+    def __init__(self, model, level=None, kind='above', every=1, conn=4, mask=None, max_waves=256, capacity=None, var=0, also=None,
+                 links=False, max_links=None):
         from .activation import default_thresholds
         from .sharded import ShardedStepper
         st = model._stepper
@@ -94,6 +106,11 @@ class WaveRecorder:
         self.max_waves = int(max_waves)
         if not 1 <= self.max_waves <= MAX_WAVES:
             raise ValueError('record_waves: max_waves is 1 .. %d (got %d)' % (MAX_WAVES, self.max_waves))
+        self.max_links = 0
+        if links:
+            self.max_links = min(2 * self.max_waves, MAX_WAVE_LINKS) if max_links is None else int(max_links)
+            if not 1 <= self.max_links <= MAX_WAVE_LINKS:
+                raise ValueError('record_waves: max_links is 1 .. %d (got %d)' % (MAX_WAVE_LINKS, self.max_links))
         self.tick_ms = float(model.dt_per_step * model.dt)
         if capacity is None:                     # the samples of a whole run of model.duration (whatever has run already), at least 1
             ticks = int(model.duration / (model.dt_per_step * model.dt))
@@ -111,6 +128,12 @@ class WaveRecorder:
         st.waves_begin(self.var, self.kind, self.level, self.var2, self.kind2, self.level2, self.conn, mask, self.max_waves, self.every,
                        self.capacity)
         self.open = True
+        if self.max_links:
+            try:
+                st.waves_links_begin(self.max_links)
+            except Exception:
+                self.close()
+                raise
 
     def _check(self):
         if not self.open:
@@ -153,6 +176,56 @@ class WaveRecorder:
             out.append(a)
         return out
 
+    # ---- links -------------------------------------------------------------------------------------------------------------
+    def _check_links(self):
+        self._check()
+        if not self.max_links:
+            raise ValueError('this wave recorder keeps no links: attach it with record_waves(links=True)')
+
+    def link_counts(self, first=0, count=None):
+        """int32 [samples, 4]: links (distinct pairs that found a place in the table), stored (records kept), cells (cells set in
+        this sample and in the one before: exact), lost (cells whose pair found no place; while 0, `links` is exact)"""
+        self._check_links()
+        return self._st.waves_links_read(first, count, records=False)[0]
+
+    def links_raw(self, first=0, count=None):
+        """(counts, records) exactly as the device wrote them: records [samples, max_links] of struct fibhip_wave_link, the first
+        `stored` of a sample valid, in the order of arrival"""
+        self._check_links()
+        return self._st.waves_links_read(first, count)
+
+    def links_truncated(self):
+        """indices of the samples whose link list is not complete: more links than `max_links`, or cells lost"""
+        c = self.link_counts()
+        return np.flatnonzero((c[:, 0] > self.max_links) | (c[:, 3] > 0))
+
+    def links(self, first=0, count=None):
+        """a list with one structured array (t_ms, prev, seed, overlap) per sample, sorted by (prev, seed): `prev` is a seed of the
+        sample before, `seed` one of this sample, `overlap` the cells the two waves share.  Sample 0 has none"""
+        counts, records = self.links_raw(first, count)
+        out = []
+        for s in range(len(counts)):
+            r = records[s, :int(counts[s, 1])]
+            r = r[np.lexsort((r['seed'], r['prev']))]
+            a = np.empty(len(r), LINK_DTYPE)
+            a['t_ms'] = (int(first) + s + 1) * self.every * self.tick_ms
+            for f in ('prev', 'seed', 'overlap'):
+                a[f] = r[f]
+            out.append(a)
+        return out
+
+    def events(self, min_overlap=1):
+        """`events` of every sample taken so far; a cut wave list or link list is refused (ValueError naming the sample)"""
+        self._check_links()
+        return events(self.waves(), self.links(), min_overlap, wave_counts=self.counts(), link_counts=self.link_counts(),
+                      times_ms=self.times_ms())
+
+    def tracks(self, min_overlap=1):
+        """`track` of every sample taken so far; a cut wave list or link list is refused (ValueError naming the sample)"""
+        self._check_links()
+        return track(self.waves(), self.links(), min_overlap, wave_counts=self.counts(), link_counts=self.link_counts(),
+                     times_ms=self.times_ms())
+
     def labels(self):
         """the label plane of the latest sample: int32 [height, width], the seed of the cell's wave, -1 where the cell is not set"""
         self._check()
@@ -174,3 +247,148 @@ class WaveRecorder:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+# ---- what the links say: events and tracks (host code on the lists) --------------------------------------------------------------
+class Track:
+    """one wave followed along `continued` links: `id`; `born` 'start' (there at sample 0), 'birth' (no wave before it overlaps it),
+    'split' (its one predecessor went on into several) or 'merge' (several predecessors); `ended` 'death' (nothing overlaps it
+    in the next sample), 'split', 'merge' or 'end' (alive at the last sample); `parents` and `children` are track ids; `points`
+    is structured (t_ms, seed, area, cy, cx), one row per sample it lived through"""
+    __slots__ = ('id', 'born', 'ended', 'parents', 'children', 'points')
+
+    def __init__(self, id, born):
+        self.id, self.born, self.ended, self.parents, self.children, self.points = id, born, 'end', [], [], []
+
+    @property
+    def lifetime_ms(self):
+        return float(self.points['t_ms'][-1] - self.points['t_ms'][0])
+
+    def __repr__(self):
+        return 'Track(id=%d, born=%r, ended=%r, parents=%r, children=%r, points=%d)' % (self.id, self.born, self.ended, self.parents,
+                                                                                       self.children, len(self.points))
+
+
+def _checked(waves_per_sample, links_per_sample, wave_counts, link_counts):
+    n = len(waves_per_sample)
+    if len(links_per_sample) != n:
+        raise ValueError('%d wave lists but %d link lists' % (n, len(links_per_sample)))
+    if wave_counts is not None:
+        wave_counts = np.asarray(wave_counts)
+        for s in range(n):
+            if not (wave_counts[s, 0] == wave_counts[s, 1] == len(waves_per_sample[s])):
+                raise ValueError('sample %d: the wave list was cut (%d waves, %d given): raise max_waves'
+                                 % (s, wave_counts[s, 0], len(waves_per_sample[s])))
+    if link_counts is not None:
+        link_counts = np.asarray(link_counts)
+        for s in range(n):
+            if not (link_counts[s, 0] == link_counts[s, 1] == len(links_per_sample[s])) or link_counts[s, 3] != 0:
+                raise ValueError('sample %d: the link list was cut (%d links, %d given, %d cells lost): raise max_links'
+                                 % (s, link_counts[s, 0], len(links_per_sample[s]), link_counts[s, 3]))
+    if n and len(links_per_sample[0]):
+        raise ValueError('sample 0: the first sample has no links')
+
+
+def _graph(s, waves_per_sample, links_per_sample, min_overlap):
+    """the overlap graph between the samples s - 1 and s: (seeds before, seeds now, links kept, out-degrees, in-degrees)"""
+    P = [int(x) for x in waves_per_sample[s - 1]['seed']]
+    Q = [int(x) for x in waves_per_sample[s]['seed']]
+    L = links_per_sample[s]
+    kept = [(int(p), int(q)) for p, q, o in zip(L['prev'], L['seed'], L['overlap']) if o >= min_overlap]
+    out, into = dict.fromkeys(P, 0), dict.fromkeys(Q, 0)
+    for p, q in kept:
+        if p not in out or q not in into:
+            raise ValueError('sample %d: the link (%d, %d) names a wave that is not in the wave lists (a cut list?)' % (s, p, q))
+        out[p] += 1
+        into[q] += 1
+    return P, Q, kept, out, into
+
+
+def _time_of(s, waves_per_sample, links_per_sample, times_ms):
+    if times_ms is not None:
+        return float(times_ms[s])
+    for a in (waves_per_sample[s], links_per_sample[s]):
+        if len(a) and 't_ms' in (a.dtype.names or ()):
+            return float(a['t_ms'][0])
+    return float('nan')
+
+
+def events(waves_per_sample, links_per_sample, min_overlap=1, wave_counts=None, link_counts=None, times_ms=None):
+    """what happened between consecutive samples, from `WaveRecorder.waves()` and `.links()` (or lists like them): a structured
+    array with one row per sample, (t_ms, waves, births, deaths, splits, merges, continued).  With d+(p) and d-(q) the out- and
+    in-degrees of the overlap graph between the samples s - 1 and s over the links of overlap >= `min_overlap`: a birth is a
+    wave q of s with d- = 0, a death a wave p of s - 1 with d+ = 0, a split a p with d+ >= 2, a merge a q with d- >= 2, and
+    `continued` counts the links whose two ends both have degree 1.  Row 0 has its waves and zeros.  The lists must be whole:
+    with `wave_counts` / `link_counts` (the recorder's `counts()` / `link_counts()`) a cut list is refused by sample; a link
+    that names a wave that is in no list is refused either way.  `times_ms`: the sample times where a sample may be empty."""
+    _checked(waves_per_sample, links_per_sample, wave_counts, link_counts)
+    out = np.zeros(len(waves_per_sample), EVENT_DTYPE)
+    for s in range(len(out)):
+        out['t_ms'][s] = _time_of(s, waves_per_sample, links_per_sample, times_ms)
+        out['waves'][s] = len(waves_per_sample[s])
+        if s == 0:
+            continue
+        P, Q, kept, dout, din = _graph(s, waves_per_sample, links_per_sample, min_overlap)
+        out['births'][s] = sum(1 for q in Q if din[q] == 0)
+        out['deaths'][s] = sum(1 for p in P if dout[p] == 0)
+        out['splits'][s] = sum(1 for p in P if dout[p] >= 2)
+        out['merges'][s] = sum(1 for q in Q if din[q] >= 2)
+        out['continued'][s] = sum(1 for p, q in kept if dout[p] == 1 and din[q] == 1)
+    return out
+
+
+def track(waves_per_sample, links_per_sample, min_overlap=1, wave_counts=None, link_counts=None, times_ms=None):
+    """the waves followed from sample to sample: a list of `Track`, ids in the order of first appearance (by sample, then by
+    seed).  A track runs along `continued` links only (both ends of degree 1); every other link ends a track and starts
+    another, and is kept as parent -> child.  A wave with several predecessors is born by 'merge' (whatever else its parents
+    did), one whose single predecessor went on into several by 'split'.  The same lists and checks as `events`."""
+    _checked(waves_per_sample, links_per_sample, wave_counts, link_counts)
+    tracks, alive = [], {}                               # alive: seed in the latest sample -> track
+
+    def point(s, rec):
+        t = _time_of(s, waves_per_sample, links_per_sample, times_ms)
+        names = rec.dtype.names
+        if 'cy' in names:
+            cy, cx = float(rec['cy']), float(rec['cx'])
+        else:
+            cy, cx = float(rec['sum_r']) / float(rec['area']), float(rec['sum_c']) / float(rec['area'])
+        return (t, int(rec['seed']), int(rec['area']), cy, cx)
+
+    for s in range(len(waves_per_sample)):
+        W = waves_per_sample[s]
+        now = {}
+        if s == 0:
+            for rec in W:
+                t = Track(len(tracks), 'start')
+                tracks.append(t)
+                t.points.append(point(s, rec))
+                now[int(rec['seed'])] = t
+        else:
+            P, Q, kept, dout, din = _graph(s, waves_per_sample, links_per_sample, min_overlap)
+            before = {q: [] for q in Q}
+            for p, q in kept:
+                before[q].append(p)
+            for rec in W:
+                q = int(rec['seed'])
+                ps = sorted(before[q])
+                if len(ps) == 1 and dout[ps[0]] == 1:
+                    t = alive[ps[0]]
+                else:
+                    t = Track(len(tracks), 'birth' if not ps else 'merge' if len(ps) >= 2 else 'split')
+                    tracks.append(t)
+                    for p in ps:
+                        parent = alive[p]
+                        t.parents.append(parent.id)
+                        parent.children.append(t.id)
+                        parent.ended = 'split' if dout[p] >= 2 else 'merge'
+                t.points.append(point(s, rec))
+                now[q] = t
+            for p in P:
+                if dout[p] == 0:
+                    alive[p].ended = 'death'
+        alive = now
+    for t in tracks:
+        t.parents.sort()
+        t.children.sort()
+        t.points = np.array(t.points, POINT_DTYPE)
+    return tracks

@@ -604,6 +604,34 @@ int fibhip_waves_read(fibhip_t h, long long first, long long count, int *counts 
                       fibhip_wave_record *records /* [count][max_waves] or NULL */);
 int fibhip_waves_labels(fibhip_t h, int *dst /* [H*W] */);
 int fibhip_waves_end(fibhip_t h);
+/* Links: which wave of the sample before a wave of this sample shares cells with — what a host needs to tell a wave that split
+ * from one that died while another was born beside it.  Opt-in; with links off the recorder launches and writes what it always
+ * did.  Restated in tests/wave_link_ref.py.  With L[s] the label plane of sample s:
+ *     link    for s >= 1 a pair (prev, seed) such that some cell c has L[s-1][c] = prev >= 0 and L[s][c] = seed >= 0; its
+ *             OVERLAP is the number of such cells.  Sample 0 has no links.  Links depend on the label planes alone, not on
+ *             max_waves or on which records were stored.
+ *     counts  per sample int32[4] = links, stored, cells, lost: the number of distinct pairs that found a place in the sample's
+ *             table; the records written = min(links, max_links); the cells set in both planes (always exact); and the cells
+ *             whose pair found no place in the table.  While lost == 0, `links` is the exact number of distinct pairs.
+ *     records fibhip_wave_link, up to max_links per sample, in the order of arrival (sort by (prev, seed)).  Every stored record
+ *             is whole, its overlap exact, and no pair appears twice; where links > max_links, WHICH pairs are stored is
+ *             unspecified.
+ *     table   the pairs of a sample are collected in a hash table of T entries, T the smallest power of two >= 4 * max_links,
+ *             probed at most 32 times per insertion (the walk visits every entry of a table of T <= 32).  A sample with at
+ *             most max_links pairs loses none when T <= 32 and otherwise one with probability <= 4^-32 per pair.
+ *   fibhip_waves_links_begin   turns links on for the attached wave recorder: right behind fibhip_waves_begin — refused once the
+ *                              recorder has seen a tick (launched or pending), when links are on already, without a recorder,
+ *                              inside an open tick, for max_links outside 1 .. FIBHIP_MAX_WAVE_LINKS or lists that would not
+ *                              fit size_t.  FIBHIP_ENOMEM leaves the wave recorder attached without links
+ *   fibhip_waves_links_read    samples [first, first + count): counts as [count][4] and (unless NULL) records as
+ *                              [count][max_links], the first `stored` of each sample valid; flushes and blocks like
+ *                              fibhip_waves_read; refused while links are off
+ * fibhip_waves_end, fibhip_waves_begin (again) and fibhip_destroy free the link buffers with the rest.                            */
+#define FIBHIP_MAX_WAVE_LINKS 65536
+typedef struct { int prev, seed, overlap; } fibhip_wave_link;      /* 12 bytes */
+int fibhip_waves_links_begin(fibhip_t h, int max_links);
+int fibhip_waves_links_read(fibhip_t h, long long first, long long count, int *counts /* [count][4] */,
+                            fibhip_wave_link *links /* [count][max_links] or NULL */);
 
 /* Spectrum recorder: per-cell power spectra (a Welch periodogram) folded on the device while the run goes on, and the
  * dominant-frequency maps made from them — the sixth recorder and the fifth sampler.  All device arithmetic is float32, every
