@@ -52,6 +52,10 @@
             }
         }
         // currents from the OLD gates, br.py:150-165
+        // i_K1's second quotient (V+23) / (1 - exp(-0.04 (V+23))) is 0/0 at V0 == -23.0f and at no other float32 potential;
+        // there it is DEFINED as its limit 1/0.04 = 25 under both policies and both gate forms (DESIGN.md 9, "op contract":
+        // the reference's NaN ends as V = -85 through the clip) — a select on the finished quotient
+        const auto at23 = vcmp_eq(V0, -23.0f);
         if constexpr (same_type<P, Fast>::value) {
             // Fast: the five exponentials of iK1 and ix1 are all powers of ONE e = exp(0.04 V0) times constants
             // (exp(0.08 (V0+53)) = (e*E53)^2, exp(-0.04 (V0+23)) = 1 / (e*E23), ...): one v_exp and three v_rcp instead
@@ -62,7 +66,9 @@
             const T re = P::rcp(e);
             const T a = e * E53;
             const T t1 = vfma(e, 4.0f * E85, -4.0f) * P::rcp(vfma(a, a, a));          // 4 (e^{.04(V+85)} - 1) / (a^2 + a)
-            const T t2 = (V0 + 23.0f) * P::rcp(vfma(re, FC(-1.0 / 2.5092903899362979), 1.0f));   // (V+23) / (1 - e^{-.04(V+23)})
+            // (V+23) / (1 - e^{-.04(V+23)}), at V0 == -23.0f DEFINED as its limit 25 (at23 above; the denominator of THIS form
+            // need not be an exact zero there, so the quotient without the select could be 0 or NaN)
+            const T t2 = vsel(at23, T_of<T>(25.0f), (V0 + 23.0f) * P::rcp(vfma(re, FC(-1.0 / 2.5092903899362979), 1.0f)));
             const T iK1x = vfma(t2, 0.2f, t1);                         // iK1 / 0.35
             const T ix1 = XI * vfma(re, FC(-0.8 / 4.0551999668446745), FC(0.8 * 21.7584023961970 / 4.0551999668446745));   // 0.8 (e*E77 - 1) / (e*E35)
             (void)E23; (void)E35; (void)E77; (void)E85;
@@ -83,7 +89,7 @@
         } else {
             const T iK1 = 0.35f * (P::div(4.0f * (P::exp(0.04f * (V0 + 85.0f)) - 1.0f),
                                           P::exp(0.08f * (V0 + 53.0f)) + P::exp(0.04f * (V0 + 53.0f))) +
-                                   0.2f * P::div(V0 + 23.0f, 1.0f - P::exp(-0.04f * (V0 + 23.0f))));
+                                   0.2f * vsel(at23, T_of<T>(25.0f), P::div(V0 + 23.0f, 1.0f - P::exp(-0.04f * (V0 + 23.0f)))));
             const T ix1 = P::div((XI * 0.8f) * (P::exp(0.04f * (V0 + 77.0f)) - 1.0f), P::exp(0.04f * (V0 + 35.0f)));
             const T iNa = (1.0f * (((((4.0f * M) * M) * M) * H) * J + 0.005f)) * (V0 - 50.0f);
             const T ECa = FC(0.0 - 82.3) - 13.0278f * P::log(C);

@@ -508,7 +508,10 @@ struct BeelerReuter {
         const T e1 = P::exp(c1 * (v + c2));
         const T den = P::exp(c5 * (v + c2)) + c6;
         if (c3 == 0.0f) return P::div(c0 * e1, den);
-        return P::div(c0 * e1 + c3 * (v + c4), den);
+        // the one row with a linear term is alpha_m = -(v + 47) / (exp(-0.1 (v + 47)) - 1): 0/0 at v == -47.0f and there
+        // only, where it is DEFINED as its limit 10 ("op contract": the reference's NaN ends as the clip
+        // floor of M) — a select on the finished quotient, so no other potential changes a bit
+        return vsel(vcmp_eq(v, -c4), T_of<T>(10.0f), P::div(c0 * e1 + c3 * (v + c4), den));
     }
     template <class P, class T>
     static FIB_DEV void inf_tau(const T &a, const T &b, T &inf, T &tau)

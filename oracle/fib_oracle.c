@@ -214,6 +214,10 @@ static inline float br_ab(float v, const float *c)
 {
     if (c[3] == 0.0f)
         return (c[0] * expf(c[1] * (v + c[2]))) / (expf(c[5] * (v + c[2])) + c[6]);
+    /* the one row with a linear term is alpha_m = -(v + 47) / (exp(-0.1 (v + 47)) - 1): 0/0 at v == -47.0f and at no other
+     * float32 potential.  DEFINED there as its limit 10, as the kernels define it ("op contract"): a
+     * departure from the reference, whose NaN a clip turns into the floor of M.                                    */
+    if (v == -c[4]) return 10.0f;
     return (c[0] * expf(c[1] * (v + c[2])) + c[3] * (v + c[4])) / (expf(c[5] * (v + c[2])) + c[6]);
 }
 
@@ -282,9 +286,12 @@ void orc_br_step(int H, int W, double dt, double diff, const float *phi, const f
             }
         }
         /* currents, br.py:150-165 (old gate values) */
+        /* (V+23) / (1 - exp(-0.04 (V+23))) is 0/0 at V0 == -23.0f and nowhere else: DEFINED there as its limit 25, as the
+         * kernels define it ("op contract"; the reference's NaN ends as V = -85 through the clip)   */
+        const float q23 = V0 == -23.0f ? 25.0f : (V0 + 23.0f) / (1.0f - expf(-0.04f * (V0 + 23.0f)));
         const float iK1 = 0.35f * ((4.0f * (expf(0.04f * (V0 + 85.0f)) - 1.0f)) /
                                        (expf(0.08f * (V0 + 53.0f)) + expf(0.04f * (V0 + 53.0f))) +
-                                   0.2f * ((V0 + 23.0f) / (1.0f - expf(-0.04f * (V0 + 23.0f)))));
+                                   0.2f * q23);
         const float ix1 = ((XI * 0.8f) * (expf(0.04f * (V0 + 77.0f)) - 1.0f)) / expf(0.04f * (V0 + 35.0f));
         const float iNa = (1.0f * (((((4.0f * M) * M) * M) * Hg) * J + 0.005f)) * (V0 - 50.0f);
         const float ECa = F(0.0 - 82.3) - 13.0278f * logf(C);
