@@ -33,6 +33,7 @@ WAVE_LINK_DTYPE = np.dtype([('prev', np.int32), ('seed', np.int32), ('overlap', 
 STIM_MODES = ('max', 'add')                                       # enum fibhip_stim_mode, in order
 STIM_SHAPES = ('rect', 'plane')                                   # enum fibhip_stim_shape, in order
 MAX_STIM_ENTRIES, MAX_STIM_PLANES = 64, 8
+MAX_LESION_ENTRIES = 256
 TRIG_EDGES = ('rise', 'fall')                                     # enum fibhip_trig_edge, in order
 TRIG_SITES = ('rect', 'mask')                                     # enum fibhip_trig_site, in order
 TRIG_FIELDS = ('c', 'a', 't', 'n', 'cause', 'fired')              # enum fibhip_trig_field, in order: one row of the log
@@ -134,6 +135,11 @@ class StimEntry(C.Structure):
     _fields_ = [('var', C.c_int), ('mode', C.c_int), ('shape', C.c_int), ('r0', C.c_int), ('r1', C.c_int), ('c0', C.c_int),
                 ('c1', C.c_int), ('v', C.c_float), ('floor', C.c_float), ('plane', C.c_int), ('first', C.c_int), ('period', C.c_int),
                 ('count', C.c_int), ('hold', C.c_int)]
+
+
+class LesionEntry(C.Structure):
+    _fields_ = [('offset', C.c_longlong), ('tick', C.c_int), ('r0', C.c_int), ('r1', C.c_int), ('c0', C.c_int), ('c1', C.c_int),
+                ('reserved', C.c_int)]
 
 
 class TrigSensor(C.Structure):
@@ -258,6 +264,11 @@ SYMBOLS = {
     'fibhip_stim_begin': ([_h, C.c_int, C.POINTER(StimEntry), C.c_int, _fp], C.c_int),
     'fibhip_stim_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_stim_end': ([_h], C.c_int),
+    'fibhip_lesion_begin': ([_h, C.c_int, C.POINTER(LesionEntry), C.c_longlong, _fp], C.c_int),
+    'fibhip_lesion_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_lesion_end': ([_h], C.c_int),
+    'fibhip_lesion_apply': ([_h, _ip, _fp], C.c_int),
+    'fibhip_get_phase': ([_h, _fp], C.c_int),
     'fibhip_trig_begin': ([_h, C.c_int, C.POINTER(TrigSensor), C.POINTER(C.c_ubyte), C.c_int, C.POINTER(TrigRule), C.c_int, _fp, C.c_int,
                            C.c_longlong], C.c_int),
     'fibhip_trig_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
@@ -1186,6 +1197,49 @@ class Stepper:
 
     def stim_end(self):
         self._ck(self._L.fibhip_stim_end(self._h))
+
+    # ---- lesion program (include/fibhip.h fibhip_lesion_*) --------------------------------------------------------
+    def lesion_begin(self, lesions):
+        """attaches a lesion program: `lesions` is a list of (tick, (r0, r1, c0, c1), patch) — the patch a float32
+        [r1 - r0, c1 - c0] array of factors in [0, 1] — applied to the phase field right after tick `tick`, in list order"""
+        arr = (LesionEntry * max(len(lesions), 1))()
+        flat, off = [], 0
+        for i, (tick, box, patch) in enumerate(lesions):
+            r0, r1, c0, c1 = (int(a) for a in box)
+            p = np.ascontiguousarray(patch, np.float32)
+            if p.shape != (r1 - r0, c1 - c0):
+                raise ValueError('lesion_begin: entry %d: a patch of shape %s on the box rows [%d, %d) x columns [%d, %d)' % (i, p.shape, r0, r1, c0, c1))
+            arr[i].offset, arr[i].tick = off, int(tick)
+            arr[i].r0, arr[i].r1, arr[i].c0, arr[i].c1 = r0, r1, c0, c1
+            flat.append(p.ravel())
+            off += p.size
+        packed = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(1), np.float32)
+        self._ck(self._L.fibhip_lesion_begin(self._h, len(lesions), arr, off, packed.ctypes.data_as(_fp)))
+
+    def lesion_count(self):
+        """entries applied since lesion_begin (ticks accepted but not launched yet count)"""
+        k = C.c_longlong()
+        self._ck(self._L.fibhip_lesion_count(self._h, C.byref(k)))
+        return int(k.value)
+
+    def lesion_end(self):
+        self._ck(self._L.fibhip_lesion_end(self._h))
+
+    def lesion_apply(self, box, patch):
+        """one lesion now: phi = max(phi * patch, 1e-5) on the box (r0, r1, c0, c1), the derived planes recomputed around it"""
+        b = np.asarray([int(a) for a in box], np.int32)
+        p = np.ascontiguousarray(patch, np.float32)
+        if b.shape != (4,) or p.shape != (int(b[1] - b[0]), int(b[3] - b[2])):
+            raise ValueError('lesion_apply: a patch of shape %s on the box %s' % (p.shape, tuple(int(a) for a in b)))
+        self._ck(self._L.fibhip_lesion_apply(self._h, b.ctypes.data_as(_ip), p.ctypes.data_as(_fp)))
+        self._fallback_warning()
+
+    def get_phase(self):
+        """the handle's current phase field, float32 [height, width]"""
+        out = np.empty((self.height, self.width), np.float32)
+        self._ck(self._L.fibhip_get_phase(self._h, out.ctypes.data_as(_fp)))
+        self._fallback_warning()
+        return out
 
     # ---- trigger program (include/fibhip.h fibhip_trig_*) ---------------------------------------------------------
     def trig_begin(self, sensors, rules, planes=None, every=1, capacity=4096):

@@ -113,7 +113,7 @@ struct Journal {
 };
 
 // ---- the recorders (record.inc) ----------------------------------------------------------------------------------------
-// Every recorder but the activation recorder and the stimulus program is a Sampler (sampler.hpp): `on`, `every`, `k` — the ticks
+// Every recorder but the activation recorder and the two event-driven programs (stimulus, lesion) is a Sampler (sampler.hpp): `on`, `every`, `k` — the ticks
 // LAUNCHED since it was attached, which recover() rewinds by the ticks it replays — and `cap`.  recorders.hpp lists them in hook
 // order; what they ask of the scheduler is stated in sched.inc.
 
@@ -276,6 +276,24 @@ struct TrigRec : Sampler {
     unsigned *fire;         // device: [cap], bit r: rule r fires after sample s
 };
 
+// lesion program (fibhip_lesion_begin): the second event-driven actuator — its hook writes the PHASE FIELD, not the state.  No
+// Sampler, like StimRec: no launch spans an event tick (lesion_room, a term of sample_room), and lesion_apply_kernel and
+// lesion_prep_kernel go behind the launch that ends one, behind every sample and stimulus of that tick (the last row of
+// RECORDERS: the geometry a lesion leaves belongs to the next tick)
+struct LesionEntry {
+    long long tick;         // applied right after tick `tick` since attach: when k == tick + 1
+    int r0, r1, c0, c1;     // the box
+    size_t off;             // where its patch starts in LesionRec::patches, in floats
+};
+struct LesionRec {
+    bool on;
+    long long k;            // ticks LAUNCHED since the program was attached (recover() rewinds it by the ticks it replays)
+    long long next;         // the tick count (k) of the next event tick, LLONG_MAX: no event left; follows from k and the entries
+                            // alone (lesion_next): set at attach, in lesion_advance and in recover()
+    std::vector<LesionEntry> entries;
+    float *patches;         // device: the patches, packed back to back
+};
+
 // fibhip_trace_begin / _end: the launches in between, each between two HIP events
 struct TraceRec {
     hipEvent_t e0, e1;
@@ -296,6 +314,7 @@ struct fibhip_ctx {
     float *phase3;          // dpy | dpx | q4 | r4 | dpy*r4 | dpx*r4, each `cells` floats
     float *phi_dev;
     bool has_phase;
+    bool phi_floored;       // phi >= 1e-5f everywhere has been checked for the field that stands (lesion_field_ready; set_phase resets it)
     int cur[FIB_MAXVAR];            // which slab holds variable v
     int nxt[FIB_MAXVAR];            // where the tick in flight writes it (valid between edges and commit)
     bool has_consts;
@@ -344,6 +363,7 @@ struct fibhip_ctx {
     BeatRec bt;
     StimRec stim;
     TrigRec trig;
+    LesionRec les;
     std::vector<TraceRec> trace;
     bool tracing;
     // ---- the rest ----

@@ -34,7 +34,7 @@ using namespace fib;
 #include "recorders.hpp"    // the table of the hooks behind a committed launch, in hook order
 #include "tick.inc"         // one tick: pointer tables, rows, edges / interior / commit
 #include "sched.inc"        // when ticks are launched: deferral, multi-tick launches, run-ahead, journal and recovery, fibhip_step
-#include "record.inc"       // activation, electrode, tip, frame, statistics, lead, wave, spectrum and beat recorders; the stimulus program and the trigger program
+#include "record.inc"       // activation, electrode, tip, frame, statistics, lead, wave, spectrum and beat recorders; the stimulus program, the trigger program and the lesion program
 #include "plan.inc"         // build_plan, autotune
 #include "comm.inc"         // the RCCL halo path and fibhip_halo_plan
 // this file: create / destroy, state get / set, pointwise modes, pace / probe / sync / timing, run-time modules, accessors and
@@ -327,6 +327,7 @@ extern "C" int fibhip_set_phase(fibhip_t h, const float *phi)
     FLUSH(h);
     CONFIRM(h);
     if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "set_phase inside an open tick");
+    h->phi_floored = false;
     if (!phi) {
         h->has_phase = false;
         return build_plan(h);

@@ -59,27 +59,32 @@ __global__ void unit_op_kernel(int op, int H, int W, const float *a, const float
 }
 
 // ϕ -> (dpy, dpx, q4, r4) and the fast policy's two products, REFLECT-padded in GLOBAL coordinates (ionic.py:75-80)
+// (one cell of it: lesion_prep_kernel, record_kernels.inc, recomputes the cells around a lesion with the same expression)
+static FIB_DEV void phase_prep_cell(const Geo &g, int y, int x, const float *phi, float *dpy, float *dpx, float *q4, float *r4, float *pyr,
+                                    float *pxr)
+{
+    const int e = y * g.W + x, yg = y + g.row_off;
+    int yn = yg - 1, ys = yg + 1, xw = x - 1, xe = x + 1;
+    if (yn < 0) yn = 1;
+    if (ys > g.Hg - 1) ys = g.Hg - 2;
+    if (xw < 0) xw = 1;
+    if (xe > g.W - 1) xe = g.W - 2;
+    yn = clampi(yn - g.row_off, 0, g.H - 1);
+    ys = clampi(ys - g.row_off, 0, g.H - 1);
+    dpy[e] = phi[ys * g.W + x] - phi[yn * g.W + x];
+    dpx[e] = phi[y * g.W + xe] - phi[y * g.W + xw];
+    q4[e] = 4.0f * phi[e];
+    r4[e] = 1.0f / q4[e];                           // IEEE division: correctly rounded reciprocal
+    if (pyr) {                                      // one rounding each (-ffp-contract=off), as add_phase<Fast> forms them
+        pyr[e] = dpy[e] * r4[e];
+        pxr[e] = dpx[e] * r4[e];
+    }
+}
 __global__ void phase_prep_kernel(Geo g, const float *phi, float *dpy, float *dpx, float *q4, float *r4, float *pyr, float *pxr)
 {
     const int n = g.H * g.W;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
-        const int y = e / g.W, x = e % g.W, yg = y + g.row_off;
-        int yn = yg - 1, ys = yg + 1, xw = x - 1, xe = x + 1;
-        if (yn < 0) yn = 1;
-        if (ys > g.Hg - 1) ys = g.Hg - 2;
-        if (xw < 0) xw = 1;
-        if (xe > g.W - 1) xe = g.W - 2;
-        yn = clampi(yn - g.row_off, 0, g.H - 1);
-        ys = clampi(ys - g.row_off, 0, g.H - 1);
-        dpy[e] = phi[ys * g.W + x] - phi[yn * g.W + x];
-        dpx[e] = phi[y * g.W + xe] - phi[y * g.W + xw];
-        q4[e] = 4.0f * phi[e];
-        r4[e] = 1.0f / q4[e];                       // IEEE division: correctly rounded reciprocal
-        if (pyr) {                                  // one rounding each (-ffp-contract=off), as add_phase<Fast> forms them
-            pyr[e] = dpy[e] * r4[e];
-            pxr[e] = dpx[e] * r4[e];
-        }
-    }
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x)
+        phase_prep_cell(g, e / g.W, e % g.W, phi, dpy, dpx, q4, r4, pyr, pxr);
 }
 
 // pace op, ionic.py:144-163:  pot = max(pot, s), s = v inside the global rectangle, min_v outside

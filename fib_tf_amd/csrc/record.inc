@@ -701,6 +701,110 @@ static void stim_free(fibhip_ctx *h)
     h->stim.on = false;
 }
 
+// The lesions `due` (boxes validated at attach; `patches`: the device buffer their offsets index), applied IN ORDER to the phase
+// field and the derived planes recomputed around them: lesion_apply_kernel, LESION_MAX_DUE entries per launch, then
+// lesion_prep_kernel for the same entries — what the program's hook and fibhip_lesion_apply share.  The launch shape comes
+// from the boxes: entries whose boxes overlap, directly or through others, form a cluster (grid.y; a cell's entries are all in
+// one cluster, which is what keeps their order), grid.x covers the largest cluster's bounding box; the prep launch has one
+// grid.y per entry's dilated box.  A lesion is a few hundred to a few thousand cells: what costs is the two launches.
+static int lesion_launch(fibhip_ctx *h, const std::vector<const LesionEntry *> &due, const float *patches, bool behind_mt)
+{
+    const int H = h->d.height, W = h->d.width;
+    for (int pass = 0; pass < 2; ++pass)
+        for (size_t first = 0; first < due.size(); first += LESION_MAX_DUE) {
+            const int n = (int)(due.size() - first < (size_t)LESION_MAX_DUE ? due.size() - first : (size_t)LESION_MAX_DUE);
+            LesionArgs a;
+            memset(&a, 0, sizeof a);
+            a.n = n;
+            a.give_up = give_up_of(h, behind_mt);
+            int root[LESION_MAX_DUE];
+            for (int i = 0; i < n; ++i) {
+                const LesionEntry &e = *due[first + i];
+                a.e[i].patch = patches + e.off;
+                a.e[i].r0 = e.r0; a.e[i].r1 = e.r1; a.e[i].c0 = e.c0; a.e[i].c1 = e.c1;
+                root[i] = i;
+            }
+            size_t most = 0;
+            if (pass == 0) {
+                // clusters: the classes of "the boxes share a cell" (n <= 8: merged until nothing moves)
+                for (bool moved = true; moved;) {
+                    moved = false;
+                    for (int i = 0; i < n; ++i)
+                        for (int j = 0; j < i; ++j) {
+                            const LesionDue &p = a.e[i], &q = a.e[j];
+                            if (root[i] != root[j] && p.r0 < q.r1 && q.r0 < p.r1 && p.c0 < q.c1 && q.c0 < p.c1) {
+                                const int from = imax(root[i], root[j]), to = imin(root[i], root[j]);
+                                for (int k = 0; k < n; ++k)
+                                    if (root[k] == from) root[k] = to;
+                                moved = true;
+                            }
+                        }
+                }
+                for (int i = 0; i < n; ++i) {
+                    if (root[i] != i) continue;
+                    LesionBox &b = a.box[a.nbox++];
+                    b.r0 = H; b.c0 = W; b.r1 = b.c1 = 0;
+                    for (int k = 0; k < n; ++k)
+                        if (root[k] == i) {
+                            b.r0 = imin(b.r0, a.e[k].r0); b.r1 = imax(b.r1, a.e[k].r1);
+                            b.c0 = imin(b.c0, a.e[k].c0); b.c1 = imax(b.c1, a.e[k].c1);
+                            b.member |= 1u << k;
+                        }
+                }
+            } else {
+                for (int i = 0; i < n; ++i) {
+                    LesionBox &b = a.box[a.nbox++];
+                    b.r0 = imax(a.e[i].r0 - 1, 0); b.r1 = imin(a.e[i].r1 + 1, H);
+                    b.c0 = imax(a.e[i].c0 - 1, 0); b.c1 = imin(a.e[i].c1 + 1, W);
+                }
+            }
+            for (int c = 0; c < a.nbox; ++c) {
+                const size_t area = (size_t)(a.box[c].r1 - a.box[c].r0) * (size_t)(a.box[c].c1 - a.box[c].c0);
+                if (area > most) most = area;
+            }
+            const dim3 grid(blocks_of(most).x, (unsigned)a.nbox);
+            if (pass == 0) {
+                if (int rc = launch_traced(h, "lesion_apply_kernel", 0, [&] {
+                        hipLaunchKernelGGL(lesion_apply_kernel, grid, dim3(256), 0, h->s0, a, h->phi_dev, W);
+                    }))
+                    return rc;
+            } else {
+                const Geo g = base_geo(h);
+                float *p3 = h->phase3;
+                const size_t cells = h->cells;
+                if (int rc = launch_traced(h, "lesion_prep_kernel", 0, [&] {
+                        hipLaunchKernelGGL(lesion_prep_kernel, grid, dim3(256), 0, h->s0, a, g, (const float *)h->phi_dev, p3, p3 + cells,
+                                           p3 + 2 * cells, p3 + 3 * cells, p3 + 4 * cells, p3 + 5 * cells);
+                    }))
+                    return rc;
+            }
+        }
+    return 0;
+}
+// The lesion program's hook behind a launch of `ticks` ticks, the LAST hook of the tick (recorders.hpp says why).  No launch
+// spans an event tick (lesion_room), so the entries due are those of the tick the counter has landed on, in program order.
+// `behind_mt`: as for stim_advance — the apply is handed the give-up word and writes nothing once a launch in front of it gave
+// up; behind a plain tick, which stands behind a confirmed stream, it gets no word.  What is due follows from the host's counter
+// alone: nothing about the program lives on the device but the patches.
+static int lesion_advance(fibhip_ctx *h, int ticks, bool behind_mt)
+{
+    LesionRec &r = h->les;
+    r.k += ticks;
+    if (r.k < r.next) return 0;                                     // (no launch spans an event tick: k lands on it or stays below)
+    std::vector<const LesionEntry *> due;
+    for (const LesionEntry &e : r.entries)
+        if (e.tick + 1 == r.k) due.push_back(&e);
+    r.next = lesion_next(r);
+    if (due.empty()) return 0;
+    return lesion_launch(h, due, r.patches, behind_mt);
+}
+static void lesion_free(fibhip_ctx *h)
+{
+    dev_free(h->les.patches);
+    h->les.entries.clear();
+    h->les.on = false;
+}
+
 static_assert(TRIG_MAX == FIBHIP_MAX_TRIG_SENSORS && TRIG_MAX == FIBHIP_MAX_TRIG_RULES && TRIG_MAX <= STIM_MAX_DUE && TRIG_ROW == FIBHIP_TRIG_ROW &&
                   (int)TRIG_RISE == (int)FIBHIP_TRIG_RISE && (int)TRIG_FALL == (int)FIBHIP_TRIG_FALL && SENSE_MAX_CHUNKS == 4 * 64 &&
                   SENSE_MIN_CHUNK % SENSE_THREADS == 0,
@@ -1962,4 +2066,157 @@ extern "C" int fibhip_trig_end(fibhip_t h)
 {
     NEED(h);
     return detach(h, h->trig.on, trig_free);
+}
+
+// ---- lesion program -----------------------------------------------------------------------------------------------------
+static_assert(LESION_MAX_DUE <= FIBHIP_MAX_LESION_ENTRIES, "lesion_apply_kernel's constants follow include/fibhip.h");
+// what no lesion is applied to: a row block, an open tick, a model without a phase term
+static int lesion_refusals(const fibhip_ctx *h, const char *who)
+{
+    if (int rc = attach_refusals(h, who)) return rc;
+    if (zero_padded(h))
+        return fail(FIBHIP_EINVAL, "%s: not on a model with the zero-padded Laplacian (FIBHIP_ZEROPAD): its diffusion term has no phase field", who);
+    return 0;
+}
+// one lesion's box and factors: the box inside the grid and not empty, every factor finite and in [0, 1]
+static int lesion_check(const fibhip_ctx *h, const char *who, int i, int r0, int r1, int c0, int c1, const float *patch)
+{
+    if (int rc = rect_check(h, r0, r1, c0, c1, "%s: entry %d: ", who, i)) return rc;
+    const size_t n = (size_t)(r1 - r0) * (size_t)(c1 - c0);
+    for (size_t j = 0; j < n; ++j)
+        if (!(patch[j] >= 0.0f && patch[j] <= 1.0f))                // (a NaN fails both compares)
+            return fail(FIBHIP_EINVAL, "%s: entry %d: factor %zu of the patch is %g: every factor is finite and in [0, 1]", who, i, j, (double)patch[j]);
+    return 0;
+}
+// The field a lesion multiplies into: a handle without one is given a field of ones first, through fibhip_set_phase (the kernels
+// switch to their phase variants from then on: the one visible effect of attaching to a model without a field); and the identity
+// with add_hole_to_phase_field's whole-plane update needs phi >= 1e-5f everywhere beforehand — checked once per field
+// (fibhip_set_phase resets the mark).  Behind a FLUSH and a confirmed stream.
+static int lesion_field_ready(fibhip_ctx *h, const char *who)
+{
+    if (!h->has_phase) {
+        const std::vector<float> ones(h->cells, 1.0f);
+        if (int rc = fibhip_set_phase(h, ones.data())) return rc;
+    }
+    if (h->phi_floored) return 0;
+    std::vector<float> phi(h->cells);
+    HIPCHK(hipMemcpyAsync(phi.data(), h->phi_dev, h->cells * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+    HIPCHK(wait_stream(h->s0));
+    for (size_t j = 0; j < h->cells; ++j)
+        if (!(phi[j] >= LESION_FLOOR))
+            return fail(FIBHIP_EINVAL, "%s: the phase field is %g at row %zu, column %zu: a lesion needs a field that is >= 1e-5 everywhere", who,
+                        (double)phi[j], j / (size_t)h->d.width, j % (size_t)h->d.width);
+    h->phi_floored = true;
+    return 0;
+}
+
+extern "C" int fibhip_lesion_begin(fibhip_t h, int n, const fibhip_lesion_entry *entries, long long nfloats, const float *patches)
+{
+    NEED(h);
+    if (!entries || !patches) return fail(FIBHIP_EINVAL, "lesion_begin: null argument");
+    if (n < 1 || n > FIBHIP_MAX_LESION_ENTRIES) return fail(FIBHIP_EINVAL, "lesion_begin: 1 .. %d entries (got %d)", FIBHIP_MAX_LESION_ENTRIES, n);
+    const long long budget = (long long)FIBHIP_MAX_STIM_PLANES * (long long)h->cells;
+    if (nfloats < 1 || nfloats > budget)
+        return fail(FIBHIP_EINVAL, "lesion_begin: 1 .. %lld floats of patches (%d planes of the grid; got %lld)", budget, FIBHIP_MAX_STIM_PLANES, nfloats);
+    if (int rc = lesion_refusals(h, "lesion_begin")) return rc;
+    std::vector<LesionEntry> list;
+    for (int i = 0; i < n; ++i) {
+        const fibhip_lesion_entry &s = entries[i];
+        if (s.tick < 0) return fail(FIBHIP_EINVAL, "lesion_begin: entry %d: tick must be >= 0 (got %d)", i, s.tick);
+        if (s.reserved != 0) return fail(FIBHIP_EINVAL, "lesion_begin: entry %d: the reserved field must be 0 (got %d)", i, s.reserved);
+        if (int rc = rect_check(h, s.r0, s.r1, s.c0, s.c1, "lesion_begin: entry %d: ", i)) return rc;
+        const long long area = (long long)(s.r1 - s.r0) * (long long)(s.c1 - s.c0);
+        if (s.offset < 0 || s.offset + area > nfloats)
+            return fail(FIBHIP_EINVAL, "lesion_begin: entry %d: a patch of %lld floats at offset %lld of %lld", i, area, s.offset, nfloats);
+        if (int rc = lesion_check(h, "lesion_begin", i, s.r0, s.r1, s.c0, s.c1, patches + s.offset)) return rc;
+        LesionEntry e;
+        e.tick = s.tick;
+        e.r0 = s.r0; e.r1 = s.r1; e.c0 = s.c0; e.c1 = s.c1;
+        e.off = (size_t)s.offset;
+        list.push_back(e);
+    }
+    if (h->les.on) return fail(FIBHIP_EINVAL, "lesion_begin: a program is attached already (fibhip_lesion_end first)");
+    // everything accepted so far runs on the old geometry and is confirmed: a multi-tick launch that gave up is recovered HERE,
+    // before tick k = 0 is defined (the rule of fibhip_electrode_begin)
+    FLUSH(h);
+    CONFIRM(h);
+    SYNC_S0(h);
+    if (int rc = lesion_field_ready(h, "lesion_begin")) return rc;
+    lesion_free(h);
+    const size_t bytes = (size_t)nfloats * sizeof(float);
+    if (hipMalloc((void **)&h->les.patches, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->les.patches = nullptr;
+        return fail(FIBHIP_ENOMEM, "lesion_begin: hipMalloc of %lld floats of patches failed", nfloats);
+    }
+    HIPCHK(hipMemcpyAsync(h->les.patches, patches, bytes, hipMemcpyHostToDevice, h->s0));
+    HIPCHK(wait_stream(h->s0));                        // the caller's patches are free again
+    h->les.entries.swap(list);
+    h->les.k = 0;
+    h->les.next = lesion_next(h->les);
+    h->les.on = true;
+    return 0;
+}
+
+extern "C" int fibhip_lesion_count(fibhip_t h, long long *applied)
+{
+    NEED(h);
+    if (!applied) return fail(FIBHIP_EINVAL, "lesion_count: null argument");
+    if (!h->les.on) return fail(FIBHIP_EINVAL, "lesion_count: no program attached (fibhip_lesion_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its events)
+    const long long k = h->les.k + h->pending;         // (ticks accepted but not launched yet get their events when they are)
+    long long total = 0;
+    for (const LesionEntry &e : h->les.entries) total += e.tick + 1 <= k;
+    *applied = total;
+    return 0;
+}
+
+extern "C" int fibhip_lesion_end(fibhip_t h)
+{
+    NEED(h);
+    return detach(h, h->les.on, lesion_free);
+}
+
+// One lesion NOW, at the state the caller has reached — with or without a program, beside every recorder: what a host-side
+// closed loop uses (read the tips, ablate there).  The pending ticks run on the old geometry first and are confirmed (a host
+// write never stands behind an unconfirmed launch: the rule above confirm()), so the kernels get no give-up word.
+extern "C" int fibhip_lesion_apply(fibhip_t h, const int *box, const float *patch)
+{
+    NEED(h);
+    if (!box || !patch) return fail(FIBHIP_EINVAL, "lesion_apply: null argument");
+    if (int rc = lesion_refusals(h, "lesion_apply")) return rc;
+    if (int rc = lesion_check(h, "lesion_apply", 0, box[0], box[1], box[2], box[3], patch)) return rc;
+    FLUSH(h);
+    CONFIRM(h);
+    if (int rc = lesion_field_ready(h, "lesion_apply")) return rc;
+    LesionEntry e;
+    e.tick = 0;
+    e.r0 = box[0]; e.r1 = box[1]; e.c0 = box[2]; e.c1 = box[3];
+    e.off = 0;
+    const size_t bytes = (size_t)(e.r1 - e.r0) * (size_t)(e.c1 - e.c0) * sizeof(float);
+    float *dev = nullptr;
+    if (hipMalloc((void **)&dev, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FIBHIP_ENOMEM, "lesion_apply: hipMalloc of %zu bytes failed", bytes);
+    }
+    int rc = hipMemcpyAsync(dev, patch, bytes, hipMemcpyHostToDevice, h->s0) == hipSuccess ? 0 : fail(FIBHIP_EHIP, "lesion_apply: the upload failed");
+    if (!rc) rc = lesion_launch(h, std::vector<const LesionEntry *>(1, &e), dev, false);
+    if (!rc) rc = sync_s0(h);
+    else (void)hipStreamSynchronize(h->s0);
+    hipFree(dev);
+    return rc;
+}
+
+// the current phase field as [H][W].  A reader: it synchronises behind its copy and takes the copy again when a recovery
+// happened in between (the events of the replayed ticks are applied again by then)
+extern "C" int fibhip_get_phase(fibhip_t h, float *dst)
+{
+    NEED(h);
+    if (!dst) return fail(FIBHIP_EINVAL, "get_phase: null destination");
+    if (!h->has_phase) return fail(FIBHIP_EINVAL, "get_phase: the handle has no phase field (fibhip_set_phase)");
+    FLUSH(h);
+    return read_confirmed(h, [&] {
+        HIPCHK(hipMemcpyAsync(dst, h->phi_dev, h->cells * sizeof(float), hipMemcpyDeviceToHost, h->s0));
+        return 0;
+    });
 }

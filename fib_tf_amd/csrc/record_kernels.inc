@@ -1863,3 +1863,79 @@ __global__ void __launch_bounds__(256) wave_link_pack_kernel(const unsigned long
         rec[rank] = w;
     }
 }
+
+// ---- lesion program (fibhip_lesion_begin, fibhip_lesion_apply): the hook that writes the PHASE FIELD, not the state ----------
+// A lesion is a float32 factor patch m on a box [r0, r1) x [c0, c1): phi = fmaxf(phi * m, 1e-5f) on the cells of the box — one
+// multiplication rounded on its own (-ffp-contract=off) and one maximum, add_hole_to_phase_field's update restricted to the
+// cells where its mask is not 1.0f.  The entries due after one tick — at most LESION_MAX_DUE per launch, the host issues further
+// launches in program order beyond that — travel BY VALUE in the kernel argument (stim_kernel's note: every field is
+// wave-uniform).  The product does not commute with the floor, so a cell takes the entries that hold it IN PROGRAM ORDER: the
+// host has put entries whose boxes overlap, directly or through others, into one CLUSTER (two entries of different clusters
+// share no cell and commute); grid.y is the cluster, grid.x covers the bounding box of the largest one, one cell per thread, and
+// a thread walks the entries of its cluster (`member`, a bit per entry) in order with the cell in a register.  It loads phi
+// once and stores it once, and only if an entry held the cell: the bounding box of a cluster may reach into another cluster's
+// cells, which are that cluster's to write.  Only the boxes are visited, never the grid.  The patches are plain cached loads,
+// the store a plain vector store; no LDS, no atomics.  `give_up`: the give-up word of the multi-tick launches (null behind a
+// plain tick and in fibhip_lesion_apply, which confirm first) — once a launch in front gave up this kernel writes NOTHING, so
+// the field that launch started from is intact when recover() replays its ticks and applies the events of those ticks again.
+#define LESION_MAX_DUE 8
+struct LesionDue {
+    const float *patch;     // the factors, [r1 - r0][c1 - c0]
+    int r0, r1, c0, c1;
+};
+struct LesionBox {
+    int r0, r1, c0, c1;
+    unsigned member;        // apply: bit i — entry i belongs to this cluster
+};
+struct LesionArgs {
+    LesionDue e[LESION_MAX_DUE];
+    LesionBox box[LESION_MAX_DUE];  // apply: the clusters' bounding boxes; prep: the entries' boxes dilated by one cell, cut at the grid
+    int n, nbox;
+    const unsigned *give_up;
+};
+#define LESION_FLOOR 1e-5f
+
+__global__ void __launch_bounds__(256) lesion_apply_kernel(LesionArgs a, float *__restrict__ phi, int W)
+{
+    if (a.give_up && *a.give_up != 0u) return;                        // (wave-uniform: one scalar load)
+    LesionBox b = a.box[0];
+#pragma unroll
+    for (int i = 1; i < LESION_MAX_DUE; ++i)
+        if ((int)blockIdx.y == i) b = a.box[i];                       // (no run-time index into the argument)
+    const int bw = b.c1 - b.c0;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)(b.r1 - b.r0) * (size_t)bw) return;
+    const int y = b.r0 + (int)(t / (size_t)bw), x = b.c0 + (int)(t % (size_t)bw);
+    const size_t at = (size_t)y * (size_t)W + (size_t)x;
+    float p = phi[at];
+    bool held = false;
+#pragma unroll
+    for (int i = 0; i < LESION_MAX_DUE; ++i) {
+        if (i >= a.n || !((b.member >> i) & 1u)) continue;            // (wave-uniform)
+        const LesionDue &d = a.e[i];
+        if (y >= d.r0 && y < d.r1 && x >= d.c0 && x < d.c1) {
+            const float m = d.patch[(size_t)(y - d.r0) * (size_t)(d.c1 - d.c0) + (size_t)(x - d.c0)];
+            p = fmaxf(p * m, LESION_FLOOR);
+            held = true;
+        }
+    }
+    if (held) phi[at] = p;
+}
+
+// The six derived planes (dpy, dpx, q4, r4, dpy*r4, dpx*r4) on the boxes dilated by one cell and cut at the grid, from the new
+// phi: phase_prep_kernel's own expression and reflection (phase_prep_cell), one cell per thread, grid.y the box.  A launch of
+// its own BEHIND lesion_apply_kernel: a cell reads its neighbours' phi, which other threads have just written.  It is a pure
+// function of phi — idempotent — so it needs no gate: behind an apply that wrote nothing it rewrites the values that stand
+// there, and two dilated boxes that overlap write the same values twice.
+__global__ void __launch_bounds__(256) lesion_prep_kernel(LesionArgs a, Geo g, const float *phi, float *dpy, float *dpx, float *q4, float *r4,
+                                                          float *pyr, float *pxr)
+{
+    LesionBox b = a.box[0];
+#pragma unroll
+    for (int i = 1; i < LESION_MAX_DUE; ++i)
+        if ((int)blockIdx.y == i) b = a.box[i];
+    const int bw = b.c1 - b.c0;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)(b.r1 - b.r0) * (size_t)bw) return;
+    phase_prep_cell(g, b.r0 + (int)(t / (size_t)bw), b.c0 + (int)(t % (size_t)bw), phi, dpy, dpx, q4, r4, pyr, pxr);
+}

@@ -9,24 +9,44 @@
 
 typedef int recorder_advance_fn(fibhip_ctx *h, int ticks, bool behind_mt);
 typedef void recorder_free_fn(fibhip_ctx *h);
+typedef bool recorder_on_fn(const fibhip_ctx *h);
+typedef void recorder_rewind_fn(fibhip_ctx *h, int lost);
 struct Recorder {
     const char *noun;                   // what sampler_full calls it
-    size_t sampler;                     // where its Sampler lives in the handle; NO_SAMPLER: the stimulus program, driven by events
+    size_t sampler;                     // where its Sampler lives in the handle; NO_SAMPLER: an event-driven row (the two programs)
     recorder_advance_fn *advance;       // the hook behind a launch of `ticks` ticks
     recorder_free_fn *release;          // frees its device buffers and detaches it
+    // event-driven rows only (a Sampler answers both itself): is it attached, and the rewind of a recovery — the counter goes
+    // back by the ticks the replay takes again and `next` is formed afresh from it
+    recorder_on_fn *on = nullptr;
+    recorder_rewind_fn *rewind = nullptr;
 };
 constexpr size_t NO_SAMPLER = ~(size_t)0;
 
-static recorder_advance_fn electrode_advance, tips_advance, frames_advance, stats_advance, leads_advance, waves_advance, spectrum_advance, beats_advance, stim_advance, trig_advance;
-static recorder_free_fn electrode_free, tips_free, frames_free, stats_free, leads_free, waves_free, spectrum_free, beats_free, stim_free, trig_free;
+static recorder_advance_fn electrode_advance, tips_advance, frames_advance, stats_advance, leads_advance, waves_advance, spectrum_advance, beats_advance, stim_advance, trig_advance, lesion_advance;
+static recorder_free_fn electrode_free, tips_free, frames_free, stats_free, leads_free, waves_free, spectrum_free, beats_free, stim_free, trig_free, lesion_free;
 static long long stim_next(const StimRec &r);                   // sched.inc
+static long long lesion_next(const LesionRec &r);               // sched.inc
+static inline bool stim_on(const fibhip_ctx *h) { return h->stim.on; }
+static inline bool lesion_on(const fibhip_ctx *h) { return h->les.on; }
+static inline void stim_rewind(fibhip_ctx *h, int lost)
+{
+    h->stim.k -= lost;
+    h->stim.next = stim_next(h->stim);
+}
+static inline void lesion_rewind(fibhip_ctx *h, int lost)
+{
+    h->les.k -= lost;
+    h->les.next = lesion_next(h->les);
+}
 
 // (`on` is the Sampler's first member; the handle holds vectors, which is all that makes offsetof conditionally supported here)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winvalid-offsetof"
 #define SAMPLER_AT(member) offsetof(fibhip_ctx, member.on)
 // The ORDER is the order of the launches behind a tick and is load-bearing: the samplers see the state as the tick left it; the
-// stimulus belongs to the next tick and comes behind them; the trigger program senses what the stimulus left and fires last.
+// stimulus belongs to the next tick and comes behind them; the trigger program senses what the stimulus left and fires; the lesion program
+// changes the geometry for the next tick, behind everything that looks at this one.
 // Behind a multi-tick launch every hook stands UNCONFIRMED (behind_mt), and a recovery rewinds every counter by the ticks it
 // replays — the slot is the host's counter, so the replay fills the same slots again.  Why each row may be rewound:
 static constexpr Recorder RECORDERS[] = {
@@ -61,13 +81,23 @@ static constexpr Recorder RECORDERS[] = {
     // it WRITES the state, the slab the launch wrote: stim_kernel reads the give-up word first, so the state the first lost
     // launch started from stays intact; the replay applies the events of the replayed ticks again, and no others — the events
     // of older ticks stand in the restored state.  Its rewind recomputes `next` (recorders_rewind)
-    {"stimulus", NO_SAMPLER, stim_advance, stim_free},
+    {"stimulus", NO_SAMPLER, stim_advance, stim_free, stim_on, stim_rewind},
     // its automaton's state is the log itself, row s a pure function of row s - 1 and the state.  The rows the lost samples
     // wrote were made from a void slab, and the gated apply behind them wrote nothing (it reads the give-up word first).  The
     // replay rewrites those rows IN ORDER, each from a predecessor that is older than the lost launch (good: trig_begin
     // confirms before it attaches) or has just been rewritten: no detection lost, none doubled, and a delay or a train that
     // straddles the lost launch goes on as in the untouched run
     {"trigger", SAMPLER_AT(trig), trig_advance, trig_free},
+    // the lesion program, LAST: the geometry a lesion leaves belongs to the next tick, so every sample of the event tick — the
+    // lead recorder's, whose source term reads the handle's phase planes, included — and every stimulus of it sees the geometry
+    // the tick was computed with.  It WRITES the phase field, which no tick writes; the stimulus row's argument carries over:
+    // lesion_apply_kernel reads the give-up word first, so the field the first lost launch started from stays intact — every
+    // launch behind the one that gave up left without writing, and so did every lesion queued behind those; an event OLDER than
+    // the first lost launch stands in the field and is not applied again, because what is due follows from `k` alone and `next`
+    // is formed afresh from the rewound `k` (lesion_rewind); the replay, plain ticks behind a confirmed stream, applies the
+    // events of the replayed ticks again, in order, and no others.  lesion_prep_kernel is ungated: it is a pure function of phi
+    // (idempotent), and behind an apply that wrote nothing it rewrites the values that stand there
+    {"lesion", NO_SAMPLER, lesion_advance, lesion_free, lesion_on, lesion_rewind},
 };
 #undef SAMPLER_AT
 #pragma clang diagnostic pop
@@ -80,7 +110,7 @@ static inline const Sampler *sampler_of(const fibhip_ctx *h, const Recorder &r) 
 static inline bool attached(const fibhip_ctx *h, const Recorder &r)
 {
     const Sampler *s = sampler_of(h, r);
-    return s ? s->on : h->stim.on;
+    return s ? s->on : r.on(h);
 }
 
 // the hooks behind a launch of `ticks` ticks the handle's state has moved with.  `behind_mt`: that launch is a multi-tick launch
@@ -104,8 +134,7 @@ static void recorders_rewind(fibhip_ctx *h, int lost)
         if (Sampler *s = sampler_of(h, r)) {
             s->rewind(lost);
         } else {
-            h->stim.k -= lost;
-            h->stim.next = stim_next(h->stim);
+            r.rewind(h, lost);
         }
     }
 }

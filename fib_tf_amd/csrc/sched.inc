@@ -80,12 +80,12 @@ static int sync_s0(fibhip_ctx *h)
 // gave up leaves the state it started from intact only as long as whatever follows it writes nothing — multi-tick launches find
 // the give-up word and leave; a plain tick, a pace, a host write would not.  So those wait for the stream first.
 // The entry points that confirm, each right behind its flush: fibhip_set_phase, fibhip_set_state, fibhip_set_consts,
-// fibhip_pace, fibhip_step_mode (every branch: a pointwise update is in place), fibhip_step_edges, fibhip_state_ptr (the
+// fibhip_pace, fibhip_lesion_apply, fibhip_step_mode (every branch: a pointwise update is in place), fibhip_step_edges, fibhip_state_ptr (the
 // pointer must name the slab the state is in AFTER a recovery, and the caller writes through it), fibhip_trace_begin (every
 // traced tick is a plain launch) — and inside the scheduler tick_mt for a launch of one tick and fibhip_step in front of its
 // plain launches.  The entry points that only READ synchronise behind their copy (sync_s0) and take the copy again when a
 // recovery happened in between: fibhip_get_state, fibhip_get_state_direct (both branches of ahead_read_back hand the frame
-// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read, fibhip_frames_read, fibhip_stats_read, fibhip_leads_read, fibhip_waves_read / _labels, fibhip_spectrum_read / _peak, fibhip_beats_read / _summary; fibhip_observe_begin,
+// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read, fibhip_frames_read, fibhip_stats_read, fibhip_leads_read, fibhip_waves_read / _labels, fibhip_spectrum_read / _peak, fibhip_beats_read / _summary, fibhip_get_phase; fibhip_observe_begin,
 // fibhip_electrode_begin / _end, fibhip_tips_begin / _end, fibhip_frames_begin / _end, fibhip_stats_begin / _end, fibhip_leads_begin / _end, fibhip_waves_begin / _end, fibhip_spectrum_begin / _end and fibhip_beats_begin / _end synchronise
 // outright.
 static int confirm(fibhip_ctx *h)
@@ -179,17 +179,25 @@ static const Variant *mt_variant(const fibhip_ctx *h, bool long_declared = false
 //    before_slow, set at attach — is taken before 'slow' rides on its tick (slow_sample_due); one that has no slot left refuses further
 //    ticks (sampler_full; the spectrum and the beat recorder never fill up, their cap is LLONG_MAX).  On a shared tick the
 //    samples go out in the table's order, behind a multi-tick launch unconfirmed (recorders_advance);
-//  * the stimulus program (h->stim.on), the one row without a Sampler and the one hook that WRITES the state on the host's
+//  * the stimulus program (h->stim.on), a row without a Sampler and the one hook that WRITES the state on the host's
 //    word: no launch spans an event tick (stim_room, one more
 //    term of sample_room), and while events are still to come a launch goes out when the ticks up to the next one are waiting
 //    (cutting); nothing runs ahead while a program is attached (may_run_ahead: a stimulus cannot be queued behind a launch that
 //    may be stopped or recomputed); a tick with an event due is never fused with the 'slow' behind it, whatever array the event
 //    names — the stimulus comes right after its tick (slow_sample_due).  The stimulus is queued behind its launch WITHOUT
 //    confirming it: stim_kernel writes nothing once a launch in front of it gave up (the rule above confirm());
-//  * the trigger program, the last row: a sampler like the others (launches are cut at its samples and nothing runs ahead)
+//  * the trigger program, the last row that writes the STATE: a sampler like the others (launches are cut at its samples and nothing runs ahead)
 //    whose sample also WRITES the state: sense, decide and the gated apply come behind the programmed stimuli of the tick,
 //    unconfirmed like them (the gated apply reads the give-up word first); every sample tick comes before the 'slow' behind it
-//    (its before_slow is always true), whatever arrays it names.
+//    (its before_slow is always true), whatever arrays it names;
+//  * the lesion program (h->les.on), the LAST row of the table, the other row without a Sampler and the one hook that writes the PHASE FIELD: it asks what
+//    the stimulus program asks — no launch spans an event tick (lesion_room, one more term of sample_room); while events are
+//    still to come a launch goes out when the ticks up to the next one are waiting (cutting); nothing runs ahead while a program
+//    is attached (may_run_ahead, and the first-tick series launch of fibhip_step); the lesion is queued behind its launch
+//    WITHOUT confirming it, lesion_apply_kernel writes nothing once a launch in front of it gave up.  One thing it does NOT ask:
+//    a tick with a lesion due MAY be fused with the 'slow' behind it (slow_sample_due does not look at the program) — 'slow' is
+//    pointwise and never reads the geometry, so tick, slow, lesion leaves the bytes of tick, lesion, slow, and not asking is
+//    the simpler of the two.  A handle without a lesion program launches exactly as before: every term here is INT_MAX or false.
 // (sample_room and cutting are on fibhip_step's per-call path: they read the Samplers through the rows' offsets and call nothing)
 static inline bool sampling(const fibhip_ctx *h)
 {
@@ -242,16 +250,31 @@ static inline int stim_room(const fibhip_ctx *h)
     const long long room = h->stim.next - h->stim.k;
     return room < (long long)INT_MAX ? (int)room : INT_MAX;
 }
-// ... and of any attached sampler, and of the stimulus program: no launch may span one
+// the lesion program's next event tick (LLONG_MAX: no event left) behind the r.k ticks launched so far: an entry is applied when
+// k == tick + 1.  Kept in LesionRec::next like the stimulus program's: asked at attach, in lesion_advance and in recover()
+static long long lesion_next(const LesionRec &r)
+{
+    long long best = LLONG_MAX;
+    for (const LesionEntry &e : r.entries)
+        if (e.tick + 1 > r.k && e.tick + 1 < best) best = e.tick + 1;
+    return best;
+}
+static inline int lesion_room(const fibhip_ctx *h)
+{
+    if (!h->les.on || h->les.next == LLONG_MAX) return INT_MAX;
+    const long long room = h->les.next - h->les.k;
+    return room < (long long)INT_MAX ? (int)room : INT_MAX;
+}
+// ... and of any attached sampler, and of the two programs: no launch may span one
 static inline int sample_room(const fibhip_ctx *h)
 {
-    int room = stim_room(h);
+    int room = imin(stim_room(h), lesion_room(h));
     for (const Recorder &r : RECORDERS)
         if (r.sampler != NO_SAMPLER) room = imin(room, sampler_of(h, r)->room());
     return room;
 }
 // launches are cut at ticks still to come: a launch goes out when the ticks up to the next cut are waiting (fibhip_step)
-static inline bool cutting(const fibhip_ctx *h) { return sampling(h) || stim_room(h) != INT_MAX; }
+static inline bool cutting(const fibhip_ctx *h) { return sampling(h) || stim_room(h) != INT_MAX || lesion_room(h) != INT_MAX; }
 // consecutive ticks one plain launch may fuse (Courtemanche on aggregates: up to multi_max; one while an activation recorder
 // is attached; never across a sample tick)
 static inline int multi_cap(const fibhip_ctx *h) { return h->obs.on ? 1 : imin(h->multi_max, sample_room(h)); }
@@ -522,7 +545,7 @@ static bool may_run_ahead(const fibhip_ctx *h, int L, bool repeats, bool declare
     if (L < 2 || L > launch_cap(h, declared)) return false;
     // nothing forbids it: the switch and the caller's access to the state (Ahead::ok), no launch ahead already, no sampler
     // (see "what the recorders ask of the scheduler"), no timeline being taken (every launch there is the caller's own)
-    if (!h->ahead.ok || h->ahead.n != 0 || sampling(h) || h->stim.on || h->tracing) return false;
+    if (!h->ahead.ok || h->ahead.n != 0 || sampling(h) || h->stim.on || h->les.on || h->tracing) return false;
     // the launch is the one the handle would make anyway: its plan is chosen (`tuned`, which is only ever set behind
     // check_ready — so has_consts holds with it and is stated for the reader, not tested twice), the slab is planar.
     // Nothing accepted is still waiting and no tick is open: fibhip_step refuses an open tick and tests `pending` here; at the
@@ -809,7 +832,7 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
         return fail(FIBHIP_EINVAL, "step: trace full (the %s recorder holds %lld samples; read it, then detach or re-attach)", who, full_cap);
     if (int rc = journal_bound(h)) return rc;
     // (the guards in front are may_run_ahead's own, taken first because most calls end at one of them)
-    if (nticks > 0 && h->ahead.n == 0 && h->mt.max > 1 && !sampling(h) && !h->stim.on) {
+    if (nticks > 0 && h->ahead.n == 0 && h->mt.max > 1 && !sampling(h) && !h->stim.on && !h->les.on) {
         bool repeats = false;
         const bool declared = h->series.expect > 0;
         int L = 0;
@@ -843,7 +866,7 @@ extern "C" int fibhip_step(fibhip_t h, int nticks)
             h->pending += nticks;
             // (a call that goes past the end of its declaration leaves undeclared ticks behind the declared ones: none counts)
             h->series.covered = covered == nticks ? h->series.covered + covered : 0;
-            // With a sampler attached (or a stimulus program with events to come) a launch goes out when the ticks up to the next sample tick are waiting (or mt.max of
+            // With a sampler attached (or a stimulus or lesion program with events to come) a launch goes out when the ticks up to the next sample tick are waiting (or mt.max of
             // them) and ends there: between two samples the handle runs the fewest launches `every` allows, whatever the
             // caller's call pattern.  (Without one: mt.cur, as described above.)
             while (h->pending >= (cutting(h) ? imin(sample_room(h), launch_cap(h, pending_declared(h))) : h->mt.cur)) {

@@ -388,6 +388,35 @@ class IonicModel:
             ensure()
         return StimulusProgram(self, stimuli)
 
+    def program_lesions(self, lesions):
+        """attaches a lesion program (fib_tf_amd/lesions.py) to this model's handle: a list of `Lesion` entries — a site
+        (('disc', row, col, radius), ('line', r0, c0, r1, c1, halfwidth) or a plane of factors) and the tick (or millisecond)
+        after which it is burnt — that the library multiplies into the phase field on the device, each right after its tick,
+        while every recorder and both stimulus programs stay attached; `drag` draws a catheter along a path.  Tick 0 is the
+        first tick after this call.  The state is not touched: cells inside a lesion go on with their own kinetics, uncoupled
+        from the tissue, as cells inside a hole do.  A model without a phase field gets a field of ones.  On end() / __exit__
+        `model.phase` becomes the field as it now is.  Call after define(); single device only (row blocks raise
+        NotImplementedError); a model with the zero-padded Laplacian is refused."""
+        from .lesions import LesionProgram
+        if not self.defined:
+            raise AssertionError('program_lesions should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
+        if ensure is not None:
+            ensure()
+        return LesionProgram(self, lesions)
+
+    def ablate(self, site):
+        """one lesion NOW, at the state the loop has reached (the immediate form of program_lesions: what a host-side closed
+        loop uses — read rec.tips(), then ablate there).  Works with or without a program, beside every recorder; updates
+        `model.phase` to the field as it now is.  Returns the box (r0, r1, c0, c1) that was visited."""
+        from .lesions import ablate
+        if not self.defined:
+            raise AssertionError('ablate should be called after calling define')
+        ensure = getattr(self, '_ensure_compiled', None)
+        if ensure is not None:
+            ensure()
+        return ablate(self, site)
+
     def trigger_stimuli(self, rules, every=1, capacity=None):
         """attaches a trigger program (fib_tf_amd/triggers.py) to this model's handle: a list of `Trigger` rules — a `Sensor`
         (a site, a level, the cells that must be above it), an edge ('rise': an arrival, 'fall': the waveback), a delay, a

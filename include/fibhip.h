@@ -871,6 +871,59 @@ int fibhip_trig_count(fibhip_t h, long long *samples);
 int fibhip_trig_read(fibhip_t h, long long first, long long count, int *dst /* [count][nrules][6] */);
 int fibhip_trig_end(fibhip_t h);
 
+/* Lesion program: the tissue's geometry changed during a run, on the device — ablating a rotor's core, drawing a line of block,
+ * isolating a region — while every recorder and both stimulus programs stay attached.  The second event-driven program: its
+ * hook writes the PHASE FIELD instead of the state.  The definition is exact (no tolerance anywhere; restated in NumPy in
+ * tests/lesion_ref.py; the device equals that bit for bit).
+ * A lesion is a float32 factor patch m on a box [r0, r1) x [c0, c1) of the grid.  Applying it is
+ *     phi[r][c] = fmaxf(phi[r][c] * m[r - r0][c - c0], 1e-5f)       for the cells of the box
+ * in plain float32 (one multiplication, one maximum, nothing contracted), followed by the six derived planes (dpy, dpx, 4 phi,
+ * 1 / (4 phi), dpy / (4 phi), dpx / (4 phi)) recomputed, with fibhip_set_phase's arithmetic and reflection, on the box dilated
+ * by one cell and cut at the grid.  This is add_hole_to_phase_field's update (ionic.py:83-105) restricted to the cells where its
+ * mask is not exactly 1.0f; the identity needs phi >= 1e-5f everywhere beforehand, which attaching checks.
+ * Event ticks.  With k = ticks since lesion_begin (the first tick after it is k = 0), entry e is applied right after tick e.tick:
+ * where `for i in m.run(): if i == e.tick: ...` stands, and where the stimulus program puts a stimulus with first = e.tick.  A
+ * run with a lesion after tick i EQUALS: run i + 1 ticks, read the state, create a handle whose phase field is the old one with
+ * the same lesion applied on the host, set the state, run the remaining ticks.  Entries due after the same tick are applied IN
+ * PROGRAM ORDER, each with its own floor (float32 products do not commute with the floor).
+ * The state is not touched: cells inside a lesion go on with their own kinetics, uncoupled from the tissue, exactly as cells
+ * inside a hole of the reference do.
+ * Order on a tick.  The lesion comes LAST, behind every recorder's sample and every stimulus of that tick: the geometry it leaves
+ * belongs to the next tick, and every sample of the event tick — the lead recorder's, whose source term reads the handle's phase
+ * planes, included — sees the geometry the tick was computed with.  Planes a recorder was handed at attach (weights, masks) stay
+ * what they were.  Courtemanche: a tick with a lesion due MAY be fused with the fibhip_step_slow behind it — 'slow' is pointwise
+ * and never reads the geometry, so the bytes are the same.
+ * Launches.  No launch spans an event tick; while events are still to come a launch goes out when the ticks up to the next one
+ * are waiting, and nothing runs ahead of the caller while a program is attached.  The two kernels are queued on the handle's
+ * stream behind the launch that ends at the event tick; nothing waits for them.  A multi-tick launch that gives up is recovered
+ * as ever: a lesion queued behind it wrote nothing, an older one stands, and the replay applies the lost ones again, once.
+ * A handle WITHOUT a phase field is given a field of ones first (through fibhip_set_phase): its kernels are the phase variants
+ * from then on — the one visible effect of attaching to such a handle.
+ * Refused: a row block (a handle with ghost rows), a handle with the zero-padded Laplacian (FIBHIP_ZEROPAD: no phase term), an
+ * open tick, an empty box or one outside the grid, a factor that is not finite or not in [0, 1], tick < 0, reserved != 0, an offset outside the
+ * patches, n or nfloats out of range (1 .. FIBHIP_MAX_LESION_ENTRIES entries, up to FIBHIP_MAX_STIM_PLANES * height * width
+ * floats of patches), a second lesion_begin without a lesion_end, a phase field below 1e-5f somewhere.
+ *   fibhip_lesion_begin  flushes, confirms and synchronises pending work, copies the patches and attaches
+ *   fibhip_lesion_count  the number of entries applied so far (ticks accepted but not launched yet count: their events are
+ *                        applied when they are)
+ *   fibhip_lesion_end    flushes, synchronises, detaches and frees (no program attached: nothing); fibhip_destroy frees too
+ *   fibhip_lesion_apply  ONE lesion now, at the state the caller has reached: flushes, confirms, uploads, the same two kernels,
+ *                        synchronises.  With or without a program, beside every recorder: what a host-side closed loop uses
+ *                        (read the tips, ablate there).  box = {r0, r1, c0, c1}, patch [r1 - r0][c1 - c0]
+ *   fibhip_get_phase     the current phase field as [height][width]; refused on a handle that has none                          */
+#define FIBHIP_MAX_LESION_ENTRIES 256
+typedef struct fibhip_lesion_entry {
+    long long offset;           /* where the entry's patch [r1 - r0][c1 - c0] starts in `patches`, in floats */
+    int tick;
+    int r0, r1, c0, c1;
+    int reserved;               /* 0 */
+} fibhip_lesion_entry;
+int fibhip_lesion_begin(fibhip_t h, int n, const fibhip_lesion_entry *entries, long long nfloats, const float *patches /* [nfloats] */);
+int fibhip_lesion_count(fibhip_t h, long long *applied);
+int fibhip_lesion_end(fibhip_t h);
+int fibhip_lesion_apply(fibhip_t h, const int *box /* [4] */, const float *patch);
+int fibhip_get_phase(fibhip_t h, float *dst /* [height*width] */);
+
 const char *fibhip_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)
