@@ -541,8 +541,12 @@ def court_inter(V, fast=False, device=0):
     return {k: out[i].reshape(v.shape) for i, k in enumerate(COURT_INTER_KEYS)}
 
 
-class Stepper:
-    """One fibhip handle: a grid (or a row block of it) resident on one MI355X."""
+from ._stepper_record import RecorderBindings           # noqa: E402  (down here: it imports the structs and constants above)
+
+
+class Stepper(RecorderBindings):
+    """One fibhip handle: a grid (or a row block of it) resident on one MI355X.  The recorder and program bindings
+    (observe_*, electrode_*, ... trig_*, lesion_*, get_phase) are in _stepper_record.py."""
 
     def __init__(self, model, height, width, dt, diff, flags=0, device=0, steps_per_tick=0,
                  global_height=0, row_offset=0, ghost_top=0, ghost_bottom=0, stream=None, ext_slabs=None,
@@ -773,538 +777,3 @@ class Stepper:
         grid whose tiles are all resident at once: FIBHIP_MT_MAX, default 32, and 256 while a series of 128 ticks or more
         declared with expect() is running; otherwise 1)"""
         return self._ck(self._L.fibhip_ticks_per_launch(self._h))
-
-    # ---- activation recorder (include/fibhip.h fibhip_observe_*) --------------------------------------------------
-    def observe_begin(self, var, up, down):
-        """attaches (or re-attaches, clearing the maps) the per-cell activation recorder on array `var`"""
-        self._ck(self._L.fibhip_observe_begin(self._h, int(var), float(up), float(down)))
-
-    def observe_get(self, which):
-        """one map as a [height, width] array: 'first_up', 'last_up', 'prev_up', 'apd' (float32) or 'count' (int32)"""
-        k = OBS_MAPS.index(which)
-        out = np.empty((self.height, self.width), np.int32 if which == 'count' else np.float32)
-        self._ck(self._L.fibhip_observe_get(self._h, k, out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def observe_ticks(self):
-        """ticks observed since observe_begin"""
-        k = C.c_longlong()
-        self._ck(self._L.fibhip_observe_ticks(self._h, C.byref(k)))
-        return int(k.value)
-
-    def observe_end(self):
-        self._ck(self._L.fibhip_observe_end(self._h))
-
-    # ---- electrode recorder (include/fibhip.h fibhip_electrode_*) -------------------------------------------------
-    def electrode_begin(self, var, rects, patches, every=1, capacity=1):
-        """attaches (or re-attaches, with an empty trace) the electrode recorder on array `var`: `rects` is a list of
-        (r0, r1, c0, c1), `patches` the float32 weight arrays of those shapes; one sample every `every` ticks, `capacity`
-        samples at the most"""
-        rects = np.ascontiguousarray(rects, np.intc).reshape(-1, 4)
-        if len(patches) != len(rects):
-            raise ValueError('electrode_begin: %d rectangles but %d weight patches' % (len(rects), len(patches)))
-        flat = []
-        for (r0, r1, c0, c1), w in zip(rects, patches):
-            w = np.asarray(w, np.float32)
-            if w.shape != (r1 - r0, c1 - c0):
-                raise ValueError('electrode_begin: a patch of shape %s for rows [%d, %d) x columns [%d, %d)' % (w.shape, r0, r1, c0, c1))
-            flat.append(w.ravel())
-        weights = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(1), np.float32)
-        self._ck(self._L.fibhip_electrode_begin(self._h, int(var), len(rects), rects.ctypes.data_as(_ip), weights.ctypes.data_as(_fp),
-                                                int(every), int(capacity)))
-        self._el_n = len(rects)
-
-    def electrode_count(self):
-        """samples taken since electrode_begin (ticks accepted but not launched yet included)"""
-        k = C.c_longlong()
-        self._ck(self._L.fibhip_electrode_count(self._h, C.byref(k)))
-        return int(k.value)
-
-    def electrode_read(self, first=0, count=None):
-        """samples [first, first + count) as a float32 [count, n] array (count=None: all taken so far); blocks like
-        get_state, detaches nothing"""
-        if count is None:
-            count = self.electrode_count() - int(first)
-        n = getattr(self, '_el_n', 0)
-        out = np.empty((max(int(count), 0), n), np.float32)
-        self._ck(self._L.fibhip_electrode_read(self._h, int(first), int(count), out.ctypes.data_as(_fp)))
-        return out
-
-    def electrode_end(self):
-        self._ck(self._L.fibhip_electrode_end(self._h))
-
-    # ---- tip recorder (include/fibhip.h fibhip_tips_*) ------------------------------------------------------------
-    def tips_begin(self, var, var2, a0, b0, mask=None, every=1, max_tips=256, capacity=1):
-        """attaches (or re-attaches, with empty lists) the tip recorder on arrays `var`, `var2` with the levels `a0`, `b0`;
-        `mask`: [height, width], non-zero where a cell counts, or None; one sample every `every` ticks, `capacity` samples of
-        up to `max_tips` tips at the most"""
-        mp = None
-        if mask is not None:
-            mask = np.ascontiguousarray(mask, np.uint8)
-            if mask.shape != (self.height, self.width):
-                raise ValueError('tips_begin: a mask of shape %s on a %d x %d grid' % (mask.shape, self.height, self.width))
-            mp = mask.ctypes.data_as(C.POINTER(C.c_ubyte))
-        self._ck(self._L.fibhip_tips_begin(self._h, int(var), int(var2), float(a0), float(b0), mp, int(every), int(max_tips),
-                                           int(capacity)))
-        self._tip_max = int(max_tips)
-
-    def tips_count(self):
-        """samples taken since tips_begin (ticks accepted but not launched yet included)"""
-        k = C.c_longlong()
-        self._ck(self._L.fibhip_tips_count(self._h, C.byref(k)))
-        return int(k.value)
-
-    def tips_read(self, first=0, count=None, records=True):
-        """samples [first, first + count) (count=None: all taken so far) as (counts, records): counts int32 [count, 3] =
-        n_pos, n_neg, stored; records int32 [count, max_tips, 4] = row, column, charge, 0, of which the first
-        min(stored, max_tips) of each sample are valid, in no fixed order (records=False: None).  Blocks like get_state,
-        detaches nothing"""
-        if count is None:
-            count = self.tips_count() - int(first)
-        n = max(int(count), 0)
-        counts = np.zeros((n, 3), np.int32)
-        recs = np.zeros((n, getattr(self, '_tip_max', 0), 4), np.int32) if records else None
-        self._ck(self._L.fibhip_tips_read(self._h, int(first), int(count), counts.ctypes.data_as(_ip),
-                                          recs.ctypes.data_as(_ip) if records else None))
-        return counts, recs
-
-    def tips_end(self):
-        self._ck(self._L.fibhip_tips_end(self._h))
-
-    # ---- frame recorder (include/fibhip.h fibhip_frames_*) --------------------------------------------------------
-    def frames_begin(self, var=0, window=None, block=(1, 1), reduce='mean', lo=0.0, span=1.0, weight=None, fmt='float32', every=1,
-                     first=None, capacity=1):
-        """attaches (or re-attaches, with an empty cube) the frame recorder on array `var`: `window` = (r0, r1, c0, c1) (None:
-        the whole grid), `block` = (by, bx), `reduce` 'point' / 'mean', the levels of y = (X - lo) / span, `weight` an
-        [height, width] float32 plane or None, `fmt` 'float32' / 'uint8'; a frame after ticks first, first + every, ...
-        (first=None: every), `capacity` frames at the most"""
-        win = np.ascontiguousarray((0, self.height, 0, self.width) if window is None else window, np.intc).reshape(4)
-        wp = None
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, np.float32)
-            if weight.shape != (self.height, self.width):
-                raise ValueError('frames_begin: a weight plane of shape %s on a %d x %d grid' % (weight.shape, self.height, self.width))
-            wp = weight.ctypes.data_as(_fp)
-        self._ck(self._L.fibhip_frames_begin(self._h, int(var), win.ctypes.data_as(_ip), int(block[0]), int(block[1]),
-                                             FRAME_REDUCE.index(reduce), float(lo), float(span), wp, FRAME_FORMAT.index(fmt),
-                                             int(every), int(every if first is None else first), int(capacity)))
-
-    def frames_count(self):
-        """frames taken since frames_begin (ticks accepted but not launched yet included)"""
-        k = C.c_longlong()
-        self._ck(self._L.fibhip_frames_count(self._h, C.byref(k)))
-        return int(k.value)
-
-    def frames_shape(self):
-        """(oh, ow, dtype) of the attached recorder's frames"""
-        oh, ow, bpp = C.c_int(), C.c_int(), C.c_int()
-        self._ck(self._L.fibhip_frames_shape(self._h, C.byref(oh), C.byref(ow), C.byref(bpp)))
-        return int(oh.value), int(ow.value), np.dtype(np.uint8 if bpp.value == 1 else np.float32)
-
-    def frames_read(self, first=0, count=None):
-        """frames [first, first + count) as a [count, oh, ow] array of float32 or uint8 (count=None: all taken so far); blocks
-        like get_state, detaches nothing"""
-        if count is None:
-            count = self.frames_count() - int(first)
-        oh, ow, dtype = self.frames_shape()
-        out = np.empty((max(int(count), 0), oh, ow), dtype)
-        self._ck(self._L.fibhip_frames_read(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def frames_end(self):
-        self._ck(self._L.fibhip_frames_end(self._h))
-
-    # ---- spectrum recorder (include/fibhip.h fibhip_spectrum_*) ----------------------------------------------------
-    def spectrum_begin(self, var=0, window=None, block=(1, 1), reduce='mean', weight=None, every=1, nfft=128, win=None, tw=None,
-                       bins=(2,), chunk=1):
-        """attaches the spectrum recorder on array `var`: the frame recorder's `window`, `block`, `reduce` and `weight` (levels
-        0 and 1), a sample every `every` ticks, segments of `nfft` samples weighted by `win` [nfft] float32, the twiddle table
-        `tw` [nfft, 2] float32 (cos, -sin of 2 pi m / nfft), the strictly ascending frequency indices `bins` (at most 128, each
-        in [0, nfft / 2]) and `chunk` (1 .. 32, a divisor of nfft): the samples folded by one launch"""
-        wnd = np.ascontiguousarray((0, self.height, 0, self.width) if window is None else window, np.intc).reshape(4)
-        wp = None
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, np.float32)
-            if weight.shape != (self.height, self.width):
-                raise ValueError('spectrum_begin: a weight plane of shape %s on a %d x %d grid' % (weight.shape, self.height, self.width))
-            wp = weight.ctypes.data_as(_fp)
-        win = np.ascontiguousarray(win, np.float32)
-        tw = np.ascontiguousarray(tw, np.float32)
-        if win.shape != (int(nfft),) or tw.shape != (int(nfft), 2):
-            raise ValueError('spectrum_begin: win must be [nfft] and tw [nfft, 2] (got %s and %s for nfft = %d)' % (win.shape, tw.shape, nfft))
-        b = np.ascontiguousarray(bins, np.intc).reshape(-1)
-        self._ck(self._L.fibhip_spectrum_begin(self._h, int(var), wnd.ctypes.data_as(_ip), int(block[0]), int(block[1]),
-                                               FRAME_REDUCE.index(reduce), wp, int(every), int(nfft), win.ctypes.data_as(_fp),
-                                               tw.ctypes.data_as(_fp), int(b.size), b.ctypes.data_as(_ip), int(chunk)))
-
-    def spectrum_count(self):
-        """(samples taken, segments finished) since spectrum_begin (ticks accepted but not launched yet included)"""
-        s, g = C.c_longlong(), C.c_longlong()
-        self._ck(self._L.fibhip_spectrum_count(self._h, C.byref(s), C.byref(g)))
-        return int(s.value), int(g.value)
-
-    def spectrum_shape(self):
-        """(oh, ow, nb) of the attached recorder"""
-        oh, ow, nb = C.c_int(), C.c_int(), C.c_int()
-        self._ck(self._L.fibhip_spectrum_shape(self._h, C.byref(oh), C.byref(ow), C.byref(nb)))
-        return int(oh.value), int(ow.value), int(nb.value)
-
-    def spectrum_read(self):
-        """(P [nb, oh, ow] float32, segments): the power summed over the finished segments; blocks like get_state"""
-        oh, ow, nb = self.spectrum_shape()
-        out = np.empty((nb, oh, ow), np.float32)
-        seg = C.c_longlong()
-        self._ck(self._L.fibhip_spectrum_read(self._h, out.ctypes.data_as(_fp), C.byref(seg)))
-        return out, int(seg.value)
-
-    def spectrum_peak(self, a, b, halfwidth=1):
-        """(kpeak int32, ppeak, pband, pnear float32), each [oh, ow], over the bin positions a <= i <= b"""
-        oh, ow, _ = self.spectrum_shape()
-        kp = np.empty((oh, ow), np.int32)
-        pp, pb, pn = (np.empty((oh, ow), np.float32) for _ in range(3))
-        self._ck(self._L.fibhip_spectrum_peak(self._h, int(a), int(b), int(halfwidth), kp.ctypes.data_as(_ip), pp.ctypes.data_as(_fp),
-                                              pb.ctypes.data_as(_fp), pn.ctypes.data_as(_fp)))
-        return kp, pp, pb, pn
-
-    def spectrum_end(self):
-        self._ck(self._L.fibhip_spectrum_end(self._h))
-
-    # ---- beat recorder (include/fibhip.h fibhip_beats_*) -----------------------------------------------------------
-    def beats_begin(self, var=0, window=None, block=(1, 1), reduce='mean', weight=None, every=1, up=0.5, down=0.1, depth=8):
-        """attaches the beat recorder on array `var`: the frame recorder's `window`, `block`, `reduce` and `weight` (levels 0
-        and 1), a sample every `every` ticks, the levels `down` <= `up` and a ring of `depth` (1 .. 16) beats per pixel"""
-        wnd = np.ascontiguousarray((0, self.height, 0, self.width) if window is None else window, np.intc).reshape(4)
-        wp = None
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, np.float32)
-            if weight.shape != (self.height, self.width):
-                raise ValueError('beats_begin: a weight plane of shape %s on a %d x %d grid' % (weight.shape, self.height, self.width))
-            wp = weight.ctypes.data_as(_fp)
-        self._ck(self._L.fibhip_beats_begin(self._h, int(var), wnd.ctypes.data_as(_ip), int(block[0]), int(block[1]),
-                                            FRAME_REDUCE.index(reduce), wp, int(every), float(np.float32(up)), float(np.float32(down)),
-                                            int(depth)))
-
-    def beats_count(self):
-        """samples taken since beats_begin (ticks accepted but not launched yet included)"""
-        s = C.c_longlong()
-        self._ck(self._L.fibhip_beats_count(self._h, C.byref(s)))
-        return int(s.value)
-
-    def beats_shape(self):
-        """(oh, ow, depth) of the attached recorder"""
-        oh, ow, d = C.c_int(), C.c_int(), C.c_int()
-        self._ck(self._L.fibhip_beats_shape(self._h, C.byref(oh), C.byref(ow), C.byref(d)))
-        return int(oh.value), int(ow.value), int(d.value)
-
-    def beats_read(self):
-        """(t_up, t_down, peak float32 [depth, oh, ow] in SLOT order — beat b in slot b % depth —, count int32 [oh, ow], pk
-        float32 [oh, ow]); blocks like get_state"""
-        oh, ow, d = self.beats_shape()
-        tu, td, pe = (np.empty((d, oh, ow), np.float32) for _ in range(3))
-        n = np.empty((oh, ow), np.int32)
-        pk = np.empty((oh, ow), np.float32)
-        self._ck(self._L.fibhip_beats_read(self._h, tu.ctypes.data_as(_fp), td.ctypes.data_as(_fp), pe.ctypes.data_as(_fp),
-                                           n.ctypes.data_as(_ip), pk.ctypes.data_as(_fp)))
-        return tu, td, pe, n, pk
-
-    def beats_summary(self, last):
-        """(nused int32, apd_mean, cl_mean, apd_alt float32), each [oh, ow], over the newest `last` beats"""
-        oh, ow, _ = self.beats_shape()
-        nu = np.empty((oh, ow), np.int32)
-        am, cm, al = (np.empty((oh, ow), np.float32) for _ in range(3))
-        self._ck(self._L.fibhip_beats_summary(self._h, int(last), nu.ctypes.data_as(_ip), am.ctypes.data_as(_fp), cm.ctypes.data_as(_fp),
-                                              al.ctypes.data_as(_fp)))
-        return nu, am, cm, al
-
-    def beats_end(self):
-        self._ck(self._L.fibhip_beats_end(self._h))
-
-    # ---- statistics recorder (include/fibhip.h fibhip_stats_*) ----------------------------------------------------
-    def stats_begin(self, cols, weight=None, mask=None, every=1, capacity=1):
-        """attaches the statistics recorder: `cols` is a list of (var, kind, level) with kind one of STAT_KINDS (or its
-        number), `weight` an [height, width] float32 plane or None (what SUM columns weigh with), `mask` an [height, width]
-        array, non-zero where a cell counts for the other kinds, or None; one row of float64 every `every` ticks, `capacity`
-        rows at the most"""
-        arr = (StatCol * max(len(cols), 1))()
-        for i, (var, kind, level) in enumerate(cols):
-            arr[i].var, arr[i].kind = int(var), STAT_KINDS.index(kind) if isinstance(kind, str) else int(kind)
-            arr[i].level = float(level)
-        wp = mp = None
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, np.float32)
-            if weight.shape != (self.height, self.width):
-                raise ValueError('stats_begin: a weight plane of shape %s on a %d x %d grid' % (weight.shape, self.height, self.width))
-            wp = weight.ctypes.data_as(_fp)
-        if mask is not None:
-            mask = np.ascontiguousarray(mask, np.uint8)
-            if mask.shape != (self.height, self.width):
-                raise ValueError('stats_begin: a mask of shape %s on a %d x %d grid' % (mask.shape, self.height, self.width))
-            mp = mask.ctypes.data_as(C.POINTER(C.c_ubyte))
-        self._ck(self._L.fibhip_stats_begin(self._h, len(cols), arr, wp, mp, int(every), int(capacity)))
-        self._st_n = len(cols)
-
-    def stats_count(self):
-        """samples taken since stats_begin (ticks accepted but not launched yet included)"""
-        k = C.c_longlong()
-        self._ck(self._L.fibhip_stats_count(self._h, C.byref(k)))
-        return int(k.value)
-
-    def stats_read(self, first=0, count=None):
-        """samples [first, first + count) as a float64 [count, ncols] array (count=None: all taken so far); blocks like
-        get_state, detaches nothing"""
-        if count is None:
-            count = self.stats_count() - int(first)
-        out = np.empty((max(int(count), 0), getattr(self, '_st_n', 0)), np.float64)
-        self._ck(self._L.fibhip_stats_read(self._h, int(first), int(count), out.ctypes.data_as(C.POINTER(C.c_double))))
-        return out
-
-    def stats_end(self):
-        self._ck(self._L.fibhip_stats_end(self._h))
-
-    # ---- lead recorder (include/fibhip.h fibhip_leads_*) ----------------------------------------------------------
-    def leads_begin(self, pos, tables, weight=None, var=0, every=1, capacity=1):
-        """attaches the lead recorder: `pos` is a list of (row, col, table), `tables` a float32 [ntables, height, width] array
-        of lead-field tables, `weight` an [height, width] float32 plane or None (weight 1); one row of float64, one value per
-        lead, every `every` ticks, `capacity` rows at the most"""
-        pos = np.ascontiguousarray(pos, np.int32).reshape(-1, 3)
-        tables = np.ascontiguousarray(tables, np.float32)
-        if tables.ndim != 3 or tables.shape[1:] != (self.height, self.width):
-            raise ValueError('leads_begin: tables of shape %s on a %d x %d grid' % (tables.shape, self.height, self.width))
-        wp = None
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, np.float32)
-            if weight.shape != (self.height, self.width):
-                raise ValueError('leads_begin: a weight plane of shape %s on a %d x %d grid' % (weight.shape, self.height, self.width))
-            wp = weight.ctypes.data_as(_fp)
-        self._ck(self._L.fibhip_leads_begin(self._h, int(var), len(pos), pos.ctypes.data_as(_ip), len(tables), tables.ctypes.data_as(_fp), wp,
-                                            int(every), int(capacity)))
-        self._ld_n = len(pos)
-
-    def leads_count(self):
-        """samples taken since leads_begin (ticks accepted but not launched yet included)"""
-        k = C.c_longlong()
-        self._ck(self._L.fibhip_leads_count(self._h, C.byref(k)))
-        return int(k.value)
-
-    def leads_read(self, first=0, count=None):
-        """samples [first, first + count) as a float64 [count, nleads] array (count=None: all taken so far); blocks like
-        get_state, detaches nothing"""
-        if count is None:
-            count = self.leads_count() - int(first)
-        out = np.empty((max(int(count), 0), getattr(self, '_ld_n', 0)), np.float64)
-        self._ck(self._L.fibhip_leads_read(self._h, int(first), int(count), out.ctypes.data_as(C.POINTER(C.c_double))))
-        return out
-
-    def leads_end(self):
-        self._ck(self._L.fibhip_leads_end(self._h))
-
-    # ---- wave recorder (include/fibhip.h fibhip_waves_*) ----------------------------------------------------------
-    def waves_begin(self, var=0, kind=0, level=0.0, var2=-1, kind2=0, level2=0.0, conn=4, mask=None, max_waves=256, every=1, capacity=1):
-        """attaches (or re-attaches, with empty lists) the wave recorder: a cell is set where `mask` ([height, width], or None:
-        everywhere) is non-zero and array `var` is above (`kind` 0) or below (1) `level`, and array `var2` (-1: none) meets
-        (`kind2`, `level2`) too; the connected components under `conn` = 4 or 8 are the waves; one sample every `every` ticks,
-        `capacity` samples of up to `max_waves` records at the most"""
-        mp = None
-        if mask is not None:
-            mask = np.ascontiguousarray(mask, np.uint8)
-            if mask.shape != (self.height, self.width):
-                raise ValueError('waves_begin: a mask of shape %s on a %d x %d grid' % (mask.shape, self.height, self.width))
-            mp = mask.ctypes.data_as(C.POINTER(C.c_ubyte))
-        self._ck(self._L.fibhip_waves_begin(self._h, int(var), int(kind), float(level), int(var2), int(kind2), float(level2), int(conn), mp,
-                                            int(max_waves), int(every), int(capacity)))
-        self._wave_max = int(max_waves)
-        self._wave_link_max = 0
-
-    def waves_links_begin(self, max_links=512):
-        """turns links on for the wave recorder just attached (before its first tick): per sample, which waves of the sample
-        before share cells with which waves of this one, up to `max_links` records (prev, seed, overlap)"""
-        self._ck(self._L.fibhip_waves_links_begin(self._h, int(max_links)))
-        self._wave_link_max = int(max_links)
-
-    def waves_links_read(self, first=0, count=None, records=True):
-        """samples [first, first + count) (count=None: all taken so far) as (counts, links): counts int32 [count, 4] = links,
-        stored, cells, lost; links WAVE_LINK_DTYPE [count, max_links], of which the first `stored` of each sample are valid, in
-        no fixed order (records=False: None).  Blocks like waves_read; refused while links are off"""
-        if count is None:
-            count = self.waves_count() - int(first)
-        n = max(int(count), 0)
-        counts = np.zeros((n, 4), np.int32)
-        recs = np.zeros((n, getattr(self, '_wave_link_max', 0)), WAVE_LINK_DTYPE) if records else None
-        self._ck(self._L.fibhip_waves_links_read(self._h, int(first), int(count), counts.ctypes.data_as(_ip),
-                                                 recs.ctypes.data_as(C.c_void_p) if records else None))
-        return counts, recs
-
-    def waves_count(self):
-        """samples taken since waves_begin (ticks accepted but not launched yet included)"""
-        k = C.c_longlong()
-        self._ck(self._L.fibhip_waves_count(self._h, C.byref(k)))
-        return int(k.value)
-
-    def waves_read(self, first=0, count=None, records=True):
-        """samples [first, first + count) (count=None: all taken so far) as (counts, records): counts int32 [count, 3] = n,
-        stored, cells; records WAVE_RECORD_DTYPE [count, max_waves], of which the first `stored` of each sample are valid, in
-        no fixed order (records=False: None).  Blocks like get_state, detaches nothing"""
-        if count is None:
-            count = self.waves_count() - int(first)
-        n = max(int(count), 0)
-        counts = np.zeros((n, 3), np.int32)
-        recs = np.zeros((n, getattr(self, '_wave_max', 0)), WAVE_RECORD_DTYPE) if records else None
-        self._ck(self._L.fibhip_waves_read(self._h, int(first), int(count), counts.ctypes.data_as(_ip),
-                                           recs.ctypes.data_as(C.c_void_p) if records else None))
-        return counts, recs
-
-    def waves_labels(self):
-        """the label plane of the latest sample: int32 [height, width], the seed of the cell's wave or -1"""
-        out = np.empty((self.height, self.width), np.int32)
-        self._ck(self._L.fibhip_waves_labels(self._h, out.ctypes.data_as(_ip)))
-        return out
-
-    def waves_end(self):
-        self._ck(self._L.fibhip_waves_end(self._h))
-        self._wave_link_max = 0
-
-    # ---- stimulus program (include/fibhip.h fibhip_stim_*) --------------------------------------------------------
-    def stim_begin(self, entries, planes=None):
-        """attaches a stimulus program: `entries` is a list of dicts with the fields of fibhip_stim_entry (`mode` 'max' / 'add'
-        or its number, `shape` 'rect' / 'plane' or its number; fields left out are 0, hold and count 1), `planes` a list of
-        [height, width] float32 arrays the 'plane' entries index"""
-        arr = (StimEntry * max(len(entries), 1))()
-        for i, e in enumerate(entries):
-            d = dict(e)
-            mode, shape = d.pop('mode', 0), d.pop('shape', 0)
-            arr[i].mode = STIM_MODES.index(mode) if isinstance(mode, str) else int(mode)
-            arr[i].shape = STIM_SHAPES.index(shape) if isinstance(shape, str) else int(shape)
-            arr[i].hold, arr[i].count = int(d.pop('hold', 1)), int(d.pop('count', 1))
-            arr[i].v, arr[i].floor = float(d.pop('v', 0.0)), float(d.pop('floor', 0.0))
-            for k, val in d.items():
-                if k not in ('var', 'r0', 'r1', 'c0', 'c1', 'plane', 'first', 'period'):
-                    raise ValueError('stim_begin: entry %d: unknown field %r' % (i, k))
-                setattr(arr[i], k, int(val))
-        pp, stack = None, None
-        if planes is not None and len(planes):
-            for p in planes:
-                if np.shape(p) != (self.height, self.width):
-                    raise ValueError('stim_begin: a plane of shape %s on a %d x %d grid' % (np.shape(p), self.height, self.width))
-            stack = np.ascontiguousarray(np.stack([np.asarray(p, np.float32) for p in planes]), np.float32)
-            pp = stack.ctypes.data_as(_fp)
-        self._ck(self._L.fibhip_stim_begin(self._h, len(entries), arr, 0 if stack is None else len(stack), pp))
-
-    def stim_count(self):
-        """events applied since stim_begin (flushes: the ticks accepted so far are launched first)"""
-        k = C.c_longlong()
-        self._ck(self._L.fibhip_stim_count(self._h, C.byref(k)))
-        return int(k.value)
-
-    def stim_end(self):
-        self._ck(self._L.fibhip_stim_end(self._h))
-
-    # ---- lesion program (include/fibhip.h fibhip_lesion_*) --------------------------------------------------------
-    def lesion_begin(self, lesions):
-        """attaches a lesion program: `lesions` is a list of (tick, (r0, r1, c0, c1), patch) — the patch a float32
-        [r1 - r0, c1 - c0] array of factors in [0, 1] — applied to the phase field right after tick `tick`, in list order"""
-        arr = (LesionEntry * max(len(lesions), 1))()
-        flat, off = [], 0
-        for i, (tick, box, patch) in enumerate(lesions):
-            r0, r1, c0, c1 = (int(a) for a in box)
-            p = np.ascontiguousarray(patch, np.float32)
-            if p.shape != (r1 - r0, c1 - c0):
-                raise ValueError('lesion_begin: entry %d: a patch of shape %s on the box rows [%d, %d) x columns [%d, %d)' % (i, p.shape, r0, r1, c0, c1))
-            arr[i].offset, arr[i].tick = off, int(tick)
-            arr[i].r0, arr[i].r1, arr[i].c0, arr[i].c1 = r0, r1, c0, c1
-            flat.append(p.ravel())
-            off += p.size
-        packed = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(1), np.float32)
-        self._ck(self._L.fibhip_lesion_begin(self._h, len(lesions), arr, off, packed.ctypes.data_as(_fp)))
-
-    def lesion_count(self):
-        """entries applied since lesion_begin (ticks accepted but not launched yet count)"""
-        k = C.c_longlong()
-        self._ck(self._L.fibhip_lesion_count(self._h, C.byref(k)))
-        return int(k.value)
-
-    def lesion_end(self):
-        self._ck(self._L.fibhip_lesion_end(self._h))
-
-    def lesion_apply(self, box, patch):
-        """one lesion now: phi = max(phi * patch, 1e-5) on the box (r0, r1, c0, c1), the derived planes recomputed around it"""
-        b = np.asarray([int(a) for a in box], np.int32)
-        p = np.ascontiguousarray(patch, np.float32)
-        if b.shape != (4,) or p.shape != (int(b[1] - b[0]), int(b[3] - b[2])):
-            raise ValueError('lesion_apply: a patch of shape %s on the box %s' % (p.shape, tuple(int(a) for a in b)))
-        self._ck(self._L.fibhip_lesion_apply(self._h, b.ctypes.data_as(_ip), p.ctypes.data_as(_fp)))
-        self._fallback_warning()
-
-    def get_phase(self):
-        """the handle's current phase field, float32 [height, width]"""
-        out = np.empty((self.height, self.width), np.float32)
-        self._ck(self._L.fibhip_get_phase(self._h, out.ctypes.data_as(_fp)))
-        self._fallback_warning()
-        return out
-
-    # ---- trigger program (include/fibhip.h fibhip_trig_*) ---------------------------------------------------------
-    def trig_begin(self, sensors, rules, planes=None, every=1, capacity=4096):
-        """attaches a trigger program: `sensors` is a list of dicts with the fields of fibhip_trig_sensor (`site` 'rect' with r0,
-        r1, c0, c1, or 'mask' with `mask`, a [height, width] array whose non-zero cells are the site), `rules` a list of dicts
-        with the fields of fibhip_trig_rule (`edge` 'rise' / 'fall', `mode` 'max' / 'add', `shape` 'rect' / 'plane', or their
-        numbers; fields left out are 0, count and hold 1), `planes` the [height, width] float32 arrays the 'plane' stimuli index"""
-        sa = (TrigSensor * max(len(sensors), 1))()
-        masks = []
-        for i, q in enumerate(sensors[:MAX_TRIG_SENSORS]):
-            d = dict(q)
-            site = d.pop('site', 0)
-            sa[i].site = TRIG_SITES.index(site) if isinstance(site, str) else int(site)
-            sa[i].level, sa[i].need = float(d.pop('level', 0.0)), int(d.pop('need', 1))
-            mask = d.pop('mask', None)
-            if sa[i].site == 1:
-                if mask is None or np.shape(mask) != (self.height, self.width):
-                    raise ValueError('trig_begin: sensor %d: a mask of shape %s on a %d x %d grid' % (i, np.shape(mask), self.height, self.width))
-                masks.append((np.asarray(mask) != 0).astype(np.uint8))
-            for k, val in d.items():
-                if k not in ('var', 'r0', 'r1', 'c0', 'c1'):
-                    raise ValueError('trig_begin: sensor %d: unknown field %r' % (i, k))
-                setattr(sa[i], k, int(val))
-        ra = (TrigRule * max(len(rules), 1))()
-        for i, q in enumerate(rules[:MAX_TRIG_RULES]):
-            d = dict(q)
-            edge, mode, shape = d.pop('edge', 0), d.pop('mode', 0), d.pop('shape', 0)
-            ra[i].edge = TRIG_EDGES.index(edge) if isinstance(edge, str) else int(edge)
-            ra[i].mode = STIM_MODES.index(mode) if isinstance(mode, str) else int(mode)
-            ra[i].shape = STIM_SHAPES.index(shape) if isinstance(shape, str) else int(shape)
-            ra[i].hold, ra[i].count = int(d.pop('hold', 1)), int(d.pop('count', 1))
-            ra[i].v, ra[i].floor = float(d.pop('v', 0.0)), float(d.pop('floor', 0.0))
-            for k, val in d.items():
-                if k not in ('sensor', 'arm', 'blank', 'escape', 'max_det', 'delay', 'period', 'var', 'r0', 'r1', 'c0', 'c1', 'plane'):
-                    raise ValueError('trig_begin: rule %d: unknown field %r' % (i, k))
-                setattr(ra[i], k, int(val))
-        mp, mstack = None, None
-        if masks:
-            mstack = np.ascontiguousarray(np.stack(masks), np.uint8)
-            mp = mstack.ctypes.data_as(C.POINTER(C.c_ubyte))
-        pp, stack = None, None
-        if planes is not None and len(planes):
-            for p in planes:
-                if np.shape(p) != (self.height, self.width):
-                    raise ValueError('trig_begin: a plane of shape %s on a %d x %d grid' % (np.shape(p), self.height, self.width))
-            stack = np.ascontiguousarray(np.stack([np.asarray(p, np.float32) for p in planes]), np.float32)
-            pp = stack.ctypes.data_as(_fp)
-        self._ck(self._L.fibhip_trig_begin(self._h, len(sensors), sa, mp, len(rules), ra, 0 if stack is None else len(stack), pp, int(every),
-                                           int(capacity)))
-        self._trig_n = len(rules)
-
-    def trig_count(self):
-        """samples taken since trig_begin (ticks accepted but not launched yet included)"""
-        k = C.c_longlong()
-        self._ck(self._L.fibhip_trig_count(self._h, C.byref(k)))
-        return int(k.value)
-
-    def trig_read(self, first=0, count=None):
-        """rows [first, first + count) of the log as an int32 [count, nrules, 6] array — c, a, t, n, cause, fired — (count=None:
-        all taken so far); blocks like get_state, detaches nothing"""
-        if count is None:
-            count = self.trig_count() - int(first)
-        out = np.empty((max(int(count), 0), getattr(self, '_trig_n', 0), len(TRIG_FIELDS)), np.int32)
-        self._ck(self._L.fibhip_trig_read(self._h, int(first), int(count), out.ctypes.data_as(_ip)))
-        return out
-
-    def trig_end(self):
-        self._ck(self._L.fibhip_trig_end(self._h))

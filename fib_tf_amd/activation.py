@@ -14,6 +14,8 @@ attached every tick is its own launch (no multi-tick launches, no run-ahead): DE
 """
 import numpy as np
 
+from ._recorder import DeviceRecorder, attach
+
 MAPS = ('first_up', 'last_up', 'prev_up', 'apd', 'count')
 
 
@@ -24,28 +26,19 @@ def default_thresholds(min_v, max_v):
     return np.float32(min_v + 0.5 * span), np.float32(min_v + 0.1 * span)
 
 
-class ActivationRecorder:
-    """the recorder attached to one model's handle; see `IonicModel.record_activation`"""
+class ActivationRecorder(DeviceRecorder):
+    """the recorder attached to one model's handle; see `IonicModel.record_activation`.  close() detaches it (the handle goes
+    back to its usual launch plan)"""
+    NOUN, END = 'activation recorder', 'observe_end'
 
     def __init__(self, model, up=None, down=None, var=0):
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('record_activation should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('record_activation: activation maps are recorded on a single device only; this model '
-                                      'runs as row blocks over %d ranks' % st.world)
+        self._st = st = attach(model, 'record_activation', 'activation maps are recorded')
         d_up, d_down = default_thresholds(float(model.min_v), float(model.max_v))
         self.up = np.float32(d_up if up is None else up)
         self.down = np.float32(d_down if down is None else down)
         self.var = int(var)
-        self._st = st
         st.observe_begin(self.var, self.up, self.down)
         self.open = True
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the activation recorder has been closed')
 
     def ticks(self):
         """ticks observed since the recorder was attached"""
@@ -57,19 +50,6 @@ class ActivationRecorder:
         'count': [H, W] int32 upstrokes}"""
         self._check()
         return {k: self._st.observe_get(k) for k in MAPS}
-
-    def close(self):
-        """detaches the recorder (the handle goes back to its usual launch plan)"""
-        if self.open:
-            self.open = False
-            self._st.observe_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
 def conduction_velocity(t_map, row, c0, c1):

@@ -17,6 +17,8 @@ restated in NumPy in tests/beat_ref.py).
 All times are milliseconds since the recorder was attached."""
 import numpy as np
 
+from ._recorder import DeviceRecorder, attach, check_every, tick_ms, weight_plane
+
 MAX_DEPTH = 16                                   # include/fibhip.h FIBHIP_BEATS_MAX_DEPTH
 SUMMARY_MAPS = ('nused', 'apd_mean', 'cl_mean', 'apd_alt')
 
@@ -29,8 +31,7 @@ def default_levels(min_v, max_v):
 
 def check_args(every, depth, up, down, block, reduce):
     """the refusals that need no device: raises ValueError"""
-    if int(every) < 1:
-        raise ValueError('record_beats: every must be >= 1')
+    check_every('record_beats', every)
     if not 1 <= int(depth) <= MAX_DEPTH:
         raise ValueError('record_beats: depth must be 1 .. %d (got %d)' % (MAX_DEPTH, depth))
     if not np.float32(down) <= np.float32(up):
@@ -97,19 +98,14 @@ def restitution_of(beats, mask=None):
     return di[ok], apd[ok]
 
 
-class BeatRecorder:
+class BeatRecorder(DeviceRecorder):
     """the last `depth` beats of every pixel, kept on the device; see `IonicModel.record_beats`"""
+    NOUN, END = 'beat recorder', 'beats_end'
 
     def __init__(self, model, every=10, depth=8, up=None, down=None, var=0, region=None, block=(1, 1), reduce='mean', weight=None):
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('record_beats should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('record_beats: beats are recorded on a single device only; this model '
-                                      'runs as row blocks over %d ranks' % st.world)
+        self._st = st = attach(model, 'record_beats', 'beats are recorded')
         self.every, self.depth, self.var = int(every), int(depth), int(var)
-        self.tick_ms = float(model.dt_per_step * model.dt)
+        self.tick_ms = tick_ms(model)
         if (up is None or down is None) and self.var != 0:
             raise ValueError('record_beats: the default levels are those of array 0; pass up and down for var = %d' % self.var)
         d_up, d_down = default_levels(float(model.min_v), float(model.max_v))
@@ -119,24 +115,11 @@ class BeatRecorder:
         self.reduce = reduce
         check_args(self.every, self.depth, self.up, self.down, self.block, reduce)
         self.window = (0, model.height, 0, model.width) if region is None else tuple(int(v) for v in region)
-        if isinstance(weight, str):
-            if weight != 'phase':
-                raise ValueError("record_beats: weight is 'phase', None or an [height, width] array")
-            weight = getattr(model, 'phase', None)
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, np.float32)
-            if weight.shape != (model.height, model.width):
-                raise ValueError('record_beats: a weight plane of shape %s on a %d x %d grid' % (weight.shape, model.height, model.width))
-        self.weight = weight
-        self._st = st
+        self.weight = weight = weight_plane(model, weight, 'record_beats')
         st.beats_begin(self.var, self.window, self.block, self.reduce, weight, self.every, self.up, self.down, self.depth)
         oh, ow, _ = st.beats_shape()
         self.shape = (oh, ow)
         self.open = True
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the beat recorder has been closed')
 
     def samples(self):
         """samples taken since the recorder was attached"""
@@ -178,16 +161,3 @@ class BeatRecorder:
         if not 1 <= int(last) <= self.depth:
             raise ValueError('summary: last must be 1 .. depth = %d (got %d)' % (self.depth, last))
         return dict(zip(SUMMARY_MAPS, self._st.beats_summary(int(last))))
-
-    def close(self):
-        """detaches the recorder and frees its planes"""
-        if self.open:
-            self.open = False
-            self._st.beats_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False

@@ -6,6 +6,8 @@ millisecond while the model runs; `delay_ms()` / `conduction_velocity()` turn th
 (pixels per millisecond — the reference does not record its length unit per pixel)."""
 import numpy as np
 
+from ._recorder import SampledRecorder, attach, check_every, run_capacity, run_ticks
+
 
 def create_mask(model, x, y, radius):
     """float32 [height, width] Gaussian exp(-(dist/radius)^2) centred at column x, row y (egm.py:5-12)"""
@@ -42,7 +44,7 @@ def crop_mask(mask):
     return rect, np.ascontiguousarray(m[rect[0]:rect[1], rect[2]:rect[3]])
 
 
-class ElectrodeRecorder:
+class ElectrodeRecorder(SampledRecorder):
     """electrode traces recorded on the device; see `IonicModel.record_electrodes`.
 
         with model.record_electrodes([mask1, mask2], every=10) as rec:
@@ -58,26 +60,16 @@ class ElectrodeRecorder:
     traced model's image() is the user's own) must override that hook.  With var = 0 the hook is checked against image()
     on the current state when the recorder is attached (two read-backs; `check_affine=False` skips them) and a mismatch
     raises ValueError.  For any other `var` there is no image(): `traces()` returns mean(X_var * mask)."""
+    NOUN, END, COUNT = 'electrode recorder', 'electrode_end', 'electrode_count'
 
     def __init__(self, model, masks, every=1, capacity=None, var=0, check_affine=True):
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('record_electrodes should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('record_electrodes: electrode traces are recorded on a single device only; this model '
-                                      'runs as row blocks over %d ranks' % st.world)
+        self._st = st = attach(model, 'record_electrodes', 'electrode traces are recorded')
         masks = [np.asarray(m, np.float32) for m in masks]
         for m in masks:
             if m.shape != (model.height, model.width):
                 raise ValueError('record_electrodes: a mask of shape %s on a %d x %d grid' % (m.shape, model.height, model.width))
-        self.every = int(every)
-        if self.every < 1:
-            raise ValueError('record_electrodes: every must be >= 1')
-        if capacity is None:                     # the samples of a whole run of model.duration (whatever has run already), at least 1
-            ticks = int(model.duration / (model.dt_per_step * model.dt))
-            capacity = max(1, ticks // self.every)
-        self.capacity = int(capacity)
+        self.every = check_every('record_electrodes', every)
+        self.capacity = int(run_capacity(model, self.every) if capacity is None else capacity)
         self.var = int(var)
         crops = [crop_mask(m) for m in masks]
         self.rects = [c[0] for c in crops]
@@ -92,18 +84,8 @@ class ElectrodeRecorder:
             if want.shape != got.shape or not np.all(np.abs(got - want) <= tol):
                 raise ValueError('record_electrodes: image() is not %g * X + %g on the current state: a model whose image() '
                                  'rescales must override _image_affine()' % self.affine)
-        self._st = st
         st.electrode_begin(self.var, self.rects, [c[1] for c in crops], self.every, self.capacity)
         self.open = True
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the electrode recorder has been closed')
-
-    def count(self):
-        """samples taken since the recorder was attached"""
-        self._check()
-        return self._st.electrode_count()
 
     def convert(self, raw):
         """raw float32 sums of w * X -> the reference's mean(image() * mask), in float64: image() = scale * X + offset
@@ -118,19 +100,6 @@ class ElectrodeRecorder:
         got = self._st.electrode_read(first, count)
         return got.astype(np.float64) if raw else self.convert(got)
 
-    def close(self):
-        """detaches the recorder and frees the trace"""
-        if self.open:
-            self.open = False
-            self._st.electrode_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
 
 def record_on_device(model, mask1, mask2, im=None, every_ms=1.0, on_tick=None):
     """`record()` with the electrodes on the device: same signature, same stride rule, same sample times, same float64
@@ -140,7 +109,7 @@ def record_on_device(model, mask1, mask2, im=None, every_ms=1.0, on_tick=None):
     recorded by a recorder of its own with every = 1 (one sample), and a second one with every = stride is attached after it:
     its samples fall after ticks stride, 2 * stride, ..."""
     stride = max(1, int(round(every_ms / (model.dt * model.dt_per_step))))
-    ticks = int(model.duration / (model.dt_per_step * model.dt))
+    ticks = run_ticks(model)
     if ticks < 1:
         return np.zeros((0, 2), np.float64)
     head = None

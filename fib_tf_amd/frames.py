@@ -8,6 +8,8 @@ array, optionally block-reduced, mapped the way `image()` maps it, optionally we
 8-bit grey.  The definition is exact (include/fibhip.h, fibhip_frames_*; restated in NumPy in tests/frame_ref.py)."""
 import numpy as np
 
+from ._recorder import SampledRecorder, attach, check_every, run_ticks, tick_ms, weight_plane
+
 
 def round_levels(min_v, max_v):
     """(lo, span) of a model whose image() is (V - min_v) / (max_v - min_v): the subtraction in double, both rounded to
@@ -15,7 +17,7 @@ def round_levels(min_v, max_v):
     return float(np.float32(min_v)), float(np.float32(float(max_v) - float(min_v)))
 
 
-class FrameRecorder:
+class FrameRecorder(SampledRecorder):
     """frames recorded on the device; see `IonicModel.record_frames`.
 
         with model.record_frames(every=10, first=1) as rec:      # run(im)'s own cadence: after ticks 0, 10, 20, ...
@@ -24,20 +26,13 @@ class FrameRecorder:
             rec.save('cube')                     # what the drivers' np.save('cube', cube) writes; playcube replays it
 
     `frames()` returns [n, oh, ow] float32 (or uint8 with fmt='uint8'); `times()` the model time of every frame in ms since
-    the recorder was attached: frame s follows tick first + s * every."""
+    the recorder was attached: frame s follows tick first + s * every.  `count()` counts frames."""
+    NOUN, END, COUNT = 'frame recorder', 'frames_end', 'frames_count'
 
     def __init__(self, model, every=1, first=None, window=None, block=(1, 1), reduce='mean', fmt='float32', var=0, weight='phase',
                  levels=None, capacity=None):
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('record_frames should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('record_frames: frames are recorded on a single device only; this model '
-                                      'runs as row blocks over %d ranks' % st.world)
-        self.every = int(every)
-        if self.every < 1:
-            raise ValueError('record_frames: every must be >= 1')
+        self._st = st = attach(model, 'record_frames', 'frames are recorded')
+        self.every = check_every('record_frames', every)
         self.first = self.every if first is None else int(first)
         if not 1 <= self.first <= self.every:
             raise ValueError('record_frames: first must be 1 .. every = %d (got %d)' % (self.every, self.first))
@@ -45,15 +40,7 @@ class FrameRecorder:
         self.window = (0, model.height, 0, model.width) if window is None else tuple(int(v) for v in window)
         self.block = (int(block[0]), int(block[1]))
         self.reduce, self.fmt = reduce, {'f32': 'float32', 'u8': 'uint8'}.get(fmt, fmt)
-        if isinstance(weight, str):
-            if weight != 'phase':
-                raise ValueError("record_frames: weight is 'phase', None or an [height, width] array")
-            weight = getattr(model, 'phase', None)
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, np.float32)
-            if weight.shape != (model.height, model.width):
-                raise ValueError('record_frames: a weight plane of shape %s on a %d x %d grid' % (weight.shape, model.height, model.width))
-        self.weight = weight
+        self.weight = weight = weight_plane(model, weight, 'record_frames')
         given = levels is not None
         lo, span = levels if given else model._frame_levels()
         self.levels = (float(np.float32(lo)), float(np.float32(span)))
@@ -66,26 +53,16 @@ class FrameRecorder:
             if want.shape != got.shape or want.tobytes() != got.tobytes():
                 raise ValueError('record_frames: image() is not (X - %g) / %g on the current state, bit for bit: a model whose '
                                  'image() rescales must pass levels=(lo, span) (or override _frame_levels())' % self.levels)
-        self.tick_ms = float(model.dt_per_step * model.dt)
+        self.tick_ms = tick_ms(model)
         if capacity is None:                     # the frames of a whole run of model.duration, at least 1
-            ticks = int(model.duration / (model.dt_per_step * model.dt))
+            ticks = run_ticks(model)
             capacity = max(1, (ticks - self.first) // self.every + 1 if ticks >= self.first else 1)
         self.capacity = int(capacity)
-        self._st = st
         st.frames_begin(self.var, self.window, self.block, self.reduce, self.levels[0], self.levels[1], weight, self.fmt,
                         self.every, self.first, self.capacity)
         oh, ow, self.dtype = st.frames_shape()
         self.shape = (oh, ow)
         self.open = True
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the frame recorder has been closed')
-
-    def count(self):
-        """frames taken since the recorder was attached"""
-        self._check()
-        return self._st.frames_count()
 
     def frames(self, first=0, count=None):
         """[n, oh, ow] float32 or uint8: frames [first, first + count) (count=None: all taken so far)"""
@@ -94,8 +71,7 @@ class FrameRecorder:
 
     def times(self, first=0, count=None):
         """float64 [n]: the model time in ms since attach at which each of those frames was taken"""
-        n = self.count() - int(first) if count is None else int(count)
-        return (self.first + (int(first) + np.arange(max(n, 0))) * self.every) * self.tick_ms
+        return (self.first + (int(first) + np.arange(max(self._span(first, count), 0))) * self.every) * self.tick_ms
 
     def save(self, path):
         """writes the cube `playcube` replays (np.save: '.npy' is appended when missing); a uint8 cube stays uint8"""
@@ -106,16 +82,3 @@ class FrameRecorder:
         from . import playcube
         kw.setdefault('delay', 0)
         return playcube.play(self.frames(), screen=screen, **kw)
-
-    def close(self):
-        """detaches the recorder and frees the cube"""
-        if self.open:
-            self.open = False
-            self._st.frames_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False

@@ -213,18 +213,23 @@ class IonicModel:
             watch['last_spike'] = i
         watch['v0'] = v1
 
+    def _attachable(self, who):
+        """this model, ready for a recorder or a program to attach to its handle: define() has been called, and a traced model
+        (traced.py), which compiles on first use, has compiled"""
+        if not self.defined:
+            raise AssertionError('%s should be called after calling define' % who)
+        ensure = getattr(self, '_ensure_compiled', None)
+        if ensure is not None:
+            ensure()
+        return self
+
     def record_activation(self, up=None, down=None, var=0):
         """attaches an activation recorder (fib_tf_amd/activation.py) to this model's handle: per-cell maps of the first,
         last and previous upstroke through `up`, the APD down to `down` and the number of upstrokes, updated on the device
         after every tick.  Defaults: up at 50 %, down at 10 % of [min_v, max_v].  Call after define(); single device only
         (row blocks raise NotImplementedError)."""
         from .activation import ActivationRecorder
-        if not self.defined:
-            raise AssertionError('record_activation should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return ActivationRecorder(self, up=up, down=down, var=var)
+        return ActivationRecorder(self._attachable('record_activation'), up=up, down=down, var=var)
 
     def record_electrodes(self, masks, every=1, capacity=None, var=0):
         """attaches an electrode recorder (fib_tf_amd/egm.py) to this model's handle: every `every` ticks the weighted sum of
@@ -234,12 +239,7 @@ class IonicModel:
         the samples of a whole run of `duration`.  Call after define(); single device only (row blocks raise
         NotImplementedError)."""
         from .egm import ElectrodeRecorder
-        if not self.defined:
-            raise AssertionError('record_electrodes should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return ElectrodeRecorder(self, masks, every=every, capacity=capacity, var=var)
+        return ElectrodeRecorder(self._attachable('record_electrodes'), masks, every=every, capacity=capacity, var=var)
 
     def record_tips(self, var2=None, levels=None, every=1, max_tips=256, capacity=None, var=0, mask=None):
         """attaches a tip recorder (fib_tf_amd/tips.py) to this model's handle: every `every` ticks the phase singularities of
@@ -250,12 +250,7 @@ class IonicModel:
         count.  Default capacity: the samples of a whole run of `duration`.  Call after define(); single device only (row
         blocks raise NotImplementedError)."""
         from .tips import TipRecorder
-        if not self.defined:
-            raise AssertionError('record_tips should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return TipRecorder(self, var2=var2, levels=levels, every=every, max_tips=max_tips, capacity=capacity, var=var, mask=mask)
+        return TipRecorder(self._attachable('record_tips'), var2=var2, levels=levels, every=every, max_tips=max_tips, capacity=capacity, var=var, mask=mask)
 
     def record_frames(self, every=1, first=None, window=None, block=(1, 1), reduce='mean', fmt='float32', var=0, weight='phase',
                       levels=None, capacity=None):
@@ -268,12 +263,7 @@ class IonicModel:
         state, bit for bit.  Default capacity: the frames of a whole run of `duration`.  Call after define(); single device
         only (row blocks raise NotImplementedError)."""
         from .frames import FrameRecorder
-        if not self.defined:
-            raise AssertionError('record_frames should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return FrameRecorder(self, every=every, first=first, window=window, block=block, reduce=reduce, fmt=fmt, var=var,
+        return FrameRecorder(self._attachable('record_frames'), every=every, first=first, window=window, block=block, reduce=reduce, fmt=fmt, var=var,
                              weight=weight, levels=levels, capacity=capacity)
 
     def record_stats(self, columns, every=1, weight='phase', mask=None, capacity=None):
@@ -286,12 +276,7 @@ class IonicModel:
         capacity: the samples of a whole run of `duration`.  Call after define(); single device only (row blocks raise
         NotImplementedError)."""
         from .stats import StatsRecorder
-        if not self.defined:
-            raise AssertionError('record_stats should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return StatsRecorder(self, columns, every=every, weight=weight, mask=mask, capacity=capacity)
+        return StatsRecorder(self._attachable('record_stats'), columns, every=every, weight=weight, mask=mask, capacity=capacity)
 
     def record_leads(self, positions, tables, table_of=None, every=1, weight='phase', var=0, capacity=None):
         """attaches a lead recorder (fib_tf_amd/leads.py) to this model's handle: every `every` ticks the unipolar electrogram of
@@ -304,12 +289,7 @@ class IonicModel:
         capacity: the samples of a whole run of `duration`.  Call after define(); single device only (row blocks raise
         NotImplementedError); a model with the zero-padded Laplacian is refused."""
         from .leads import LeadRecorder
-        if not self.defined:
-            raise AssertionError('record_leads should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return LeadRecorder(self, positions, tables, table_of=table_of, every=every, weight=weight, var=var, capacity=capacity)
+        return LeadRecorder(self._attachable('record_leads'), positions, tables, table_of=table_of, every=every, weight=weight, var=var, capacity=capacity)
 
     def record_waves(self, level=None, kind='above', every=1, conn=4, mask=None, max_waves=256, capacity=None, var=0, also=None,
                      links=False, max_links=None):
@@ -326,12 +306,7 @@ class IonicModel:
         choose `every` so that a wave overlaps itself from one sample to the next.  Call after define(); single
         device only (row blocks raise NotImplementedError)."""
         from .waves import WaveRecorder
-        if not self.defined:
-            raise AssertionError('record_waves should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return WaveRecorder(self, level=level, kind=kind, every=every, conn=conn, mask=mask, max_waves=max_waves, capacity=capacity,
+        return WaveRecorder(self._attachable('record_waves'), level=level, kind=kind, every=every, conn=conn, mask=mask, max_waves=max_waves, capacity=capacity,
                             var=var, also=also, links=links, max_links=max_links)
 
     def record_spectrum(self, every=10, nfft=128, fmin=None, fmax=None, bins=None, window='hann', chunk=None, var=0, block=(1, 1),
@@ -346,12 +321,7 @@ class IonicModel:
         no result.  `power()`, `dominant_frequency()` and `peak_maps()` read the maps; nothing else leaves the device.  Call
         after define(); single device only (row blocks raise NotImplementedError)."""
         from .spectrum import SpectrumRecorder
-        if not self.defined:
-            raise AssertionError('record_spectrum should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return SpectrumRecorder(self, every=every, nfft=nfft, fmin=fmin, fmax=fmax, bins=bins, window=window, chunk=chunk, var=var,
+        return SpectrumRecorder(self._attachable('record_spectrum'), every=every, nfft=nfft, fmin=fmin, fmax=fmax, bins=bins, window=window, chunk=chunk, var=var,
                                 block=block, reduce=reduce, region=region, weight=weight)
 
     def record_beats(self, every=10, depth=8, up=None, down=None, var=0, region=None, block=(1, 1), reduce='mean', weight=None):
@@ -365,12 +335,7 @@ class IonicModel:
         Between two samples the handle keeps its multi-tick launches.  Call after define(); single device only (row blocks
         raise NotImplementedError)."""
         from .beats import BeatRecorder
-        if not self.defined:
-            raise AssertionError('record_beats should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return BeatRecorder(self, every=every, depth=depth, up=up, down=down, var=var, region=region, block=block, reduce=reduce,
+        return BeatRecorder(self._attachable('record_beats'), every=every, depth=depth, up=up, down=down, var=var, region=region, block=block, reduce=reduce,
                             weight=weight)
 
     def program_stimuli(self, stimuli):
@@ -381,12 +346,7 @@ class IonicModel:
         where `for i in model.run(): if i == s2: model.fire_op('s2')` puts it.  add_pace_op / fire_op work as ever, also while
         a program is attached.  Call after define(); single device only (row blocks raise NotImplementedError)."""
         from .stimulus import StimulusProgram
-        if not self.defined:
-            raise AssertionError('program_stimuli should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return StimulusProgram(self, stimuli)
+        return StimulusProgram(self._attachable('program_stimuli'), stimuli)
 
     def program_lesions(self, lesions):
         """attaches a lesion program (fib_tf_amd/lesions.py) to this model's handle: a list of `Lesion` entries — a site
@@ -398,24 +358,14 @@ class IonicModel:
         `model.phase` becomes the field as it now is.  Call after define(); single device only (row blocks raise
         NotImplementedError); a model with the zero-padded Laplacian is refused."""
         from .lesions import LesionProgram
-        if not self.defined:
-            raise AssertionError('program_lesions should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return LesionProgram(self, lesions)
+        return LesionProgram(self._attachable('program_lesions'), lesions)
 
     def ablate(self, site):
         """one lesion NOW, at the state the loop has reached (the immediate form of program_lesions: what a host-side closed
         loop uses — read rec.tips(), then ablate there).  Works with or without a program, beside every recorder; updates
         `model.phase` to the field as it now is.  Returns the box (r0, r1, c0, c1) that was visited."""
         from .lesions import ablate
-        if not self.defined:
-            raise AssertionError('ablate should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)
-        if ensure is not None:
-            ensure()
-        return ablate(self, site)
+        return ablate(self._attachable('ablate'), site)
 
     def trigger_stimuli(self, rules, every=1, capacity=None):
         """attaches a trigger program (fib_tf_amd/triggers.py) to this model's handle: a list of `Trigger` rules — a `Sensor`
@@ -427,12 +377,7 @@ class IonicModel:
         Default capacity: the samples of a whole run of `duration`.  Call after define(); single device only (row blocks raise
         NotImplementedError)."""
         from .triggers import TriggerProgram
-        if not self.defined:
-            raise AssertionError('trigger_stimuli should be called after calling define')
-        ensure = getattr(self, '_ensure_compiled', None)      # a traced model (traced.py) compiles on first use
-        if ensure is not None:
-            ensure()
-        return TriggerProgram(self, rules, every=every, capacity=capacity)
+        return TriggerProgram(self._attachable('trigger_stimuli'), rules, every=every, capacity=capacity)
 
     def _frame_levels(self):
         """(lo, span) with image() == (X - lo) / span in float32, X the array pot() names: what a frame recorder maps the

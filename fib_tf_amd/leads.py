@@ -13,6 +13,7 @@ above the sheet; a finite-size electrode or a far-field ECG lead is any other fi
 import numpy as np
 
 from ._lib import MAX_LEAD_TABLES, MAX_LEADS
+from ._recorder import SampledRecorder, array_index, attach, check_every, run_capacity, sample_times, tick_ms, weight_plane
 
 
 def point_table(h, w, z, dx=1.0):
@@ -72,7 +73,7 @@ def _zero_padded(model):
     return isinstance(c, dict) and 'ZEROPAD = true' in c.get('source', '')
 
 
-class LeadRecorder:
+class LeadRecorder(SampledRecorder):
     """unipolar electrograms recorded on the device; see `IonicModel.record_leads`.
 
         tab = leads.point_table(m.height, m.width, z=2.0)
@@ -84,58 +85,23 @@ class LeadRecorder:
 
     `times_ms()` is the model time since the recorder was attached at which a sample was taken: (s + 1) * every ticks of
     `dt_per_step * dt` ms."""
+    NOUN, END, COUNT = 'lead recorder', 'leads_end', 'leads_count'
 
     def __init__(self, model, positions, tables, table_of=None, every=1, weight='phase', var=0, capacity=None):
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('record_leads should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('record_leads: electrograms are recorded on a single device only; this model runs as row '
-                                      'blocks over %d ranks' % st.world)
+        self._st = st = attach(model, 'record_leads', 'electrograms are recorded')
         if _zero_padded(model):
             raise ValueError('record_leads: not on a model with the zero-padded Laplacian (ZEROPAD): its diffusion term is not this source')
-        H, W = model.height, model.width
-        self.pos, self.tables = parse_leads(positions, tables, table_of, H, W)
-        self.every = int(every)
-        if self.every < 1:
-            raise ValueError('record_leads: every must be >= 1')
-        if isinstance(var, str):
-            if var not in model.VAR_NAMES:
-                raise ValueError('record_leads: unknown array %r (the model has %s)' % (var, ', '.join(model.VAR_NAMES)))
-            var = model.VAR_NAMES.index(var)
-        self.var = int(var)
-        if isinstance(weight, str):
-            if weight != 'phase':
-                raise ValueError("record_leads: weight is 'phase', None or an [height, width] array")
-            weight = getattr(model, 'phase', None)
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, np.float32)
-            if weight.shape != (H, W):
-                raise ValueError('record_leads: a weight plane of shape %s on a %d x %d grid' % (weight.shape, H, W))
-            if not np.all(np.isfinite(weight)):
-                raise ValueError('record_leads: the weight plane has a value that is not finite')
-        self.weight = weight
+        self.pos, self.tables = parse_leads(positions, tables, table_of, model.height, model.width)
+        self.every = check_every('record_leads', every)
+        self.var = array_index(model.VAR_NAMES, var, 'record_leads', check_range=False)      # (an index is the library's to refuse)
+        self.weight = weight = weight_plane(model, weight, 'record_leads', finite=True)
         self.scale = float(getattr(model, 'diff', 1.0))
-        self.tick_ms = float(model.dt_per_step * model.dt)
-        if capacity is None:                     # the samples of a whole run of model.duration (whatever has run already), at least 1
-            ticks = int(model.duration / (model.dt_per_step * model.dt))
-            capacity = max(1, ticks // self.every)
-        self.capacity = int(capacity)
+        self.tick_ms = tick_ms(model)
+        self.capacity = int(run_capacity(model, self.every) if capacity is None else capacity)
         if self.capacity < 1:
             raise ValueError('record_leads: capacity must be >= 1')
-        self._st = st
         st.leads_begin(self.pos, self.tables, weight, self.var, self.every, self.capacity)
         self.open = True
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the lead recorder has been closed')
-
-    def count(self):
-        """samples taken since the recorder was attached"""
-        self._check()
-        return self._st.leads_count()
 
     def raw(self, first=0, count=None):
         """float64 [samples, electrodes] exactly as the device wrote it"""
@@ -159,18 +125,4 @@ class LeadRecorder:
         return t[:, pairs[:, 0]] - t[:, pairs[:, 1]]
 
     def times_ms(self, first=0, count=None):
-        n = self.count() - int(first) if count is None else int(count)
-        return (int(first) + 1 + np.arange(max(n, 0))) * self.every * self.tick_ms
-
-    def close(self):
-        """detaches the recorder and frees the trace"""
-        if self.open:
-            self.open = False
-            self._st.leads_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
+        return sample_times(first, self._span(first, count), self.every, self.tick_ms)

@@ -17,6 +17,7 @@ the ticks, and the lead recorder's source term — see the new geometry from the
 import numpy as np
 
 from ._lib import MAX_LESION_ENTRIES, MAX_STIM_PLANES
+from ._recorder import DeviceRecorder, attach, tick_ms
 
 FLOOR = np.float32(1e-5)
 
@@ -133,20 +134,14 @@ def expand(entries, n_ticks):
 
 def _device_stepper(model, who):
     from .leads import _zero_padded
-    from .sharded import ShardedStepper
-    st = model._stepper
-    if st is None:
-        raise AssertionError('%s should be called after calling define' % who)
-    if isinstance(st, ShardedStepper):
-        raise NotImplementedError('%s: the geometry changes on a single device only; this model runs as row blocks over %d ranks'
-                                  % (who, st.world))
+    st = attach(model, who, 'the geometry changes')
     if _zero_padded(model) or getattr(model, 'ZEROPAD', False):
         raise ValueError('%s: not on a model with the zero-padded Laplacian (ZEROPAD): its diffusion term has no phase field' % who)
     check_field(model.phase)
     return st
 
 
-class LesionProgram:
+class LesionProgram(DeviceRecorder):
     """a lesion program attached to a model's handle; see `IonicModel.program_lesions`.
 
         tips = model.record_tips()
@@ -157,19 +152,16 @@ class LesionProgram:
         # model.phase is the field as it now is
 
     Tick 0 is the first tick after the program was attached.  `events(n)` is the host-side expansion of the program."""
+    NOUN, END = 'lesion program', 'lesion_end'
 
     def __init__(self, model, lesions):
         st = _device_stepper(model, 'program_lesions')
         self.lesions = list(lesions)
         self.entries = compile_program(model, self.lesions)
-        self.tick_ms = float(model.dt_per_step * model.dt)
+        self.tick_ms = tick_ms(model)
         self._model, self._st = model, st
         st.lesion_begin(self.entries)
         self.open = True
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the lesion program has been closed')
 
     def events(self, n_ticks):
         """[(tick, entry index)] the program applies during the first n_ticks ticks (pure Python: no device)"""
@@ -194,13 +186,6 @@ class LesionProgram:
             self.open = False                         # (only now: had either call raised, the program would still be attached)
 
     close = end
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.end()
-        return False
 
 
 def ablate(model, site):

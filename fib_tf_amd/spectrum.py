@@ -8,6 +8,8 @@ the maps come back.  The definition is exact (include/fib
 tests/spectrum_ref.py): segments of `nfft` samples without overlap and without detrending, a window the caller supplies."""
 import numpy as np
 
+from ._recorder import DeviceRecorder, attach, check_every, tick_ms, weight_plane
+
 MAX_BINS, MAX_CHUNK, MIN_NFFT, MAX_NFFT = 128, 32, 4, 65536      # include/fibhip.h FIBHIP_SPECTRUM_*
 
 
@@ -68,8 +70,7 @@ def bins_from_band(fmin, fmax, nfft, every, tick_ms):
 
 def check_args(every, nfft, bins, chunk, block, reduce):
     """the refusals that need no device: raises ValueError"""
-    if int(every) < 1:
-        raise ValueError('record_spectrum: every must be >= 1')
+    check_every('record_spectrum', every)
     if not MIN_NFFT <= int(nfft) <= MAX_NFFT:
         raise ValueError('record_spectrum: nfft must be %d .. %d (got %d)' % (MIN_NFFT, MAX_NFFT, nfft))
     if not 1 <= int(chunk) <= MAX_CHUNK or int(nfft) % int(chunk):
@@ -134,7 +135,7 @@ def dominant_from_maps(kpeak, pband, pnear, freqs, power=None, refine=False):
     return df, reg
 
 
-class SpectrumRecorder:
+class SpectrumRecorder(DeviceRecorder):
     """per-cell power spectra folded on the device; see `IonicModel.record_spectrum`.
 
         with model.record_spectrum(every=10, nfft=128, fmin=2, fmax=30) as rec:
@@ -145,18 +146,13 @@ class SpectrumRecorder:
     `power()` returns float64 [nb, oh, ow], the mean periodogram over the finished segments; `freqs()` the Hz of each recorded
     bin.  There is no detrending: with the periodic Hann window a constant leaks into bins 0 and +-1 only, so the band defaults
     to the frequency indices >= 2."""
+    NOUN, END = 'spectrum recorder', 'spectrum_end'
 
     def __init__(self, model, every=10, nfft=128, fmin=None, fmax=None, bins=None, window='hann', chunk=None, var=0, block=(1, 1),
                  reduce='mean', region=None, weight=None):
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('record_spectrum should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('record_spectrum: spectra are recorded on a single device only; this model '
-                                      'runs as row blocks over %d ranks' % st.world)
+        self._st = st = attach(model, 'record_spectrum', 'spectra are recorded')
         self.every, self.nfft, self.var = int(every), int(nfft), int(var)
-        self.tick_ms = float(model.dt_per_step * model.dt)
+        self.tick_ms = tick_ms(model)
         self.chunk = default_chunk(self.nfft) if chunk is None else int(chunk)
         self.block = tuple(int(b) for b in block)
         self.reduce = reduce
@@ -167,25 +163,12 @@ class SpectrumRecorder:
         self.window = (0, model.height, 0, model.width) if region is None else tuple(int(v) for v in region)
         self.win = window_table(window, self.nfft)
         self.tw = twiddle_table(self.nfft)
-        if isinstance(weight, str):
-            if weight != 'phase':
-                raise ValueError("record_spectrum: weight is 'phase', None or an [height, width] array")
-            weight = getattr(model, 'phase', None)
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, np.float32)
-            if weight.shape != (model.height, model.width):
-                raise ValueError('record_spectrum: a weight plane of shape %s on a %d x %d grid' % (weight.shape, model.height, model.width))
-        self.weight = weight
-        self._st = st
+        self.weight = weight = weight_plane(model, weight, 'record_spectrum')
         st.spectrum_begin(self.var, self.window, self.block, self.reduce, weight, self.every, self.nfft, self.win, self.tw, self.bins,
                           self.chunk)
         oh, ow, _ = st.spectrum_shape()
         self.shape = (oh, ow)
         self.open = True
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the spectrum recorder has been closed')
 
     def freqs(self):
         """float64 [nb]: Hz per recorded bin, k / (nfft * every * tick_ms * 1e-3)"""
@@ -227,16 +210,3 @@ class SpectrumRecorder:
         kpeak, _, pband, pnear = self.peak_maps(fmin, fmax, halfwidth)
         power = self.raw()[0] if refine else None
         return dominant_from_maps(kpeak, pband, pnear, self.freqs(), power, refine)
-
-    def close(self):
-        """detaches the recorder and frees its planes"""
-        if self.open:
-            self.open = False
-            self._st.spectrum_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False

@@ -14,6 +14,7 @@ from collections import namedtuple
 import numpy as np
 
 from ._lib import MAX_STAT_COLS, MAX_STAT_COLS_PER_ARRAY
+from ._recorder import SampledRecorder, array_index, attach, check_every, mask_plane, run_capacity, sample_times, tick_ms, weight_plane
 
 # Python kind -> (device kind, what the host divides the device's value by: None, the sum of the weights, the masked cells)
 KINDS = {'sum': ('sum', None), 'min': ('min', None), 'max': ('max', None), 'below': ('below', None), 'above': ('above', None),
@@ -37,14 +38,7 @@ def parse_columns(columns, var_names):
         if isinstance(c, (str, int)) or not 2 <= len(c) <= 3:
             raise ValueError('record_stats: a column is (array, kind) or (array, kind, level), got %r' % (c,))
         arr, kind = c[0], c[1]
-        if isinstance(arr, str):
-            if arr not in var_names:
-                raise ValueError('record_stats: unknown array %r (the model has %s)' % (arr, ', '.join(var_names)))
-            var = var_names.index(arr)
-        else:
-            var = int(arr)
-            if not 0 <= var < len(var_names):
-                raise ValueError('record_stats: array index %d outside 0 .. %d' % (var, len(var_names) - 1))
+        var = array_index(var_names, arr, 'record_stats')
         if kind not in KINDS:
             raise ValueError('record_stats: unknown kind %r (one of %s)' % (kind, ', '.join(sorted(KINDS))))
         if kind in NEED_LEVEL:
@@ -100,7 +94,7 @@ def make_table(raw, cols, wsum, cells, every, tick_ms, first=0):
     """structured array: t_ms (model time since attach of sample first, first + 1, ...) + one float64 field per column"""
     vals = finish(raw, cols, wsum, cells)
     t = np.empty(len(vals), table_dtype(cols))
-    t['t_ms'] = (int(first) + 1 + np.arange(len(vals))) * int(every) * float(tick_ms)
+    t['t_ms'] = sample_times(first, len(vals), int(every), float(tick_ms))
     for j, c in enumerate(cols):
         t[c.field] = vals[:, j]
     return t
@@ -132,7 +126,7 @@ def check_finite(raw, cols, cells, every, tick_ms, first=0):
                                  % (sample, tick, (tick + 1) * float(tick_ms), cols[j].field, float(np.asarray(raw).reshape(-1, len(cols))[s, j])))
 
 
-class StatsRecorder:
+class StatsRecorder(SampledRecorder):
     """tissue statistics recorded on the device; see `IonicModel.record_stats`.
 
         with model.record_stats([('V', 'mean'), ('_Na_i_', 'mean'), ('V', 'frac_below', -55.0), ('V', 'nonfinite')], every=10) as rec:
@@ -143,54 +137,21 @@ class StatsRecorder:
 
     `t_ms` is the model time since the recorder was attached at which the sample was taken: (s + 1) * every ticks of
     `dt_per_step * dt` ms.  'sum' and 'mean' weigh with `weight`; every other kind looks at the cells of `mask`."""
+    NOUN, END, COUNT = 'statistics recorder', 'stats_end', 'stats_count'
 
     def __init__(self, model, columns, every=1, weight='phase', mask=None, capacity=None):
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('record_stats should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('record_stats: tissue statistics are recorded on a single device only; this model '
-                                      'runs as row blocks over %d ranks' % st.world)
+        self._st = st = attach(model, 'record_stats', 'tissue statistics are recorded')
         self.columns = parse_columns(columns, model.VAR_NAMES)
-        self.every = int(every)
-        if self.every < 1:
-            raise ValueError('record_stats: every must be >= 1')
-        H, W = model.height, model.width
-        if isinstance(weight, str):
-            if weight != 'phase':
-                raise ValueError("record_stats: weight is 'phase', None or an [height, width] array")
-            weight = getattr(model, 'phase', None)
-        if weight is not None:
-            weight = np.ascontiguousarray(weight, np.float32)
-            if weight.shape != (H, W):
-                raise ValueError('record_stats: a weight plane of shape %s on a %d x %d grid' % (weight.shape, H, W))
-        if mask is None and getattr(model, 'phase', None) is not None:
-            mask = np.asarray(model.phase) > 0.5              # inside a hole of the phase field the state is noise
-        if mask is not None:
-            mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-            if mask.shape != (H, W):
-                raise ValueError('record_stats: a mask of shape %s on a %d x %d grid' % (mask.shape, H, W))
-        self.weight, self.mask = weight, mask
-        self.weight_sum = weight_sum(weight, H * W)
-        self.cells = int(np.count_nonzero(mask)) if mask is not None else H * W
-        self.tick_ms = float(model.dt_per_step * model.dt)
-        if capacity is None:                     # the samples of a whole run of model.duration (whatever has run already), at least 1
-            ticks = int(model.duration / (model.dt_per_step * model.dt))
-            capacity = max(1, ticks // self.every)
-        self.capacity = int(capacity)
-        self._st = st
+        self.every = check_every('record_stats', every)
+        cells = model.height * model.width
+        self.weight = weight = weight_plane(model, weight, 'record_stats')
+        self.mask = mask = mask_plane(model, mask, 'record_stats')
+        self.weight_sum = weight_sum(weight, cells)
+        self.cells = int(np.count_nonzero(mask)) if mask is not None else cells
+        self.tick_ms = tick_ms(model)
+        self.capacity = int(run_capacity(model, self.every) if capacity is None else capacity)
         st.stats_begin(device_columns(self.columns), weight, mask, self.every, self.capacity)
         self.open = True
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the statistics recorder has been closed')
-
-    def count(self):
-        """samples taken since the recorder was attached"""
-        self._check()
-        return self._st.stats_count()
 
     def raw(self, first=0, count=None):
         """float64 [samples, ncols] exactly as the device wrote it: sums for 'mean', counts for the fractions"""
@@ -202,8 +163,7 @@ class StatsRecorder:
         return finish(self.raw(first, count), self.columns, self.weight_sum, self.cells)
 
     def times(self, first=0, count=None):
-        n = self.count() - int(first) if count is None else int(count)
-        return (int(first) + 1 + np.arange(max(n, 0))) * self.every * self.tick_ms
+        return sample_times(first, self._span(first, count), self.every, self.tick_ms)
 
     def table(self, first=0, count=None):
         """structured array: t_ms + one float64 field per column, named '<array>_<kind>'"""
@@ -212,16 +172,3 @@ class StatsRecorder:
     def check_finite(self):
         """raises FloatingPointError naming the first sample / tick whose row shows a value that is not finite"""
         check_finite(self.raw(), self.columns, self.cells, self.every, self.tick_ms)
-
-    def close(self):
-        """detaches the recorder and frees the table"""
-        if self.open:
-            self.open = False
-            self._st.stats_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False

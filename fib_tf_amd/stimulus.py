@@ -12,6 +12,7 @@ import math
 import numpy as np
 
 from ._lib import MAX_STIM_ENTRIES, MAX_STIM_PLANES, STIM_MODES
+from ._recorder import DeviceRecorder, array_index, attach, tick_ms
 
 _DEFAULT = object()
 
@@ -112,15 +113,7 @@ class Stimulus:
         return ('plane', np.ascontiguousarray(a, np.float32))
 
     def var_index(self, model):
-        names = tuple(model.VAR_NAMES)
-        if isinstance(self.var, str):
-            if self.var not in names:
-                raise ValueError('Stimulus: unknown array %r (the model has %s)' % (self.var, ', '.join(names)))
-            return names.index(self.var)
-        var = int(self.var)
-        if not 0 <= var < len(names):
-            raise ValueError('Stimulus: array index %d outside 0 .. %d' % (var, len(names) - 1))
-        return var
+        return array_index(model.VAR_NAMES, self.var, 'Stimulus')
 
 
 def check_timing(first, period, count, hold):
@@ -188,7 +181,7 @@ def expand(entries, n_ticks):
     return [(k, i) for k in range(int(n_ticks)) for i, e in enumerate(entries) if entry_due(e, k)]
 
 
-class StimulusProgram:
+class StimulusProgram(DeviceRecorder):
     """a stimulus program attached to a model's handle; see `IonicModel.program_stimuli`.
 
         with model.program_stimuli(s1s2('left', 1.0, s1_ms=300, n_s1=5, s2_ms=190, s2_site=('disc', 90, 100, 12))) as prog:
@@ -197,25 +190,15 @@ class StimulusProgram:
             print(prog.applied())
 
     Tick 0 is the first tick after the program was attached.  `events(n)` is the host-side expansion of the program."""
+    NOUN, END = 'stimulus program', 'stim_end'
 
     def __init__(self, model, stimuli):
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('program_stimuli should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('program_stimuli: a stimulus program runs on a single device only; this model '
-                                      'runs as row blocks over %d ranks' % st.world)
+        self._st = st = attach(model, 'program_stimuli', 'a stimulus program runs')
         self.stimuli = list(stimuli)
         self.entries, self.planes = compile_program(model, self.stimuli)
-        self.tick_ms = float(model.dt_per_step * model.dt)
-        self._st = st
+        self.tick_ms = tick_ms(model)
         st.stim_begin(self.entries, self.planes)
         self.open = True
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the stimulus program has been closed')
 
     def events(self, n_ticks):
         """[(tick, entry index)] the program applies during the first n_ticks ticks (pure Python: no device)"""
@@ -225,19 +208,6 @@ class StimulusProgram:
         """events applied since the program was attached"""
         self._check()
         return self._st.stim_count()
-
-    def close(self):
-        """detaches the program"""
-        if self.open:
-            self.open = False
-            self._st.stim_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
 # ---- protocols ------------------------------------------------------------------------------------------------------

@@ -10,13 +10,15 @@ from collections import namedtuple
 
 import numpy as np
 
+from ._recorder import SampledRecorder, attach, check_every, mask_plane, run_capacity, tick_ms
+
 TIP_DTYPE = np.dtype([('t_ms', np.float64), ('y', np.float32), ('x', np.float32), ('charge', np.int32)])
 POINT_DTYPE = np.dtype([('t_ms', np.float64), ('y', np.float32), ('x', np.float32)])
 
 Trajectory = namedtuple('Trajectory', ['charge', 'points'])     # points: structured (t_ms, y, x), one per sample it lived
 
 
-class TipRecorder:
+class TipRecorder(SampledRecorder):
     """spiral tips recorded on the device; see `IonicModel.record_tips`.
 
         with model.record_tips(every=10) as rec:
@@ -29,15 +31,10 @@ class TipRecorder:
     `dt_per_step * dt` ms.  `y`, `x` are plaquette centres (row + 0.5, column + 0.5).  At most `max_tips` tips are kept per
     sample (`truncated()` names the samples that had more); `counts()` is exact regardless.  Between two samples the handle
     keeps its multi-tick launches."""
+    NOUN, END, COUNT = 'tip recorder', 'tips_end', 'tips_count'
 
     def __init__(self, model, var2=None, levels=None, every=1, max_tips=256, capacity=None, var=0, mask=None):
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('record_tips should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('record_tips: spiral tips are recorded on a single device only; this model '
-                                      'runs as row blocks over %d ranks' % st.world)
+        self._st = st = attach(model, 'record_tips', 'spiral tips are recorded')
         signals = getattr(model, 'tip_signals', None)
         if var2 is None or levels is None:
             if signals is None:
@@ -52,34 +49,13 @@ class TipRecorder:
                 levels = (signals[2], signals[3])
         self.var, self.var2 = int(var), int(var2)
         self.levels = (float(levels[0]), float(levels[1]))
-        self.every = int(every)
-        if self.every < 1:
-            raise ValueError('record_tips: every must be >= 1')
+        self.every = check_every('record_tips', every)
         self.max_tips = int(max_tips)
-        self.tick_ms = float(model.dt_per_step * model.dt)
-        if capacity is None:                     # the samples of a whole run of model.duration (whatever has run already), at least 1
-            ticks = int(model.duration / (model.dt_per_step * model.dt))
-            capacity = max(1, ticks // self.every)
-        self.capacity = int(capacity)
-        if mask is None and getattr(model, 'phase', None) is not None:
-            mask = np.asarray(model.phase) > 0.5             # inside a hole of the phase field the state is noise
-        if mask is not None:
-            mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-            if mask.shape != (model.height, model.width):
-                raise ValueError('record_tips: a mask of shape %s on a %d x %d grid' % (mask.shape, model.height, model.width))
-        self.mask = mask
-        self._st = st
+        self.tick_ms = tick_ms(model)
+        self.capacity = int(run_capacity(model, self.every) if capacity is None else capacity)
+        self.mask = mask = mask_plane(model, mask, 'record_tips')
         st.tips_begin(self.var, self.var2, self.levels[0], self.levels[1], mask, self.every, self.max_tips, self.capacity)
         self.open = True
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the tip recorder has been closed')
-
-    def count(self):
-        """samples taken since the recorder was attached"""
-        self._check()
-        return self._st.tips_count()
 
     def counts(self, first=0, count=None):
         """int32 [samples, 3]: n_pos, n_neg, stored of every sample taken so far (exact even where the list was cut)"""
@@ -105,19 +81,6 @@ class TipRecorder:
             a['charge'] = r[:, 2]
             out.append(a)
         return out
-
-    def close(self):
-        """detaches the recorder and frees the lists"""
-        if self.open:
-            self.open = False
-            self._st.tips_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
 def link(tips_per_sample, max_jump):

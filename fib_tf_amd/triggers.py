@@ -10,6 +10,7 @@ definition is exact integer arithmetic (include/fibhip.h, fibhip_trig_*; restate
 import numpy as np
 
 from ._lib import MAX_TRIG_RULES, MAX_TRIG_SENSORS, TRIG_EDGES, TRIG_FIELDS, TRIG_MAX_TIME
+from ._recorder import DeviceRecorder, attach, run_capacity, tick_ms
 from .stimulus import _DEFAULT, Stimulus, check_timing
 
 CAUSES = (None, 'edge', 'escape')
@@ -158,7 +159,7 @@ def compile_program(model, rules, every):
     return sensors, out, planes
 
 
-class TriggerProgram:
+class TriggerProgram(DeviceRecorder):
     """a trigger program attached to a model's handle; see `IonicModel.trigger_stimuli`.
 
         with model.trigger_stimuli(s2_on_waveback(probe, 'luq', 1.0, level=0.2, delay_ms=20), every=10) as prog:
@@ -167,29 +168,21 @@ class TriggerProgram:
             print(prog.fired())
 
     Sample s follows tick (s + 1) * every - 1; tick 0 is the first tick after the program was attached."""
+    NOUN, END = 'trigger program', 'trig_end'
 
     def __init__(self, model, rules, every=1, capacity=None):
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('trigger_stimuli should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('trigger_stimuli: a trigger program runs on a single device only; this model '
-                                      'runs as row blocks over %d ranks' % st.world)
+        self._st = st = attach(model, 'trigger_stimuli', 'a trigger program runs')
         self.triggers, self.every = list(rules), int(every)
         self.sensors, self.rules, self.planes = compile_program(model, self.triggers, self.every)
-        if capacity is None:
-            capacity = max(1, int(model.duration / (model.dt_per_step * model.dt)) // self.every)     # a whole run of `duration`
-        self.capacity = int(capacity)
-        self.tick_ms = float(model.dt_per_step * model.dt)
-        self._st = st
+        self.capacity = int(run_capacity(model, self.every) if capacity is None else capacity)
+        self.tick_ms = tick_ms(model)
         st.trig_begin(self.sensors, self.rules, self.planes, every=self.every, capacity=self.capacity)
         self.open = True
         self._kept = None
 
     def _check(self):
-        if not self.open and self._kept is None:
-            raise AssertionError('the trigger program has been closed')
+        if self._kept is None:                   # (closed with its log kept: the readers go on)
+            super()._check()
 
     def samples(self):
         """samples taken so far"""
@@ -251,15 +244,7 @@ class TriggerProgram:
         """detaches the program (the log read so far stays readable)"""
         if self.open:
             self._kept = self._st.trig_read()
-            self.open = False
-            self._st.trig_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
+            super().close()
 
 
 # ---- protocols ------------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ counts and into a genealogy of the waves — plain NumPy on the lists, nothing o
 import numpy as np
 
 from ._lib import MAX_WAVE_LINKS, MAX_WAVES, WAVE_KINDS
+from ._recorder import SampledRecorder, attach, check_every, mask_plane, run_capacity, sample_times, tick_ms
 
 WAVE_DTYPE = np.dtype([('t_ms', np.float64), ('seed', np.int32), ('area', np.int32), ('cy', np.float64), ('cx', np.float64),
                        ('r0', np.int32), ('r1', np.int32), ('c0', np.int32), ('c1', np.int32)])
@@ -61,7 +62,7 @@ def default_mask(model):
     return mask
 
 
-class WaveRecorder:
+class WaveRecorder(SampledRecorder):
     """excited domains recorded on the device; see `IonicModel.record_waves`.
 
         with model.record_waves(every=10) as rec:
@@ -74,17 +75,12 @@ class WaveRecorder:
     `t_ms` is the model time since the recorder was attached at which the sample was taken: (s + 1) * every ticks of
     `dt_per_step * dt` ms.  At most `max_waves` waves are kept per sample (`truncated()` names the samples that had more);
     `counts()` is exact regardless."""
+    NOUN, END, COUNT = 'wave recorder', 'waves_end', 'waves_count'
 
     def __init__(self, model, level=None, kind='above', every=1, conn=4, mask=None, max_waves=256, capacity=None, var=0, also=None,
                  links=False, max_links=None):
         from .activation import default_thresholds
-        from .sharded import ShardedStepper
-        st = model._stepper
-        if st is None:
-            raise AssertionError('record_waves should be called after calling define')
-        if isinstance(st, ShardedStepper):
-            raise NotImplementedError('record_waves: waves are labelled on a single device only; this model runs as row '
-                                      'blocks over %d ranks' % st.world)
+        self._st = st = attach(model, 'record_waves', 'waves are labelled')
         self.var = _array_index(model, var, 'var')
         self.kind = _kind_index(kind, 'kind')
         if level is None:
@@ -100,9 +96,7 @@ class WaveRecorder:
         self.conn = int(conn)
         if self.conn not in (4, 8):
             raise ValueError('record_waves: conn is 4 or 8 (got %r)' % (conn,))
-        self.every = int(every)
-        if self.every < 1:
-            raise ValueError('record_waves: every must be >= 1')
+        self.every = check_every('record_waves', every)
         self.max_waves = int(max_waves)
         if not 1 <= self.max_waves <= MAX_WAVES:
             raise ValueError('record_waves: max_waves is 1 .. %d (got %d)' % (MAX_WAVES, self.max_waves))
@@ -111,20 +105,11 @@ class WaveRecorder:
             self.max_links = min(2 * self.max_waves, MAX_WAVE_LINKS) if max_links is None else int(max_links)
             if not 1 <= self.max_links <= MAX_WAVE_LINKS:
                 raise ValueError('record_waves: max_links is 1 .. %d (got %d)' % (MAX_WAVE_LINKS, self.max_links))
-        self.tick_ms = float(model.dt_per_step * model.dt)
-        if capacity is None:                     # the samples of a whole run of model.duration (whatever has run already), at least 1
-            ticks = int(model.duration / (model.dt_per_step * model.dt))
-            capacity = max(1, ticks // self.every)
-        self.capacity = int(capacity)
+        self.tick_ms = tick_ms(model)
+        self.capacity = int(run_capacity(model, self.every) if capacity is None else capacity)
         if self.capacity < 1:
             raise ValueError('record_waves: capacity must be >= 1')
-        if mask is None:
-            mask = default_mask(model)
-        mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-        if mask.shape != (model.height, model.width):
-            raise ValueError('record_waves: a mask of shape %s on a %d x %d grid' % (mask.shape, model.height, model.width))
-        self.mask = mask
-        self._st = st
+        self.mask = mask = mask_plane(model, default_mask(model) if mask is None else mask, 'record_waves')
         st.waves_begin(self.var, self.kind, self.level, self.var2, self.kind2, self.level2, self.conn, mask, self.max_waves, self.every,
                        self.capacity)
         self.open = True
@@ -134,15 +119,6 @@ class WaveRecorder:
             except Exception:
                 self.close()
                 raise
-
-    def _check(self):
-        if not self.open:
-            raise AssertionError('the wave recorder has been closed')
-
-    def count(self):
-        """samples taken since the recorder was attached"""
-        self._check()
-        return self._st.waves_count()
 
     def counts(self, first=0, count=None):
         """int32 [samples, 3]: n (waves), stored (records kept), cells (set cells) of every sample; exact even where the list was cut"""
@@ -232,21 +208,7 @@ class WaveRecorder:
         return self._st.waves_labels()
 
     def times_ms(self, first=0, count=None):
-        n = self.count() - int(first) if count is None else int(count)
-        return (int(first) + 1 + np.arange(max(n, 0))) * self.every * self.tick_ms
-
-    def close(self):
-        """detaches the recorder and frees the lists"""
-        if self.open:
-            self.open = False
-            self._st.waves_end()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
+        return sample_times(first, self._span(first, count), self.every, self.tick_ms)
 
 
 # ---- what the links say: events and tracks (host code on the lists) --------------------------------------------------------------
