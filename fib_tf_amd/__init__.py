@@ -16,6 +16,7 @@ from . import frames                            # noqa: F401  (FrameRecorder: th
 from . import stats                             # noqa: F401  (StatsRecorder: tissue statistics recorded on the device)
 from . import spectrum                          # noqa: F401  (SpectrumRecorder: per-cell power spectra and dominant-frequency maps)
 from . import beats                             # noqa: F401  (BeatRecorder: per-cell beat history, restitution and alternans maps)
+from . import velocity                          # noqa: F401  (conduction-velocity maps and CV restitution, fitted on the device)
 from . import leads                             # noqa: F401  (LeadRecorder: unipolar electrograms from the membrane current)
 from . import waves                             # noqa: F401  (WaveRecorder: excited domains labelled and counted on the device)
 from . import stimulus                        # noqa: F401  (Stimulus, StimulusProgram: pacing protocols run on the device)

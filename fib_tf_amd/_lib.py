@@ -20,6 +20,7 @@ FRAME_REDUCE = ('point', 'mean')                                  # enum fibhip_
 FRAME_FORMAT = ('float32', 'uint8')                               # enum fibhip_frame_format, in order
 SPECTRUM_MAX_BINS, SPECTRUM_MAX_CHUNK, SPECTRUM_MIN_NFFT, SPECTRUM_MAX_NFFT = 128, 32, 4, 65536
 BEATS_MAX_DEPTH = 16
+VEL_MAX_RADIUS = 4                                                # FIBHIP_VEL_MAX_RADIUS
 STAT_KINDS = ('sum', 'min', 'max', 'below', 'above', 'nonfinite')  # enum fibhip_stat_kind, in order
 MAX_STAT_COLS, MAX_STAT_COLS_PER_ARRAY = 64, 8
 MAX_LEADS, MAX_LEAD_TABLES = 64, 4
@@ -261,6 +262,10 @@ SYMBOLS = {
     'fibhip_beats_read': ([_h, _fp, _fp, _fp, _ip, _fp], C.c_int),
     'fibhip_beats_summary': ([_h, C.c_int, _ip, _fp, _fp, _fp], C.c_int),
     'fibhip_beats_end': ([_h], C.c_int),
+    'fibhip_beats_velocity': ([_h, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_ubyte), _ip, _fp, _fp, _fp], C.c_int),
+    'fibhip_observe_velocity': ([_h, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_ubyte), _ip, _fp, _fp, _fp], C.c_int),
+    'fibhip_velocity_fit': ([C.c_int, C.c_int, C.c_int, C.c_int, _fp, _ip, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_ubyte), _ip, _fp,
+                             _fp, _fp], C.c_int),
     'fibhip_stim_begin': ([_h, C.c_int, C.POINTER(StimEntry), C.c_int, _fp], C.c_int),
     'fibhip_stim_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_stim_end': ([_h], C.c_int),
@@ -539,6 +544,28 @@ def court_inter(V, fast=False, device=0):
     out = np.empty((len(COURT_INTER_KEYS), v.size), np.float32)
     check(lib().fibhip_court_inter(device, v.size, _ptr(v.reshape(-1)), int(fast), _ptr(out)))
     return {k: out[i].reshape(v.shape) for i, k in enumerate(COURT_INTER_KEYS)}
+
+
+def velocity_fit(t, count, back=0, radius=2, max_dt=20.0, min_cells=None, mask=None, device=0):
+    """the velocity fit (include/fibhip.h fibhip_velocity_fit) on host planes: `t` float32 [depth, oh, ow] in slot order, `count`
+    int32 [oh, ow], `mask` [oh, ow] (non-zero: the pixel counts) or None -> (nfit int32, gy, gx, rms float32), each [oh, ow]"""
+    t = _f32(t)
+    count = np.ascontiguousarray(count, np.int32)
+    if t.ndim != 3 or count.shape != t.shape[1:]:
+        raise ValueError('velocity_fit: t must be [depth, oh, ow] and count [oh, ow] (got %s and %s)' % (t.shape, count.shape))
+    depth, oh, ow = t.shape
+    if min_cells is None:
+        min_cells = (2 * int(radius) + 1) ** 2 // 2 + 1
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        if mask.shape != (oh, ow):
+            raise ValueError('velocity_fit: a mask of shape %s on a plane of shape %s' % (mask.shape, (oh, ow)))
+    nfit = np.empty((oh, ow), np.int32)
+    gy, gx, rms = (np.empty((oh, ow), np.float32) for _ in range(3))
+    check(lib().fibhip_velocity_fit(int(device), depth, oh, ow, _ptr(t), count.ctypes.data_as(_ip), int(back), int(radius),
+                                    float(np.float32(max_dt)), int(min_cells), None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                    nfit.ctypes.data_as(_ip), _ptr(gy), _ptr(gx), _ptr(rms)))
+    return nfit, gy, gx, rms
 
 
 from ._stepper_record import RecorderBindings           # noqa: E402  (down here: it imports the structs and constants above)

@@ -90,6 +90,14 @@ class RecorderBindings:
         stack = np.ascontiguousarray(np.stack([np.asarray(p, np.float32) for p in planes]), np.float32)
         return len(stack), stack.ctypes.data_as(_fp)
 
+    def _fit_maps(self, fn, first, shape, radius, max_dt, min_cells, mp):
+        """the four maps of a velocity fit: `first` is the call's own leading argument (back, or which plane)"""
+        nf = np.empty(shape, np.int32)
+        gy, gx, rms = (np.empty(shape, np.float32) for _ in range(3))
+        self._ck(fn(self._h, int(first), int(radius), float(np.float32(max_dt)), int(min_cells), mp, nf.ctypes.data_as(_ip),
+                    gy.ctypes.data_as(_fp), gx.ctypes.data_as(_fp), rms.ctypes.data_as(_fp)))
+        return nf, gy, gx, rms
+
     # ---- activation recorder (include/fibhip.h fibhip_observe_*) --------------------------------------------------
     def observe_begin(self, var, up, down):
         """attaches (or re-attaches, clearing the maps) the per-cell activation recorder on array `var`"""
@@ -105,6 +113,12 @@ class RecorderBindings:
     def observe_ticks(self):
         """ticks observed since observe_begin"""
         return self._count(self._L.fibhip_observe_ticks)
+
+    def observe_velocity(self, which, radius, max_dt, min_cells, mask=None):
+        """(nfit int32, gy, gx, rms float32), each [height, width]: the velocity fit on the time plane `which` ('first_up',
+        'last_up' or 'prev_up'); `mask`: [height, width], non-zero where a cell counts, or None"""
+        mp = self._plane('observe_velocity', 'mask', mask, np.uint8)
+        return self._fit_maps(self._L.fibhip_observe_velocity, OBS_MAPS.index(which), (self.height, self.width), radius, max_dt, min_cells, mp)
 
     def observe_end(self):
         self._ck(self._L.fibhip_observe_end(self._h))
@@ -283,6 +297,18 @@ class RecorderBindings:
         self._ck(self._L.fibhip_beats_summary(self._h, int(last), nu.ctypes.data_as(_ip), am.ctypes.data_as(_fp), cm.ctypes.data_as(_fp),
                                               al.ctypes.data_as(_fp)))
         return nu, am, cm, al
+
+    def beats_velocity(self, back, radius, max_dt, min_cells, mask=None):
+        """(nfit int32, gy, gx, rms float32), each [oh, ow]: the velocity fit on the beat `back` beats before every pixel's
+        newest; `mask`: [oh, ow] of the pixel plane, non-zero where a pixel counts, or None"""
+        oh, ow, _ = self.beats_shape()
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.shape != (oh, ow):
+                raise ValueError('beats_velocity: a mask of shape %s on a pixel plane of %d x %d' % (mask.shape, oh, ow))
+            mp = mask.ctypes.data_as(_ubp)
+        return self._fit_maps(self._L.fibhip_beats_velocity, back, (oh, ow), radius, max_dt, min_cells, mp)
 
     def beats_end(self):
         self._ck(self._L.fibhip_beats_end(self._h))

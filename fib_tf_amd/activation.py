@@ -51,6 +51,18 @@ class ActivationRecorder(DeviceRecorder):
         self._check()
         return {k: self._st.observe_get(k) for k in MAPS}
 
+    def velocity(self, which='last_up', radius=2, max_dt=20.0, min_cells=None, mask=None):
+        """{'nfit': int32, 'gy', 'gx', 'rms': float32}, each [H, W]: the plane fit of fib_tf_amd/velocity.py on the time map
+        `which` ('first_up', 'last_up' or 'prev_up'), made on the device — the gradient of activation time in ms per cell, its
+        residual and the cells that took part; velocity.speed_of and direction_of turn it into speed and direction.  `mask`:
+        [H, W], non-zero where a cell counts"""
+        from . import velocity as vel
+        self._check()
+        if which not in MAPS[:3]:
+            raise ValueError("velocity: which is 'first_up', 'last_up' or 'prev_up' (got %r)" % (which,))
+        radius, max_dt, min_cells = vel.check_args(radius, max_dt, min_cells, who='velocity')
+        return dict(zip(vel.MAPS, self._st.observe_velocity(which, radius, max_dt, min_cells, mask)))
+
 
 def conduction_velocity(t_map, row, c0, c1):
     """speed of a front crossing columns [c0, c1) of `row`, in pixels per ms: the least-squares slope of column against

@@ -17,6 +17,7 @@ restated in NumPy in tests/beat_ref.py).
 All times are milliseconds since the recorder was attached."""
 import numpy as np
 
+from . import velocity as _velocity
 from ._recorder import DeviceRecorder, attach, check_every, tick_ms, weight_plane
 
 MAX_DEPTH = 16                                   # include/fibhip.h FIBHIP_BEATS_MAX_DEPTH
@@ -161,3 +162,36 @@ class BeatRecorder(DeviceRecorder):
         if not 1 <= int(last) <= self.depth:
             raise ValueError('summary: last must be 1 .. depth = %d (got %d)' % (self.depth, last))
         return dict(zip(SUMMARY_MAPS, self._st.beats_summary(int(last))))
+
+    def velocity(self, last=1, radius=2, max_dt=20.0, min_cells=None, mask=None):
+        """{'gy', 'gx', 'rms': float32 [last, oh, ow], 'nfit': int32 [last, oh, ow]}: the gradient of activation time (ms per
+        pixel along rows and columns), the residual of the fit and the cells that took part, for the newest `last` (1 .. depth)
+        beats of every pixel in beats()'s order, index -1 the newest — a plane fitted on the device to the upstroke times of the
+        (2 * radius + 1)^2 pixels around each that lie within `max_dt` ms of its own (fib_tf_amd/velocity.py).  NaN where fewer
+        than `min_cells` (default: a majority of the window) match or they lie on one line.  One device call per beat: memory
+        stays at four maps.  `max_dt`: below half the shortest cycle length, so that two beats of a neighbour are never
+        confused, and above the time a front needs to cross `radius` pixels.  `mask`: [oh, ow], non-zero where a pixel counts"""
+        self._check()
+        radius, max_dt, min_cells = _velocity.check_args(radius, max_dt, min_cells, self.depth, last, 'velocity')
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if mask.shape != self.shape:
+                raise ValueError('velocity: a mask of shape %s on a map of shape %s' % (mask.shape, self.shape))
+        out = {k: np.empty((int(last),) + self.shape, np.int32 if k == 'nfit' else np.float32) for k in _velocity.MAPS}
+        for back in range(int(last)):
+            for k, m in zip(_velocity.MAPS, self._st.beats_velocity(back, radius, max_dt, min_cells, mask)):
+                out[k][int(last) - 1 - back] = m
+        return out
+
+    def speed(self, last=1, **kw):
+        """float64 [last, oh, ow]: the conduction velocity in CELLS per ms (the block is taken out), NaN where there is no fit;
+        the keywords are velocity()'s"""
+        return _velocity.speed_of(self.velocity(last, **kw), self.block)
+
+    def cv_restitution(self, last=None, mask=None, max_rms=None, **kw):
+        """(di, cv): the flat pairs of every pixel (of `mask`) and beat of the newest `last` (None: depth) that has a diastolic
+        interval in front of it and a fit, with a residual of at most `max_rms` ms if given — CV restitution, the other half of
+        restitution()'s pair.  The other keywords are velocity()'s"""
+        last = self.depth if last is None else int(last)
+        vel = self.velocity(last, mask=mask, **kw)
+        return _velocity.cv_restitution_of(self.beats(), vel, self.block, mask, max_rms)

@@ -123,6 +123,7 @@ struct ObsRec {
     int var;
     float up, down;
     float *buf;             // 6 planes of `cells` (W-pitched): Vp | first_up | last_up | prev_up | apd | count (int32)
+    float *vel;             // fibhip_observe_velocity's four maps, `cells` each: made on first use, freed with the recorder
     long long k;            // observed ticks since the recorder was attached
 };
 // electrode recorder (fibhip_electrode_begin): electrode_kernel behind the launch that ends a sample tick

@@ -298,6 +298,7 @@ extern "C" int fibhip_destroy(fibhip_t h)
     if (h->phi_dev) hipFree(h->phi_dev);
     if (h->agg) hipFree(h->agg);
     if (h->obs.buf) hipFree(h->obs.buf);
+    if (h->obs.vel) hipFree(h->obs.vel);
     recorders_free(h);
     if (h->mt.xbuf) hipFree(h->mt.xbuf);
     if (h->mt.epochs) hipFree(h->mt.epochs);

@@ -938,6 +938,10 @@ extern "C" int fibhip_observe_end(fibhip_t h)
         HIPCHK(hipFree(h->obs.buf));
         h->obs.buf = nullptr;
     }
+    if (h->obs.vel) {                                  // (fibhip_observe_velocity's maps: every call waited for its own copies)
+        HIPCHK(hipFree(h->obs.vel));
+        h->obs.vel = nullptr;
+    }
     h->obs.on = false;
     return 0;
 }
@@ -1826,6 +1830,98 @@ extern "C" int fibhip_beats_summary(fibhip_t h, int last, int *nused, float *apd
             return rc;
         return copy_maps(h, r.maps, npix, dst);
     });
+}
+
+// ---- velocity fit: what fibhip_beats_velocity, fibhip_observe_velocity and fibhip_velocity_fit (unit.inc) share ------------
+static_assert(VEL_MAX_RADIUS == FIBHIP_VEL_MAX_RADIUS, "velocity_fit_kernel's LDS tile follows include/fibhip.h");
+// the refusals that need no plane; `who` names the function
+static int vel_refusals(const char *who, int depth, int back, int radius, float max_dt, int min_cells)
+{
+    if (depth < 1 || depth > FIBHIP_BEATS_MAX_DEPTH) return fail(FIBHIP_EINVAL, "%s: depth must be 1 .. %d (got %d)", who, FIBHIP_BEATS_MAX_DEPTH, depth);
+    if (back < 0 || back >= depth) return fail(FIBHIP_EINVAL, "%s: back must be 0 .. depth - 1 = %d (got %d)", who, depth - 1, back);
+    if (radius < 1 || radius > FIBHIP_VEL_MAX_RADIUS)
+        return fail(FIBHIP_EINVAL, "%s: radius must be 1 .. %d (got %d)", who, FIBHIP_VEL_MAX_RADIUS, radius);
+    if (!std::isfinite(max_dt) || !(max_dt > 0.f)) return fail(FIBHIP_EINVAL, "%s: max_dt must be finite and > 0 (got %g)", who, (double)max_dt);
+    const int window = (2 * radius + 1) * (2 * radius + 1);
+    if (min_cells < 3 || min_cells > window)
+        return fail(FIBHIP_EINVAL, "%s: min_cells must be 3 .. (2 * radius + 1)^2 = %d (got %d)", who, window, min_cells);
+    return 0;
+}
+static inline VelArgs vel_args(const float *t, const int *n, const unsigned char *mask, int depth, int oh, int ow, int back, int radius,
+                               float max_dt, int min_cells, float *maps)
+{
+    const size_t npix = (size_t)oh * (size_t)ow;
+    VelArgs a;
+    a.t = t; a.n = n; a.mask = mask;
+    a.depth = depth; a.oh = oh; a.ow = ow;
+    a.back = back; a.radius = radius; a.min_cells = min_cells;
+    a.max_dt = max_dt;
+    a.nfit = reinterpret_cast<int *>(maps);
+    a.gy = maps + npix; a.gx = maps + 2 * npix; a.rms = maps + 3 * npix;
+    return a;
+}
+static inline dim3 vel_grid(int oh, int ow) { return dim3((unsigned)((ow + VEL_TX - 1) / VEL_TX), (unsigned)((oh + VEL_TY - 1) / VEL_TY)); }
+static inline void vel_launch(const VelArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(velocity_fit_kernel, vel_grid(a.oh, a.ow), dim3(256), 0, st, a);
+}
+// the fit on planes of the handle, behind whatever is pending: the caller's mask goes up for the call, the four maps come back
+// through read_confirmed — the planes read are confirmed ones, like beats_summary's
+static int vel_on_handle(fibhip_ctx *h, const char *who, const float *t, const int *n, int depth, int oh, int ow, int back, int radius,
+                         float max_dt, int min_cells, const unsigned char *mask, float *maps, void *const dst[4])
+{
+    const size_t npix = (size_t)oh * (size_t)ow;
+    unsigned char *dmask = nullptr;
+    if (mask) {
+        if (hipMalloc((void **)&dmask, npix) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(FIBHIP_ENOMEM, "%s: hipMalloc failed (a mask of %d x %d pixels)", who, oh, ow);
+        }
+        if (hipMemcpyAsync(dmask, mask, npix, hipMemcpyHostToDevice, h->s0) != hipSuccess) {
+            hipFree(dmask);
+            return fail(FIBHIP_EHIP, "%s: the mask's copy to the device failed", who);
+        }
+    }
+    const VelArgs a = vel_args(t, n, dmask, depth, oh, ow, back, radius, max_dt, min_cells, maps);
+    const int rc = read_confirmed(h, [&] {
+        if (int rc = launch_traced(h, "velocity_fit_kernel", 0, [&] { vel_launch(a, h->s0); })) return rc;
+        return copy_maps(h, maps, npix, dst);
+    });
+    if (dmask) hipFree(dmask);                         // (read_confirmed waited for the stream; after a failure hipFree waits itself)
+    return rc;
+}
+
+extern "C" int fibhip_beats_velocity(fibhip_t h, int back, int radius, float max_dt, int min_cells, const unsigned char *mask, int *nfit,
+                                     float *gy, float *gx, float *rms)
+{
+    NEED(h);
+    if (!h->bt.on) return fail(FIBHIP_EINVAL, "beats_velocity: no recorder attached (fibhip_beats_begin)");
+    const BeatRec &r = h->bt;
+    if (int rc = vel_refusals("beats_velocity", r.depth, back, radius, max_dt, min_cells)) return rc;
+    FLUSH(h);
+    void *const dst[4] = {nfit, gy, gx, rms};
+    return vel_on_handle(h, "beats_velocity", r.ring, reinterpret_cast<const int *>(r.state + 2 * r.npix()), r.depth, r.oh, r.ow, back, radius,
+                         max_dt, min_cells, mask, r.maps, dst);
+}
+
+extern "C" int fibhip_observe_velocity(fibhip_t h, int which, int radius, float max_dt, int min_cells, const unsigned char *mask, int *nfit,
+                                       float *gy, float *gx, float *rms)
+{
+    NEED(h);
+    if (!h->obs.on) return fail(FIBHIP_EINVAL, "observe_velocity: no recorder attached (fibhip_observe_begin)");
+    if (which != FIBHIP_OBS_FIRST_UP && which != FIBHIP_OBS_LAST_UP && which != FIBHIP_OBS_PREV_UP)
+        return fail(FIBHIP_EINVAL, "observe_velocity: which must be FIRST_UP, LAST_UP or PREV_UP (got %d)", which);
+    if (int rc = vel_refusals("observe_velocity", 1, 0, radius, max_dt, min_cells)) return rc;
+    FLUSH(h);
+    const size_t n = h->cells;
+    if (!h->obs.vel && hipMalloc((void **)&h->obs.vel, 4 * n * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        h->obs.vel = nullptr;
+        return fail(FIBHIP_ENOMEM, "observe_velocity: hipMalloc failed (four maps of %d x %d cells)", h->d.height, h->d.width);
+    }
+    void *const dst[4] = {nfit, gy, gx, rms};
+    return vel_on_handle(h, "observe_velocity", h->obs.buf + (size_t)(1 + which) * n, reinterpret_cast<const int *>(h->obs.buf + 5 * n), 1,
+                         h->d.height, h->d.width, 0, radius, max_dt, min_cells, mask, h->obs.vel, dst);
 }
 
 extern "C" int fibhip_beats_end(fibhip_t h)

@@ -1229,6 +1229,140 @@ beat_summary_kernel(const int *__restrict__ count, const float *__restrict__ t_u
     apd_alt[t] = pairs ? alt / (float)pairs : __builtin_nanf("");
 }
 
+// ---- velocity fit (fibhip_beats_velocity, fibhip_observe_velocity, fibhip_velocity_fit): a plane fitted to the activation times
+// in a space-time window around every pixel (include/fibhip.h has the definition).  Launched at read time on a ring of time
+// planes t[depth][oh * ow] with its count plane, like beat_summary_kernel; one pixel per thread.
+//   velocity_fit_kernel, grid (ceil(ow / VEL_TX), ceil(oh / VEL_TY)), 256 threads: a workgroup stages its tile with a ring of R
+//   pixels in LDS — one word per cell that packs how many beats the cell holds and the slot of the oldest (0 beats for a cell
+//   outside the plane or the mask: it then takes no part, and as a centre it has no beat), and the held slots of its ring; wave v
+//   stages the rows v, v + 4, ..., lane l the column l: consecutive lanes, consecutive words, in global memory and in LDS, and
+//   the one modulo by `depth` of a cell is taken here —, then walks the window from LDS.  The 32 lanes that share the banks of a
+//   4-byte LDS read are one row of the tile, consecutive words; a slot's stride, 640 words, is a multiple of the 32 banks, so
+//   lanes that stand at different slots of neighbouring cells (their counts differ) still hit different banks.
+// `depth` and R are run-time values: the ten sums live in registers and nothing is indexed with a run-time index (no scratch).
+// The obvious form — every ring entry of the window straight from L2 — was measured beside this one on the MI355X and is not
+// kept: 46.2 against 43.7 us at 512 x 512, depth 8, R = 2; 2294 against 1390 us at 2048 x 2048, R = 4 (profiles/velocity_cost.txt).
+// The float64 arithmetic is written one operation per statement where the order matters; -ffp-contract=off keeps it so.
+#define VEL_MAX_RADIUS 4        // FIBHIP_VEL_MAX_RADIUS
+#define VEL_TX 32
+#define VEL_TY 8
+#define VEL_LW (VEL_TX + 2 * VEL_MAX_RADIUS)
+#define VEL_LH (VEL_TY + 2 * VEL_MAX_RADIUS)
+#define VEL_CELLS (VEL_LW * VEL_LH)             // 640 words per slot: 16 slots and the packed counts are 43520 bytes
+struct VelArgs {
+    const float *t;             // [depth][oh * ow]
+    const int *n;               // [oh * ow]
+    const unsigned char *mask;  // [oh * ow], or null (every pixel counts)
+    int depth, oh, ow;
+    int back, radius, min_cells;
+    float max_dt;
+    int *nfit;                  // [oh * ow] each
+    float *gy, *gx, *rms;
+};
+
+// the sums over the used cells of one window, and the solve
+struct VelSums {
+    int N, Sy, Sx, Syy, Sxx, Sxy;
+    double St, Syt, Sxt, Stt;
+    FIB_DEV void clear() { N = Sy = Sx = Syy = Sxx = Sxy = 0; St = Syt = Sxt = Stt = 0.0; }
+    FIB_DEV void add(int dy, int dx, float d)
+    {
+        const double dd = (double)d;
+        N += 1;
+        Sy += dy; Sx += dx;
+        Syy += dy * dy; Sxx += dx * dx; Sxy += dy * dx;
+        St = St + dd;
+        Syt = Syt + (double)dy * dd;
+        Sxt = Sxt + (double)dx * dd;
+        Stt = Stt + dd * dd;
+    }
+};
+
+static FIB_DEV void vel_store(const VelArgs &a, size_t p, const VelSums &s)
+{
+    const float nanf_ = __builtin_nanf("");
+    float gy = nanf_, gx = nanf_, rms = nanf_;
+    const long long N = s.N, Sy = s.Sy, Sx = s.Sx;
+    const long long cyy = N * s.Syy - Sy * Sy, cxx = N * s.Sxx - Sx * Sx, cxy = N * s.Sxy - Sy * Sx;
+    const long long det = cyy * cxx - cxy * cxy;
+    if (s.N >= a.min_cells && det != 0) {
+        const double n = (double)N;
+        const double cyt = n * s.Syt - (double)Sy * s.St;
+        const double cxt = n * s.Sxt - (double)Sx * s.St;
+        const double g_y = ((double)cxx * cyt - (double)cxy * cxt) / (double)det;
+        const double g_x = ((double)cyy * cxt - (double)cxy * cyt) / (double)det;
+        const double c = (s.St - (g_y * (double)Sy + g_x * (double)Sx)) / n;
+        const double sse = s.Stt - ((c * s.St + g_y * s.Syt) + g_x * s.Sxt);
+        const double r = __dsqrt_rn((sse > 0.0 ? sse : 0.0) / n);
+        gy = (float)g_y; gx = (float)g_x; rms = (float)r;
+    }
+    if (a.nfit) a.nfit[p] = s.N;
+    if (a.gy) a.gy[p] = gy;
+    if (a.gx) a.gx[p] = gx;
+    if (a.rms) a.rms[p] = rms;
+}
+
+__global__ void __launch_bounds__(256) velocity_fit_kernel(VelArgs a)
+{
+    __shared__ float ts[BEAT_MAX_DEPTH * VEL_CELLS];
+    __shared__ int ns[VEL_CELLS];                                     // held beats | slot of the oldest << 8
+    const int R = a.radius, depth = a.depth;
+    const int lw = VEL_TX + 2 * R, lh = VEL_TY + 2 * R;               // <= VEL_LW, VEL_LH: the host refuses R > VEL_MAX_RADIUS
+    const int x0 = (int)blockIdx.x * VEL_TX - R, y0 = (int)blockIdx.y * VEL_TY - R;
+    const size_t npix = (size_t)a.oh * (size_t)a.ow;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane < lw) {
+        for (int r = wv; r < lh; r += 4) {
+            const int y = y0 + r, x = x0 + lane;
+            const int cell = r * VEL_LW + lane;
+            int held = 0, first = 0;
+            if (y >= 0 && y < a.oh && x >= 0 && x < a.ow) {
+                const size_t q = (size_t)y * (size_t)a.ow + (size_t)x;
+                const int n = (!a.mask || a.mask[q]) ? a.n[q] : 0;
+                if (n > 0) {
+                    held = n < depth ? n : depth;
+                    first = n < depth ? 0 : n % depth;                // (n - held) % depth
+                    for (int s = 0; s < held; ++s) ts[s * VEL_CELLS + cell] = a.t[(size_t)s * npix + q];
+                }
+            }
+            ns[cell] = held | (first << 8);
+        }
+    }
+    __syncthreads();
+    const int tx = threadIdx.x & (VEL_TX - 1), ty = threadIdx.x / VEL_TX;
+    const int x = (int)blockIdx.x * VEL_TX + tx, y = (int)blockIdx.y * VEL_TY + ty;
+    if (x >= a.ow || y >= a.oh) return;
+    const size_t p = (size_t)y * (size_t)a.ow + (size_t)x;
+    const int c = (ty + R) * VEL_LW + tx + R;
+    VelSums s;
+    s.clear();
+    const int nc = ns[c], heldc = nc & 255;
+    float tc = __builtin_nanf("");
+    if (a.back < heldc) {                                             // beat n - 1 - back is held
+        int slot = (nc >> 8) + heldc - 1 - a.back;                    // < 2 * depth
+        if (slot >= depth) slot -= depth;
+        tc = ts[slot * VEL_CELLS + c];
+    }
+    if (tc == tc) {
+        for (int dy = -R; dy <= R; ++dy) {
+            for (int dx = -R; dx <= R; ++dx) {
+                const int cell = c + dy * VEL_LW + dx;
+                const int nq = ns[cell], held = nq & 255;
+                int slot = nq >> 8;
+                float best = __builtin_inff(), bd = 0.f;
+                for (int j = 0; j < held; ++j) {                      // ascending beat number; a tie keeps the older beat
+                    const float d = ts[slot * VEL_CELLS + cell] - tc;
+                    const float ad = __builtin_fabsf(d);
+                    if (ad < best) { best = ad; bd = d; }             // (a NaN compares false)
+                    slot = slot + 1 == depth ? 0 : slot + 1;
+                }
+                if (best <= a.max_dt) s.add(dy, dx, bd);              // (max_dt is finite: nothing kept, nothing used)
+            }
+        }
+    }
+    vel_store(a, p, s);
+}
+
 // ---- lead recorder (fibhip_leads_begin): unipolar electrograms, the membrane current seen through a lead field ---------------
 // The SOURCE at an interior cell (1 <= r <= H - 2, 1 <= c <= W - 2) of the watched array X is the stand-alone laplace() of
 // the boundary-enforced array: stencil9 over taps read at (clamp(r + dr, 1, H - 2), clamp(c + dc, 1, W - 2)) — tick_kernel's

@@ -85,7 +85,7 @@ static int sync_s0(fibhip_ctx *h)
 // traced tick is a plain launch) — and inside the scheduler tick_mt for a launch of one tick and fibhip_step in front of its
 // plain launches.  The entry points that only READ synchronise behind their copy (sync_s0) and take the copy again when a
 // recovery happened in between: fibhip_get_state, fibhip_get_state_direct (both branches of ahead_read_back hand the frame
-// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read, fibhip_frames_read, fibhip_stats_read, fibhip_leads_read, fibhip_waves_read / _labels, fibhip_spectrum_read / _peak, fibhip_beats_read / _summary, fibhip_get_phase; fibhip_observe_begin,
+// back to that loop when the give-up word stands), fibhip_probe, fibhip_electrode_read, fibhip_tips_read, fibhip_frames_read, fibhip_stats_read, fibhip_leads_read, fibhip_waves_read / _labels, fibhip_spectrum_read / _peak, fibhip_beats_read / _summary / _velocity, fibhip_observe_velocity, fibhip_get_phase; fibhip_observe_begin,
 // fibhip_electrode_begin / _end, fibhip_tips_begin / _end, fibhip_frames_begin / _end, fibhip_stats_begin / _end, fibhip_leads_begin / _end, fibhip_waves_begin / _end, fibhip_spectrum_begin / _end and fibhip_beats_begin / _end synchronise
 // outright.
 static int confirm(fibhip_ctx *h)

@@ -71,6 +71,40 @@ extern "C" int fibhip_court_inter(int device, int n, const float *V, int fast, f
     return rc;
 }
 
+// the velocity fit (record.inc vel_*, velocity_fit_kernel) on HOST planes: how the tests reach the kernel with rings no run makes
+extern "C" int fibhip_velocity_fit(int device, int depth, int oh, int ow, const float *t, const int *count, int back, int radius, float max_dt,
+                                   int min_cells, const unsigned char *mask, int *nfit, float *gy, float *gx, float *rms)
+{
+    if (!t || !count) return fail(FIBHIP_EINVAL, "velocity_fit: null argument (t and count are required)");
+    if (oh < 1 || ow < 1 || (long long)oh * ow > INT_MAX) return fail(FIBHIP_EINVAL, "velocity_fit: bad shape %d x %d", oh, ow);
+    if (int rc = vel_refusals("velocity_fit", depth, back, radius, max_dt, min_cells)) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(FIBHIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
+    HIPCHK(hipSetDevice(device));
+    const size_t npix = (size_t)oh * (size_t)ow, B = npix * sizeof(float);
+    float *d = nullptr;                             // t[depth] | count | the four maps | mask
+    HIPCHK(hipMalloc((void **)&d, ((size_t)depth + 5) * B + npix));
+    float *dt = d, *dn = d + (size_t)depth * npix, *maps = dn + npix;
+    unsigned char *dmask = reinterpret_cast<unsigned char *>(maps + 4 * npix);
+    void *const dst[4] = {nfit, gy, gx, rms};
+    int rc = 0;
+    do {
+        if (hipMemcpy(dt, t, (size_t)depth * B, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dn, count, B, hipMemcpyHostToDevice) != hipSuccess ||
+            (mask && hipMemcpy(dmask, mask, npix, hipMemcpyHostToDevice) != hipSuccess)) {
+            rc = fail(FIBHIP_EHIP, "velocity_fit: H2D failed");
+            break;
+        }
+        vel_launch(vel_args(dt, reinterpret_cast<const int *>(dn), mask ? dmask : nullptr, depth, oh, ow, back, radius, max_dt, min_cells, maps), 0);
+        if (hipGetLastError() != hipSuccess) { rc = fail(FIBHIP_EHIP, "velocity_fit: the launch failed"); break; }
+        for (int i = 0; i < 4 && !rc; ++i)
+            if (dst[i] && hipMemcpy(dst[i], maps + (size_t)i * npix, B, hipMemcpyDeviceToHost) != hipSuccess)
+                rc = fail(FIBHIP_EHIP, "velocity_fit: kernel or D2H failed");
+    } while (0);
+    hipFree(d);
+    return rc;
+}
+
 extern "C" int fibhip_warm(int device)
 {
     int ndev = 0;

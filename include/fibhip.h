@@ -735,6 +735,48 @@ int fibhip_beats_read(fibhip_t h, float *t_up, float *t_down, float *peak /* [de
 int fibhip_beats_summary(fibhip_t h, int last, int *nused, float *apd_mean, float *cl_mean, float *apd_alt /* [oh][ow] each */);
 int fibhip_beats_end(fibhip_t h);
 
+/* Velocity fit: the gradient of activation time at every pixel, from a plane fitted to the activation times of a space-time
+ * window around it (Bayly et al. 1998) — made on the device at read time from the planes the beat recorder and the activation
+ * recorder keep there, like the summary maps.  The conduction velocity is the gradient's reciprocal (fib_tf_amd/velocity.py).
+ * Inputs: a ring of time planes t[depth][oh * ow] (float32, ms) and a count plane n[oh * ow] (int32): beat b of a pixel lies in
+ * slot b mod depth, and the pixel HOLDS the beats n - min(n, depth) .. n - 1 (none for n <= 0).  back >= 0, the beat under the
+ * fit, counted from the newest; radius R = 1 .. FIBHIP_VEL_MAX_RADIUS; max_dt, float32, finite and > 0; min_cells =
+ * 3 .. (2R + 1)^2; an optional mask [oh * ow] of bytes, non-zero where a pixel counts.
+ * Centre.  Pixel p = (y, x) with beat b = n[p] - 1 - back.  If b is not held, the mask excludes p, or tc = t[b mod depth][p] is
+ * NaN: nfit = 0 and gy = gx = rms = NaN.
+ * Neighbour matching.  The offsets (dy, dx) are visited dy = -R .. R outermost, dx = -R .. R inside it.  A neighbour
+ * q = (y + dy, x + dx) takes part if it lies inside the plane and inside the mask.  Its held beats are walked in ascending beat
+ * number with d = t_q - tc, ONE float32 subtraction; the beat with the smallest |d| under a strict < is kept (a tie keeps the
+ * older beat; a NaN d is never kept); q is USED if a beat was kept and |d| <= max_dt.  The centre meets itself with d = 0, no
+ * special case.  Neighbours whose beat numbers differ from the centre's (a missed beat, a ring that wrapped) are so matched by
+ * time, not by index.
+ * Sums over the used cells in visiting order.  Integers, exact: N, Sy = sum dy, Sx = sum dx, Syy, Sxx, Sxy.  float64:
+ * St = sum d, Syt = sum dy * d, Sxt = sum dx * d, Stt = sum d * d, each product formed in float64 from the float32 d, every
+ * addition rounded on its own (no fma), each sum starting from +0.
+ * Solve.  Integers: cyy = N Syy - Sy^2, cxx = N Sxx - Sx^2, cxy = N Sxy - Sy Sx, det = cyy cxx - cxy^2.  float64, in the order
+ * written: cyt = N Syt - Sy St, cxt = N Sxt - Sx St.  If N < min_cells or det == 0: nfit = N, the rest NaN.  Otherwise
+ *   gy  = (cxx cyt - cxy cxt) / det
+ *   gx  = (cyy cxt - cxy cyt) / det
+ *   a   = (St - (gy Sy + gx Sx)) / N
+ *   sse = Stt - ((a St + gy Syt) + gx Sxt)
+ *   rms = sqrt(max(sse, 0) / N)
+ * with IEEE float64 division and square root.  Stored: nfit = N (int32); gy, gx, rms rounded once to float32.  gy and gx are the
+ * gradient of activation time in ms per pixel along rows and columns, rms the residual of the fit in ms.
+ *   fibhip_beats_velocity    on the beat recorder's t_up ring and counts (depth its own; back = 0 .. depth - 1); the mask is
+ *                            [oh][ow] of its pixel plane, or NULL.  Any map may be NULL; flushes and blocks like beats_summary
+ *   fibhip_observe_velocity  the same at depth 1, back 0 on one time plane of the activation recorder, which = FIBHIP_OBS_FIRST_UP,
+ *                            _LAST_UP or _PREV_UP, with its count plane: a NaN time (prev_up after one upstroke) is never used.
+ *                            The mask is [height][width] or NULL
+ *   fibhip_velocity_fit      the same on host planes copied through `device`, without a handle (for the tests)               */
+#define FIBHIP_VEL_MAX_RADIUS 4
+int fibhip_beats_velocity(fibhip_t h, int back, int radius, float max_dt, int min_cells, const unsigned char *mask /* [oh*ow] or NULL */,
+                          int *nfit, float *gy, float *gx, float *rms /* [oh][ow] each */);
+int fibhip_observe_velocity(fibhip_t h, int which, int radius, float max_dt, int min_cells, const unsigned char *mask /* [H*W] or NULL */,
+                            int *nfit, float *gy, float *gx, float *rms /* [height][width] each */);
+int fibhip_velocity_fit(int device, int depth, int oh, int ow, const float *t /* [depth][oh*ow] */, const int *count /* [oh*ow] */, int back,
+                        int radius, float max_dt, int min_cells, const unsigned char *mask /* [oh*ow] or NULL */, int *nfit, float *gy,
+                        float *gx, float *rms /* [oh][ow] each */);
+
 /* Stimulus program: stimuli applied on the device at programmed ticks, from sites of any shape, without a call per stimulus
  * (the reference's only stimulus is add_pace_op / fire_op, fired from the caller's loop body: `if i == s2: fire_op('s2')`;
  * fibhip_pace stands in for it and stays as it is).  A program is 1 .. FIBHIP_MAX_STIM_ENTRIES entries
