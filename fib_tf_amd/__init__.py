@@ -18,6 +18,7 @@ from . import spectrum                          # noqa: F401  (SpectrumRecorder:
 from . import beats                             # noqa: F401  (BeatRecorder: per-cell beat history, restitution and alternans maps)
 from . import velocity                          # noqa: F401  (conduction-velocity maps and CV restitution, fitted on the device)
 from . import leads                             # noqa: F401  (LeadRecorder: unipolar electrograms from the membrane current)
+from . import potential                         # noqa: F401  (PotentialMapRecorder: unipolar electrograms at every site of a lattice)
 from . import waves                             # noqa: F401  (WaveRecorder: excited domains labelled and counted on the device)
 from . import stimulus                        # noqa: F401  (Stimulus, StimulusProgram: pacing protocols run on the device)
 from . import triggers                          # noqa: F401  (Sensor, Trigger, TriggerProgram: triggered stimulation on the device)

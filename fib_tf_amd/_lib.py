@@ -24,6 +24,7 @@ VEL_MAX_RADIUS = 4                                                # FIBHIP_VEL_M
 STAT_KINDS = ('sum', 'min', 'max', 'below', 'above', 'nonfinite')  # enum fibhip_stat_kind, in order
 MAX_STAT_COLS, MAX_STAT_COLS_PER_ARRAY = 64, 8
 MAX_LEADS, MAX_LEAD_TABLES = 64, 4
+PMAP_MAX_RADIUS, PMAP_MAX_STEP = 32, 16
 WAVE_KINDS = ('above', 'below')                                   # enum fibhip_wave_kind, in order
 MAX_WAVES = 65536
 # struct fibhip_wave_record (40 bytes)
@@ -242,6 +243,12 @@ SYMBOLS = {
     'fibhip_leads_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
     'fibhip_leads_read': ([_h, C.c_longlong, C.c_longlong, C.POINTER(C.c_double)], C.c_int),
     'fibhip_leads_end': ([_h], C.c_int),
+    'fibhip_pmap_begin': ([_h, C.c_int, C.c_int, _fp, _fp, _ip, C.c_int, C.c_int, C.c_int, C.c_longlong], C.c_int),
+    'fibhip_pmap_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),
+    'fibhip_pmap_read': ([_h, C.c_longlong, C.c_longlong, C.POINTER(C.c_double)], C.c_int),
+    'fibhip_pmap_summary': ([_h, C.c_longlong, C.c_longlong, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _ip, _ip, _ip],
+                            C.c_int),
+    'fibhip_pmap_end': ([_h], C.c_int),
     'fibhip_waves_begin': ([_h, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int,
                             C.c_longlong], C.c_int),
     'fibhip_waves_count': ([_h, C.POINTER(C.c_longlong)], C.c_int),

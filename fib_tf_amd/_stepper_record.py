@@ -366,6 +366,44 @@ class RecorderBindings:
     def leads_end(self):
         self._ck(self._L.fibhip_leads_end(self._h))
 
+    # ---- potential-map recorder (include/fibhip.h fibhip_pmap_*) ---------------------------------------------------
+    def pmap_begin(self, table, weight=None, window=None, step=(1, 1), var=0, every=1, capacity=1):
+        """attaches the potential-map recorder: `table` is the float32 [R + 1, R + 1] lead-field table (its shape gives the
+        radius R), `weight` an [height, width] float32 plane or None (weight 1), `window` = (r0, r1, c0, c1) (None: the whole
+        grid) and `step` = (sy, sx) the lattice of sites; one float64 [oh, ow] plane every `every` ticks, `capacity` planes at
+        the most"""
+        table = np.ascontiguousarray(table, np.float32)
+        if table.ndim != 2 or table.shape[0] != table.shape[1] or table.shape[0] < 2:
+            raise ValueError('pmap_begin: a table of shape %s is not [R + 1, R + 1]' % (table.shape,))
+        win = np.ascontiguousarray((0, self.height, 0, self.width) if window is None else window, np.intc).reshape(4)
+        sy, sx = int(step[0]), int(step[1])
+        wp = self._plane('pmap_begin', 'weight plane', weight, np.float32)
+        self._ck(self._L.fibhip_pmap_begin(self._h, int(var), table.shape[0] - 1, table.ctypes.data_as(_fp), wp, win.ctypes.data_as(_ip), sy, sx,
+                                           int(every), int(capacity)))
+        self._pm_shape = (-(-int(win[1] - win[0]) // sy), -(-int(win[3] - win[2]) // sx))
+
+    def pmap_count(self):
+        """samples taken since pmap_begin (ticks accepted but not launched yet included)"""
+        return self._count(self._L.fibhip_pmap_count)
+
+    def pmap_read(self, first=0, count=None):
+        """samples [first, first + count) as a float64 [count, oh, ow] array (count=None: all taken so far); blocks like
+        get_state, detaches nothing"""
+        return self._rows(self._L.fibhip_pmap_count, self._L.fibhip_pmap_read, first, count, getattr(self, '_pm_shape', (0, 0)), np.float64, _dp)
+
+    def pmap_summary(self, first=0, count=None):
+        """(vmin, vmax, dmin float64, kmin, kmax, kd int32), each [oh, ow], over the samples [first, first + count) (count=None:
+        all taken so far; at least 2)"""
+        first, count, _ = self._span(self._L.fibhip_pmap_count, first, count)
+        shape = getattr(self, '_pm_shape', (0, 0))
+        f = [np.empty(shape, np.float64) for _ in range(3)]
+        k = [np.empty(shape, np.int32) for _ in range(3)]
+        self._ck(self._L.fibhip_pmap_summary(self._h, first, count, *([a.ctypes.data_as(_dp) for a in f] + [a.ctypes.data_as(_ip) for a in k])))
+        return tuple(f + k)
+
+    def pmap_end(self):
+        self._ck(self._L.fibhip_pmap_end(self._h))
+
     # ---- wave recorder (include/fibhip.h fibhip_waves_*) ----------------------------------------------------------
     def waves_begin(self, var=0, kind=0, level=0.0, var2=-1, kind2=0, level2=0.0, conn=4, mask=None, max_waves=256, every=1, capacity=1):
         """attaches (or re-attaches, with empty lists) the wave recorder: a cell is set where `mask` ([height, width], or None:

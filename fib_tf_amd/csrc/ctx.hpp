@@ -189,6 +189,20 @@ struct LeadRec : Sampler {
     double *rows;           // device: [cap][n]
 };
 
+// potential-map recorder (fibhip_pmap_begin): pmap_source_kernel and pmap_conv_kernel behind the launch that ends a sample tick.
+// Both rewrite whole slots (every cell of the scratch plane, every site of the sample's slot) from the state alone
+struct PMapRec : Sampler {
+    int var, R;
+    int r0, c0, sy, sx, oh, ow;     // the lattice: site (i, j) at the cell (r0 + i * sy, c0 + j * sx)
+    int pw, roww, slab;             // pmap_conv_kernel's LDS layout, from R and sx alone
+    float *weight;          // device: the weight plane [H][W], or null (weight 1)
+    double *tab;            // device: [R + 1][2R + 1], the table's rows in float64, mirrored about dc = 0
+    float *q;               // device: the source plane [H + 2R][W + 2R], R zeros on every side
+    double *cube;           // device: [cap][oh][ow]
+    double *maps;           // device: the summary's planes, 3 x float64 [oh][ow] then 3 x int32 [oh][ow]
+    size_t npix() const { return (size_t)oh * (size_t)ow; }
+};
+
 // wave recorder (fibhip_waves_begin): wave_label_kernel, wave_merge_kernel, wave_root_kernel and wave_reduce_kernel behind the
 // launch that ends a sample tick.  The two planes are scratch that every sample rewrites before it reads them; the sample's
 // counts are zeroed and its records written whole
@@ -359,6 +373,7 @@ struct fibhip_ctx {
     FrRec fr;
     StRec st;
     LeadRec ld;
+    PMapRec pm;
     WaveRec wv;
     SpRec sp;
     BeatRec bt;

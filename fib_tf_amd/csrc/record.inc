@@ -1,6 +1,6 @@
-// record.inc — what runs on the device behind the ticks while a model runs.  Nine recorders: the per-cell activation maps
+// record.inc — what runs on the device behind the ticks while a model runs.  Ten recorders: the per-cell activation maps
 // (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
-// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the unipolar electrograms (fibhip_leads_*), the excited domains and their links from sample to sample (fibhip_waves_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell
+// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the unipolar electrograms (fibhip_leads_*), the potential map (fibhip_pmap_*), the excited domains and their links from sample to sample (fibhip_waves_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell
 // beat history (fibhip_beats_*); and the two hooks that write the state: the stimulus program (fibhip_stim_*) and the trigger
 // program (fibhip_trig_*), which senses, decides and fires on the device.
 // The file has three parts: the helpers every recorder shares; the hooks — per recorder its _advance (behind a launch that the
@@ -357,6 +357,59 @@ static void leads_free(fibhip_ctx *h)
     dev_free(h->ld.part);
     dev_free(h->ld.rows);
     h->ld.on = false;
+}
+
+static_assert(PM_MAX_RADIUS == FIBHIP_PMAP_MAX_RADIUS && PM_MAX_STEP == FIBHIP_PMAP_MAX_STEP && PM_THREADS == 256 && PM_TY % (PM_THREADS / 64) == 0 &&
+                  PM_MAX_STEP * (PM_TX - 1 + (2 * PM_MAX_RADIUS + PM_MAX_STEP) / PM_MAX_STEP) <= PM_LDS_FLOATS,
+              "pmap_conv_kernel's constants follow include/fibhip.h; four waves, PM_SPL site rows each; one row of the widest span fits in LDS");
+// The potential-map recorder's hook: at a sample tick pmap_source_kernel is enqueued on s0 behind the launch that ended there
+// (every cell of the scratch plane) and pmap_conv_kernel behind it (every site of the sample's slot).  The slot is a kernel
+// argument computed from the host's counter, so a replay (recover()) writes the same slot again.
+static int pmap_advance(fibhip_ctx *h, int ticks, bool)
+{
+    PMapRec &r = h->pm;
+    long long s;
+    if (!r.advance(ticks, &s)) return 0;
+    if (s >= r.cap) return fail(FIBHIP_EINVAL, "potential-map recorder: trace full");          // (fibhip_step refuses before this)
+    const int H = h->d.height, W = h->d.width;
+    PMapSourceArgs q;
+    q.x = array_of(h, r.var);
+    q.w = r.weight;
+    q.dpy = h->has_phase ? h->phase3 : nullptr;
+    q.dpx = h->has_phase ? h->phase3 + h->cells : nullptr;
+    q.q4 = h->has_phase ? h->phase3 + 2 * h->cells : nullptr;
+    q.r4 = h->has_phase ? h->phase3 + 3 * h->cells : nullptr;
+    q.q = r.q;
+    q.H = H; q.W = W; q.pitch = h->pitch; q.R = r.R;
+    const dim3 qgrid((unsigned)((W + LD_TX - 1) / LD_TX), (unsigned)((H + LD_TY - 1) / LD_TY));
+    if (int rc = launch_traced(h, "pmap_source_kernel", 0, [&] { hipLaunchKernelGGL(pmap_source_kernel, qgrid, dim3(LD_THREADS), 0, h->s0, q); }))
+        return rc;
+    PMapArgs a;
+    a.q = r.q;
+    a.tab = r.tab;
+    a.out = r.cube + (size_t)s * r.npix();
+    a.R = r.R; a.r0 = r.r0; a.c0 = r.c0; a.sy = r.sy; a.sx = r.sx; a.oh = r.oh; a.ow = r.ow;
+    a.qh = H + 2 * r.R; a.qw = W + 2 * r.R;
+    a.pw = r.pw; a.roww = r.roww; a.slab = r.slab;
+    // a tile is 64 sites wide and four site rows per wave high: a small lattice gets workgroups of fewer waves, so that there are
+    // workgroups for the machine's 256 compute units (the sums do not depend on the tile: their order is R's alone)
+    const int tiles_x = (r.ow + PM_TX - 1) / PM_TX;
+    int waves = PM_THREADS / 64;
+    while (waves > 1 && tiles_x * ((r.oh + waves * PM_SPL - 1) / (waves * PM_SPL)) < 256) waves /= 2;
+    const dim3 grid((unsigned)tiles_x, (unsigned)((r.oh + waves * PM_SPL - 1) / (waves * PM_SPL)));
+    return launch_traced(h, "pmap_conv_kernel", 0, [&] {
+        if (r.sx == 1) hipLaunchKernelGGL(pmap_conv_kernel<true>, grid, dim3(64 * waves), 0, h->s0, a);
+        else hipLaunchKernelGGL(pmap_conv_kernel<false>, grid, dim3(64 * waves), 0, h->s0, a);
+    });
+}
+static void pmap_free(fibhip_ctx *h)
+{
+    dev_free(h->pm.weight);
+    dev_free(h->pm.tab);
+    dev_free(h->pm.q);
+    dev_free(h->pm.cube);
+    dev_free(h->pm.maps);
+    h->pm.on = false;
 }
 
 static_assert(sizeof(WaveRecord) == sizeof(fibhip_wave_record) && offsetof(WaveRecord, sum_r) == offsetof(fibhip_wave_record, sum_r) &&
@@ -1446,6 +1499,132 @@ extern "C" int fibhip_leads_end(fibhip_t h)
 {
     NEED(h);
     return detach(h, h->ld.on, leads_free);
+}
+
+// ---- potential-map recorder ---------------------------------------------------------------------------------------------
+extern "C" int fibhip_pmap_begin(fibhip_t h, int var, int radius, const float *table, const float *weight, const int *window, int sy, int sx,
+                                 int every, long long capacity)
+{
+    NEED(h);
+    if (!table || !window) return fail(FIBHIP_EINVAL, "pmap_begin: null argument");
+    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "pmap_begin: bad var %d", var);
+    if (radius < 1 || radius > FIBHIP_PMAP_MAX_RADIUS)
+        return fail(FIBHIP_EINVAL, "pmap_begin: radius must be 1 .. %d (got %d)", FIBHIP_PMAP_MAX_RADIUS, radius);
+    if (sy < 1 || sy > FIBHIP_PMAP_MAX_STEP || sx < 1 || sx > FIBHIP_PMAP_MAX_STEP)
+        return fail(FIBHIP_EINVAL, "pmap_begin: a step is 1 .. %d cells each way (got %d x %d)", FIBHIP_PMAP_MAX_STEP, sy, sx);
+    if (every < 1) return fail(FIBHIP_EINVAL, "pmap_begin: every must be >= 1 (got %d)", every);
+    const int H = h->d.height, W = h->d.width, R = radius, K = 2 * R + 1;
+    if (H < 3 || W < 3) return fail(FIBHIP_EINVAL, "pmap_begin: a %d x %d grid has no interior cell", H, W);
+    if (int rc = rect_check(h, window[0], window[1], window[2], window[3], "pmap_begin: the window ")) return rc;
+    const int r0 = window[0], c0 = window[2], oh = (window[1] - r0 + sy - 1) / sy, ow = (window[3] - c0 + sx - 1) / sx;
+    const size_t npix = (size_t)oh * (size_t)ow;
+    if (capacity < 1 || capacity > INT_MAX || capacity > (long long)(SIZE_MAX / sizeof(double) / npix))
+        return fail(FIBHIP_EINVAL, "pmap_begin: bad capacity %lld", capacity);
+    if (zero_padded(h))
+        return fail(FIBHIP_EINVAL, "pmap_begin: not on a model with the zero-padded Laplacian (FIBHIP_ZEROPAD): its diffusion term is not this source");
+    for (int i = 0; i < (R + 1) * (R + 1); ++i)
+        if (!std::isfinite(table[i]))
+            return fail(FIBHIP_EINVAL, "pmap_begin: the table has a value that is not finite (row %d, column %d)", i / (R + 1), i % (R + 1));
+    if (weight)
+        for (size_t i = 0; i < h->cells; ++i)
+            if (!std::isfinite(weight[i]))
+                return fail(FIBHIP_EINVAL, "pmap_begin: the weight plane has a value that is not finite (row %zu, column %zu)", i / (size_t)W,
+                            i % (size_t)W);
+    if (int rc = attach_refusals(h, "pmap_begin")) return rc;
+    // the table's rows as pmap_conv_kernel walks them: float64, dc = -R .. R
+    std::vector<double> tab((size_t)(R + 1) * K);
+    for (int a = 0; a <= R; ++a)
+        for (int x = 0; x < K; ++x) tab[(size_t)a * K + x] = (double)table[a * (R + 1) + std::abs(x - R)];
+    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
+    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
+    FLUSH(h);
+    SYNC_S0(h);
+    pmap_free(h);
+    PMapRec &r = h->pm;
+    const size_t qcells = (size_t)(H + 2 * R) * (size_t)(W + 2 * R);
+    bool ok = hipMalloc((void **)&r.cube, (size_t)capacity * npix * sizeof(double)) == hipSuccess &&
+              hipMalloc((void **)&r.tab, tab.size() * sizeof(double)) == hipSuccess && hipMalloc((void **)&r.q, qcells * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&r.maps, npix * (3 * sizeof(double) + 3 * sizeof(int))) == hipSuccess;
+    if (ok && weight) ok = hipMalloc((void **)&r.weight, h->cells * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        pmap_free(h);
+        return fail(FIBHIP_ENOMEM, "pmap_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d x %d sites)", capacity, oh, ow);
+    }
+    HIPCHK(hipMemcpyAsync(r.tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->s0));
+    if (weight) HIPCHK(hipMemcpyAsync(r.weight, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemsetAsync(r.q, 0, qcells * sizeof(float), h->s0));                            // (the border stays: the kernel writes the grid's cells only)
+    HIPCHK(hipMemsetAsync(r.cube, 0, (size_t)capacity * npix * sizeof(double), h->s0));
+    HIPCHK(wait_stream(h->s0));                        // `tab` and the caller's arrays are free again
+    r.on = true;
+    r.start(every, capacity);
+    r.before_slow = slow_array(var);
+    r.var = var;
+    r.R = R;
+    r.r0 = r0; r.c0 = c0; r.sy = sy; r.sx = sx; r.oh = oh; r.ow = ow;
+    r.pw = PM_TX - 1 + (K + sx - 1) / sx;              // ceil(((PM_TX - 1) * sx + K) / sx)
+    r.roww = sx * r.pw;
+    r.slab = PM_LDS_FLOATS / r.roww;
+    return 0;
+}
+
+extern "C" int fibhip_pmap_count(fibhip_t h, long long *samples)
+{
+    NEED(h);
+    if (!samples) return fail(FIBHIP_EINVAL, "pmap_count: null argument");
+    if (!h->pm.on) return fail(FIBHIP_EINVAL, "pmap_count: no recorder attached (fibhip_pmap_begin)");
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    *samples = h->pm.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+
+extern "C" int fibhip_pmap_read(fibhip_t h, long long first, long long count, double *dst)
+{
+    NEED(h);
+    if (!h->pm.on) return fail(FIBHIP_EINVAL, "pmap_read: no recorder attached (fibhip_pmap_begin)");
+    FLUSH(h);
+    if (int rc = range_check("pmap_read", "samples", first, count, h->pm.taken())) return rc;
+    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "pmap_read: null destination");
+    const size_t npix = h->pm.npix();
+    return read_confirmed(h, [&] {
+        if (count > 0) HIPCHK(hipMemcpyAsync(dst, h->pm.cube + (size_t)first * npix, (size_t)count * npix * sizeof(double), hipMemcpyDeviceToHost, h->s0));
+        return 0;
+    });
+}
+
+extern "C" int fibhip_pmap_summary(fibhip_t h, long long first, long long count, double *vmin, double *vmax, double *dmin, int *kmin, int *kmax,
+                                   int *kd)
+{
+    NEED(h);
+    if (!h->pm.on) return fail(FIBHIP_EINVAL, "pmap_summary: no recorder attached (fibhip_pmap_begin)");
+    FLUSH(h);
+    if (int rc = range_check("pmap_summary", "samples", first, count, h->pm.taken())) return rc;
+    if (count < 2) return fail(FIBHIP_EINVAL, "pmap_summary: a summary takes at least 2 samples (got %lld)", count);
+    const PMapRec &r = h->pm;
+    const size_t npix = r.npix();
+    PMapSummaryArgs a;
+    a.cube = r.cube;
+    a.npix = npix;
+    a.first = (int)first; a.count = (int)count;
+    a.vmin = r.maps; a.vmax = r.maps + npix; a.dmin = r.maps + 2 * npix;
+    a.kmin = reinterpret_cast<int *>(r.maps + 3 * npix); a.kmax = a.kmin + npix; a.kd = a.kmin + 2 * npix;
+    void *const dst[6] = {vmin, vmax, dmin, kmin, kmax, kd};
+    const void *const src[6] = {a.vmin, a.vmax, a.dmin, a.kmin, a.kmax, a.kd};
+    // the samples read are confirmed ones when the copies are taken: a launch that gave up in front is recovered and the kernel
+    // runs again (read_confirmed), as for beats_summary
+    return read_confirmed(h, [&] {
+        if (int rc = launch_traced(h, "pmap_summary_kernel", 0, [&] { hipLaunchKernelGGL(pmap_summary_kernel, blocks_of(npix), dim3(256), 0, h->s0, a); }))
+            return rc;
+        for (int i = 0; i < 6; ++i)
+            if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], src[i], npix * (i < 3 ? sizeof(double) : sizeof(int)), hipMemcpyDeviceToHost, h->s0));
+        return 0;
+    });
+}
+
+extern "C" int fibhip_pmap_end(fibhip_t h)
+{
+    NEED(h);
+    return detach(h, h->pm.on, pmap_free);
 }
 
 // ---- wave recorder ------------------------------------------------------------------------------------------------------

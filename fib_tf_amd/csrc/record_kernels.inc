@@ -1,4 +1,4 @@
-// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame, statistics, spectrum, beat, lead and wave recorders, and the
+// record_kernels.inc — the streaming kernels behind a committed tick: the activation, electrode, tip, frame, statistics, spectrum, beat, lead, potential-map and wave recorders, and the
 // plain copy whose shape they take (the bandwidth yardstick).  (included by kernels.hpp; the host side is record.inc)
 
 // ---- activation recorder (fibhip_observe_begin): per-cell event maps, updated after every observed tick ----------------
@@ -1402,6 +1402,17 @@ struct LeadArgs {
     int H, W, pitch, n;
 };
 
+// q of one interior cell, what lead_kernel and pmap_source_kernel share: `t` points at the cell's word of an LDS tile of X that
+// has its one-cell ring staged through the clamp, LP floats per row; `o` is the cell's index r * W + c in the [H][W] planes
+template <int LP>
+static FIB_DEV float membrane_source(const float *t, size_t o, const float *w, const float *dpy, const float *dpx, const float *q4, const float *r4)
+{
+    const float N = t[-LP], S = t[LP], Wv = t[-1], E = t[1];
+    float s = stencil9(N, S, Wv, E, t[-LP - 1], t[LP - 1], t[-LP + 1], t[LP + 1], t[0]);
+    if (dpy) s = s + phase_term<Exact>(N, S, Wv, E, dpy[o], dpx[o], q4[o], r4[o]);
+    return w ? w[o] * s : s;
+}
+
 static FIB_DEV double lead_wave_sum(double v)
 {
 #pragma unroll
@@ -1463,12 +1474,7 @@ __global__ void __launch_bounds__(LD_THREADS) lead_kernel(LeadArgs a)
         ra[j] = min(r, H - 1);
         q[j] = 0.f;
         if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
-            const float *t = tile + (ly + 1) * LP + lane + 1;
-            const float N = t[-LP], S = t[LP], Wv = t[-1], E = t[1];
-            float s = stencil9(N, S, Wv, E, t[-LP - 1], t[LP - 1], t[-LP + 1], t[LP + 1], t[0]);
-            const size_t o = (size_t)r * (size_t)W + (size_t)c;
-            if (a.dpy) s = s + phase_term<Exact>(N, S, Wv, E, a.dpy[o], a.dpx[o], a.q4[o], a.r4[o]);
-            q[j] = a.w ? a.w[o] * s : s;
+            q[j] = membrane_source<LP>(tile + (ly + 1) * LP + lane + 1, (size_t)r * (size_t)W + (size_t)c, a.w, a.dpy, a.dpx, a.q4, a.r4);
         }
     }
     const size_t cells = (size_t)H * (size_t)W;
@@ -1511,6 +1517,245 @@ __global__ void __launch_bounds__(256) lead_combine_kernel(const double *__restr
     if ((threadIdx.x & 63u) == 0) wres[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) row[blockIdx.x] = (wres[0] + wres[1]) + (wres[2] + wres[3]);
+}
+
+// ---- potential-map recorder (fibhip_pmap_begin): the unipolar electrogram at every site of a lattice -----------------------
+// The source plane q is the lead recorder's (membrane_source on the interior cells, +0.0 on the outer ring).  Site (i, j) of the
+// lattice sits at the cell (r, c) = (r0 + i * sy, c0 + j * sx); its value is the truncated convolution of q with the table
+// T[R + 1][R + 1], summed in float64 in an order that R alone fixes:
+//     phi = +0.0;  for dr = -R .. R:  p = +0.0;  for dc = -R .. R:  p = fma((double)T[|dr|][|dc|], (double)q[r + dr][c + dc], p);
+//                                     phi = phi + p
+// with q = +0.0 off the grid.  The product of two float32 values is exact in float64, so the fma rounds what multiply-then-add
+// rounds: the same bits.  Three kernels:
+//   pmap_source_kernel, lead_kernel's grid and tile: writes q of every cell of the grid into a scratch plane that carries R
+//     zeros on every side (zeroed at attach, never written), cell (r, c) at (r + R, c + R): the window of a site at (r, c)
+//     starts at (r, c) of the padded plane and the convolution needs no bounds logic on the grid.
+//   pmap_conv_kernel, a workgroup of 4, 2 or 1 waves (the host's choice: more workgroups for a small lattice; the sums do not
+//     depend on it) owns a tile of PM_TX x (PM_SPL * waves) sites: lane l of wave v owns the sites (row PM_SPL * v + j, column
+//     l) of the tile, j = 0 .. PM_SPL - 1, one float64 accumulator each.  The q rows the tile needs —
+//     its span plus 2R — are staged in LDS in slabs of as many rows as PM_LDS_FLOATS hold (step 1: the whole span at any
+//     radius, 80 x 128 floats at R = 32), ascending, so every site meets its rows in the order of dr.  A row is stored
+//     de-interleaved by the column step: column x of the span at (x % sx) * pw + x / sx, so that for every tap the 64 lanes
+//     read 64 consecutive words whatever the step — no bank conflict.  For a q row that all PM_SPL sites of the lane use (at
+//     step 1 and R = 32: 62 of a wave's 68 rows) one LDS word and one conversion serve PM_SPL fmas on independent chains;
+//     a row that only some use is walked site by site.  Which sites a row serves, the table row of each and the LDS address
+//     are wave-uniform: the table (float64, expanded to [R + 1][2R + 1] at attach) comes through scalar loads.  Plain 64-bit
+//     stores into the sample's slot; no atomics.
+//   pmap_summary_kernel, one thread per site, at read time on the cube where it lies: walks the samples [first, first + count).
+#define PM_TX 64
+#define PM_TY 16
+#define PM_THREADS 256
+#define PM_SPL (PM_TY / (PM_THREADS / 64))      // sites per lane
+#define PM_MAX_RADIUS 32        // FIBHIP_PMAP_MAX_RADIUS
+#define PM_MAX_STEP 16          // FIBHIP_PMAP_MAX_STEP
+#define PM_LDS_FLOATS (80 * 128)
+struct PMapSourceArgs {
+    const float *x;             // the watched array (its first row), `pitch` floats between rows
+    const float *w;             // the weight plane [H][W], or null
+    const float *dpy, *dpx, *q4, *r4;   // the prepared phase arrays [H][W], or all null: no phase field
+    float *q;                   // the padded plane [H + 2R][W + 2R]
+    int H, W, pitch, R;
+};
+struct PMapArgs {
+    const float *q;             // the padded plane [qh][qw]
+    const double *tab;          // [R + 1][2R + 1]: tab[a][x] = (double)T[a][|x - R|]
+    double *out;                // the sample's slot [oh][ow]
+    int R, r0, c0, sy, sx, oh, ow, qh, qw;
+    int pw, roww, slab;         // the LDS layout: words per phase of a row, words per row (sx * pw), rows per slab
+};
+struct PMapSummaryArgs {
+    const double *cube;         // [samples][npix]
+    size_t npix;
+    int first, count;           // count >= 2
+    double *vmin, *vmax, *dmin; // [npix] each
+    int *kmin, *kmax, *kd;
+};
+
+__global__ void __launch_bounds__(LD_THREADS) pmap_source_kernel(PMapSourceArgs a)
+{
+    constexpr int LP = LD_TX + 2, LQ = LD_TY + 2, NW = LD_THREADS / 64;
+    __shared__ float tile[LQ * LP];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x0 = (int)blockIdx.x * LD_TX, y0 = (int)blockIdx.y * LD_TY;
+    const int H = a.H, W = a.W;
+    for (int i = tid; i < LQ * LP; i += LD_THREADS) {
+        const int ly = i / LP, lx = i - ly * LP;
+        const int yy = clampi(y0 - 1 + ly, 1, H - 2), xx = clampi(x0 - 1 + lx, 1, W - 2);
+        tile[i] = a.x[(size_t)yy * (size_t)a.pitch + (size_t)xx];
+    }
+    __syncthreads();
+    const int c = x0 + lane;
+    const size_t qw = (size_t)W + 2 * (size_t)a.R;
+#pragma unroll
+    for (int j = 0; j < LD_CPT; ++j) {
+        const int ly = wave + NW * j, r = y0 + ly;
+        if (r >= H || c >= W) continue;
+        float q = 0.f;
+        if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2)
+            q = membrane_source<LP>(tile + (ly + 1) * LP + lane + 1, (size_t)r * (size_t)W + (size_t)c, a.w, a.dpy, a.dpx, a.q4, a.r4);
+        a.q[(size_t)(r + a.R) * qw + (size_t)(c + a.R)] = q;
+    }
+}
+
+// N taps of one q row for the four sites of a lane: the 4 N table values (wave-uniform: scalar loads) and the N words of the row
+// are all asked for in front of the arithmetic, so that one wait covers them — a scalar load per tap, waited for on its own,
+// cost the first version of this kernel most of its time.  `x0` is the first tap, (ph, ix) the place of tap x0 in a row that is
+// de-interleaved by the column step (UNIT: the step is 1 and the place is x0 itself)
+template <int N, bool UNIT>
+static FIB_DEV void pmap_taps4(const float *row, const double *__restrict__ t0, const double *__restrict__ t1, const double *__restrict__ t2,
+                               const double *__restrict__ t3, int x0, int &ph, int &ix, int sx, int pw, double &p0, double &p1, double &p2,
+                               double &p3)
+{
+    double a0[N], a1[N], a2[N], a3[N];
+    float q[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        a0[i] = t0[x0 + i]; a1[i] = t1[x0 + i]; a2[i] = t2[x0 + i]; a3[i] = t3[x0 + i];
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        q[i] = row[UNIT ? x0 + i : ph * pw + ix];
+        if (!UNIT && ++ph == sx) { ph = 0; ++ix; }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const double qd = (double)q[i];
+        p0 = __builtin_fma(a0[i], qd, p0);
+        p1 = __builtin_fma(a1[i], qd, p1);
+        p2 = __builtin_fma(a2[i], qd, p2);
+        p3 = __builtin_fma(a3[i], qd, p3);
+    }
+}
+// ... and for ONE site of the lane
+template <int N, bool UNIT>
+static FIB_DEV void pmap_taps1(const float *row, const double *__restrict__ t, int x0, int &ph, int &ix, int sx, int pw, double &p)
+{
+    double a[N];
+    float q[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) a[i] = t[x0 + i];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        q[i] = row[UNIT ? x0 + i : ph * pw + ix];
+        if (!UNIT && ++ph == sx) { ph = 0; ++ix; }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) p = __builtin_fma(a[i], (double)q[i], p);
+}
+// one q row for ONE site of the lane: p = the sum over the row's K taps, ascending; `t` is the site's table row (wave-uniform)
+template <bool UNIT>
+static FIB_DEV double pmap_row1(const float *row, const double *__restrict__ t, int K, int sx, int pw)
+{
+    double p = 0.0;
+    int x = 0, ph = 0, ix = 0;
+    for (; x + 16 <= K; x += 16) pmap_taps1<16, UNIT>(row, t, x, ph, ix, sx, pw, p);
+    if (x + 8 <= K) { pmap_taps1<8, UNIT>(row, t, x, ph, ix, sx, pw, p); x += 8; }
+    if (x + 4 <= K) { pmap_taps1<4, UNIT>(row, t, x, ph, ix, sx, pw, p); x += 4; }
+    if (x + 2 <= K) { pmap_taps1<2, UNIT>(row, t, x, ph, ix, sx, pw, p); x += 2; }
+    if (x < K) pmap_taps1<1, UNIT>(row, t, x, ph, ix, sx, pw, p);
+    return p;
+}
+
+template <bool UNIT>
+__global__ void __launch_bounds__(PM_THREADS) pmap_conv_kernel(PMapArgs a)
+{
+    static_assert(PM_SPL == 4, "the shared row below names four sites");
+    __shared__ float lds[PM_LDS_FLOATS];
+    const int tid = (int)threadIdx.x, lane = tid & 63, threads = (int)blockDim.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // (wave-uniform, and known to be)
+    const int ty = (threads >> 6) * PM_SPL;                             // site rows of a tile: 4 per wave of the workgroup
+    const int R = a.R, K = 2 * R + 1, sy = a.sy, sx = UNIT ? 1 : a.sx, pw = a.pw;
+    const int sr0 = (int)blockIdx.y * ty, sc0 = (int)blockIdx.x * PM_TX;         // the tile's first site
+    const int py0 = a.r0 + sr0 * sy, px0 = a.c0 + sc0 * sx;                      // where its span starts in the padded plane
+    const int span = (min(ty, a.oh - sr0) - 1) * sy + K;                         // q rows the tile needs
+    const int width = (PM_TX - 1) * sx + K;                                      // q columns of a full tile
+    // the lane's sites: site j's window starts at row top[j] of the span; a site below the lattice's last row is left out
+    int top[PM_SPL];
+    bool have[PM_SPL];
+#pragma unroll
+    for (int j = 0; j < PM_SPL; ++j) {
+        top[j] = (wave * PM_SPL + j) * sy;
+        have[j] = sr0 + wave * PM_SPL + j < a.oh;
+    }
+    double phi[PM_SPL] = {0.0, 0.0, 0.0, 0.0};
+    for (int s0 = 0; s0 < span; s0 += a.slab) {
+        const int ns = min(a.slab, span - s0);
+        __syncthreads();                                                         // (the slab before has been read)
+        // (every load is made from an address clamped into the plane and its value dropped where the cell is outside: with no
+        // branch around them, eight loads of a thread are in flight together — one at a time, their latency was the sample's time)
+#pragma unroll 8
+        for (int i = tid; i < ns * a.roww; i += threads) {
+            const int ly = i / a.roww, p = i - ly * a.roww;
+            int x = p;
+            if (!UNIT) {
+                const int ph = p / pw, ix = p - ph * pw;
+                x = ix * sx + ph;
+            }
+            const int gy = py0 + s0 + ly, gx = px0 + x;
+            const float v = a.q[(size_t)min(gy, a.qh - 1) * (size_t)a.qw + (size_t)min(gx, a.qw - 1)];
+            lds[i] = (x < width && gy < a.qh && gx < a.qw) ? v : 0.f;
+        }
+        __syncthreads();
+        if (!have[0]) continue;                                                  // (a wave with no site of the lattice: it only stages)
+        const int ylo = max(s0, top[0]), yhi = min(s0 + ns, top[PM_SPL - 1] + K);
+        for (int y = ylo; y < yhi; ++y) {
+            const float *row = lds + (y - s0) * a.roww + lane;
+            int d[PM_SPL];                                                       // dr + R of this row for site j
+            bool act[PM_SPL];
+#pragma unroll
+            for (int j = 0; j < PM_SPL; ++j) {
+                d[j] = y - top[j];
+                act[j] = have[j] && d[j] >= 0 && d[j] < K;
+            }
+            if (act[0] && act[1] && act[2] && act[3]) {
+                const double *__restrict__ t0 = a.tab + (size_t)__builtin_abs(d[0] - R) * K;
+                const double *__restrict__ t1 = a.tab + (size_t)__builtin_abs(d[1] - R) * K;
+                const double *__restrict__ t2 = a.tab + (size_t)__builtin_abs(d[2] - R) * K;
+                const double *__restrict__ t3 = a.tab + (size_t)__builtin_abs(d[3] - R) * K;
+                double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
+                int x = 0, ph = 0, ix = 0;
+                for (; x + 8 <= K; x += 8) pmap_taps4<8, UNIT>(row, t0, t1, t2, t3, x, ph, ix, sx, pw, p0, p1, p2, p3);
+                if (x + 4 <= K) { pmap_taps4<4, UNIT>(row, t0, t1, t2, t3, x, ph, ix, sx, pw, p0, p1, p2, p3); x += 4; }
+                if (x + 2 <= K) { pmap_taps4<2, UNIT>(row, t0, t1, t2, t3, x, ph, ix, sx, pw, p0, p1, p2, p3); x += 2; }
+                if (x < K) pmap_taps4<1, UNIT>(row, t0, t1, t2, t3, x, ph, ix, sx, pw, p0, p1, p2, p3);
+                phi[0] = phi[0] + p0;
+                phi[1] = phi[1] + p1;
+                phi[2] = phi[2] + p2;
+                phi[3] = phi[3] + p3;
+            } else {
+#pragma unroll
+                for (int j = 0; j < PM_SPL; ++j)
+                    if (act[j]) phi[j] = phi[j] + pmap_row1<UNIT>(row, a.tab + (size_t)__builtin_abs(d[j] - R) * K, K, sx, pw);
+            }
+        }
+    }
+    const int sc = sc0 + lane;
+    if (sc < a.ow) {
+#pragma unroll
+        for (int j = 0; j < PM_SPL; ++j) {
+            const int sr = sr0 + wave * PM_SPL + j;
+            if (sr < a.oh) a.out[(size_t)sr * (size_t)a.ow + (size_t)sc] = phi[j];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) pmap_summary_kernel(PMapSummaryArgs a)
+{
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.npix) return;
+    const double *__restrict__ c = a.cube + (size_t)a.first * a.npix + p;
+    double prev = c[0], lo = prev, hi = prev, dm = 0.0;
+    int klo = a.first, khi = a.first, kd = a.first + 1;
+    for (int s = 1; s < a.count; ++s) {
+        const double v = c[(size_t)s * a.npix];
+        if (v < lo) { lo = v; klo = a.first + s; }
+        if (v > hi) { hi = v; khi = a.first + s; }
+        const double d = v - prev;
+        if (s == 1 || d < dm) { dm = d; kd = a.first + s; }
+        prev = v;
+    }
+    a.vmin[p] = lo; a.vmax[p] = hi; a.dmin[p] = dm;
+    a.kmin[p] = klo; a.kmax[p] = khi; a.kd[p] = kd;
 }
 
 // ---- wave recorder (fibhip_waves_begin): connected components of the cells that meet a condition -------------------------

@@ -23,8 +23,8 @@ struct Recorder {
 };
 constexpr size_t NO_SAMPLER = ~(size_t)0;
 
-static recorder_advance_fn electrode_advance, tips_advance, frames_advance, stats_advance, leads_advance, waves_advance, spectrum_advance, beats_advance, stim_advance, trig_advance, lesion_advance;
-static recorder_free_fn electrode_free, tips_free, frames_free, stats_free, leads_free, waves_free, spectrum_free, beats_free, stim_free, trig_free, lesion_free;
+static recorder_advance_fn electrode_advance, tips_advance, frames_advance, stats_advance, leads_advance, pmap_advance, waves_advance, spectrum_advance, beats_advance, stim_advance, trig_advance, lesion_advance;
+static recorder_free_fn electrode_free, tips_free, frames_free, stats_free, leads_free, pmap_free, waves_free, spectrum_free, beats_free, stim_free, trig_free, lesion_free;
 static long long stim_next(const StimRec &r);                   // sched.inc
 static long long lesion_next(const LesionRec &r);               // sched.inc
 static inline bool stim_on(const fibhip_ctx *h) { return h->stim.on; }
@@ -60,6 +60,13 @@ static constexpr Recorder RECORDERS[] = {
     // whole from those partials.  Nothing is accumulated across samples and the slot follows from the counter, so a sample taken
     // from a void slab is overwritten, partials and row, when the replay takes it again
     {"lead", SAMPLER_AT(ld), leads_advance, leads_free},
+    // ... and the potential-map recorder, of the same kind: pmap_source_kernel reads the state, the phase arrays and the
+    // recorder's weight plane and writes EVERY cell of the scratch plane q (its border of zeros is written at attach and by
+    // nobody after); pmap_conv_kernel reads q and the recorder's constant table and writes every site of the sample's slot
+    // with plain stores.  Nothing is accumulated across samples and the slot follows from the counter: a sample taken from a
+    // void slab is overwritten, scratch plane and slot, when the replay takes it again.  No give-up word is needed: both
+    // kernels end on any state.  (pmap_summary_kernel runs at read time, behind a confirmed stream: read_confirmed)
+    {"potential map", SAMPLER_AT(pm), pmap_advance, pmap_free},
     // ... and the wave recorder, a sixth: the label plane and the slot plane are scratch that every sample rewrites before it
     // reads them (wave_label_kernel writes every label from the state, wave_root_kernel every slot that is read); the sample's
     // counts are zeroed in front of its kernels and its records initialised and filled whole; the slot follows from the counter.

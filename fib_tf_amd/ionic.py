@@ -291,6 +291,19 @@ class IonicModel:
         from .leads import LeadRecorder
         return LeadRecorder(self._attachable('record_leads'), positions, tables, table_of=table_of, every=every, weight=weight, var=var, capacity=capacity)
 
+    def record_potential_map(self, table, radius=None, every=10, window=None, step=(1, 1), var=0, weight='phase', max_samples=None):
+        """attaches a potential-map recorder (fib_tf_amd/potential.py) to this model's handle: every `every` ticks the unipolar
+        electrogram at every site of a lattice — the cells (r0 + i * sy, c0 + j * sx) of `window` = (r0, r1, c0, c1) (None: the
+        whole grid) with `step` = (sy, sx), each 1 .. 16 — is formed on the device and kept there, one float64 per sample and
+        site, until `maps()` or `summary()` read it: the lead recorder's source w * laplace(X) summed in float64 through the ONE
+        lead-field `table` [R + 1, R + 1] truncated at `radius` R = 1 .. 32 (None: the table's; `potential.truncated_table` makes
+        a point electrode's).  `weight` as for record_leads.  Default `max_samples`: the samples of a whole run of `duration`.
+        Call after define(); single device only (row blocks raise NotImplementedError); a model with the zero-padded Laplacian
+        is refused."""
+        from .potential import PotentialMapRecorder
+        return PotentialMapRecorder(self._attachable('record_potential_map'), table, radius=radius, every=every, window=window, step=step, var=var,
+                                    weight=weight, max_samples=max_samples)
+
     def record_waves(self, level=None, kind='above', every=1, conn=4, mask=None, max_waves=256, capacity=None, var=0, also=None,
                      links=False, max_links=None):
         """attaches a wave recorder (fib_tf_amd/waves.py) to this model's handle: every `every` ticks the cells of `mask` where

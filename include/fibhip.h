@@ -560,6 +560,53 @@ int fibhip_leads_count(fibhip_t h, long long *samples);
 int fibhip_leads_read(fibhip_t h, long long first, long long count, double *dst /* [count][n] */);
 int fibhip_leads_end(fibhip_t h);
 
+/* Potential-map recorder: the unipolar electrogram at every site of a lattice.  The lead recorder's source, seen through ONE
+ * lead-field table truncated at a radius R, at as many sites as the grid has cells: every `every` ticks one float64 per site is
+ * appended to a cube that stays on the device until it is read.  With X the array `var` on the height x width grid, one sample is
+ * (restated in NumPy in tests/potential_ref.py):
+ *     source   the plane q, float32: on the interior cells q = w * S exactly as the lead recorder forms it (S the 9-point
+ *              Laplacian of the boundary-enforced array plus the phase-field term where the handle has a phase field, read from
+ *              the handle's CURRENT phase planes — a lesion shows from the next sample on —, always in the exact form; w the
+ *              caller's plane, or 1 without one); q = +0.0 on the outer ring of the grid and off the grid.
+ *     sites    the window (r0, r1, c0, c1) and the step (sy, sx), each 1 .. FIBHIP_PMAP_MAX_STEP: site (i, j) sits at the cell
+ *              (r0 + i * sy, c0 + j * sx), oh = ceil((r1 - r0) / sy) rows of ow = ceil((c1 - c0) / sx) sites.  A site may be
+ *              any cell of the grid, the outer ring included.
+ *     table    ONE float32 table T[R + 1][R + 1], R = 1 .. FIBHIP_PMAP_MAX_RADIUS: the weight of the cell (r + dr, c + dc) for
+ *              the site at (r, c) is T[|dr|][|dc|], |dr|, |dc| <= R.
+ *     sum      phi = +0.0; for dr = -R .. R ascending: p = +0.0; for dc = -R .. R ascending:
+ *              p = p + (double)T[|dr|][|dc|] * (double)q[r + dr][c + dc]; then phi = phi + p.  Every addition is rounded on its
+ *              own in float64; the product of two float32 values is exact in float64, so a fused multiply-add gives the same
+ *              bits and is what the device uses.  The order depends on R alone — not on the grid, the lattice, the launch plan,
+ *              the stride or the run.  Against the exact sum of the (2R + 1)^2 terms: |phi - sum| <= n u / (1 - n u) * sum |term|,
+ *              n = (2R + 1)^2 + 2R + 1, u = 2^-53.
+ * A NaN in one cell of X makes the sites within Chebyshev distance R + 1 of it NaN and no others.  The sample ticks, the
+ * capacity rule ("trace full"), and the 'slow' rule are those of the lead recorder; the recorder may be attached beside every
+ * other recorder, each with its own stride; on a shared tick its two kernels come directly behind the lead recorder's.
+ *     summary  over the samples [first, first + count), count >= 2, per site, made on the device where the cube lies: vmin and
+ *              vmax with the sample indices kmin and kmax (counted from the recorder's first sample), and dmin, the most
+ *              negative d[s] = phi[s] - phi[s - 1] (one rounded subtraction) over s = first + 1 .. first + count - 1, with its
+ *              index kd = s.  Strict compares, the first occurrence wins; each value starts from the first element (vmin = vmax
+ *              = phi[first], dmin = d[first + 1]), so a NaN that is not first never replaces anything and one that is first stays.
+ * Refused with FIBHIP_EINVAL, the message naming the offender: var out of range, a radius outside 1 .. FIBHIP_PMAP_MAX_RADIUS, a
+ * step outside 1 .. FIBHIP_PMAP_MAX_STEP, a window that is empty or outside the grid, a table or weight value that is not
+ * finite, every < 1, capacity < 1, a grid smaller than 3 x 3, a handle with the zero-padded Laplacian, inside an open tick, a
+ * row block; with FIBHIP_ENOMEM, and nothing attached, a cube that cannot be allocated.
+ *   fibhip_pmap_begin    flushes, synchronises and confirms pending work, copies the table and the plane and attaches
+ *   fibhip_pmap_count    samples taken so far (ticks accepted but not launched yet included)
+ *   fibhip_pmap_read     samples [first, first + count) as [count][oh][ow] float64; flushes and blocks like get_state; does not
+ *                        detach and does not reset the sample index
+ *   fibhip_pmap_summary  the six planes [oh][ow] of the summary (a null destination is skipped); flushes and blocks like _read
+ *   fibhip_pmap_end      detaches and frees the cube (no recorder attached: nothing); fibhip_destroy does the same             */
+#define FIBHIP_PMAP_MAX_RADIUS 32
+#define FIBHIP_PMAP_MAX_STEP 16
+int fibhip_pmap_begin(fibhip_t h, int var, int radius, const float *table /* [(R+1)*(R+1)] */, const float *weight /* [H*W] or NULL */,
+                      const int *window /* r0, r1, c0, c1 */, int sy, int sx, int every, long long capacity);
+int fibhip_pmap_count(fibhip_t h, long long *samples);
+int fibhip_pmap_read(fibhip_t h, long long first, long long count, double *dst /* [count][oh][ow] */);
+int fibhip_pmap_summary(fibhip_t h, long long first, long long count, double *vmin, double *vmax, double *dmin, int *kmin, int *kmax,
+                        int *kd /* [oh][ow] each */);
+int fibhip_pmap_end(fibhip_t h);
+
 /* Wave recorder: the excited domains of the sheet, labelled and measured on the device.  Every `every` ticks the cells that meet
  * a condition are grouped into connected components, the WAVES; their number, and per wave its size, centroid sums and bounding
  * box, are appended to lists that stay on the device until they are read.  Restated in NumPy in tests/wave_ref.py.
