@@ -292,12 +292,11 @@ SYMBOLS = {
 _lib = None
 
 
-DEPS = [SRC, HDR] + [os.path.join(HERE, "csrc", f) for f in ("kernels.hpp", "stencil.hpp", "tick_kernel.inc", "strip_mt.hpp",
-                                                             "strip_kernel.inc", "rows_kernel.inc", "pointwise.inc", "record_kernels.inc",
-                                                             "models.hpp", "fenton_step.inc", "br_step.inc",
-                                                             "court_step.inc", "court_inter.inc", "host_util.hpp", "launch.hpp",
-                                                             "ctx.hpp", "sampler.hpp", "recorders.hpp", "tick.inc", "sched.inc", "record.inc", "plan.inc", "comm.inc",
-                                                             "unit.inc")]
+# what the library is built from: the public header and every source file under csrc, found and not listed — a file that is
+# added there cannot be forgotten here, and so cannot leave a stale build behind a passing test run (sorted: the specialised and
+# traced builds hash the files in this order)
+DEPS = [SRC, HDR] + sorted(os.path.join(HERE, 'csrc', f) for f in os.listdir(os.path.join(HERE, 'csrc'))
+                           if f.endswith(('.hpp', '.inc', '.hip')) and os.path.join(HERE, 'csrc', f) != SRC)
 
 
 def build(force=False, verbose=False):

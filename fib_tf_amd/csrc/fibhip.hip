@@ -27,14 +27,15 @@
 
 using namespace fib;
 
-// One translation unit, in dependency order.  Every file below is listed in fib_tf_amd/_lib.py DEPS.
+// One translation unit, in dependency order.  fib_tf_amd/_lib.py DEPS is every *.hpp, *.inc and *.hip of this directory.
 #include "host_util.hpp"    // fail, HIPCHK, the spin-waits
 #include "launch.hpp"       // LaunchCtx, the launchers, the variant table
 #include "ctx.hpp"          // fibhip_ctx and its parts, NEED / FLUSH / CONFIRM / SYNC_S0, the timeline
 #include "recorders.hpp"    // the table of the hooks behind a committed launch, in hook order
 #include "tick.inc"         // one tick: pointer tables, rows, edges / interior / commit
 #include "sched.inc"        // when ticks are launched: deferral, multi-tick launches, run-ahead, journal and recovery, fibhip_step
-#include "record.inc"       // activation, electrode, tip, frame, statistics, lead, wave, spectrum and beat recorders; the stimulus program, the trigger program and the lesion program
+#include "record.inc"       // the ten recorders (activation, electrode, tip, frame, statistics, lead, potential map, wave, spectrum,
+                            // beat) and the velocity fit; the stimulus, trigger and lesion programs; includes attach_checks.hpp
 #include "plan.inc"         // build_plan, autotune
 #include "comm.inc"         // the RCCL halo path and fibhip_halo_plan
 // this file: create / destroy, state get / set, pointwise modes, pace / probe / sync / timing, run-time modules, accessors and

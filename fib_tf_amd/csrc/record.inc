@@ -1,14 +1,20 @@
 // record.inc — what runs on the device behind the ticks while a model runs.  Ten recorders: the per-cell activation maps
 // (fibhip_observe_*), the electrode traces (fibhip_electrode_*), the spiral-tip lists (fibhip_tips_*), the movie cube
-// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the unipolar electrograms (fibhip_leads_*), the potential map (fibhip_pmap_*), the excited domains and their links from sample to sample (fibhip_waves_*), the per-cell power spectra (fibhip_spectrum_*) and the per-cell
-// beat history (fibhip_beats_*); and the two hooks that write the state: the stimulus program (fibhip_stim_*) and the trigger
-// program (fibhip_trig_*), which senses, decides and fires on the device.
+// (fibhip_frames_*), the tissue statistics (fibhip_stats_*), the unipolar electrograms (fibhip_leads_*), the potential map
+// (fibhip_pmap_*), the excited domains and their links from sample to sample (fibhip_waves_*), the per-cell power spectra
+// (fibhip_spectrum_*) and the per-cell beat history (fibhip_beats_*), with the velocity fit on the beat and activation
+// recorders' planes (fibhip_beats_velocity, fibhip_observe_velocity); the two hooks that write the state: the stimulus program
+// (fibhip_stim_*) and the trigger program (fibhip_trig_*), which senses, decides and fires on the device; and the one that
+// writes the phase field: the lesion program (fibhip_lesion_*, with fibhip_lesion_apply and fibhip_get_phase beside it).
 // The file has three parts: the helpers every recorder shares; the hooks — per recorder its _advance (behind a launch that the
 // handle's state has moved with) and its _free, the two functions its row of RECORDERS (recorders.hpp) names —; and the entry
-// points.  Every hook but the activation recorder's (it sees every tick) and the stimulus program's (event-driven: its own k and
-// next) counts with a Sampler (sampler.hpp) and computes the slot it writes from that counter alone, so a replay (sched.inc recover()) writes the same slots again.  What the recorders ask
-// of the scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
+// points, which are one routine with per-recorder content: the argument checks of attach_checks.hpp, attach_ready, Attach,
+// sampler_count, ranged_read and detach.  Every hook but the activation recorder's (it sees every tick) and the two programs'
+// (stimulus, lesion: event-driven, their own k and next) counts with a Sampler (sampler.hpp) and computes the slot it writes
+// from that counter alone, so a replay (sched.inc recover()) writes the same slots again.  What the recorders ask of the
+// scheduler is stated in sched.inc ("what the recorders ask of the scheduler").
 // (included by fibhip.hip, behind sched.inc)
+#include "attach_checks.hpp"    // var, every, capacity, a finite plane, a rectangle, a window, the range of a _read
 
 // ---- helpers ------------------------------------------------------------------------------------------------------------
 // where array `var` of the state lives now
@@ -49,6 +55,19 @@ static int launch_traced(fibhip_ctx *h, const char *name, int K, F launch)
     return 0;
 }
 static inline dim3 blocks_of(size_t threads) { return dim3((unsigned)((threads + 255) / 256)); }
+// may a kernel read four cells of a row with one 16-byte load?  The arrays are not row-interleaved, a row is a whole number of
+// such loads, and every pointer ORed into `align` is 16-byte aligned
+static inline bool rows_vec_ok(const fibhip_ctx *h, uintptr_t align) { return h->pitch == h->d.width && h->d.width % 4 == 0 && (align & 15u) == 0; }
+// the four planes of the phase field that the source term of the lead and potential-map recorders reads (LeadArgs,
+// PMapSourceArgs), null on a handle without a field
+template <class Args>
+static inline void phase_planes_fill(const fibhip_ctx *h, Args &a)
+{
+    a.dpy = h->has_phase ? h->phase3 : nullptr;
+    a.dpx = h->has_phase ? h->phase3 + h->cells : nullptr;
+    a.q4 = h->has_phase ? h->phase3 + 2 * h->cells : nullptr;
+    a.r4 = h->has_phase ? h->phase3 + 3 * h->cells : nullptr;
+}
 
 // what no recorder attaches to: a row block, an open tick
 static int attach_refusals(const fibhip_ctx *h, const char *who)
@@ -57,29 +76,95 @@ static int attach_refusals(const fibhip_ctx *h, const char *who)
     if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "%s inside an open tick", who);
     return 0;
 }
-// "<prefix>rows [r0, r1) x columns [c0, c1) is empty or outside the H x W grid"; the prefix is printf's
-static int rect_check(const fibhip_ctx *h, int r0, int r1, int c0, int c1, const char *prefix, ...)
+// The step in front of every attach, before anything is allocated: attach_refusals, then the refusals of the recorder's own
+// that come behind them (`late`, which returns a status), then the recorder that may still be attached goes (`release`).  In
+// between, everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE,
+// before tick k = 0 of the new recorder is defined and before anything of the state is copied for it — it must not start from
+// the slab such a launch left void.  The scheduler depends on the order: every journal record is younger than every recorder
+// (recorders.hpp recorders_rewind), so `on` is set last, behind the uploads and the wait (Attach)
+template <class F>
+static int attach_ready(fibhip_ctx *h, const char *who, recorder_free_fn *release, F late)
 {
-    const int H = h->d.height, W = h->d.width;
-    if (r0 >= 0 && r1 <= H && c0 >= 0 && c1 <= W && r0 < r1 && c0 < c1) return 0;
-    char who[128];
-    va_list ap;
-    va_start(ap, prefix);
-    vsnprintf(who, sizeof who, prefix, ap);
-    va_end(ap);
-    return fail(FIBHIP_EINVAL, "%srows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d grid", who, r0, r1, c0, c1, H, W);
+    if (int rc = attach_refusals(h, who)) return rc;
+    if (int rc = late()) return rc;
+    FLUSH(h);
+    SYNC_S0(h);
+    if (release) release(h);
+    return 0;
 }
+static int attach_ready(fibhip_ctx *h, const char *who, recorder_free_fn *release)
+{
+    return attach_ready(h, who, release, [] { return 0; });
+}
+// The device buffers of one attach, each named ONCE with how it starts — alloc: n elements of T, left as they are or filled
+// whole with a byte (0, 0xFF) or with quiet NaNs (QNAN: 4-byte elements); upload: n elements of T from the host; alloc_bytes: a
+// buffer that holds more than one type — and then the sequence every _begin runs:
+//   the allocations happen as they are named; the first failure sticks and the later ones are skipped;
+//   failed(): on failure the HIP error is cleared and the recorder's _free releases what had been allocated — the caller
+//             returns FIBHIP_ENOMEM with its own message;
+//   enqueue(): the fills and uploads, on s0 — none before every allocation has succeeded, so the failure path has no work in
+//             flight on buffers being released;
+//   wait(): the stream is waited for: the host tables and the caller's arrays are free again.  finish() is both.
+// Not an allocator: it owns nothing once _begin returns, and the _free functions stay the lists they are.
+struct Attach {
+    enum Fill { KEEP = -1, ZERO = 0, ONES = 0xFF, QNAN = 0x100 };
+    struct Start {
+        void *dst;
+        const void *src;        // an upload, or null: a fill (or nothing)
+        Fill fill;
+        size_t bytes;
+    };
+    fibhip_ctx *h;
+    hipError_t err = hipSuccess;
+    std::vector<Start> starts;
+    explicit Attach(fibhip_ctx *h_) : h(h_) {}
+    template <class T>
+    void alloc_bytes(T *&p, size_t bytes, Fill fill = KEEP, const void *src = nullptr)
+    {
+        if (err != hipSuccess) return;
+        err = hipMalloc((void **)&p, bytes);
+        if (err == hipSuccess && (src || fill != KEEP)) starts.push_back({p, src, fill, bytes});
+    }
+    template <class T>
+    void alloc(T *&p, size_t n, Fill fill = KEEP)
+    {
+        alloc_bytes(p, n * sizeof(T), fill);
+    }
+    template <class T>
+    void upload(T *&p, size_t n, const T *src) { alloc_bytes(p, n * sizeof(T), KEEP, src); }
+    bool failed(recorder_free_fn *release)
+    {
+        if (err == hipSuccess) return false;
+        (void)hipGetLastError();
+        release(h);
+        return true;
+    }
+    int enqueue()
+    {
+        for (const Start &s : starts) {
+            if (s.src) HIPCHK(hipMemcpyAsync(s.dst, s.src, s.bytes, hipMemcpyHostToDevice, h->s0));
+            else if (s.fill == QNAN) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)s.dst, (int)qnan_bits(), s.bytes / 4, h->s0));
+            else HIPCHK(hipMemsetAsync(s.dst, (int)s.fill, s.bytes, h->s0));
+        }
+        starts.clear();
+        return 0;
+    }
+    int wait()
+    {
+        HIPCHK(wait_stream(h->s0));
+        return 0;
+    }
+    int finish()
+    {
+        if (int rc = enqueue()) return rc;
+        return wait();
+    }
+};
 // the pixel plane of the frame, spectrum and beat recorders from the caller's window, block and reduction
 static int window_from(const fibhip_ctx *h, const char *who, const int *window, int by, int bx, int reduce, Window &out)
 {
-    const int r0 = window[0], r1 = window[1], c0 = window[2], c1 = window[3];
-    if (int rc = rect_check(h, r0, r1, c0, c1, "%s: the window ", who)) return rc;
-    if (by < 1 || by > FIBHIP_MAX_FRAME_BLOCK || bx < 1 || bx > FIBHIP_MAX_FRAME_BLOCK)
-        return fail(FIBHIP_EINVAL, "%s: a block is 1 .. %d cells each way (got %d x %d)", who, FIBHIP_MAX_FRAME_BLOCK, by, bx);
-    const int oh = (r1 - r0) / by, ow = (c1 - c0) / bx;
-    if (oh < 1 || ow < 1) return fail(FIBHIP_EINVAL, "%s: a window of %d x %d cells holds no block of %d x %d", who, r1 - r0, c1 - c0, by, bx);
-    if (reduce != FIBHIP_FRAME_POINT && reduce != FIBHIP_FRAME_MEAN) return fail(FIBHIP_EINVAL, "%s: bad reduction %d", who, reduce);
-    out.r0 = r0; out.c0 = c0; out.oh = oh; out.ow = ow; out.by = by; out.bx = bx;
+    if (int rc = window_check(who, h->d.height, h->d.width, window, by, bx, reduce, out.oh, out.ow)) return rc;
+    out.r0 = window[0]; out.c0 = window[2]; out.by = by; out.bx = bx;
     out.reduce = reduce;
     out.w = nullptr;
     return 0;
@@ -88,8 +173,7 @@ static int window_from(const fibhip_ctx *h, const char *who, const int *window, 
 // whole blocks of them: what the three pixel kernels' vector paths share (each adds the alignment of what it writes)
 static inline bool window_vec_ok(const fibhip_ctx *h, const Window &p, const float *x)
 {
-    return h->pitch == h->d.width && h->d.width % 4 == 0 && p.c0 % 4 == 0 && p.ow % 4 == 0 &&
-           ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(p.w)) & 15u) == 0;
+    return rows_vec_ok(h, reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(p.w)) && p.c0 % 4 == 0 && p.ow % 4 == 0;
 }
 // the window's part of FrameArgs, SpecSampleArgs and BeatArgs
 template <class Args>
@@ -100,13 +184,6 @@ static inline void window_fill(const fibhip_ctx *h, const Window &p, int var, Ar
     a.pitch = h->pitch;
     a.wpitch = h->d.width;
     a.r0 = p.r0; a.c0 = p.c0; a.oh = p.oh; a.ow = p.ow; a.by = p.by; a.bx = p.bx;
-}
-// "[first, first + count) of `taken`": the range a _read may ask for (`what`: "samples", "frames")
-static int range_check(const char *who, const char *what, long long first, long long count, long long taken)
-{
-    if (first < 0 || count < 0 || first + count > taken)
-        return fail(FIBHIP_EINVAL, "%s: %s [%lld, %lld) of %lld taken", who, what, first, first + count, taken);
-    return 0;
 }
 // A read-back: `copies` enqueues it on s0 (launches and asynchronous copies; it returns a status), then the stream is waited
 // for.  If that wait found a launch in front of the copies that had given up, the state was recovered and the lost samples
@@ -121,6 +198,46 @@ static int read_confirmed(fibhip_ctx *h, F copies)
         if (h->journal.n_fallbacks == fb0) break;
     }
     return 0;
+}
+// "<who>: no recorder attached (fibhip_<begin>)" (`noun`: the trigger program is a "program")
+static int need_attached(bool on, const char *who, const char *begin, const char *noun = "recorder")
+{
+    if (!on) return fail(FIBHIP_EINVAL, "%s: no %s attached (%s)", who, noun, begin);
+    return 0;
+}
+// every _count.  count_taken is the part the spectrum and beat recorders share with the rest (their outputs may be null)
+static int count_taken(fibhip_ctx *h, const Sampler &r, const char *who, const char *begin, const char *noun, long long *n)
+{
+    if (int rc = need_attached(r.on, who, begin, noun)) return rc;
+    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
+    *n = r.taken_with(h->pending);                     // (ticks accepted but not launched yet are sampled when they are)
+    return 0;
+}
+static int sampler_count(fibhip_ctx *h, const Sampler &r, const char *who, const char *begin, long long *samples, const char *noun = "recorder")
+{
+    if (!samples) return fail(FIBHIP_EINVAL, "%s: null argument", who);
+    return count_taken(h, r, who, begin, noun, samples);
+}
+// every _read that takes a range, behind the caller's "attached?": the pending ticks are launched, [first, first + count) is
+// checked against the samples taken (`what`: "samples", "frames"), and each copy moves `count` samples of `per` bytes from
+// `src` + first * per to `dst`.  The first destination must not be null; a later one that is null is left out
+struct ReadCopy {
+    void *dst;
+    const void *src;
+    size_t per;
+};
+static int ranged_read(fibhip_ctx *h, const Sampler &r, const char *who, const char *what, long long first, long long count,
+                       std::initializer_list<ReadCopy> copies)
+{
+    FLUSH(h);
+    if (int rc = range_check(who, what, first, count, r.taken())) return rc;
+    if (count > 0 && !copies.begin()->dst) return fail(FIBHIP_EINVAL, "%s: null destination", who);
+    return read_confirmed(h, [&] {
+        for (const ReadCopy &c : copies)
+            if (count > 0 && c.dst)
+                HIPCHK(hipMemcpyAsync(c.dst, static_cast<const char *>(c.src) + (size_t)first * c.per, (size_t)count * c.per, hipMemcpyDeviceToHost, h->s0));
+        return 0;
+    });
 }
 // every _end: nothing to do unless attached; else the ticks accepted while attached are sampled (their events applied), and
 // confirmed, so that no replay is left that would want the recorder; then its buffers go
@@ -209,7 +326,7 @@ static int tips_advance(fibhip_ctx *h, int ticks, bool)
     int *cnt = r.counts + 3 * (size_t)s;
     int4 *rec = reinterpret_cast<int4 *>(r.records) + (size_t)s * (size_t)r.max_tips;
     const Geo g = base_geo(h);
-    const bool vec = h->pitch == g.W && g.W % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
+    const bool vec = rows_vec_ok(h, reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b));
     const dim3 grid = blocks_of((size_t)(g.H - 1) * (size_t)(vec ? g.W / 4 : g.W - 1));
     HIPCHK(hipMemsetAsync(cnt, 0, 3 * sizeof(int), h->s0));
     return launch_traced(h, "tip_kernel", 0, [&] {
@@ -297,7 +414,7 @@ static int stats_advance(fibhip_ctx *h, int ticks, bool)
     a.part = r.part;
     a.nchunks = r.nchunks;
     // (the chunk table was cut for the vector path exactly when pitch == W and W % 4 == 0; the pointers are looked at here)
-    const bool vec = h->pitch == h->d.width && h->d.width % 4 == 0 && (align & 15u) == 0;
+    const bool vec = rows_vec_ok(h, align);
     const dim3 grid((unsigned)r.nchunks, (unsigned)r.narr);
     if (int rc = launch_traced(h, "stats_kernel", 0, [&] {
             if (vec) hipLaunchKernelGGL(stats_kernel<true>, grid, dim3(ST_THREADS), 0, h->s0, a);
@@ -334,10 +451,7 @@ static int leads_advance(fibhip_ctx *h, int ticks, bool)
     LeadArgs a;
     a.x = array_of(h, r.var);
     a.w = r.weight;
-    a.dpy = h->has_phase ? h->phase3 : nullptr;
-    a.dpx = h->has_phase ? h->phase3 + h->cells : nullptr;
-    a.q4 = h->has_phase ? h->phase3 + 2 * h->cells : nullptr;
-    a.r4 = h->has_phase ? h->phase3 + 3 * h->cells : nullptr;
+    phase_planes_fill(h, a);
     a.pos = r.pos;
     a.tables = r.tables;
     a.part = r.part;
@@ -375,10 +489,7 @@ static int pmap_advance(fibhip_ctx *h, int ticks, bool)
     PMapSourceArgs q;
     q.x = array_of(h, r.var);
     q.w = r.weight;
-    q.dpy = h->has_phase ? h->phase3 : nullptr;
-    q.dpx = h->has_phase ? h->phase3 + h->cells : nullptr;
-    q.q4 = h->has_phase ? h->phase3 + 2 * h->cells : nullptr;
-    q.r4 = h->has_phase ? h->phase3 + 3 * h->cells : nullptr;
+    phase_planes_fill(h, q);
     q.q = r.q;
     q.H = H; q.W = W; q.pitch = h->pitch; q.R = r.R;
     const dim3 qgrid((unsigned)((W + LD_TX - 1) / LD_TX), (unsigned)((H + LD_TY - 1) / LD_TY));
@@ -623,13 +734,13 @@ static int stim_entry_from(const fibhip_ctx *h, const char *who, const char *wha
 {
     const int H = h->d.height, W = h->d.width;
     const float ninf = -std::numeric_limits<float>::infinity();
-    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "%s: %s %d: bad var %d", who, what, i, var);
+    if (int rc = var_check(var, h->nvar, "%s: %s %d", who, what, i)) return rc;
     if (mode != FIBHIP_STIM_MAX && mode != FIBHIP_STIM_ADD) return fail(FIBHIP_EINVAL, "%s: %s %d: unknown mode %d", who, what, i, mode);
     if (shape != FIBHIP_STIM_RECT && shape != FIBHIP_STIM_PLANE) return fail(FIBHIP_EINVAL, "%s: %s %d: unknown shape %d", who, what, i, shape);
     e.var = var; e.mode = mode;
     const float untouched = mode == FIBHIP_STIM_MAX ? ninf : 0.f;
     if (shape == FIBHIP_STIM_RECT) {
-        if (int rc = rect_check(h, r0, r1, c0, c1, "%s: %s %d: ", who, what, i)) return rc;
+        if (int rc = rect_check(h->d.height, h->d.width, r0, r1, c0, c1, "%s: %s %d: ", who, what, i)) return rc;
         if (!std::isfinite(v)) return fail(FIBHIP_EINVAL, "%s: %s %d: v must be finite (got %g)", who, what, i, v);
         if (!(std::isfinite(floor) || (mode == FIBHIP_STIM_MAX && floor == ninf)))
             return fail(FIBHIP_EINVAL, "%s: %s %d: floor must be finite%s (got %g)", who, what, i, mode == FIBHIP_STIM_MAX ? " or -inf" : "", floor);
@@ -692,7 +803,7 @@ static bool stim_args_finish(const fibhip_ctx *h, StimArgs &a, int n, uintptr_t 
     a.W = W;
     a.pitch = h->pitch;
     a.give_up = give_up_of(h, behind_mt);
-    vec = h->pitch == W && W % 4 == 0 && (align & 15u) == 0;
+    vec = rows_vec_ok(h, align);
     if (vec) {
         a.c0 = a.c0 / 4 * 4;
         a.c1 = (a.c1 + 3) / 4 * 4;                                  // (<= W: W is a multiple of 4)
@@ -939,14 +1050,10 @@ static void trig_free(fibhip_ctx *h)
 extern "C" int fibhip_observe_begin(fibhip_t h, int var, float up, float down)
 {
     NEED(h);
-    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "observe_begin: bad var %d", var);
+    if (int rc = var_check(var, h->nvar, "observe_begin")) return rc;
     if (std::isnan(up) || std::isnan(down) || down > up)
         return fail(FIBHIP_EINVAL, "observe_begin: thresholds must be numbers with down <= up (got up %g, down %g)", up, down);
-    if (int rc = attach_refusals(h, "observe_begin")) return rc;
-    // everything accepted so far runs unobserved and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // Vp is copied (the recorder must not start from the slab such a launch left void)
-    FLUSH(h);
-    SYNC_S0(h);
+    if (int rc = attach_ready(h, "observe_begin", nullptr)) return rc;     // (the planes are kept from attach to attach: nothing to release)
     const size_t n = h->cells;
     if (!h->obs.buf) HIPCHK(hipMalloc((void **)&h->obs.buf, 6 * n * sizeof(float)));
     HIPCHK(hipMemcpy2DAsync(h->obs.buf, (size_t)h->d.width * sizeof(float), array_of(h, var), (size_t)h->pitch * sizeof(float),
@@ -1004,63 +1111,55 @@ extern "C" int fibhip_electrode_begin(fibhip_t h, int var, int n, const int *rec
 {
     NEED(h);
     if (!rects || !weights) return fail(FIBHIP_EINVAL, "electrode_begin: null argument");
-    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "electrode_begin: bad var %d", var);
+    if (int rc = var_check(var, h->nvar, "electrode_begin")) return rc;
     if (n < 1 || n > FIBHIP_MAX_ELECTRODES) return fail(FIBHIP_EINVAL, "electrode_begin: 1 .. %d electrodes (got %d)", FIBHIP_MAX_ELECTRODES, n);
-    if (every < 1) return fail(FIBHIP_EINVAL, "electrode_begin: every must be >= 1 (got %d)", every);
-    if (capacity < 1 || capacity > (long long)(SIZE_MAX / sizeof(float) / (size_t)n))
-        return fail(FIBHIP_EINVAL, "electrode_begin: bad capacity %lld", capacity);
-    if (int rc = attach_refusals(h, "electrode_begin")) return rc;
+    if (int rc = every_check("electrode_begin", every)) return rc;
+    if (int rc = capacity_check("electrode_begin", capacity, (size_t)n * sizeof(float))) return rc;
     // the chunk table: one chunk per patch of up to EL_CHUNK cells, larger patches in at most 256 equal chunks
     std::vector<ElChunk> chunks;
     std::vector<ElComb> combs;
     size_t woff = 0;
     int nparts = 0;
-    for (int e = 0; e < n; ++e) {
-        const int r0 = rects[4 * e], r1 = rects[4 * e + 1], c0 = rects[4 * e + 2], c1 = rects[4 * e + 3];
-        if (int rc = rect_check(h, r0, r1, c0, c1, "electrode_begin: electrode %d: ", e)) return rc;
-        const size_t m = (size_t)(r1 - r0) * (size_t)(c1 - c0);
-        if (woff + m > 0x7FFFFFFFu) return fail(FIBHIP_EINVAL, "electrode_begin: more than 2^31 - 1 weights");
-        for (size_t i = 0; i < m; ++i)
-            if (!std::isfinite(weights[woff + i])) return fail(FIBHIP_EINVAL, "electrode_begin: electrode %d has a weight that is not finite", e);
-        const size_t cs = m <= EL_CHUNK ? m : (m + 255) / 256 > EL_CHUNK ? (m + 255) / 256 : (size_t)EL_CHUNK;
-        const int nc = (int)((m + cs - 1) / cs);                       // <= 256
-        if (nc > 1) {
-            ElComb cb;
-            cb.e = e; cb.part0 = nparts; cb.nparts = nc;
-            combs.push_back(cb);
+    const auto cut = [&] {
+        for (int e = 0; e < n; ++e) {
+            const int r0 = rects[4 * e], r1 = rects[4 * e + 1], c0 = rects[4 * e + 2], c1 = rects[4 * e + 3];
+            if (int rc = rect_check(h->d.height, h->d.width, r0, r1, c0, c1, "electrode_begin: electrode %d: ", e)) return rc;
+            const size_t m = (size_t)(r1 - r0) * (size_t)(c1 - c0);
+            if (woff + m > 0x7FFFFFFFu) return fail(FIBHIP_EINVAL, "electrode_begin: more than 2^31 - 1 weights");
+            for (size_t i = 0; i < m; ++i)
+                if (!std::isfinite(weights[woff + i])) return fail(FIBHIP_EINVAL, "electrode_begin: electrode %d has a weight that is not finite", e);
+            const size_t cs = m <= EL_CHUNK ? m : (m + 255) / 256 > EL_CHUNK ? (m + 255) / 256 : (size_t)EL_CHUNK;
+            const int nc = (int)((m + cs - 1) / cs);                   // <= 256
+            if (nc > 1) {
+                ElComb cb;
+                cb.e = e; cb.part0 = nparts; cb.nparts = nc;
+                combs.push_back(cb);
+            }
+            for (int k = 0; k < nc; ++k) {
+                ElChunk c;
+                c.r0 = r0; c.c0 = c0; c.pw = c1 - c0;
+                c.first = (unsigned)((size_t)k * cs);
+                c.count = (unsigned)((size_t)(k + 1) * cs <= m ? cs : m - (size_t)k * cs);
+                c.woff = (unsigned)woff;
+                c.out = nc > 1 ? -1 - nparts++ : e;
+                chunks.push_back(c);
+            }
+            woff += m;
         }
-        for (int k = 0; k < nc; ++k) {
-            ElChunk c;
-            c.r0 = r0; c.c0 = c0; c.pw = c1 - c0;
-            c.first = (unsigned)((size_t)k * cs);
-            c.count = (unsigned)((size_t)(k + 1) * cs <= m ? cs : m - (size_t)k * cs);
-            c.woff = (unsigned)woff;
-            c.out = nc > 1 ? -1 - nparts++ : e;
-            chunks.push_back(c);
-        }
-        woff += m;
+        return 0;
+    };
+    if (int rc = attach_ready(h, "electrode_begin", electrode_free, cut)) return rc;    // (the rectangles are looked at behind attach_refusals)
+    Attach a(h);
+    a.upload(h->el.chunks, chunks.size(), chunks.data());
+    a.upload(h->el.w, woff, weights);
+    a.alloc(h->el.trace, (size_t)capacity * (size_t)n, Attach::ZERO);
+    if (nparts) {
+        a.upload(h->el.comb, combs.size(), combs.data());
+        a.alloc(h->el.part, (size_t)nparts);
     }
-    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // tick k = 0 is defined (the rule of fibhip_observe_begin)
-    FLUSH(h);
-    SYNC_S0(h);
-    electrode_free(h);
-    bool ok = hipMalloc((void **)&h->el.chunks, chunks.size() * sizeof(ElChunk)) == hipSuccess &&
-              hipMalloc((void **)&h->el.w, woff * sizeof(float)) == hipSuccess &&
-              hipMalloc((void **)&h->el.trace, (size_t)capacity * (size_t)n * sizeof(float)) == hipSuccess;
-    if (ok && nparts)
-        ok = hipMalloc((void **)&h->el.comb, combs.size() * sizeof(ElComb)) == hipSuccess &&
-             hipMalloc((void **)&h->el.part, (size_t)nparts * sizeof(float)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        electrode_free(h);
+    if (a.failed(electrode_free))
         return fail(FIBHIP_ENOMEM, "electrode_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d electrodes)", capacity, n);
-    }
-    HIPCHK(hipMemcpyAsync(h->el.chunks, chunks.data(), chunks.size() * sizeof(ElChunk), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemcpyAsync(h->el.w, weights, woff * sizeof(float), hipMemcpyHostToDevice, h->s0));
-    if (nparts) HIPCHK(hipMemcpyAsync(h->el.comb, combs.data(), combs.size() * sizeof(ElComb), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemsetAsync(h->el.trace, 0, (size_t)capacity * (size_t)n * sizeof(float), h->s0));
-    HIPCHK(wait_stream(h->s0));                        // `chunks`, `combs` and the caller's arrays are free again
+    if (int rc = a.finish()) return rc;                // `chunks`, `combs` and the caller's arrays are free again
     h->el.on = true;
     h->el.start(every, capacity);
     h->el.before_slow = slow_array(var);
@@ -1074,25 +1173,14 @@ extern "C" int fibhip_electrode_begin(fibhip_t h, int var, int n, const int *rec
 extern "C" int fibhip_electrode_count(fibhip_t h, long long *samples)
 {
     NEED(h);
-    if (!samples) return fail(FIBHIP_EINVAL, "electrode_count: null argument");
-    if (!h->el.on) return fail(FIBHIP_EINVAL, "electrode_count: no recorder attached (fibhip_electrode_begin)");
-    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = h->el.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
-    return 0;
+    return sampler_count(h, h->el, "electrode_count", "fibhip_electrode_begin", samples);
 }
 
 extern "C" int fibhip_electrode_read(fibhip_t h, long long first, long long count, float *dst)
 {
     NEED(h);
-    if (!h->el.on) return fail(FIBHIP_EINVAL, "electrode_read: no recorder attached (fibhip_electrode_begin)");
-    FLUSH(h);
-    if (int rc = range_check("electrode_read", "samples", first, count, h->el.taken())) return rc;
-    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "electrode_read: null destination");
-    return read_confirmed(h, [&] {
-        if (count > 0)
-            HIPCHK(hipMemcpyAsync(dst, h->el.trace + (size_t)first * h->el.n, (size_t)count * h->el.n * sizeof(float), hipMemcpyDeviceToHost, h->s0));
-        return 0;
-    });
+    if (int rc = need_attached(h->el.on, "electrode_read", "fibhip_electrode_begin")) return rc;
+    return ranged_read(h, h->el, "electrode_read", "samples", first, count, {{dst, h->el.trace, h->el.n * sizeof(float)}});
 }
 
 extern "C" int fibhip_electrode_end(fibhip_t h)
@@ -1109,28 +1197,21 @@ extern "C" int fibhip_tips_begin(fibhip_t h, int var, int var2, float a0, float 
     if (var < 0 || var >= h->nvar || var2 < 0 || var2 >= h->nvar) return fail(FIBHIP_EINVAL, "tips_begin: bad var %d / %d", var, var2);
     if (var == var2) return fail(FIBHIP_EINVAL, "tips_begin: the two watched arrays must differ (got %d twice)", var);
     if (std::isnan(a0) || std::isnan(b0)) return fail(FIBHIP_EINVAL, "tips_begin: the levels must be numbers");
-    if (every < 1) return fail(FIBHIP_EINVAL, "tips_begin: every must be >= 1 (got %d)", every);
+    if (int rc = every_check("tips_begin", every)) return rc;
     if (max_tips < 1 || max_tips > FIBHIP_MAX_TIPS) return fail(FIBHIP_EINVAL, "tips_begin: 1 .. %d tips per sample (got %d)", FIBHIP_MAX_TIPS, max_tips);
-    if (capacity < 1 || capacity > (long long)(SIZE_MAX / (4 * sizeof(int)) / (size_t)max_tips))
-        return fail(FIBHIP_EINVAL, "tips_begin: bad capacity %lld", capacity);
-    if (int rc = attach_refusals(h, "tips_begin")) return rc;
-    if (h->d.height < 2 || h->d.width < 2) return fail(FIBHIP_EINVAL, "tips_begin: a %d x %d grid has no plaquette", h->d.height, h->d.width);
-    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
-    FLUSH(h);
-    SYNC_S0(h);
-    tips_free(h);
-    bool ok = hipMalloc((void **)&h->tip.counts, (size_t)capacity * 3 * sizeof(int)) == hipSuccess &&
-              hipMalloc((void **)&h->tip.records, (size_t)capacity * (size_t)max_tips * 4 * sizeof(int)) == hipSuccess;
-    if (ok && mask) ok = hipMalloc((void **)&h->tip.mask, h->cells) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        tips_free(h);
+    if (int rc = capacity_check("tips_begin", capacity, (size_t)max_tips * 4 * sizeof(int))) return rc;
+    if (int rc = attach_ready(h, "tips_begin", tips_free, [&] {
+            if (h->d.height < 2 || h->d.width < 2) return fail(FIBHIP_EINVAL, "tips_begin: a %d x %d grid has no plaquette", h->d.height, h->d.width);
+            return 0;
+        }))
+        return rc;
+    Attach a(h);
+    a.alloc(h->tip.counts, (size_t)capacity * 3, Attach::ZERO);
+    a.alloc(h->tip.records, (size_t)capacity * (size_t)max_tips * 4);
+    if (mask) a.upload(h->tip.mask, h->cells, mask);
+    if (a.failed(tips_free))
         return fail(FIBHIP_ENOMEM, "tips_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d tips)", capacity, max_tips);
-    }
-    if (mask) HIPCHK(hipMemcpyAsync(h->tip.mask, mask, h->cells, hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemsetAsync(h->tip.counts, 0, (size_t)capacity * 3 * sizeof(int), h->s0));
-    HIPCHK(wait_stream(h->s0));                        // the caller's mask is free again
+    if (int rc = a.finish()) return rc;                // the caller's mask is free again
     h->tip.on = true;
     h->tip.start(every, capacity);
     h->tip.before_slow = slow_array(var) || slow_array(var2);
@@ -1145,30 +1226,15 @@ extern "C" int fibhip_tips_begin(fibhip_t h, int var, int var2, float a0, float 
 extern "C" int fibhip_tips_count(fibhip_t h, long long *samples)
 {
     NEED(h);
-    if (!samples) return fail(FIBHIP_EINVAL, "tips_count: null argument");
-    if (!h->tip.on) return fail(FIBHIP_EINVAL, "tips_count: no recorder attached (fibhip_tips_begin)");
-    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = h->tip.taken_with(h->pending);          // (ticks accepted but not launched yet are sampled when they are)
-    return 0;
+    return sampler_count(h, h->tip, "tips_count", "fibhip_tips_begin", samples);
 }
 
 extern "C" int fibhip_tips_read(fibhip_t h, long long first, long long count, int *counts, int *records)
 {
     NEED(h);
-    if (!h->tip.on) return fail(FIBHIP_EINVAL, "tips_read: no recorder attached (fibhip_tips_begin)");
-    FLUSH(h);
-    if (int rc = range_check("tips_read", "samples", first, count, h->tip.taken())) return rc;
-    if (count > 0 && !counts) return fail(FIBHIP_EINVAL, "tips_read: null destination");
-    const size_t per = (size_t)h->tip.max_tips * 4;
-    return read_confirmed(h, [&] {
-        if (count > 0) {
-            HIPCHK(hipMemcpyAsync(counts, h->tip.counts + 3 * (size_t)first, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost, h->s0));
-            if (records)
-                HIPCHK(hipMemcpyAsync(records, h->tip.records + (size_t)first * per, (size_t)count * per * sizeof(int), hipMemcpyDeviceToHost,
-                                      h->s0));
-        }
-        return 0;
-    });
+    if (int rc = need_attached(h->tip.on, "tips_read", "fibhip_tips_begin")) return rc;
+    return ranged_read(h, h->tip, "tips_read", "samples", first, count,
+                       {{counts, h->tip.counts, 3 * sizeof(int)}, {records, h->tip.records, (size_t)h->tip.max_tips * 4 * sizeof(int)}});
 }
 
 extern "C" int fibhip_tips_end(fibhip_t h)
@@ -1183,35 +1249,25 @@ extern "C" int fibhip_frames_begin(fibhip_t h, int var, const int *window, int b
 {
     NEED(h);
     if (!window) return fail(FIBHIP_EINVAL, "frames_begin: null window");
-    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "frames_begin: bad var %d", var);
+    if (int rc = var_check(var, h->nvar, "frames_begin")) return rc;
     Window px;
     if (int rc = window_from(h, "frames_begin", window, by, bx, reduce, px)) return rc;
     const int oh = px.oh, ow = px.ow;
     if (format != FIBHIP_FRAME_F32 && format != FIBHIP_FRAME_U8) return fail(FIBHIP_EINVAL, "frames_begin: bad format %d", format);
     if (std::isnan(lo)) return fail(FIBHIP_EINVAL, "frames_begin: the level lo must be a number");
     if (!std::isfinite(span) || span == 0.f) return fail(FIBHIP_EINVAL, "frames_begin: span must be finite and not zero (got %g)", span);
-    if (every < 1) return fail(FIBHIP_EINVAL, "frames_begin: every must be >= 1 (got %d)", every);
+    if (int rc = every_check("frames_begin", every)) return rc;
     if (first < 1 || first > every) return fail(FIBHIP_EINVAL, "frames_begin: first must be 1 .. every = %d (got %d)", every, first);
     const size_t per = (size_t)oh * (size_t)ow * (format == FIBHIP_FRAME_U8 ? 1u : 4u);
-    if (capacity < 1 || capacity > (long long)(SIZE_MAX / 2 / per)) return fail(FIBHIP_EINVAL, "frames_begin: bad capacity %lld", capacity);
-    if (int rc = attach_refusals(h, "frames_begin")) return rc;
-    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // tick 0 is defined (the rule of fibhip_electrode_begin)
-    FLUSH(h);
-    SYNC_S0(h);
-    frames_free(h);
+    if (int rc = capacity_check("frames_begin", capacity, per, LLONG_MAX, SIZE_MAX / 2)) return rc;
+    if (int rc = attach_ready(h, "frames_begin", frames_free)) return rc;
     static_cast<Window &>(h->fr) = px;
-    bool ok = hipMalloc((void **)&h->fr.cube, (size_t)capacity * per) == hipSuccess;
-    if (ok && weight) ok = hipMalloc((void **)&h->fr.w, h->cells * sizeof(float)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        frames_free(h);
+    Attach a(h);
+    a.alloc(h->fr.cube, (size_t)capacity * per);       // (not filled: a frame is written whole before it can be read)
+    if (weight) a.upload(h->fr.w, h->cells, weight);
+    if (a.failed(frames_free))
         return fail(FIBHIP_ENOMEM, "frames_begin: hipMalloc of the cube failed (%lld frames of %d x %d, %zu bytes each)", capacity, oh, ow, per);
-    }
-    if (weight) {
-        HIPCHK(hipMemcpyAsync(h->fr.w, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
-        HIPCHK(wait_stream(h->s0));                    // the caller's plane is free again
-    }
+    if (int rc = a.finish()) return rc;                // the caller's plane is free again
     h->fr.on = true;
     h->fr.start(every, capacity, every - first);       // sample s follows tick first + s * every, ticks counted from 1 here
     h->fr.before_slow = slow_array(var);
@@ -1225,11 +1281,7 @@ extern "C" int fibhip_frames_begin(fibhip_t h, int var, const int *window, int b
 extern "C" int fibhip_frames_count(fibhip_t h, long long *samples)
 {
     NEED(h);
-    if (!samples) return fail(FIBHIP_EINVAL, "frames_count: null argument");
-    if (!h->fr.on) return fail(FIBHIP_EINVAL, "frames_count: no recorder attached (fibhip_frames_begin)");
-    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = h->fr.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
-    return 0;
+    return sampler_count(h, h->fr, "frames_count", "fibhip_frames_begin", samples);
 }
 
 extern "C" int fibhip_frames_shape(fibhip_t h, int *oh, int *ow, int *bytes_per_pixel)
@@ -1245,15 +1297,8 @@ extern "C" int fibhip_frames_shape(fibhip_t h, int *oh, int *ow, int *bytes_per_
 extern "C" int fibhip_frames_read(fibhip_t h, long long first, long long count, void *dst)
 {
     NEED(h);
-    if (!h->fr.on) return fail(FIBHIP_EINVAL, "frames_read: no recorder attached (fibhip_frames_begin)");
-    FLUSH(h);
-    if (int rc = range_check("frames_read", "frames", first, count, h->fr.taken())) return rc;
-    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "frames_read: null destination");
-    const size_t per = h->fr.frame_bytes();
-    return read_confirmed(h, [&] {
-        if (count > 0) HIPCHK(hipMemcpyAsync(dst, h->fr.cube + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost, h->s0));
-        return 0;
-    });
+    if (int rc = need_attached(h->fr.on, "frames_read", "fibhip_frames_begin")) return rc;
+    return ranged_read(h, h->fr, "frames_read", "frames", first, count, {{dst, h->fr.cube, h->fr.frame_bytes()}});
 }
 
 extern "C" int fibhip_frames_end(fibhip_t h)
@@ -1274,7 +1319,7 @@ extern "C" int fibhip_stats_begin(fibhip_t h, int ncols, const fibhip_stat_col *
     bool need_w = false, need_m = false;
     for (int c = 0; c < ncols; ++c) {
         const fibhip_stat_col &col = cols[c];
-        if (col.var < 0 || col.var >= h->nvar) return fail(FIBHIP_EINVAL, "stats_begin: column %d: bad var %d", c, col.var);
+        if (int rc = var_check(col.var, h->nvar, "stats_begin: column %d", c)) return rc;
         if (col.kind < 0 || col.kind >= ST_KINDS) return fail(FIBHIP_EINVAL, "stats_begin: column %d: unknown kind %d", c, col.kind);
         if ((col.kind == FIBHIP_STAT_BELOW || col.kind == FIBHIP_STAT_ABOVE) && std::isnan(col.level))
             return fail(FIBHIP_EINVAL, "stats_begin: column %d: the level must be a number", c);
@@ -1298,19 +1343,10 @@ extern "C" int fibhip_stats_begin(fibhip_t h, int ncols, const fibhip_stat_col *
         table.push_back(t);
         A.ncols++;
     }
-    if (every < 1) return fail(FIBHIP_EINVAL, "stats_begin: every must be >= 1 (got %d)", every);
-    if (capacity < 1 || capacity > (long long)(SIZE_MAX / sizeof(double) / (size_t)ncols))
-        return fail(FIBHIP_EINVAL, "stats_begin: bad capacity %lld", capacity);
+    if (int rc = every_check("stats_begin", every)) return rc;
+    if (int rc = capacity_check("stats_begin", capacity, (size_t)ncols * sizeof(double))) return rc;
     if (weight)
-        for (size_t i = 0; i < h->cells; ++i)
-            if (!std::isfinite(weight[i]))
-                return fail(FIBHIP_EINVAL, "stats_begin: the weight plane has a value that is not finite (row %zu, column %zu)",
-                            i / (size_t)h->d.width, i % (size_t)h->d.width);
-    if (int rc = attach_refusals(h, "stats_begin")) return rc;
-    if (h->st.on) return fail(FIBHIP_EINVAL, "stats_begin: a recorder is attached already (fibhip_stats_end first)");
-    // stats_kernel counts cells in 32 bits, and a thread looks up to one batch beyond its chunk's end before it drops the cell
-    if (h->cells > (size_t)UINT_MAX - 4u * ST_VBATCH * ST_THREADS)
-        return fail(FIBHIP_EINVAL, "stats_begin: a grid of %zu cells is too large for the recorder's 32-bit cell index", h->cells);
+        if (int rc = finite_check("stats_begin", weight, (size_t)h->d.height, (size_t)h->d.width, "the weight plane")) return rc;
     // the chunk table, from H, W and the pitch alone: at most ST_MAX_CHUNKS equal chunks of at least ST_MIN_CHUNK cells, a
     // multiple of four cells each where the vector path may run (so that every chunk starts 16-byte aligned there)
     std::vector<StChunk> chunks;
@@ -1326,31 +1362,26 @@ extern "C" int fibhip_stats_begin(fibhip_t h, int ncols, const fibhip_stat_col *
             chunks.push_back(c);
         }
     }
-    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
-    FLUSH(h);
-    SYNC_S0(h);
-    stats_free(h);
+    if (int rc = attach_ready(h, "stats_begin", stats_free, [&] {
+            if (h->st.on) return fail(FIBHIP_EINVAL, "stats_begin: a recorder is attached already (fibhip_stats_end first)");
+            // stats_kernel counts cells in 32 bits, and a thread looks up to one batch beyond its chunk's end before it drops the cell
+            if (h->cells > (size_t)UINT_MAX - 4u * ST_VBATCH * ST_THREADS)
+                return fail(FIBHIP_EINVAL, "stats_begin: a grid of %zu cells is too large for the recorder's 32-bit cell index", h->cells);
+            return 0;
+        }))
+        return rc;
     StRec &r = h->st;
-    bool ok = hipMalloc((void **)&r.chunks, chunks.size() * sizeof(StChunk)) == hipSuccess &&
-              hipMalloc((void **)&r.arrs, arrs.size() * sizeof(StArr)) == hipSuccess &&
-              hipMalloc((void **)&r.cols, table.size() * sizeof(StCol)) == hipSuccess &&
-              hipMalloc((void **)&r.part, arrs.size() * ST_SLOTS * chunks.size() * sizeof(unsigned long long)) == hipSuccess &&
-              hipMalloc((void **)&r.trace, (size_t)capacity * (size_t)ncols * sizeof(double)) == hipSuccess;
-    if (ok && weight && need_w) ok = hipMalloc((void **)&r.w, h->cells * sizeof(float)) == hipSuccess;
-    if (ok && mask && need_m) ok = hipMalloc((void **)&r.mask, h->cells) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        stats_free(h);
+    Attach a(h);
+    a.upload(r.chunks, chunks.size(), chunks.data());
+    a.upload(r.arrs, arrs.size(), arrs.data());
+    a.upload(r.cols, table.size(), table.data());
+    a.alloc(r.part, arrs.size() * ST_SLOTS * chunks.size());
+    a.alloc(r.trace, (size_t)capacity * (size_t)ncols, Attach::ZERO);
+    if (weight && need_w) a.upload(r.w, h->cells, weight);
+    if (mask && need_m) a.upload(r.mask, h->cells, mask);
+    if (a.failed(stats_free))
         return fail(FIBHIP_ENOMEM, "stats_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d columns)", capacity, ncols);
-    }
-    HIPCHK(hipMemcpyAsync(r.chunks, chunks.data(), chunks.size() * sizeof(StChunk), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemcpyAsync(r.arrs, arrs.data(), arrs.size() * sizeof(StArr), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemcpyAsync(r.cols, table.data(), table.size() * sizeof(StCol), hipMemcpyHostToDevice, h->s0));
-    if (r.w) HIPCHK(hipMemcpyAsync(r.w, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
-    if (r.mask) HIPCHK(hipMemcpyAsync(r.mask, mask, h->cells, hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemsetAsync(r.trace, 0, (size_t)capacity * (size_t)ncols * sizeof(double), h->s0));
-    HIPCHK(wait_stream(h->s0));                        // the tables and the caller's planes are free again
+    if (int rc = a.finish()) return rc;                // the tables and the caller's planes are free again
     r.on = true;
     r.start(every, capacity);
     r.ncols = ncols;
@@ -1367,26 +1398,14 @@ extern "C" int fibhip_stats_begin(fibhip_t h, int ncols, const fibhip_stat_col *
 extern "C" int fibhip_stats_count(fibhip_t h, long long *samples)
 {
     NEED(h);
-    if (!samples) return fail(FIBHIP_EINVAL, "stats_count: null argument");
-    if (!h->st.on) return fail(FIBHIP_EINVAL, "stats_count: no recorder attached (fibhip_stats_begin)");
-    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = h->st.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
-    return 0;
+    return sampler_count(h, h->st, "stats_count", "fibhip_stats_begin", samples);
 }
 
 extern "C" int fibhip_stats_read(fibhip_t h, long long first, long long count, double *dst)
 {
     NEED(h);
-    if (!h->st.on) return fail(FIBHIP_EINVAL, "stats_read: no recorder attached (fibhip_stats_begin)");
-    FLUSH(h);
-    if (int rc = range_check("stats_read", "samples", first, count, h->st.taken())) return rc;
-    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "stats_read: null destination");
-    return read_confirmed(h, [&] {
-        if (count > 0)
-            HIPCHK(hipMemcpyAsync(dst, h->st.trace + (size_t)first * h->st.ncols, (size_t)count * h->st.ncols * sizeof(double),
-                                  hipMemcpyDeviceToHost, h->s0));
-        return 0;
-    });
+    if (int rc = need_attached(h->st.on, "stats_read", "fibhip_stats_begin")) return rc;
+    return ranged_read(h, h->st, "stats_read", "samples", first, count, {{dst, h->st.trace, h->st.ncols * sizeof(double)}});
 }
 
 extern "C" int fibhip_stats_end(fibhip_t h)
@@ -1411,12 +1430,12 @@ extern "C" int fibhip_leads_begin(fibhip_t h, int var, int n, const int *pos, in
 {
     NEED(h);
     if (!pos || !tables) return fail(FIBHIP_EINVAL, "leads_begin: null argument");
-    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "leads_begin: bad var %d", var);
+    if (int rc = var_check(var, h->nvar, "leads_begin")) return rc;
     if (n < 1 || n > FIBHIP_MAX_LEADS) return fail(FIBHIP_EINVAL, "leads_begin: 1 .. %d leads (got %d)", FIBHIP_MAX_LEADS, n);
     if (ntables < 1 || ntables > FIBHIP_MAX_LEAD_TABLES)
         return fail(FIBHIP_EINVAL, "leads_begin: 1 .. %d lead-field tables (got %d)", FIBHIP_MAX_LEAD_TABLES, ntables);
-    if (every < 1) return fail(FIBHIP_EINVAL, "leads_begin: every must be >= 1 (got %d)", every);
-    if (capacity < 1 || capacity > (long long)(SIZE_MAX / sizeof(double) / (size_t)n)) return fail(FIBHIP_EINVAL, "leads_begin: bad capacity %lld", capacity);
+    if (int rc = every_check("leads_begin", every)) return rc;
+    if (int rc = capacity_check("leads_begin", capacity, (size_t)n * sizeof(double))) return rc;
     const int H = h->d.height, W = h->d.width;
     if (H < 3 || W < 3) return fail(FIBHIP_EINVAL, "leads_begin: a %d x %d grid has no interior cell", H, W);
     if (zero_padded(h))
@@ -1429,38 +1448,21 @@ extern "C" int fibhip_leads_begin(fibhip_t h, int var, int n, const int *pos, in
         table[4 * e] = r; table[4 * e + 1] = c; table[4 * e + 2] = t; table[4 * e + 3] = 0;
     }
     for (int t = 0; t < ntables; ++t)
-        for (size_t i = 0; i < h->cells; ++i)
-            if (!std::isfinite(tables[(size_t)t * h->cells + i]))
-                return fail(FIBHIP_EINVAL, "leads_begin: table %d has a value that is not finite (row %zu, column %zu)", t, i / (size_t)W, i % (size_t)W);
+        if (int rc = finite_check("leads_begin", tables + (size_t)t * h->cells, (size_t)H, (size_t)W, "table %d", t)) return rc;
     if (weight)
-        for (size_t i = 0; i < h->cells; ++i)
-            if (!std::isfinite(weight[i]))
-                return fail(FIBHIP_EINVAL, "leads_begin: the weight plane has a value that is not finite (row %zu, column %zu)", i / (size_t)W,
-                            i % (size_t)W);
-    if (int rc = attach_refusals(h, "leads_begin")) return rc;
-    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
-    FLUSH(h);
-    SYNC_S0(h);
-    leads_free(h);
+        if (int rc = finite_check("leads_begin", weight, (size_t)H, (size_t)W, "the weight plane")) return rc;
+    if (int rc = attach_ready(h, "leads_begin", leads_free)) return rc;
     LeadRec &r = h->ld;
     const int tiles_x = (W + LD_TX - 1) / LD_TX, tiles_y = (H + LD_TY - 1) / LD_TY;
-    const size_t ntiles = (size_t)tiles_x * (size_t)tiles_y;
-    bool ok = hipMalloc((void **)&r.pos, table.size() * sizeof(int)) == hipSuccess &&
-              hipMalloc((void **)&r.tables, (size_t)ntables * h->cells * sizeof(float)) == hipSuccess &&
-              hipMalloc((void **)&r.part, (size_t)n * ntiles * sizeof(double)) == hipSuccess &&
-              hipMalloc((void **)&r.rows, (size_t)capacity * (size_t)n * sizeof(double)) == hipSuccess;
-    if (ok && weight) ok = hipMalloc((void **)&r.weight, h->cells * sizeof(float)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        leads_free(h);
+    Attach a(h);
+    a.upload(r.pos, table.size(), table.data());
+    a.upload(r.tables, (size_t)ntables * h->cells, tables);
+    a.alloc(r.part, (size_t)n * (size_t)tiles_x * (size_t)tiles_y);
+    a.alloc(r.rows, (size_t)capacity * (size_t)n, Attach::ZERO);
+    if (weight) a.upload(r.weight, h->cells, weight);
+    if (a.failed(leads_free))
         return fail(FIBHIP_ENOMEM, "leads_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d leads, %d tables)", capacity, n, ntables);
-    }
-    HIPCHK(hipMemcpyAsync(r.pos, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemcpyAsync(r.tables, tables, (size_t)ntables * h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
-    if (weight) HIPCHK(hipMemcpyAsync(r.weight, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemsetAsync(r.rows, 0, (size_t)capacity * (size_t)n * sizeof(double), h->s0));
-    HIPCHK(wait_stream(h->s0));                        // `table` and the caller's arrays are free again
+    if (int rc = a.finish()) return rc;                // `table` and the caller's arrays are free again
     r.on = true;
     r.start(every, capacity);
     r.before_slow = slow_array(var);
@@ -1474,25 +1476,14 @@ extern "C" int fibhip_leads_begin(fibhip_t h, int var, int n, const int *pos, in
 extern "C" int fibhip_leads_count(fibhip_t h, long long *samples)
 {
     NEED(h);
-    if (!samples) return fail(FIBHIP_EINVAL, "leads_count: null argument");
-    if (!h->ld.on) return fail(FIBHIP_EINVAL, "leads_count: no recorder attached (fibhip_leads_begin)");
-    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = h->ld.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
-    return 0;
+    return sampler_count(h, h->ld, "leads_count", "fibhip_leads_begin", samples);
 }
 
 extern "C" int fibhip_leads_read(fibhip_t h, long long first, long long count, double *dst)
 {
     NEED(h);
-    if (!h->ld.on) return fail(FIBHIP_EINVAL, "leads_read: no recorder attached (fibhip_leads_begin)");
-    FLUSH(h);
-    if (int rc = range_check("leads_read", "samples", first, count, h->ld.taken())) return rc;
-    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "leads_read: null destination");
-    return read_confirmed(h, [&] {
-        if (count > 0)
-            HIPCHK(hipMemcpyAsync(dst, h->ld.rows + (size_t)first * h->ld.n, (size_t)count * h->ld.n * sizeof(double), hipMemcpyDeviceToHost, h->s0));
-        return 0;
-    });
+    if (int rc = need_attached(h->ld.on, "leads_read", "fibhip_leads_begin")) return rc;
+    return ranged_read(h, h->ld, "leads_read", "samples", first, count, {{dst, h->ld.rows, h->ld.n * sizeof(double)}});
 }
 
 extern "C" int fibhip_leads_end(fibhip_t h)
@@ -1507,55 +1498,38 @@ extern "C" int fibhip_pmap_begin(fibhip_t h, int var, int radius, const float *t
 {
     NEED(h);
     if (!table || !window) return fail(FIBHIP_EINVAL, "pmap_begin: null argument");
-    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "pmap_begin: bad var %d", var);
+    if (int rc = var_check(var, h->nvar, "pmap_begin")) return rc;
     if (radius < 1 || radius > FIBHIP_PMAP_MAX_RADIUS)
         return fail(FIBHIP_EINVAL, "pmap_begin: radius must be 1 .. %d (got %d)", FIBHIP_PMAP_MAX_RADIUS, radius);
     if (sy < 1 || sy > FIBHIP_PMAP_MAX_STEP || sx < 1 || sx > FIBHIP_PMAP_MAX_STEP)
         return fail(FIBHIP_EINVAL, "pmap_begin: a step is 1 .. %d cells each way (got %d x %d)", FIBHIP_PMAP_MAX_STEP, sy, sx);
-    if (every < 1) return fail(FIBHIP_EINVAL, "pmap_begin: every must be >= 1 (got %d)", every);
+    if (int rc = every_check("pmap_begin", every)) return rc;
     const int H = h->d.height, W = h->d.width, R = radius, K = 2 * R + 1;
     if (H < 3 || W < 3) return fail(FIBHIP_EINVAL, "pmap_begin: a %d x %d grid has no interior cell", H, W);
-    if (int rc = rect_check(h, window[0], window[1], window[2], window[3], "pmap_begin: the window ")) return rc;
+    if (int rc = rect_check(h->d.height, h->d.width, window[0], window[1], window[2], window[3], "pmap_begin: the window ")) return rc;
     const int r0 = window[0], c0 = window[2], oh = (window[1] - r0 + sy - 1) / sy, ow = (window[3] - c0 + sx - 1) / sx;
     const size_t npix = (size_t)oh * (size_t)ow;
-    if (capacity < 1 || capacity > INT_MAX || capacity > (long long)(SIZE_MAX / sizeof(double) / npix))
-        return fail(FIBHIP_EINVAL, "pmap_begin: bad capacity %lld", capacity);
+    if (int rc = capacity_check("pmap_begin", capacity, npix * sizeof(double), INT_MAX)) return rc;
     if (zero_padded(h))
         return fail(FIBHIP_EINVAL, "pmap_begin: not on a model with the zero-padded Laplacian (FIBHIP_ZEROPAD): its diffusion term is not this source");
-    for (int i = 0; i < (R + 1) * (R + 1); ++i)
-        if (!std::isfinite(table[i]))
-            return fail(FIBHIP_EINVAL, "pmap_begin: the table has a value that is not finite (row %d, column %d)", i / (R + 1), i % (R + 1));
+    if (int rc = finite_check("pmap_begin", table, (size_t)R + 1, (size_t)R + 1, "the table")) return rc;
     if (weight)
-        for (size_t i = 0; i < h->cells; ++i)
-            if (!std::isfinite(weight[i]))
-                return fail(FIBHIP_EINVAL, "pmap_begin: the weight plane has a value that is not finite (row %zu, column %zu)", i / (size_t)W,
-                            i % (size_t)W);
-    if (int rc = attach_refusals(h, "pmap_begin")) return rc;
+        if (int rc = finite_check("pmap_begin", weight, (size_t)H, (size_t)W, "the weight plane")) return rc;
     // the table's rows as pmap_conv_kernel walks them: float64, dc = -R .. R
     std::vector<double> tab((size_t)(R + 1) * K);
     for (int a = 0; a <= R; ++a)
         for (int x = 0; x < K; ++x) tab[(size_t)a * K + x] = (double)table[a * (R + 1) + std::abs(x - R)];
-    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
-    FLUSH(h);
-    SYNC_S0(h);
-    pmap_free(h);
+    if (int rc = attach_ready(h, "pmap_begin", pmap_free)) return rc;
     PMapRec &r = h->pm;
-    const size_t qcells = (size_t)(H + 2 * R) * (size_t)(W + 2 * R);
-    bool ok = hipMalloc((void **)&r.cube, (size_t)capacity * npix * sizeof(double)) == hipSuccess &&
-              hipMalloc((void **)&r.tab, tab.size() * sizeof(double)) == hipSuccess && hipMalloc((void **)&r.q, qcells * sizeof(float)) == hipSuccess &&
-              hipMalloc((void **)&r.maps, npix * (3 * sizeof(double) + 3 * sizeof(int))) == hipSuccess;
-    if (ok && weight) ok = hipMalloc((void **)&r.weight, h->cells * sizeof(float)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        pmap_free(h);
+    Attach a(h);
+    a.alloc(r.cube, (size_t)capacity * npix, Attach::ZERO);
+    a.upload(r.tab, tab.size(), tab.data());
+    a.alloc(r.q, (size_t)(H + 2 * R) * (size_t)(W + 2 * R), Attach::ZERO);      // (the border stays: the kernel writes the grid's cells only)
+    a.alloc_bytes(r.maps, npix * (3 * sizeof(double) + 3 * sizeof(int)));
+    if (weight) a.upload(r.weight, h->cells, weight);
+    if (a.failed(pmap_free))
         return fail(FIBHIP_ENOMEM, "pmap_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d x %d sites)", capacity, oh, ow);
-    }
-    HIPCHK(hipMemcpyAsync(r.tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->s0));
-    if (weight) HIPCHK(hipMemcpyAsync(r.weight, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemsetAsync(r.q, 0, qcells * sizeof(float), h->s0));                            // (the border stays: the kernel writes the grid's cells only)
-    HIPCHK(hipMemsetAsync(r.cube, 0, (size_t)capacity * npix * sizeof(double), h->s0));
-    HIPCHK(wait_stream(h->s0));                        // `tab` and the caller's arrays are free again
+    if (int rc = a.finish()) return rc;                // `tab` and the caller's arrays are free again
     r.on = true;
     r.start(every, capacity);
     r.before_slow = slow_array(var);
@@ -1571,25 +1545,14 @@ extern "C" int fibhip_pmap_begin(fibhip_t h, int var, int radius, const float *t
 extern "C" int fibhip_pmap_count(fibhip_t h, long long *samples)
 {
     NEED(h);
-    if (!samples) return fail(FIBHIP_EINVAL, "pmap_count: null argument");
-    if (!h->pm.on) return fail(FIBHIP_EINVAL, "pmap_count: no recorder attached (fibhip_pmap_begin)");
-    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = h->pm.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
-    return 0;
+    return sampler_count(h, h->pm, "pmap_count", "fibhip_pmap_begin", samples);
 }
 
 extern "C" int fibhip_pmap_read(fibhip_t h, long long first, long long count, double *dst)
 {
     NEED(h);
-    if (!h->pm.on) return fail(FIBHIP_EINVAL, "pmap_read: no recorder attached (fibhip_pmap_begin)");
-    FLUSH(h);
-    if (int rc = range_check("pmap_read", "samples", first, count, h->pm.taken())) return rc;
-    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "pmap_read: null destination");
-    const size_t npix = h->pm.npix();
-    return read_confirmed(h, [&] {
-        if (count > 0) HIPCHK(hipMemcpyAsync(dst, h->pm.cube + (size_t)first * npix, (size_t)count * npix * sizeof(double), hipMemcpyDeviceToHost, h->s0));
-        return 0;
-    });
+    if (int rc = need_attached(h->pm.on, "pmap_read", "fibhip_pmap_begin")) return rc;
+    return ranged_read(h, h->pm, "pmap_read", "samples", first, count, {{dst, h->pm.cube, h->pm.npix() * sizeof(double)}});
 }
 
 extern "C" int fibhip_pmap_summary(fibhip_t h, long long first, long long count, double *vmin, double *vmax, double *dmin, int *kmin, int *kmax,
@@ -1632,7 +1595,7 @@ extern "C" int fibhip_waves_begin(fibhip_t h, int var, int kind, float level, in
                                   const unsigned char *mask, int max_waves, int every, long long capacity)
 {
     NEED(h);
-    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "waves_begin: bad var %d", var);
+    if (int rc = var_check(var, h->nvar, "waves_begin")) return rc;
     if (var2 < -1 || var2 >= h->nvar) return fail(FIBHIP_EINVAL, "waves_begin: bad var2 %d (-1: none)", var2);
     if (kind != FIBHIP_WAVE_ABOVE && kind != FIBHIP_WAVE_BELOW) return fail(FIBHIP_EINVAL, "waves_begin: bad kind %d", kind);
     if (!std::isfinite(level)) return fail(FIBHIP_EINVAL, "waves_begin: the level must be finite");
@@ -1643,31 +1606,19 @@ extern "C" int fibhip_waves_begin(fibhip_t h, int var, int kind, float level, in
     if (conn != 4 && conn != 8) return fail(FIBHIP_EINVAL, "waves_begin: conn is 4 or 8 (got %d)", conn);
     if (max_waves < 1 || max_waves > FIBHIP_MAX_WAVES)
         return fail(FIBHIP_EINVAL, "waves_begin: 1 .. %d waves per sample (got %d)", FIBHIP_MAX_WAVES, max_waves);
-    if (every < 1) return fail(FIBHIP_EINVAL, "waves_begin: every must be >= 1 (got %d)", every);
-    if (capacity < 1 || capacity > (long long)(SIZE_MAX / sizeof(WaveRecord) / (size_t)max_waves))
-        return fail(FIBHIP_EINVAL, "waves_begin: bad capacity %lld", capacity);
-    if (int rc = attach_refusals(h, "waves_begin")) return rc;
-    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
-    FLUSH(h);
-    SYNC_S0(h);
-    waves_free(h);
+    if (int rc = every_check("waves_begin", every)) return rc;
+    if (int rc = capacity_check("waves_begin", capacity, (size_t)max_waves * sizeof(WaveRecord))) return rc;
+    if (int rc = attach_ready(h, "waves_begin", waves_free)) return rc;
     WaveRec &r = h->wv;
-    bool ok = hipMalloc((void **)&r.counts, (size_t)capacity * 3 * sizeof(int)) == hipSuccess &&
-              hipMalloc((void **)&r.records, (size_t)capacity * (size_t)max_waves * sizeof(WaveRecord)) == hipSuccess &&
-              hipMalloc((void **)&r.labels, h->cells * sizeof(int)) == hipSuccess &&
-              hipMalloc((void **)&r.slots, h->cells * sizeof(int)) == hipSuccess;
-    if (ok && mask) ok = hipMalloc((void **)&r.mask, h->cells) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        waves_free(h);
+    Attach a(h);
+    a.alloc(r.counts, (size_t)capacity * 3, Attach::ZERO);
+    a.alloc(r.records, (size_t)capacity * (size_t)max_waves);
+    a.alloc(r.labels, h->cells, Attach::ONES);
+    a.alloc(r.slots, h->cells, Attach::ONES);
+    if (mask) a.upload(r.mask, h->cells, mask);
+    if (a.failed(waves_free))
         return fail(FIBHIP_ENOMEM, "waves_begin: hipMalloc of the recorder's buffers failed (%lld samples of %d waves)", capacity, max_waves);
-    }
-    if (mask) HIPCHK(hipMemcpyAsync(r.mask, mask, h->cells, hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemsetAsync(r.counts, 0, (size_t)capacity * 3 * sizeof(int), h->s0));
-    HIPCHK(hipMemsetAsync(r.labels, 0xFF, h->cells * sizeof(int), h->s0));
-    HIPCHK(hipMemsetAsync(r.slots, 0xFF, h->cells * sizeof(int), h->s0));
-    HIPCHK(wait_stream(h->s0));                        // the caller's mask is free again
+    if (int rc = a.finish()) return rc;                // the caller's mask is free again
     r.on = true;
     r.start(every, capacity);
     r.before_slow = slow_array(var) || (var2 >= 0 && slow_array(var2));
@@ -1681,37 +1632,22 @@ extern "C" int fibhip_waves_begin(fibhip_t h, int var, int kind, float level, in
 extern "C" int fibhip_waves_count(fibhip_t h, long long *samples)
 {
     NEED(h);
-    if (!samples) return fail(FIBHIP_EINVAL, "waves_count: null argument");
-    if (!h->wv.on) return fail(FIBHIP_EINVAL, "waves_count: no recorder attached (fibhip_waves_begin)");
-    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = h->wv.taken_with(h->pending);           // (ticks accepted but not launched yet are sampled when they are)
-    return 0;
+    return sampler_count(h, h->wv, "waves_count", "fibhip_waves_begin", samples);
 }
 
 extern "C" int fibhip_waves_read(fibhip_t h, long long first, long long count, int *counts, fibhip_wave_record *records)
 {
     NEED(h);
-    if (!h->wv.on) return fail(FIBHIP_EINVAL, "waves_read: no recorder attached (fibhip_waves_begin)");
-    FLUSH(h);
-    if (int rc = range_check("waves_read", "samples", first, count, h->wv.taken())) return rc;
-    if (count > 0 && !counts) return fail(FIBHIP_EINVAL, "waves_read: null destination");
-    const size_t per = (size_t)h->wv.max_waves;
-    return read_confirmed(h, [&] {
-        if (count > 0) {
-            HIPCHK(hipMemcpyAsync(counts, h->wv.counts + 3 * (size_t)first, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost, h->s0));
-            if (records)
-                HIPCHK(hipMemcpyAsync(records, h->wv.records + (size_t)first * per, (size_t)count * per * sizeof(WaveRecord),
-                                      hipMemcpyDeviceToHost, h->s0));
-        }
-        return 0;
-    });
+    if (int rc = need_attached(h->wv.on, "waves_read", "fibhip_waves_begin")) return rc;
+    return ranged_read(h, h->wv, "waves_read", "samples", first, count,
+                       {{counts, h->wv.counts, 3 * sizeof(int)}, {records, h->wv.records, (size_t)h->wv.max_waves * sizeof(WaveRecord)}});
 }
 
 extern "C" int fibhip_waves_links_begin(fibhip_t h, int max_links)
 {
     NEED(h);
     WaveRec &r = h->wv;
-    if (!r.on) return fail(FIBHIP_EINVAL, "waves_links_begin: no recorder attached (fibhip_waves_begin)");
+    if (int rc = need_attached(r.on, "waves_links_begin", "fibhip_waves_begin")) return rc;
     if (r.max_links) return fail(FIBHIP_EINVAL, "waves_links_begin: links are on already (%d per sample)", r.max_links);
     if (max_links < 1 || max_links > FIBHIP_MAX_WAVE_LINKS)
         return fail(FIBHIP_EINVAL, "waves_links_begin: 1 .. %d links per sample (got %d)", FIBHIP_MAX_WAVE_LINKS, max_links);
@@ -1725,18 +1661,14 @@ extern "C" int fibhip_waves_links_begin(fibhip_t h, int max_links)
     SYNC_S0(h);
     unsigned T = 4;
     while (T < 4u * (unsigned)max_links) T <<= 1;
-    const bool ok = hipMalloc((void **)&r.prev, h->cells * sizeof(int)) == hipSuccess &&
-                    hipMalloc((void **)&r.link_table, (size_t)T * (sizeof(unsigned long long) + sizeof(int))) == hipSuccess &&
-                    hipMalloc((void **)&r.link_counts, (size_t)r.cap * 4 * sizeof(int)) == hipSuccess &&
-                    hipMalloc((void **)&r.link_records, (size_t)r.cap * (size_t)max_links * sizeof(WaveLink)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        wave_links_free(h);                            // (the wave recorder stays attached, without links)
+    Attach a(h);
+    a.alloc(r.prev, h->cells, Attach::ONES);
+    a.alloc_bytes(r.link_table, (size_t)T * (sizeof(unsigned long long) + sizeof(int)));
+    a.alloc(r.link_counts, (size_t)r.cap * 4, Attach::ZERO);
+    a.alloc(r.link_records, (size_t)r.cap * (size_t)max_links);
+    if (a.failed(wave_links_free))                     // (the wave recorder stays attached, without links)
         return fail(FIBHIP_ENOMEM, "waves_links_begin: hipMalloc of the link buffers failed (%lld samples of %d links)", r.cap, max_links);
-    }
-    HIPCHK(hipMemsetAsync(r.prev, 0xFF, h->cells * sizeof(int), h->s0));
-    HIPCHK(hipMemsetAsync(r.link_counts, 0, (size_t)r.cap * 4 * sizeof(int), h->s0));
-    HIPCHK(wait_stream(h->s0));
+    if (int rc = a.finish()) return rc;
     r.max_links = max_links;
     r.link_entries = T;
     return 0;
@@ -1745,21 +1677,10 @@ extern "C" int fibhip_waves_links_begin(fibhip_t h, int max_links)
 extern "C" int fibhip_waves_links_read(fibhip_t h, long long first, long long count, int *counts, fibhip_wave_link *links)
 {
     NEED(h);
-    if (!h->wv.on) return fail(FIBHIP_EINVAL, "waves_links_read: no recorder attached (fibhip_waves_begin)");
+    if (int rc = need_attached(h->wv.on, "waves_links_read", "fibhip_waves_begin")) return rc;
     if (!h->wv.max_links) return fail(FIBHIP_EINVAL, "waves_links_read: links are off (fibhip_waves_links_begin)");
-    FLUSH(h);
-    if (int rc = range_check("waves_links_read", "samples", first, count, h->wv.taken())) return rc;
-    if (count > 0 && !counts) return fail(FIBHIP_EINVAL, "waves_links_read: null destination");
-    const size_t per = (size_t)h->wv.max_links;
-    return read_confirmed(h, [&] {
-        if (count > 0) {
-            HIPCHK(hipMemcpyAsync(counts, h->wv.link_counts + 4 * (size_t)first, (size_t)count * 4 * sizeof(int), hipMemcpyDeviceToHost, h->s0));
-            if (links)
-                HIPCHK(hipMemcpyAsync(links, h->wv.link_records + (size_t)first * per, (size_t)count * per * sizeof(WaveLink),
-                                      hipMemcpyDeviceToHost, h->s0));
-        }
-        return 0;
-    });
+    return ranged_read(h, h->wv, "waves_links_read", "samples", first, count,
+                       {{counts, h->wv.link_counts, 4 * sizeof(int)}, {links, h->wv.link_records, (size_t)h->wv.max_links * sizeof(WaveLink)}});
 }
 
 extern "C" int fibhip_waves_labels(fibhip_t h, int *dst)
@@ -1787,11 +1708,11 @@ extern "C" int fibhip_spectrum_begin(fibhip_t h, int var, const int *window, int
 {
     NEED(h);
     if (!window || !win || !tw || !bins) return fail(FIBHIP_EINVAL, "spectrum_begin: null argument");
-    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "spectrum_begin: bad var %d", var);
+    if (int rc = var_check(var, h->nvar, "spectrum_begin")) return rc;
     Window px;
     if (int rc = window_from(h, "spectrum_begin", window, by, bx, reduce, px)) return rc;
     const int oh = px.oh, ow = px.ow;
-    if (every < 1) return fail(FIBHIP_EINVAL, "spectrum_begin: every must be >= 1 (got %d)", every);
+    if (int rc = every_check("spectrum_begin", every)) return rc;
     if (nfft < FIBHIP_SPECTRUM_MIN_NFFT || nfft > FIBHIP_SPECTRUM_MAX_NFFT)
         return fail(FIBHIP_EINVAL, "spectrum_begin: nfft must be %d .. %d (got %d)", FIBHIP_SPECTRUM_MIN_NFFT, FIBHIP_SPECTRUM_MAX_NFFT, nfft);
     if (chunk < 1 || chunk > FIBHIP_SPECTRUM_MAX_CHUNK || nfft % chunk)
@@ -1802,35 +1723,26 @@ extern "C" int fibhip_spectrum_begin(fibhip_t h, int var, const int *window, int
             return fail(FIBHIP_EINVAL, "spectrum_begin: bin %d names frequency index %d outside [0, nfft / 2 = %d]", i, bins[i], nfft / 2);
         if (i > 0 && bins[i] <= bins[i - 1]) return fail(FIBHIP_EINVAL, "spectrum_begin: the bins must be strictly ascending (bin %d)", i);
     }
-    if (int rc = attach_refusals(h, "spectrum_begin")) return rc;
-    if (h->pitch != h->d.width) return fail(FIBHIP_EINVAL, "spectrum_begin: not on a row-interleaved slab");
-    if (h->sp.on) return fail(FIBHIP_EINVAL, "spectrum_begin: a recorder is attached already (fibhip_spectrum_end first)");
-    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // tick 0 is defined (the rule of fibhip_electrode_begin)
-    FLUSH(h);
-    SYNC_S0(h);
-    spectrum_free(h);
+    if (int rc = attach_ready(h, "spectrum_begin", spectrum_free, [&] {
+            if (h->pitch != h->d.width) return fail(FIBHIP_EINVAL, "spectrum_begin: not on a row-interleaved slab");
+            if (h->sp.on) return fail(FIBHIP_EINVAL, "spectrum_begin: a recorder is attached already (fibhip_spectrum_end first)");
+            return 0;
+        }))
+        return rc;
     SpRec &r = h->sp;
     static_cast<Window &>(r) = px;
     const size_t npix = px.npix();
-    bool ok = hipMalloc((void **)&r.ring, (size_t)chunk * npix * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc((void **)&r.acc, 3 * (size_t)nb * npix * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc((void **)&r.maps, 4 * npix * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc((void **)&r.win, (size_t)nfft * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc((void **)&r.tw, 2 * (size_t)nfft * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc((void **)&r.bins, (size_t)nb * sizeof(int)) == hipSuccess;
-    if (ok && weight) ok = hipMalloc((void **)&r.w, h->cells * sizeof(float)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        spectrum_free(h);
+    Attach a(h);
+    a.alloc(r.ring, (size_t)chunk * npix);
+    a.alloc(r.acc, 3 * (size_t)nb * npix, Attach::ZERO);                     // Re = Im = P = +0
+    a.alloc(r.maps, 4 * npix);
+    a.upload(r.win, (size_t)nfft, win);
+    a.upload(r.tw, 2 * (size_t)nfft, tw);
+    a.upload(r.bins, (size_t)nb, bins);
+    if (weight) a.upload(r.w, h->cells, weight);
+    if (a.failed(spectrum_free))
         return fail(FIBHIP_ENOMEM, "spectrum_begin: hipMalloc failed (%d bins and %d ring planes of %d x %d pixels)", nb, chunk, oh, ow);
-    }
-    HIPCHK(hipMemsetAsync(r.acc, 0, 3 * (size_t)nb * npix * sizeof(float), h->s0));        // Re = Im = P = +0
-    HIPCHK(hipMemcpyAsync(r.win, win, (size_t)nfft * sizeof(float), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemcpyAsync(r.tw, tw, 2 * (size_t)nfft * sizeof(float), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemcpyAsync(r.bins, bins, (size_t)nb * sizeof(int), hipMemcpyHostToDevice, h->s0));
-    if (weight) HIPCHK(hipMemcpyAsync(r.w, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(wait_stream(h->s0));                        // the caller's tables are free again
+    if (int rc = a.finish()) return rc;                // the caller's tables are free again
     r.on = true;
     r.start(every, LLONG_MAX);                         // sample s follows tick (s + 1) * every, ticks counted from 1 here
     r.before_slow = slow_array(var);
@@ -1842,9 +1754,8 @@ extern "C" int fibhip_spectrum_begin(fibhip_t h, int var, const int *window, int
 extern "C" int fibhip_spectrum_count(fibhip_t h, long long *samples, long long *segments)
 {
     NEED(h);
-    if (!h->sp.on) return fail(FIBHIP_EINVAL, "spectrum_count: no recorder attached (fibhip_spectrum_begin)");
-    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    const long long n = h->sp.taken_with(h->pending);                // (ticks accepted but not launched yet are sampled when they are)
+    long long n;
+    if (int rc = count_taken(h, h->sp, "spectrum_count", "fibhip_spectrum_begin", "recorder", &n)) return rc;
     if (samples) *samples = n;
     if (segments) *segments = n / h->sp.nfft;
     return 0;
@@ -1909,38 +1820,32 @@ extern "C" int fibhip_beats_begin(fibhip_t h, int var, const int *window, int by
 {
     NEED(h);
     if (!window) return fail(FIBHIP_EINVAL, "beats_begin: null argument");
-    if (var < 0 || var >= h->nvar) return fail(FIBHIP_EINVAL, "beats_begin: bad var %d", var);
+    if (int rc = var_check(var, h->nvar, "beats_begin")) return rc;
     Window px;
     if (int rc = window_from(h, "beats_begin", window, by, bx, reduce, px)) return rc;
     const int oh = px.oh, ow = px.ow;
-    if (every < 1) return fail(FIBHIP_EINVAL, "beats_begin: every must be >= 1 (got %d)", every);
+    if (int rc = every_check("beats_begin", every)) return rc;
     if (!(down <= up)) return fail(FIBHIP_EINVAL, "beats_begin: the levels must be numbers with down <= up (got down %g, up %g)", (double)down, (double)up);
     if (depth < 1 || depth > FIBHIP_BEATS_MAX_DEPTH)
         return fail(FIBHIP_EINVAL, "beats_begin: depth must be 1 .. %d (got %d)", FIBHIP_BEATS_MAX_DEPTH, depth);
-    if (int rc = attach_refusals(h, "beats_begin")) return rc;
-    if (h->pitch != h->d.width) return fail(FIBHIP_EINVAL, "beats_begin: not on a row-interleaved slab");
-    if (h->bt.on) return fail(FIBHIP_EINVAL, "beats_begin: a recorder is attached already (fibhip_beats_end first)");
-    // everything accepted so far runs unrecorded and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // tick 0 and the first xp are defined (the rule of fibhip_electrode_begin)
-    FLUSH(h);
-    SYNC_S0(h);
-    beats_free(h);
+    if (int rc = attach_ready(h, "beats_begin", beats_free, [&] {
+            if (h->pitch != h->d.width) return fail(FIBHIP_EINVAL, "beats_begin: not on a row-interleaved slab");
+            if (h->bt.on) return fail(FIBHIP_EINVAL, "beats_begin: a recorder is attached already (fibhip_beats_end first)");
+            return 0;
+        }))
+        return rc;
     BeatRec &r = h->bt;
     static_cast<Window &>(r) = px;
     const size_t npix = px.npix();
-    bool ok = hipMalloc((void **)&r.state, 3 * npix * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc((void **)&r.ring, 3 * (size_t)depth * npix * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc((void **)&r.maps, 4 * npix * sizeof(float)) == hipSuccess;
-    if (ok && weight) ok = hipMalloc((void **)&r.w, h->cells * sizeof(float)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        beats_free(h);
-        return fail(FIBHIP_ENOMEM, "beats_begin: hipMalloc failed (a ring of %d beats of %d x %d pixels)", depth, oh, ow);
-    }
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(r.state + npix), (int)qnan_bits(), npix, h->s0));               // pk = NaN
-    HIPCHK(hipMemsetAsync(r.state + 2 * npix, 0, npix * sizeof(int), h->s0));                                // n = 0
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)r.ring, (int)qnan_bits(), 3 * (size_t)depth * npix, h->s0));    // t_up = t_down = peak = NaN
-    if (weight) HIPCHK(hipMemcpyAsync(r.w, weight, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
+    Attach a(h);
+    a.alloc(r.state, 3 * npix);                        // xp | pk | n: three planes that start differently, filled below
+    a.alloc(r.ring, 3 * (size_t)depth * npix, Attach::QNAN);                  // t_up = t_down = peak = NaN
+    a.alloc(r.maps, 4 * npix);
+    if (weight) a.upload(r.w, h->cells, weight);
+    if (a.failed(beats_free)) return fail(FIBHIP_ENOMEM, "beats_begin: hipMalloc failed (a ring of %d beats of %d x %d pixels)", depth, oh, ow);
+    if (int rc = a.enqueue()) return rc;
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(r.state + npix), (int)qnan_bits(), npix, h->s0));   // pk = NaN
+    HIPCHK(hipMemsetAsync(r.state + 2 * npix, 0, npix * sizeof(int), h->s0));                    // n = 0
     r.start(every, LLONG_MAX);                         // sample s follows tick (s + 1) * every, ticks counted from 1 here
     r.before_slow = slow_array(var);
     r.var = var;
@@ -1950,7 +1855,7 @@ extern "C" int fibhip_beats_begin(fibhip_t h, int var, const int *window, int by
         beats_free(h);
         return rc;
     }
-    HIPCHK(wait_stream(h->s0));                        // the caller's weight plane is free again
+    if (int rc = a.wait()) return rc;                  // the caller's weight plane is free again
     r.on = true;
     return 0;
 }
@@ -1958,9 +1863,9 @@ extern "C" int fibhip_beats_begin(fibhip_t h, int var, const int *window, int by
 extern "C" int fibhip_beats_count(fibhip_t h, long long *samples)
 {
     NEED(h);
-    if (!h->bt.on) return fail(FIBHIP_EINVAL, "beats_count: no recorder attached (fibhip_beats_begin)");
-    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    if (samples) *samples = h->bt.taken_with(h->pending);            // (ticks accepted but not launched yet are sampled when they are)
+    long long n;
+    if (int rc = count_taken(h, h->bt, "beats_count", "fibhip_beats_begin", "recorder", &n)) return rc;
+    if (samples) *samples = n;
     return 0;
 }
 
@@ -2132,23 +2037,15 @@ extern "C" int fibhip_stim_begin(fibhip_t h, int n, const fibhip_stim_entry *ent
             return rc;
         list.push_back(e);
     }
-    if (int rc = attach_refusals(h, "stim_begin")) return rc;
-    if (h->stim.on) return fail(FIBHIP_EINVAL, "stim_begin: a program is attached already (fibhip_stim_end first)");
-    // everything accepted so far runs unstimulated and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // tick k = 0 is defined (the rule of fibhip_electrode_begin)
-    FLUSH(h);
-    SYNC_S0(h);
-    stim_free(h);
-    if (nplanes > 0) {
-        const size_t bytes = (size_t)nplanes * h->cells * sizeof(float);
-        if (hipMalloc((void **)&h->stim.planes, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            h->stim.planes = nullptr;
-            return fail(FIBHIP_ENOMEM, "stim_begin: hipMalloc of %d planes failed", nplanes);
-        }
-        HIPCHK(hipMemcpyAsync(h->stim.planes, planes, bytes, hipMemcpyHostToDevice, h->s0));
-        HIPCHK(wait_stream(h->s0));                    // the caller's planes are free again
-    }
+    if (int rc = attach_ready(h, "stim_begin", stim_free, [&] {
+            if (h->stim.on) return fail(FIBHIP_EINVAL, "stim_begin: a program is attached already (fibhip_stim_end first)");
+            return 0;
+        }))
+        return rc;
+    Attach a(h);
+    if (nplanes > 0) a.upload(h->stim.planes, (size_t)nplanes * h->cells, planes);
+    if (a.failed(stim_free)) return fail(FIBHIP_ENOMEM, "stim_begin: hipMalloc of %d planes failed", nplanes);
+    if (int rc = a.finish()) return rc;                // the caller's planes are free again
     h->stim.entries.swap(list);
     h->stim.k = 0;
     h->stim.next = stim_next(h->stim);
@@ -2185,8 +2082,8 @@ extern "C" int fibhip_trig_begin(fibhip_t h, int nsensors, const fibhip_trig_sen
     if (nrules < 1 || nrules > FIBHIP_MAX_TRIG_RULES) return fail(FIBHIP_EINVAL, "trig_begin: 1 .. %d rules (got %d)", FIBHIP_MAX_TRIG_RULES, nrules);
     if (nplanes < 0 || nplanes > FIBHIP_MAX_STIM_PLANES || (nplanes > 0 && !planes))
         return fail(FIBHIP_EINVAL, "trig_begin: 0 .. %d planes (got %d%s)", FIBHIP_MAX_STIM_PLANES, nplanes, nplanes > 0 && !planes ? ", null" : "");
-    if (every < 1) return fail(FIBHIP_EINVAL, "trig_begin: every must be >= 1 (got %d)", every);
-    if (capacity < 1 || capacity > (long long)INT_MAX) return fail(FIBHIP_EINVAL, "trig_begin: bad capacity %lld", capacity);
+    if (int rc = every_check("trig_begin", every)) return rc;
+    if (int rc = capacity_check("trig_begin", capacity, (size_t)nrules * TRIG_ROW * sizeof(int), INT_MAX)) return rc;
     const int H = h->d.height, W = h->d.width;
     if (h->cells > (size_t)INT_MAX) return fail(FIBHIP_EINVAL, "trig_begin: a grid of %zu cells is too large for the 32-bit counts", h->cells);
     const bool cut_vec = h->pitch == W && W % 4 == 0;
@@ -2196,11 +2093,11 @@ extern "C" int fibhip_trig_begin(fibhip_t h, int nsensors, const fibhip_trig_sen
         const fibhip_trig_sensor &q = sensors[i];
         SenseSite d;
         memset(&d, 0, sizeof d);
-        if (q.var < 0 || q.var >= h->nvar) return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: bad var %d", i, q.var);
+        if (int rc = var_check(q.var, h->nvar, "trig_begin: sensor %d", i)) return rc;
         if (std::isnan(q.level)) return fail(FIBHIP_EINVAL, "trig_begin: sensor %d: the level must be a number", i);
         long long cells_of_site = 0;
         if (q.site == FIBHIP_TRIG_RECT) {
-            if (int rc = rect_check(h, q.r0, q.r1, q.c0, q.c1, "trig_begin: sensor %d: ", i)) return rc;
+            if (int rc = rect_check(h->d.height, h->d.width, q.r0, q.r1, q.c0, q.c1, "trig_begin: sensor %d: ", i)) return rc;
             d.r0 = q.r0; d.r1 = q.r1; d.c0 = q.c0; d.c1 = q.c1;
             d.mask = -1;
             cells_of_site = (long long)(q.r1 - q.r0) * (q.c1 - q.c0);
@@ -2271,34 +2168,23 @@ extern "C" int fibhip_trig_begin(fibhip_t h, int nsensors, const fibhip_trig_sen
 #endif
         stims.push_back(e);
     }
-    if (int rc = attach_refusals(h, "trig_begin")) return rc;
-    if (h->trig.on) return fail(FIBHIP_EINVAL, "trig_begin: a program is attached already (fibhip_trig_end first)");
-    // everything accepted so far runs unsensed and is confirmed: a multi-tick launch that gave up is recovered HERE, before
-    // sample 0 is defined (the rule of fibhip_electrode_begin) — every journal record is younger than the program
-    FLUSH(h);
-    SYNC_S0(h);
-    trig_free(h);
+    if (int rc = attach_ready(h, "trig_begin", trig_free, [&] {
+            if (h->trig.on) return fail(FIBHIP_EINVAL, "trig_begin: a program is attached already (fibhip_trig_end first)");
+            return 0;
+        }))
+        return rc;
     TrigRec &r = h->trig;
-    bool ok = hipMalloc((void **)&r.sites, sites.size() * sizeof(SenseSite)) == hipSuccess &&
-              hipMalloc((void **)&r.rules, table.size() * sizeof(TrigRule)) == hipSuccess &&
-              hipMalloc((void **)&r.part, (size_t)nsensors * SENSE_MAX_CHUNKS * sizeof(unsigned)) == hipSuccess &&
-              hipMalloc((void **)&r.rows, (size_t)capacity * (size_t)nrules * TRIG_ROW * sizeof(int)) == hipSuccess &&
-              hipMalloc((void **)&r.fire, (size_t)capacity * sizeof(unsigned)) == hipSuccess;
-    if (ok && nmasks > 0) ok = hipMalloc((void **)&r.masks, (size_t)nmasks * h->cells) == hipSuccess;
-    if (ok && nplanes > 0) ok = hipMalloc((void **)&r.planes, (size_t)nplanes * h->cells * sizeof(float)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        trig_free(h);
+    Attach a(h);
+    a.upload(r.sites, sites.size(), sites.data());
+    a.upload(r.rules, table.size(), table.data());
+    a.alloc(r.part, (size_t)nsensors * SENSE_MAX_CHUNKS, Attach::ZERO);
+    a.alloc(r.rows, (size_t)capacity * (size_t)nrules * TRIG_ROW, Attach::ZERO);
+    a.alloc(r.fire, (size_t)capacity, Attach::ZERO);
+    if (nmasks > 0) a.upload(r.masks, (size_t)nmasks * h->cells, masks);
+    if (nplanes > 0) a.upload(r.planes, (size_t)nplanes * h->cells, planes);
+    if (a.failed(trig_free))
         return fail(FIBHIP_ENOMEM, "trig_begin: hipMalloc of the program's buffers failed (%lld samples of %d rules)", capacity, nrules);
-    }
-    HIPCHK(hipMemcpyAsync(r.sites, sites.data(), sites.size() * sizeof(SenseSite), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemcpyAsync(r.rules, table.data(), table.size() * sizeof(TrigRule), hipMemcpyHostToDevice, h->s0));
-    if (r.masks) HIPCHK(hipMemcpyAsync(r.masks, masks, (size_t)nmasks * h->cells, hipMemcpyHostToDevice, h->s0));
-    if (r.planes) HIPCHK(hipMemcpyAsync(r.planes, planes, (size_t)nplanes * h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
-    HIPCHK(hipMemsetAsync(r.part, 0, (size_t)nsensors * SENSE_MAX_CHUNKS * sizeof(unsigned), h->s0));
-    HIPCHK(hipMemsetAsync(r.rows, 0, (size_t)capacity * (size_t)nrules * TRIG_ROW * sizeof(int), h->s0));
-    HIPCHK(hipMemsetAsync(r.fire, 0, (size_t)capacity * sizeof(unsigned), h->s0));
-    HIPCHK(wait_stream(h->s0));                        // the tables and the caller's masks and planes are free again
+    if (int rc = a.finish()) return rc;                // the tables and the caller's masks and planes are free again
     r.on = true;
     r.start(every, capacity);
     r.before_slow = true;                              // tick, sense / stimulus, slow: whatever arrays it names
@@ -2315,26 +2201,14 @@ extern "C" int fibhip_trig_begin(fibhip_t h, int nsensors, const fibhip_trig_sen
 extern "C" int fibhip_trig_count(fibhip_t h, long long *samples)
 {
     NEED(h);
-    if (!samples) return fail(FIBHIP_EINVAL, "trig_count: null argument");
-    if (!h->trig.on) return fail(FIBHIP_EINVAL, "trig_count: no program attached (fibhip_trig_begin)");
-    SYNC_S0(h);                                        // (a launch that gave up is recovered before anybody counts on its samples)
-    *samples = h->trig.taken_with(h->pending);         // (ticks accepted but not launched yet are sampled when they are)
-    return 0;
+    return sampler_count(h, h->trig, "trig_count", "fibhip_trig_begin", samples, "program");
 }
 
 extern "C" int fibhip_trig_read(fibhip_t h, long long first, long long count, int *dst)
 {
     NEED(h);
-    if (!h->trig.on) return fail(FIBHIP_EINVAL, "trig_read: no program attached (fibhip_trig_begin)");
-    FLUSH(h);
-    if (int rc = range_check("trig_read", "samples", first, count, h->trig.taken())) return rc;
-    if (count > 0 && !dst) return fail(FIBHIP_EINVAL, "trig_read: null destination");
-    const size_t row = (size_t)h->trig.nrules * TRIG_ROW;
-    return read_confirmed(h, [&] {
-        if (count > 0)
-            HIPCHK(hipMemcpyAsync(dst, h->trig.rows + (size_t)first * row, (size_t)count * row * sizeof(int), hipMemcpyDeviceToHost, h->s0));
-        return 0;
-    });
+    if (int rc = need_attached(h->trig.on, "trig_read", "fibhip_trig_begin", "program")) return rc;
+    return ranged_read(h, h->trig, "trig_read", "samples", first, count, {{dst, h->trig.rows, (size_t)h->trig.nrules * TRIG_ROW * sizeof(int)}});
 }
 
 extern "C" int fibhip_trig_end(fibhip_t h)
@@ -2356,7 +2230,7 @@ static int lesion_refusals(const fibhip_ctx *h, const char *who)
 // one lesion's box and factors: the box inside the grid and not empty, every factor finite and in [0, 1]
 static int lesion_check(const fibhip_ctx *h, const char *who, int i, int r0, int r1, int c0, int c1, const float *patch)
 {
-    if (int rc = rect_check(h, r0, r1, c0, c1, "%s: entry %d: ", who, i)) return rc;
+    if (int rc = rect_check(h->d.height, h->d.width, r0, r1, c0, c1, "%s: entry %d: ", who, i)) return rc;
     const size_t n = (size_t)(r1 - r0) * (size_t)(c1 - c0);
     for (size_t j = 0; j < n; ++j)
         if (!(patch[j] >= 0.0f && patch[j] <= 1.0f))                // (a NaN fails both compares)
@@ -2399,7 +2273,7 @@ extern "C" int fibhip_lesion_begin(fibhip_t h, int n, const fibhip_lesion_entry 
         const fibhip_lesion_entry &s = entries[i];
         if (s.tick < 0) return fail(FIBHIP_EINVAL, "lesion_begin: entry %d: tick must be >= 0 (got %d)", i, s.tick);
         if (s.reserved != 0) return fail(FIBHIP_EINVAL, "lesion_begin: entry %d: the reserved field must be 0 (got %d)", i, s.reserved);
-        if (int rc = rect_check(h, s.r0, s.r1, s.c0, s.c1, "lesion_begin: entry %d: ", i)) return rc;
+        if (int rc = rect_check(h->d.height, h->d.width, s.r0, s.r1, s.c0, s.c1, "lesion_begin: entry %d: ", i)) return rc;
         const long long area = (long long)(s.r1 - s.r0) * (long long)(s.c1 - s.c0);
         if (s.offset < 0 || s.offset + area > nfloats)
             return fail(FIBHIP_EINVAL, "lesion_begin: entry %d: a patch of %lld floats at offset %lld of %lld", i, area, s.offset, nfloats);
@@ -2411,21 +2285,17 @@ extern "C" int fibhip_lesion_begin(fibhip_t h, int n, const fibhip_lesion_entry 
         list.push_back(e);
     }
     if (h->les.on) return fail(FIBHIP_EINVAL, "lesion_begin: a program is attached already (fibhip_lesion_end first)");
-    // everything accepted so far runs on the old geometry and is confirmed: a multi-tick launch that gave up is recovered HERE,
-    // before tick k = 0 is defined (the rule of fibhip_electrode_begin)
+    // attach_ready's step, written out: this program's refusals stand in front of its entries, and it confirms as well —
+    // everything accepted so far runs on the old geometry, and the field is looked at and maybe made behind a confirmed stream
     FLUSH(h);
     CONFIRM(h);
     SYNC_S0(h);
     if (int rc = lesion_field_ready(h, "lesion_begin")) return rc;
     lesion_free(h);
-    const size_t bytes = (size_t)nfloats * sizeof(float);
-    if (hipMalloc((void **)&h->les.patches, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->les.patches = nullptr;
-        return fail(FIBHIP_ENOMEM, "lesion_begin: hipMalloc of %lld floats of patches failed", nfloats);
-    }
-    HIPCHK(hipMemcpyAsync(h->les.patches, patches, bytes, hipMemcpyHostToDevice, h->s0));
-    HIPCHK(wait_stream(h->s0));                        // the caller's patches are free again
+    Attach a(h);
+    a.upload(h->les.patches, (size_t)nfloats, patches);
+    if (a.failed(lesion_free)) return fail(FIBHIP_ENOMEM, "lesion_begin: hipMalloc of %lld floats of patches failed", nfloats);
+    if (int rc = a.finish()) return rc;                // the caller's patches are free again
     h->les.entries.swap(list);
     h->les.k = 0;
     h->les.next = lesion_next(h->les);
