@@ -169,6 +169,7 @@ SYMBOLS = {
     'fibhip_create': ([C.POINTER(Desc), C.POINTER(_h)], C.c_int),
     'fibhip_destroy': ([_h], C.c_int),
     'fibhip_set_phase': ([_h, _fp], C.c_int),
+    'fibhip_set_tensor': ([_h, _fp, _fp, _fp], C.c_int),
     'fibhip_set_state': ([_h, C.c_int, _fp], C.c_int),
     'fibhip_get_state': ([_h, C.c_int, _fp], C.c_int),
     'fibhip_set_consts': ([_h, _fp, C.c_int], C.c_int),
@@ -190,6 +191,7 @@ SYMBOLS = {
     'fibhip_halo_due': ([_h], C.c_int),
     'fibhip_unit_op': ([C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_double, C.c_int, _fp],
                        C.c_int),
+    'fibhip_unit_laplace_tensor': ([C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp], C.c_int),
     'fibhip_court_inter': ([C.c_int, C.c_int, _fp, C.c_int, _fp], C.c_int),
     'fibhip_halo_plan': ([_h, C.c_int, C.c_int, C.POINTER(HaloMsg), _ip], C.c_int),
     'fibhip_comm_open': ([C.c_char_p], C.c_int),
@@ -217,6 +219,8 @@ SYMBOLS = {
     'fibhip_plan_tile': ([_h, _ip, _ip, _ip], C.c_int),
     'fibhip_variant_count': ([], C.c_int),
     'fibhip_variant_info': ([C.c_int, _ip], C.c_int),
+    'fibhip_tensor_variant_count': ([], C.c_int),
+    'fibhip_tensor_variant_info': ([C.c_int, _ip], C.c_int),
     'fibhip_observe_begin': ([_h, C.c_int, C.c_float, C.c_float], C.c_int),
     'fibhip_observe_get': ([_h, C.c_int, C.c_void_p], C.c_int),
     'fibhip_observe_ticks': ([_h, C.POINTER(C.c_longlong)], C.c_int),
@@ -509,6 +513,18 @@ def unit_op(op, a, b=None, c=None, phi=None, dt=0.0, fast=False, device=0):
     return out
 
 
+def unit_laplace_tensor(a, dyy, dxx, dxy, phi=None, fast=False, device=0):
+    """laplace(a) under the diffusion tensor (dyy, dxx, dxy) and the phase field `phi` (None: none), on the device
+    (include/fibhip.h fibhip_unit_laplace_tensor)"""
+    a = _f32(a)
+    H, W = a.shape
+    dyy, dxx, dxy = (_f32(np.broadcast_to(p, a.shape)) for p in (dyy, dxx, dxy))
+    phi = None if phi is None else _f32(phi)
+    out = np.empty_like(a)
+    check(lib().fibhip_unit_laplace_tensor(device, H, W, _ptr(a), _ptr(phi), _ptr(dyy), _ptr(dxx), _ptr(dxy), int(fast), _ptr(out)))
+    return out
+
+
 VARIANT_FIELDS = ('model', 'mode', 'fast', 'phase', 'K', 'TX', 'TY', 'NT', 'kind', 'has_mt')   # fibhip_variant_info, in order
 VM_FENTON_ZP, VM_COURT_AGG = 100, 101                   # table ids of the two kernel models that are no fibhip_model
 MK_TICK, MK_STRIP, MK_POINTWISE, MK_STRIP_MT, MK_ROWS = range(5)
@@ -524,6 +540,18 @@ def variants(L=None):
     rows = []
     for i in range(check(L.fibhip_variant_count(), L)):
         check(L.fibhip_variant_info(i, out), L)
+        rows.append(dict(zip(VARIANT_FIELDS, [int(x) for x in out])))
+    return rows
+
+
+def tensor_variants(L=None):
+    """the second table: the kernels of handles with a diffusion tensor (fibhip_tensor_variant_info), as `variants` lists the first"""
+    L = L or lib()
+    L = getattr(L, '_L', L)
+    out = (C.c_int * len(VARIANT_FIELDS))()
+    rows = []
+    for i in range(check(L.fibhip_tensor_variant_count(), L)):
+        check(L.fibhip_tensor_variant_info(i, out), L)
         rows.append(dict(zip(VARIANT_FIELDS, [int(x) for x in out])))
     return rows
 
@@ -625,6 +653,16 @@ class Stepper(RecorderBindings):
             phi = _f32(phi)
             assert phi.shape == (self.height, self.width)
             self._ck(self._L.fibhip_set_phase(self._h, _ptr(phi)))
+
+    def set_tensor(self, dyy, dxx=None, dxy=None):
+        """per-cell diffusion tensors D = [[dyy, dxy], [dxy, dxx]] (include/fibhip.h fibhip_set_tensor); set_tensor(None) removes them"""
+        if dyy is None:
+            self._ck(self._L.fibhip_set_tensor(self._h, None, None, None))
+            return
+        planes = [_f32(p) for p in (dyy, dxx, dxy)]
+        for p in planes:
+            assert p.shape == (self.height, self.width), (p.shape, (self.height, self.width))
+        self._ck(self._L.fibhip_set_tensor(self._h, *[_ptr(p) for p in planes]))
 
     def set_state(self, var, arr):
         arr = _f32(arr)

@@ -394,6 +394,13 @@ struct fibhip_ctx {
     size_t agg_stride;      // slab's pitch on row-block shards), `agg_stride` floats apart; or null
     bool use_agg, agg_dirty;
     bool agg_ghost_dirty;   // row-block shards: a halo exchange has rewritten the ghost rows' slow variables
+    // ---- per-cell diffusion tensors (fibhip_set_tensor) ----
+    float *tensor;          // dyy | dxx | dxy | wy | wx | wa | wb | wc, each `cells` floats; null until a tensor is first set
+    bool has_tensor;        // a tensor stands: the plan comes from g_tensor_variants, and phase3 holds tensor_prep_kernel's planes
+    bool agg_held;          // use_agg as it stood when the tensor was set (a tensor handle runs Courtemanche's plain modes)
+    Tensor<Fenton>::Consts tkf;             // what a tensor kernel is launched with: the model's constants as they stand at the
+    Tensor<BeelerReuter>::Consts tkb;       // launch, and the five weight planes (tick_consts_of)
+    Tensor<Courtemanche>::Consts tkc;
 };
 
 static const void *consts_of(fibhip_ctx *h)
@@ -406,6 +413,26 @@ static const void *consts_of(fibhip_ctx *h)
     case FIBHIP_CUSTOM: return &h->ku;
 #endif
     default: return &h->kc;
+    }
+}
+
+// ... of a launch of the handle's PLAN: a tensor handle's kernels take Tensor<M>::Consts
+static const void *tick_consts_of(fibhip_ctx *h)
+{
+    if (!h->has_tensor) return consts_of(h);
+    const float *w = h->tensor + 3 * h->cells;
+    auto planes = [&](auto &k) {
+        k.wy = w;
+        k.wx = w + h->cells;
+        k.wa = w + 2 * h->cells;
+        k.wb = w + 3 * h->cells;
+        k.wc = w + 4 * h->cells;
+        return (const void *)&k;
+    };
+    switch (h->d.model) {
+    case FIBHIP_FENTON4V: h->tkf.m = h->kf; return planes(h->tkf);
+    case FIBHIP_BR: h->tkb.m = h->kb; return planes(h->tkb);
+    default: h->tkc.m = h->kc; return planes(h->tkc);
     }
 }
 

@@ -298,6 +298,7 @@ extern "C" int fibhip_destroy(fibhip_t h)
     if (h->phase3) hipFree(h->phase3);
     if (h->phi_dev) hipFree(h->phi_dev);
     if (h->agg) hipFree(h->agg);
+    if (h->tensor) hipFree(h->tensor);
     if (h->obs.buf) hipFree(h->obs.buf);
     if (h->obs.vel) hipFree(h->obs.vel);
     recorders_free(h);
@@ -323,6 +324,26 @@ extern "C" int fibhip_destroy(fibhip_t h)
     return 0;
 }
 
+// phase3 from the field that stands: phase_prep_kernel's planes, or — on a handle with a diffusion tensor — tensor_prep_kernel's,
+// with the tensor's first-order coefficients where dpy and dpx stand, and its five weight planes (pointwise.inc)
+static int prep_planes(fibhip_ctx *h)
+{
+    const Geo g = base_geo(h);
+    float *p = h->phase3;
+    const size_t n = h->cells;
+    if (h->has_tensor) {
+        TensorPlanes t;
+        t.dyy = h->tensor; t.dxx = h->tensor + n; t.dxy = h->tensor + 2 * n;
+        t.wy = h->tensor + 3 * n; t.wx = h->tensor + 4 * n; t.wa = h->tensor + 5 * n; t.wb = h->tensor + 6 * n; t.wc = h->tensor + 7 * n;
+        hipLaunchKernelGGL(tensor_prep_kernel, dim3(1024), dim3(256), 0, h->s0, g, h->has_phase ? (const float *)h->phi_dev : (const float *)nullptr, t,
+                           p, p + n, p + 2 * n, p + 3 * n, p + 4 * n, p + 5 * n);
+    } else if (h->has_phase) {
+        hipLaunchKernelGGL(phase_prep_kernel, dim3(1024), dim3(256), 0, h->s0, g, h->phi_dev, p, p + n, p + 2 * n, p + 3 * n, p + 4 * n, p + 5 * n);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int fibhip_set_phase(fibhip_t h, const float *phi)
 {
     NEED(h);
@@ -332,16 +353,78 @@ extern "C" int fibhip_set_phase(fibhip_t h, const float *phi)
     h->phi_floored = false;
     if (!phi) {
         h->has_phase = false;
+        if (h->has_tensor) {                      // the tensor's planes without a field: ϕ = 1
+            if (int rc = prep_planes(h)) return rc;
+            SYNC_S0(h);
+        }
         return build_plan(h);
     }
     HIPCHK(hipMemcpyAsync(h->phi_dev, phi, h->cells * sizeof(float), hipMemcpyHostToDevice, h->s0));
-    const Geo g = base_geo(h);
-    hipLaunchKernelGGL(phase_prep_kernel, dim3(1024), dim3(256), 0, h->s0, g, h->phi_dev, h->phase3,
-                       h->phase3 + h->cells, h->phase3 + 2 * h->cells, h->phase3 + 3 * h->cells, h->phase3 + 4 * h->cells,
-                       h->phase3 + 5 * h->cells);
-    HIPCHK(hipGetLastError());
-    SYNC_S0(h);                                   // `phi` may be a temporary of the caller
     h->has_phase = true;
+    if (int rc = prep_planes(h)) return rc;
+    SYNC_S0(h);                                   // `phi` may be a temporary of the caller
+    return build_plan(h);
+}
+
+// what a diffusion tensor must be, cell by cell (fib_tf_amd/tensor.py check_tensor raises the same, in the same words)
+static int tensor_check(const float *dyy, const float *dxx, const float *dxy, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) {
+        const double a = dyy[i], b = dxx[i], c = dxy[i];
+        if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(c)) return fail(FIBHIP_EINVAL, "set_tensor: the tensor planes are not finite everywhere");
+        if (!(a > 0.0 && b > 0.0 && a * b - c * c > 0.0)) return fail(FIBHIP_EINVAL, "set_tensor: the tensor is not positive definite everywhere");
+        // (the entries are float32 roundings of a tensor whose largest eigenvalue is at most 1: 1e-6 is a dozen of their ulps)
+        if (0.5 * (a + b) + std::sqrt(0.25 * (a - b) * (a - b) + c * c) > 1.0 + 1e-6)
+            return fail(FIBHIP_EINVAL, "set_tensor: the largest eigenvalue is above 1: the tensor is relative to diff (raise diff instead)");
+    }
+    return 0;
+}
+
+extern "C" int fibhip_set_tensor(fibhip_t h, const float *dyy, const float *dxx, const float *dxy)
+{
+    NEED(h);
+    const bool off = !dyy && !dxx && !dxy;
+    if (!off && (!dyy || !dxx || !dxy)) return fail(FIBHIP_EINVAL, "set_tensor: three planes, or three null pointers to remove the tensor");
+    if (!off) {
+        // what reads the isotropic operator or recomputes the phase planes does not go with a tensor
+        if (h->d.ghost_top || h->d.ghost_bottom) return fail(FIBHIP_EINVAL, "set_tensor: not on a row block: a diffusion tensor is a single-device option");
+        if (h->d.flags & FIBHIP_ZEROPAD) return fail(FIBHIP_EINVAL, "set_tensor: not on a model with the zero-padded Laplacian (FIBHIP_ZEROPAD)");
+        if (h->d.model == FIBHIP_CUSTOM) return fail(FIBHIP_EINVAL, "set_tensor: not on a traced model (FIBHIP_CUSTOM): its kernels know the isotropic Laplacian only");
+        if (h->pitch != h->d.width) return fail(FIBHIP_EINVAL, "set_tensor: not on a row-interleaved slab");
+        if (h->ld.on || h->pm.on || h->les.on)
+            return fail(FIBHIP_EINVAL, "set_tensor: not while a lead recorder, a potential-map recorder or a lesion program is attached");
+        if (int rc = tensor_check(dyy, dxx, dxy, h->cells)) return rc;
+    }
+    FLUSH(h);
+    CONFIRM(h);
+    if (h->phase_of_tick) return fail(FIBHIP_EINVAL, "set_tensor inside an open tick");
+    if (off) {
+        if (!h->has_tensor) return 0;
+        h->has_tensor = false;
+        if (h->agg_held) {                        // Courtemanche, fast policy: back on the aggregates, formed afresh
+            h->use_agg = true;
+            h->agg_dirty = true;
+            h->agg_held = false;
+        }
+        if (int rc = prep_planes(h)) return rc;   // the phase planes of the field that stands, if one does
+        SYNC_S0(h);
+        return build_plan(h);
+    }
+    const size_t B = h->cells * sizeof(float);
+    if (!h->tensor && hipMalloc((void **)&h->tensor, 8 * B) != hipSuccess) {
+        h->tensor = nullptr;
+        return fail(FIBHIP_ENOMEM, "set_tensor: hipMalloc of %zu bytes failed", 8 * B);
+    }
+    HIPCHK(hipMemcpyAsync(h->tensor, dyy, B, hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemcpyAsync(h->tensor + h->cells, dxx, B, hipMemcpyHostToDevice, h->s0));
+    HIPCHK(hipMemcpyAsync(h->tensor + 2 * h->cells, dxy, B, hipMemcpyHostToDevice, h->s0));
+    if (!h->has_tensor && h->use_agg) {           // a tensor handle runs Courtemanche's plain modes (launch.hpp g_tensor_variants)
+        h->use_agg = false;
+        h->agg_held = true;
+    }
+    h->has_tensor = true;
+    if (int rc = prep_planes(h)) return rc;
+    SYNC_S0(h);                                   // the planes may be temporaries of the caller
     return build_plan(h);
 }
 
@@ -745,6 +828,20 @@ extern "C" int fibhip_variant_info(int i, int out[10])
     // (1: a multi-tick launch that exchanges once per tick, K = the tick's sub-steps; an exchange-period row is listed as the
     // plain strip launch of K sub-steps it also is)
     out[9] = v.fn_mt && !v.period ? 1 : 0;
+    return 0;
+}
+
+// the second table: the kernels of handles with a diffusion tensor (launch.hpp g_tensor_variants), the same ten fields
+extern "C" int fibhip_tensor_variant_count(void) { return g_ntensor_variants; }
+
+extern "C" int fibhip_tensor_variant_info(int i, int out[10])
+{
+    if (i < 0 || i >= g_ntensor_variants || !out) return fail(FIBHIP_EINVAL, "tensor_variant_info: bad argument");
+    const Variant &v = g_tensor_variants[i];
+    out[0] = v.model; out[1] = v.mode; out[2] = v.fast; out[3] = v.phase;
+    out[4] = v.K; out[5] = v.TX; out[6] = v.TY; out[7] = v.NT;
+    out[8] = MK_TICK;
+    out[9] = 0;
     return 0;
 }
 

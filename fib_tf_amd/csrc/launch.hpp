@@ -306,3 +306,33 @@ static const Variant g_variants[] = {
 #endif
 };
 static const int g_nvariants = (int)(sizeof g_variants / sizeof g_variants[0]);
+
+// The kernels of a handle with per-cell diffusion tensors (fibhip_set_tensor; models.hpp Tensor<M>): a table of its own, so that
+// g_variants and what fibhip_variant_count / _info enumerate stay what they are.  Flat tiles only — the tensor Laplacian exists in
+// tick_kernel alone, as FentonZP's does — and PHASE = true only: a tensor always has a first-order term, which rides on the phase
+// planes (pointwise.inc tensor_prep_cell; ϕ = 1 where the model has no field).  No aggregates: Courtemanche runs its plain modes.
+// Listed under the model's own id; the first row of a K is the default, FIBHIP_VARIANT / FIBHIP_K choose among them.
+#define T2(MODEL, MID, MODE, K, TX, TY, NT)                                                                            \
+    VROW(MK_TICK, 0, Exact, 0, true, Tensor<MODEL>, MID, MODE, K, TX, TY, NT, NT), VROW(MK_TICK, 0, Fast, 1, true, Tensor<MODEL>, MID, MODE, K, TX, TY, NT, NT)
+static const Variant g_tensor_variants[] = {
+#ifndef FIB_CUSTOM_ONLY
+#ifndef FIB_ONLY_BR
+    T2(Fenton, FIBHIP_FENTON4V, 0, 10, 32, 32, 1024),
+    T2(Fenton, FIBHIP_FENTON4V, 0, 5, 32, 32, 512),
+    T2(Fenton, FIBHIP_FENTON4V, 0, 2, 64, 16, 256),
+    T2(Fenton, FIBHIP_FENTON4V, 0, 1, 64, 4, 256),
+#endif
+    T2(BeelerReuter, FIBHIP_BR, 0, 5, 32, 32, 512),
+    T2(BeelerReuter, FIBHIP_BR, 0, 1, 64, 4, 256),
+    T2(BeelerReuter, FIBHIP_BR, 1, 5, 32, 32, 512),
+    T2(BeelerReuter, FIBHIP_BR, 1, 1, 64, 4, 256),
+#ifndef FIB_ONLY_BR
+    T2(Courtemanche, FIBHIP_COURT, Courtemanche::MODE_FAST, 1, 64, 4, 256),
+    T2(Courtemanche, FIBHIP_COURT, Courtemanche::MODE_ALL, 1, 64, 4, 256),
+    T2(Courtemanche, FIBHIP_COURT, Courtemanche::MODE_FASTSLOW, 1, 64, 4, 256),
+    T2(CourtemancheUS, FIBHIP_COURT_US, CourtemancheUS::MODE_ALL, 1, 64, 4, 256),
+#endif
+#endif
+    {-1, 0, 0, 0, 0, 0, 0, 0, nullptr},             // (ends the table: a build for one traced model has no row)
+};
+static const int g_ntensor_variants = (int)(sizeof g_tensor_variants / sizeof g_tensor_variants[0]) - 1;

@@ -480,6 +480,24 @@ struct FentonZP : Fenton {
     static constexpr bool ZEROPAD = true;
 };
 
+// Any model behind a per-cell diffusion tensor (stencil.hpp TensorOf, lap9_tensor): like ZEROPAD a compile-time property of
+// the model type, so that the other kernels carry none of it; tick_kernel only.  The constants are the model's own plus the
+// five weight planes tensor_prep_kernel makes (row-major [H][W]); the kinetics are M's, on M's constants.
+template <class M>
+struct Tensor : M {
+    static constexpr bool TENSOR = true;
+    struct Consts {
+        typename M::Consts m;
+        const float *wy, *wx, *wa, *wb, *wc;
+    };
+    static FIB_DEV decltype(auto) pinned(const Consts &k) { return M::pinned(k.m); }
+    template <class P, int MODE>
+    static FIB_DEV void step(float (&s)[M::NVAR], float Vc, float lap, const typename M::Consts &k, int sub)
+    {
+        M::template step<P, MODE>(s, Vc, lap, k, sub);
+    }
+};
+
 // =====================================================================================
 // Beeler-Reuter  (br.py:125-332)
 // =====================================================================================

@@ -10,6 +10,16 @@ static const Variant *find_variant(const fibhip_ctx *h, int K, const int *want /
     // fenton_simple.py's Laplacian is a property of the kernel's model type (FentonZP): its own rows of the table
     const int vmodel = (h->d.model == FIBHIP_FENTON4V && (h->d.flags & FIBHIP_ZEROPAD)) ? VM_FENTON_ZP
                        : (h->use_agg ? VM_COURT_AGG : h->d.model);
+    if (h->has_tensor) {
+        // per-cell diffusion tensors are a property of the kernel's model type too (Tensor<M>): their own table, phase rows only
+        for (int i = 0; i < g_ntensor_variants; ++i) {
+            const Variant &v = g_tensor_variants[i];
+            if (v.model != h->d.model || v.mode != mode || v.fast != fast || v.K != K) continue;
+            if (want && (v.TX != want[0] || v.TY != want[1] || v.NT != want[2])) continue;
+            return &v;
+        }
+        return nullptr;
+    }
     const Variant *tab = h->mod ? h->mod->variants.data() : g_variants;
     const int ntab = h->mod ? (int)h->mod->variants.size() : g_nvariants;
     for (int i = 0; i < ntab; ++i) {
@@ -105,9 +115,10 @@ static int build_plan(fibhip_ctx *h)
             // K=10: 18 us with <= 1 tile per CU, ~34 us with 2.  K=5 (two launches), R=3: 27 us with <= 2 per CU, 38 us
             // with 3; the 23-row tile fills its 11 waves exactly (33 rows) and is taken when it saves a whole round
             // of tiles.  Beyond that the fatter R=4 waves win, with the wave-exact 22-row tile.
-            if (h->d.flags & FIBHIP_ZEROPAD) {
+            if ((h->d.flags & FIBHIP_ZEROPAD) || h->has_tensor) {
                 // fenton_simple.py's Laplacian exists in the flat tick_kernel only (measured at 512^2: 10 x 32x32 x 1024
-                // threads 20.8 us per 10 steps, 5 x 32x32 x 512 25.4)
+                // threads 20.8 us per 10 steps, 5 x 32x32 x 512 25.4); so does the tensor Laplacian, whose table has the same
+                // flat rows (Beeler-Reuter's rule above names a strip: a tensor handle gets the flat row of that K instead)
                 const long t32 = tiles_of(h, 32, 32, rows);
                 prefK = t32 <= 512 ? 10 : 5; want[0] = 32; want[1] = 32; want[2] = t32 <= 512 ? 1024 : 512;
             } else if (tiles10 <= 256 || t28 <= 256) {
@@ -258,7 +269,7 @@ static int autotune(fibhip_ctx *h)
     h->tuned = true;
     if (h->use_agg && h->multi_max > 1) return autotune_multi(h);
     if ((h->d.model != FIBHIP_FENTON4V && h->d.model != FIBHIP_BR && h->d.model != FIBHIP_CUSTOM) ||
-        (h->d.flags & FIBHIP_ZEROPAD) || h->spt < 2)
+        (h->d.flags & FIBHIP_ZEROPAD) || h->has_tensor || h->spt < 2)     // (a tensor handle: its rule is its plan; no strips to time)
         return 0;
     if (getenv("FIBHIP_VARIANT") || getenv("FIBHIP_K")) return 0;
     if (const char *e = getenv("FIBHIP_AUTOTUNE"))

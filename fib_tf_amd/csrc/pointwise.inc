@@ -87,6 +87,79 @@ __global__ void phase_prep_kernel(Geo g, const float *phi, float *dpy, float *dp
         phase_prep_cell(g, e / g.W, e % g.W, phi, dpy, dpx, q4, r4, pyr, pxr);
 }
 
+// A tensor handle's prepared planes (fibhip_set_tensor): the five weights of lap9_tensor, and PhaseTab's six planes with the
+// first-order coefficients in the place of dpy, dpx —
+//     gy = (dyy dpy + dxy dpx) + (2ϕ) (δy dyy + δx dxy)        gx = (dxy dpy + dxx dpx) + (2ϕ) (δy dxy + δx dxx)
+// δ: phase_prep_cell's REFLECT-padded central difference without the 1/2; q4, r4 and the two products as there, so that
+// PhaseCoef<P>::add runs unchanged.  The ϕ part keeps the reference's weight (ionic.py:78-80: half of what a consistent
+// discretisation of D grad ϕ . grad V / ϕ would carry), the div D part the consistent one.  At D = I: gy == dpy, gx == dpx.
+// `phi` null: ϕ = 1 everywhere.  One rounding per operation (-ffp-contract=off).
+struct TensorPlanes {
+    const float *dyy, *dxx, *dxy;
+    float *wy, *wx, *wa, *wb, *wc;
+};
+static FIB_DEV void tensor_prep_cell(const Geo &g, int y, int x, const float *phi, const TensorPlanes &t, float *gy, float *gx, float *q4,
+                                     float *r4, float *pyr, float *pxr)
+{
+    const int e = y * g.W + x, yg = y + g.row_off;
+    int yn = yg - 1, ys = yg + 1, xw = x - 1, xe = x + 1;
+    if (yn < 0) yn = 1;
+    if (ys > g.Hg - 1) ys = g.Hg - 2;
+    if (xw < 0) xw = 1;
+    if (xe > g.W - 1) xe = g.W - 2;
+    yn = clampi(yn - g.row_off, 0, g.H - 1);
+    ys = clampi(ys - g.row_off, 0, g.H - 1);
+    const int n = yn * g.W + x, s = ys * g.W + x, w = y * g.W + xw, ea = y * g.W + xe;
+    const float dyy = t.dyy[e], dxx = t.dxx[e], dxy = t.dxy[e];
+    const TensorW tw = tensor_weights(dyy, dxx, dxy);
+    t.wy[e] = tw.wy;
+    t.wx[e] = tw.wx;
+    t.wa[e] = tw.wa;
+    t.wb[e] = tw.wb;
+    t.wc[e] = tw.wc;
+    const float p = phi ? phi[e] : 1.0f;
+    const float dpy = phi ? phi[s] - phi[n] : 0.0f, dpx = phi ? phi[ea] - phi[w] : 0.0f;
+    const float p2 = 2.0f * p;
+    const float vy = (dyy * dpy + dxy * dpx) + p2 * ((t.dyy[s] - t.dyy[n]) + (t.dxy[ea] - t.dxy[w]));
+    const float vx = (dxy * dpy + dxx * dpx) + p2 * ((t.dxy[s] - t.dxy[n]) + (t.dxx[ea] - t.dxx[w]));
+    gy[e] = vy;
+    gx[e] = vx;
+    const float q = 4.0f * p;
+    q4[e] = q;
+    const float r = 1.0f / q;                       // IEEE division: correctly rounded reciprocal
+    r4[e] = r;
+    if (pyr) {
+        pyr[e] = vy * r;
+        pxr[e] = vx * r;
+    }
+}
+__global__ void tensor_prep_kernel(Geo g, const float *phi, TensorPlanes t, float *gy, float *gx, float *q4, float *r4, float *pyr, float *pxr)
+{
+    const int n = g.H * g.W;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x)
+        tensor_prep_cell(g, e / g.W, e % g.W, phi, t, gy, gx, q4, r4, pyr, pxr);
+}
+
+// The tensor operator as a stand-alone array op (fibhip_unit_laplace_tensor): lap9_tensor and PhaseCoef<P>::add on the planes
+// tensor_prep_kernel made — the device functions of tick_kernel's tensor variants; `a` is read through the REFLECT pad, as
+// unit_op_kernel's laplace reads it.
+template <class P>
+__global__ void unit_tensor_kernel(int H, int W, const float *a, TensorPlanes t, PhaseTab ph, float *out)
+{
+    const int n = H * W;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
+        const int y = e / W, x = e % W;
+        const int yn = y == 0 ? 1 : y - 1, ys = y == H - 1 ? H - 2 : y + 1;
+        const int xw = x == 0 ? 1 : x - 1, xe = x == W - 1 ? W - 2 : x + 1;
+        const float N = a[yn * W + x], S = a[ys * W + x], Wv = a[y * W + xw], E = a[y * W + xe];
+        const float l = lap9_tensor<P>(N, S, Wv, E, a[yn * W + xw], a[ys * W + xw], a[yn * W + xe], a[ys * W + xe], a[e], t.wy[e], t.wx[e],
+                                       t.wa[e], t.wb[e], t.wc[e]);
+        PhaseCoef<P> pc;
+        pc.load(ph, e);
+        out[e] = pc.add(l, N, S, Wv, E);
+    }
+}
+
 // pace op, ionic.py:144-163:  pot = max(pot, s), s = v inside the global rectangle, min_v outside
 __global__ void pace_kernel(Geo g, float *pot, int r0, int r1, int c0, int c1, float v, float min_v)
 {

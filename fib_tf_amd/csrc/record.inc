@@ -1440,6 +1440,8 @@ extern "C" int fibhip_leads_begin(fibhip_t h, int var, int n, const int *pos, in
     if (H < 3 || W < 3) return fail(FIBHIP_EINVAL, "leads_begin: a %d x %d grid has no interior cell", H, W);
     if (zero_padded(h))
         return fail(FIBHIP_EINVAL, "leads_begin: not on a model with the zero-padded Laplacian (FIBHIP_ZEROPAD): its diffusion term is not this source");
+    if (h->has_tensor)
+        return fail(FIBHIP_EINVAL, "leads_begin: not on a handle with a diffusion tensor (fibhip_set_tensor): its diffusion term is not this source");
     std::vector<int> table(4 * (size_t)n);
     for (int e = 0; e < n; ++e) {
         const int r = pos[3 * e], c = pos[3 * e + 1], t = pos[3 * e + 2];
@@ -1512,6 +1514,8 @@ extern "C" int fibhip_pmap_begin(fibhip_t h, int var, int radius, const float *t
     if (int rc = capacity_check("pmap_begin", capacity, npix * sizeof(double), INT_MAX)) return rc;
     if (zero_padded(h))
         return fail(FIBHIP_EINVAL, "pmap_begin: not on a model with the zero-padded Laplacian (FIBHIP_ZEROPAD): its diffusion term is not this source");
+    if (h->has_tensor)
+        return fail(FIBHIP_EINVAL, "pmap_begin: not on a handle with a diffusion tensor (fibhip_set_tensor): its diffusion term is not this source");
     if (int rc = finite_check("pmap_begin", table, (size_t)R + 1, (size_t)R + 1, "the table")) return rc;
     if (weight)
         if (int rc = finite_check("pmap_begin", weight, (size_t)H, (size_t)W, "the weight plane")) return rc;
@@ -2225,6 +2229,8 @@ static int lesion_refusals(const fibhip_ctx *h, const char *who)
     if (int rc = attach_refusals(h, who)) return rc;
     if (zero_padded(h))
         return fail(FIBHIP_EINVAL, "%s: not on a model with the zero-padded Laplacian (FIBHIP_ZEROPAD): its diffusion term has no phase field", who);
+    if (h->has_tensor)
+        return fail(FIBHIP_EINVAL, "%s: not on a handle with a diffusion tensor (fibhip_set_tensor): a lesion recomputes the phase planes, which hold the tensor's there", who);
     return 0;
 }
 // one lesion's box and factors: the box inside the grid and not empty, every factor finite and in [0, 1]

@@ -162,6 +162,57 @@ struct ZeroPadOf<M, void_of<decltype(M::ZEROPAD)>> {
     static constexpr bool value = M::ZEROPAD;
 };
 
+// fibhip_set_tensor — per-cell diffusion tensors D = [[dyy, dxy], [dxy, dxx]] (rows y, columns x; relative to diff).  A
+// compile-time property of the model type (models.hpp Tensor<M>), tick_kernel only, as ZEROPAD is.
+template <class M, class = void>
+struct TensorOf {
+    static constexpr bool value = false;
+};
+template <class M>
+struct TensorOf<M, void_of<decltype(M::TENSOR)>> {
+    static constexpr bool value = M::TENSOR;
+};
+
+// The five weights of one cell, as tensor_prep_kernel forms them (one rounding per line, no contraction):
+//     wd = 0.25 (dyy + dxx)      wy = 1.5 dyy - 0.5 dxx  (N, S)      wx = 1.5 dxx - 0.5 dyy  (W, E)
+//     wa = wd + dxy  (NW, SE)    wb = wd - dxy  (NE, SW)              wc = 12 wd  (centre)
+// 2 h^2 D : grad grad V, second-order, with the 9-point blend that gives stencil9's weights (1, 1, 0.5, 0.5, 6) at D = I.
+struct TensorW {
+    float wy, wx, wa, wb, wc;
+};
+static FIB_DEV TensorW tensor_weights(float dyy, float dxx, float dxy)
+{
+    TensorW w;
+    const float wd = 0.25f * (dyy + dxx);
+    w.wy = 1.5f * dyy - 0.5f * dxx;
+    w.wx = 1.5f * dxx - 0.5f * dyy;
+    w.wa = wd + dxy;
+    w.wb = wd - dxy;
+    w.wc = 12.0f * wd;
+    return w;
+}
+// The second-order part under the two arithmetic policies.  Exact: every product and sum rounded once, in stencil9's order — at
+// D = I every product is exact and the value is stencil9's.  Fast: opposite taps share a weight, so they are summed first and
+// the five products contracted into FMAs:
+//     t = fma(wx, W + E, wy * (N + S))     u = fma(wb, SW + NE, wa * (NW + SE))     l = fma(-wc, C, t + u)
+// Rounded operations on the longest path: the pair sum (1), the product (2), the FMA (3), t + u (4), the last FMA (5); a weight
+// brings up to 3 of its own (wa: the sum, the scaling by 0.25, the sum with dxy): 8 for the second-order part alone.  With the
+// first-order term (PhaseCoef<Fast>::add: two more FMAs behind l) the Laplacian's terms see 10; so do the first-order ones:
+// gy or gx 5 (tensor_prep_cell), r4 1, their product 1, the tap difference 1 beside them, the two FMAs 2.  n = 10.
+template <class P>
+static FIB_DEV float lap9_tensor(float N, float S, float Wv, float E, float NW, float SW, float NE, float SE, float C, float wy, float wx,
+                                 float wa, float wb, float wc)
+{
+    if constexpr (same_type<P, Fast>::value) {
+        const float t = __builtin_fmaf(wx, Wv + E, wy * (N + S));
+        const float u = __builtin_fmaf(wb, SW + NE, wa * (NW + SE));
+        return __builtin_fmaf(-wc, C, t + u);
+    } else {
+        const float l = ((((wy * N + wy * S) + wx * Wv) + wx * E) + (((wa * NW + wb * SW) + wb * NE) + wa * SE));
+        return l - wc * C;
+    }
+}
+
 // does MODE ask for two evaluations in one launch (Courtemanche::MODE_FASTSLOW)?
 template <class M, class = void>
 struct TwoPass {

@@ -58,7 +58,7 @@ static void fill_ptrs(fibhip_ctx *h, LaunchCtx &c, int K, const int *cur, int *n
     c.ph.pyr = h->phase3 + 4 * h->cells;
     c.ph.pxr = h->phase3 + 5 * h->cells;
     c.ph.phi = h->phi_dev;
-    c.consts = consts_of(h);
+    c.consts = tick_consts_of(h);
 }
 
 static const char *family_of(const Variant *v)

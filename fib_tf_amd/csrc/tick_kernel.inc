@@ -29,7 +29,8 @@ tick_kernel(Geo g, PtrTab<M::NVAR> pt, PhaseTab ph, typename M::Consts k, int su
     constexpr int LP = CX + 2, LQ = CY + 2;                        // LDS tile (box + ring)
     constexpr int NC = CX * CY, CPT = (NC + NT - 1) / NT, NL = LP * LQ;
     constexpr unsigned WMASK = M::mask(MODE);
-    constexpr bool PHI_TILE = PHASE && K == 1;
+    constexpr bool TENSOR = TensorOf<M>::value;                    // per-cell diffusion tensors (models.hpp Tensor<M>)
+    constexpr bool PHI_TILE = PHASE && K == 1 && !TENSOR;          // (a tensor's first-order planes are prepared ones: never from a ϕ tile)
     constexpr bool ZP = ZeroPadOf<M>::value;
     __shared__ float lds[(K > 1) ? 2 : 1][NL];
     __shared__ float lphi[PHI_TILE ? NL : 1];
@@ -71,6 +72,7 @@ tick_kernel(Geo g, PtrTab<M::NVAR> pt, PhaseTab ph, typename M::Consts k, int su
     // ---- per-cell registers -------------------------------------------------------------------
     float s[CPT][NV];
     PhaseCoef<P> pc[CPT];
+    TensorW tw[TENSOR ? CPT : 1];
     int li[CPT], off[CPT];
     unsigned fl[CPT];
 #pragma unroll
@@ -87,6 +89,10 @@ tick_kernel(Geo g, PtrTab<M::NVAR> pt, PhaseTab ph, typename M::Consts k, int su
 #pragma unroll
         for (int v = 0; v < NV; ++v) s[j][v] = pt.in[v][off[j]];
         if (PHASE && !PHI_TILE) pc[j].load(ph, oy * g.W + ox);    // (the phase arrays are always planar)
+        if constexpr (TENSOR) {                                    // the cell's five weights, once per launch
+            const int op = oy * g.W + ox;
+            tw[j] = TensorW{k.wy[op], k.wx[op], k.wa[op], k.wb[op], k.wc[op]};
+        }
         const bool border = gyg == 0 || gyg == g.Hg - 1 || gx == 0 || gx == g.W - 1;
         unsigned f = 0;
         if (indom) {
@@ -117,7 +123,11 @@ tick_kernel(Geo g, PtrTab<M::NVAR> pt, PhaseTab ph, typename M::Consts k, int su
                 const float N = A[i - LP], S = A[i + LP], Wv = A[i - 1], E = A[i + 1];
                 const float NW = A[i - LP - 1], SW = A[i + LP - 1], NE = A[i - LP + 1], SE = A[i + LP + 1];
                 const float C = A[i];
-                float l = ZP ? stencil9_conv(N, S, Wv, E, NW, SW, NE, SE, C) : lap9<P>(N, S, Wv, E, NW, SW, NE, SE, C);
+                float l;
+                if constexpr (TENSOR)
+                    l = lap9_tensor<P>(N, S, Wv, E, NW, SW, NE, SE, C, tw[j].wy, tw[j].wx, tw[j].wa, tw[j].wb, tw[j].wc);
+                else
+                    l = ZP ? stencil9_conv(N, S, Wv, E, NW, SW, NE, SE, C) : lap9<P>(N, S, Wv, E, NW, SW, NE, SE, C);
                 if (PHI_TILE) {     // same arithmetic as phase_prep_kernel + add_phase (IEEE division = Exact::divc)
                     const float dy = lphi[i + LP] - lphi[i - LP], dx = lphi[i + 1] - lphi[i - 1];
                     if constexpr (same_type<P, Fast>::value) {

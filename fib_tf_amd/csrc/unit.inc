@@ -44,6 +44,53 @@ extern "C" int fibhip_unit_op(int device, int op, int H, int W, const float *a, 
     return rc;
 }
 
+// The tensor operator of a handle with per-cell diffusion tensors (fibhip_set_tensor) on HOST arrays: laplace(a) with the
+// tensor D = [[dyy, dxy], [dxy, dxx]] and the phase field phi (null: 1 everywhere) — tensor_prep_kernel's planes, then
+// lap9_tensor and the first-order term under the policy asked for, as tick_kernel's tensor variants run them.
+extern "C" int fibhip_unit_laplace_tensor(int device, int H, int W, const float *a, const float *phi, const float *dyy, const float *dxx,
+                                          const float *dxy, int fast, float *out)
+{
+    if (!a || !dyy || !dxx || !dxy || !out || H < 3 || W < 3 || (long long)H * W > INT_MAX / 16)
+        return fail(FIBHIP_EINVAL, "unit_laplace_tensor: bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(FIBHIP_ENODEV, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(FIBHIP_EINVAL, "device %d out of range", device);
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)H * W, B = n * sizeof(float);
+    float *d = nullptr;
+    HIPCHK(hipMalloc((void **)&d, 17 * B));         // a phi out | dyy dxx dxy | wy wx wa wb wc | gy gx q4 r4 pyr pxr
+    float *da = d, *dphi = d + n, *dout = d + 2 * n, *dt = d + 3 * n, *dw = d + 6 * n, *dp = d + 11 * n;
+    int rc = 0;
+    do {
+        if (hipMemcpy(da, a, B, hipMemcpyHostToDevice) != hipSuccess || (phi && hipMemcpy(dphi, phi, B, hipMemcpyHostToDevice) != hipSuccess) ||
+            hipMemcpy(dt, dyy, B, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dt + n, dxx, B, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dt + 2 * n, dxy, B, hipMemcpyHostToDevice) != hipSuccess) {
+            rc = fail(FIBHIP_EHIP, "unit_laplace_tensor: H2D failed");
+            break;
+        }
+        Geo g;
+        g.H = g.Hg = H; g.W = W; g.pitch = W; g.row_off = 0; g.r0 = 0; g.r1 = H; g.rb0 = g.rb1 = g.ty_a = 0; g.tiles_x = g.ntiles = 0;
+        TensorPlanes t;
+        t.dyy = dt; t.dxx = dt + n; t.dxy = dt + 2 * n;
+        t.wy = dw; t.wx = dw + n; t.wa = dw + 2 * n; t.wb = dw + 3 * n; t.wc = dw + 4 * n;
+        PhaseTab ph;
+        ph.dpy = dp; ph.dpx = dp + n; ph.q4 = dp + 2 * n; ph.r4 = dp + 3 * n; ph.pyr = dp + 4 * n; ph.pxr = dp + 5 * n; ph.phi = dphi;
+        hipLaunchKernelGGL(tensor_prep_kernel, dim3(256), dim3(256), 0, 0, g, phi ? (const float *)dphi : (const float *)nullptr, t, dp, dp + n,
+                           dp + 2 * n, dp + 3 * n, dp + 4 * n, dp + 5 * n);
+        if (fast)
+            hipLaunchKernelGGL(unit_tensor_kernel<Fast>, dim3(256), dim3(256), 0, 0, H, W, da, t, ph, dout);
+        else
+            hipLaunchKernelGGL(unit_tensor_kernel<Exact>, dim3(256), dim3(256), 0, 0, H, W, da, t, ph, dout);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, B, hipMemcpyDeviceToHost) != hipSuccess) {
+            rc = fail(FIBHIP_EHIP, "unit_laplace_tensor: kernel or D2H failed");
+            break;
+        }
+    } while (0);
+    hipFree(d);
+    return rc;
+}
+
 extern "C" int fibhip_court_inter(int device, int n, const float *V, int fast, float *out)
 {
     if (!V || !out || n <= 0) return fail(FIBHIP_EINVAL, "court_inter: bad argument");

@@ -50,6 +50,7 @@ class IonicModel:
         for key, val in config.items():         # every key becomes an attribute, ionic.py:35-37
             setattr(self, key, val)
         self.phase = None
+        self.tensor = None              # (dyy, dxx, dxy): per-cell diffusion tensors (set_tensor / set_fibres), or None
         self._ops = {}
         self.defined = False
         self.dt_per_step = 1
@@ -64,10 +65,16 @@ class IonicModel:
                              ('device', int(os.environ.get('LOCAL_RANK', '0'))), ('fast_math', True)):
             if not hasattr(self, key):
                 setattr(self, key, default)
+        # config['fibre_angle'] (radians from the +column axis towards the +row axis) and config['anisotropy'] (longitudinal
+        # over transverse diffusion): uniform fibres over the whole sheet
+        if hasattr(self, 'fibre_angle') or hasattr(self, 'anisotropy'):
+            self.set_fibres(getattr(self, 'fibre_angle', 0.0), getattr(self, 'anisotropy', 1.0))
 
     # ---- building blocks, callable on host arrays (ionic.py:44-123); executed on the GPU -------
     def laplace(self, X0):
         """9-point Laplacian of X0 (+ phase-field correction when self.phase is set), ionic.py:44-60"""
+        if self.tensor is not None:             # div(D grad X0) in the form of DESIGN.md 25, incl. its first-order term
+            return _lib.unit_laplace_tensor(X0, *self.tensor, phi=self.phase, fast=self.fast_math, device=self.device)
         return _lib.unit_op(1, X0, phi=self.phase, fast=self.fast_math, device=self.device)
 
     def phase_field(self, X):
@@ -111,6 +118,32 @@ class IonicModel:
         base = np.ones([self.height, self.width], dtype=np.float32) if self.phase is None else self.phase
         # floor at 1e-5: phase_field divides by 4ϕ (ionic.py:104-105)
         self.phase = np.maximum(base * mask, 1e-5)
+
+    # ---- fibres: anisotropic, heterogeneous conduction (fib_tf_amd/tensor.py) ----------------------------
+    def set_tensor(self, dyy, dxx, dxy):
+        """per-cell diffusion tensors D = [[dyy, dxy], [dxy, dxx]] (rows are y, columns are x), three [height, width] planes,
+        dimensionless and relative to `diff`: the diffusion term becomes diff * div(D grad V).  The planes must be finite and
+        positive definite with a largest eigenvalue of at most 1 (raise `diff` instead).  set_tensor(None, None, None) removes
+        the tensor.  Must be called before define(); single device only, not on traced models; record_leads,
+        record_potential_map, program_lesions and ablate do not go with it."""
+        from . import tensor as _tensor
+        if self.defined:
+            raise AssertionError('set_tensor should be called before calling define')
+        if dyy is None and dxx is None and dxy is None:
+            self.tensor = None
+            return
+        planes = _tensor.check_tensor(dyy, dxx, dxy, shape=(self.height, self.width))
+        _tensor.warn_if_not_monotone(*planes)
+        self.tensor = tuple(planes)
+
+    def set_fibres(self, angle, ratio, scale=1.0):
+        """fibres at `angle` (radians from the +column axis towards the +row axis) with longitudinal over transverse diffusion
+        `ratio` >= 1 and longitudinal diffusion `scale` * diff, scale in (0, 1]; each a scalar or a [height, width] array
+        (tensor.fibre_tensor).  Must be called before define()."""
+        from . import tensor as _tensor
+        if self.defined:
+            raise AssertionError('set_fibres should be called before calling define')
+        self.set_tensor(*_tensor.fibre_tensor(angle, ratio, scale, shape=(self.height, self.width)))
 
     # ---- pacing ----------------------------------------------------------------------------------
     def pace_rect(self, loc):
@@ -419,6 +452,8 @@ class IonicModel:
         than one rank is initialised — this rank's row block of it (fib_tf_amd/sharded.py)"""
         from .sharded import ShardedStepper, dist_world
         _, world = dist_world()
+        if self.tensor is not None and shard and world > 1:
+            raise NotImplementedError('set_tensor: a diffusion tensor is set on a single device only; this model runs as row blocks over %d ranks' % world)
         if shard and world > 1:
             st = ShardedStepper(self.MODEL_ID, self.height, self.width, self.dt, self.diff, flags=self._flags(),
                                 device=self.device, steps_per_tick=steps_per_tick,
@@ -430,6 +465,8 @@ class IonicModel:
         self._configure_stepper(st)
         if self.phase is not None:
             st.set_phase(self.phase)
+        if self.tensor is not None:
+            st.set_tensor(*self.tensor)
         return st
 
     def _configure_stepper(self, st):

@@ -14,6 +14,7 @@ import numpy as np
 
 from ._lib import MAX_LEAD_TABLES, MAX_LEADS
 from ._recorder import SampledRecorder, array_index, attach, check_every, run_capacity, sample_times, tick_ms, weight_plane
+from .tensor import refuse as refuse_tensor
 
 
 def point_table(h, w, z, dx=1.0):
@@ -91,6 +92,7 @@ class LeadRecorder(SampledRecorder):
         self._st = st = attach(model, 'record_leads', 'electrograms are recorded')
         if _zero_padded(model):
             raise ValueError('record_leads: not on a model with the zero-padded Laplacian (ZEROPAD): its diffusion term is not this source')
+        refuse_tensor(model, 'record_leads', 'its diffusion term is not this source')
         self.pos, self.tables = parse_leads(positions, tables, table_of, model.height, model.width)
         self.every = check_every('record_leads', every)
         self.var = array_index(model.VAR_NAMES, var, 'record_leads', check_range=False)      # (an index is the library's to refuse)

@@ -18,6 +18,7 @@ import numpy as np
 
 from ._lib import MAX_LESION_ENTRIES, MAX_STIM_PLANES
 from ._recorder import DeviceRecorder, attach, tick_ms
+from .tensor import refuse as refuse_tensor
 
 FLOOR = np.float32(1e-5)
 
@@ -137,6 +138,7 @@ def _device_stepper(model, who):
     st = attach(model, who, 'the geometry changes')
     if _zero_padded(model) or getattr(model, 'ZEROPAD', False):
         raise ValueError('%s: not on a model with the zero-padded Laplacian (ZEROPAD): its diffusion term has no phase field' % who)
+    refuse_tensor(model, who, 'a lesion recomputes the phase planes, which hold the tensor\'s there')
     check_field(model.phase)
     return st
 

@@ -13,6 +13,7 @@ import numpy as np
 from ._lib import PMAP_MAX_RADIUS, PMAP_MAX_STEP
 from ._recorder import SampledRecorder, array_index, attach, check_every, run_capacity, sample_times, tick_ms, weight_plane
 from .leads import _zero_padded, point_table
+from .tensor import refuse as refuse_tensor
 
 WHO = 'record_potential_map'
 
@@ -74,6 +75,7 @@ class PotentialMapRecorder(SampledRecorder):
         self._st = st = attach(model, WHO, 'potential maps are recorded')
         if _zero_padded(model):
             raise ValueError('%s: not on a model with the zero-padded Laplacian (ZEROPAD): its diffusion term is not this source' % WHO)
+        refuse_tensor(model, WHO, 'its diffusion term is not this source')
         self.table, self.radius = parse_table(table, radius)
         self.window, self.step, self.shape = parse_lattice(window, step, model.height, model.width)
         self.every = check_every(WHO, every)

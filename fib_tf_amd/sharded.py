@@ -229,6 +229,9 @@ class ShardedStepper:
     def set_phase(self, phi):
         self.eng.set_phase(None if phi is None else self._local(np.asarray(phi)))
 
+    def set_tensor(self, dyy, dxx=None, dxy=None):
+        raise NotImplementedError('set_tensor: a diffusion tensor is set on a single device only; this model runs as row blocks over %d ranks' % self.world)
+
     def set_state(self, var, arr):
         self.eng.set_state(var, self._local(np.asarray(arr)))
 

@@ -775,6 +775,10 @@ class IonicModel(_HostModel):
     def jit_scope(self):
         return self                                         # the reference's no-op fallback, ionic.py:299-307
 
+    def set_tensor(self, dyy, dxx, dxy):
+        raise NotImplementedError('set_tensor: a diffusion tensor is set on the hand-written models only; this model is traced: its generated '
+                                  'kernels know the isotropic Laplacian only')
+
     # ---- define(): called first thing by the subclass's define() -----------------------------------
     def define(self, s1=True):
         super().define(s1)

@@ -112,6 +112,21 @@ int fibhip_destroy(fibhip_t h);
  * precede the first step.  NULL removes the phase field.                                               */
 int fibhip_set_phase(fibhip_t h, const float *phi);
 
+/* Per-cell diffusion tensors: anisotropic, heterogeneous conduction.  dyy, dxx, dxy: host [height*width] each, the tensor
+ * D = [[dyy, dxy], [dxy, dxx]] of every cell (rows are y, columns are x), dimensionless and relative to `diff`; the handle's
+ * diffusion term becomes diff * div(D grad V) in the second-order 9-point form of DESIGN.md 25, which is the isotropic
+ * stencil, value for value, at D = I.  All three NULL removes the tensor.  The rules are fibhip_set_phase's: launches what is
+ * pending, waits for an unconfirmed launch, is refused inside an open tick, and chooses the plan again — a tensor handle runs
+ * the flat-tile kernels fibhip_tensor_variant_info lists, one launch per K sub-steps, never several ticks per launch, and
+ * Courtemanche under FIBHIP_FAST runs its plain modes, not the aggregates.  fibhip_set_phase on a tensor handle prepares the
+ * tensor's planes again.  Every recorder and program that only reads the state works beside it.
+ * Refused (FIBHIP_EINVAL): row blocks, FIBHIP_ZEROPAD, FIBHIP_CUSTOM and row-interleaved slabs; planes that are not finite,
+ * not positive definite, or whose largest eigenvalue is above 1 by more than rounding (raise diff instead); while a lead
+ * recorder, a potential-map recorder or a lesion program is attached.  On a tensor handle fibhip_leads_begin,
+ * fibhip_pmap_begin, fibhip_lesion_begin and fibhip_lesion_apply are refused: they read the isotropic operator or recompute
+ * the phase planes.                                                                                                       */
+int fibhip_set_tensor(fibhip_t h, const float *dyy, const float *dxx, const float *dxy);
+
 /* == tf.Variable(init) / define(state=...) (court.py:87-89).  var = -1: whole slab (restarts a row block's
  * exchange cycle: the ghost rows come with it); var >= 0: one array, the cycle position is kept.          */
 int fibhip_set_state(fibhip_t h, int var, const float *src);
@@ -207,6 +222,11 @@ int fibhip_halo_due(fibhip_t h);
 int fibhip_unit_op(int device, int op, int height, int width, const float *a, const float *b, const float *c,
                    const float *phi, double dt, int fast, float *out);
 
+/* laplace(a) of a handle with the diffusion tensor (dyy, dxx, dxy) and the phase field phi (NULL: none) as a stand-alone
+ * array op on HOST arrays [H*W]: the device functions of the tensor kernels, under the policy `fast` names.          */
+int fibhip_unit_laplace_tensor(int device, int height, int width, const float *a, const float *phi, const float *dyy,
+                               const float *dxx, const float *dxy, int fast, float *out);
+
 /* Courtemanche.calc_inter(V, mod) (court.py:273-429; court_ultra.py:445-450 for the last two) on a HOST array
  * of n voltages: out[k*n + i] = k-th intermediate of V[i], k in the insertion order of the reference's dict:
  * d_infinity tau_d f_infinity tau_f tau_w w_infinity m_inf tau_m h_inf tau_h j_inf tau_j tau_oa oa_infinity
@@ -297,6 +317,11 @@ int fibhip_plan_tile(fibhip_t h, int *tile_w, int *tile_h, int *rows_per_wave);
  * sub-steps it also is).  The kernels of a run-time module are not part of this table.                     */
 int fibhip_variant_count(void);
 int fibhip_variant_info(int i, int out[10]);
+/* ... and the second table: the kernels of a handle with a diffusion tensor (fibhip_set_tensor), the same ten fields.  Flat
+ * tiles, phase = 1 (the tensor's first-order term rides on the phase planes, with or without a field), both policies; the
+ * model is the fibhip_model itself.  A build for one traced model has no row.                                      */
+int fibhip_tensor_variant_count(void);
+int fibhip_tensor_variant_info(int i, int out[10]);
 /* Consecutive ticks one launch can cover (1 = every tick is its own launch or launches).  Courtemanche under
  * FIBHIP_FAST on one device returns 3: fibhip_step() accepts ticks and launches them three at a time, temporally
  * blocked; whatever has been accepted but not launched is launched by the next call that observes or changes the
