@@ -7,6 +7,7 @@ package.  The product (fib_tf_amd/) never does and has no CPU fallback.
 present); `lib()` loads it.  The thin wrappers below take/return NumPy float32 SoA
 slabs `[nvar, H, W]`.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -51,6 +52,8 @@ def lib():
         sig = {
             'orc_enforce_boundary': [i, i, _fp, _fp],
             'orc_laplace': [i, i, _fp, _fp, _fp],
+            'orc_laplace_tensor': [i, i, _fp, _fp, _fp, _fp, _fp, _fp],
+            'orc_set_tensor': [_fp, _fp, _fp],
             'orc_phase_field': [i, i, _fp, _fp, _fp],
             'orc_rush_larsen': [l, _fp, _fp, _fp, d, _fp],
             'orc_pace': [i, i, _fp, i, i, i, i, f, f],
@@ -102,6 +105,42 @@ def laplace(X0, phi=None):
     return out
 
 
+def laplace_tensor(X0, dyy, dxx, dxy, phi=None):
+    """the tensor operator of DESIGN.md 25 (tests/tensor_ref.py laplace32 in C); X0 is read through the REFLECT pad"""
+    X0 = _f32(X0); out = np.empty_like(X0); phi = _phi(phi, *X0.shape)
+    D = [_f32(p) for p in (dyy, dxx, dxy)]
+    assert all(p.shape == X0.shape for p in D)
+    lib().orc_laplace_tensor(X0.shape[0], X0.shape[1], _p(X0), _p(phi), *[_p(p) for p in D], _p(out))
+    return out
+
+
+_tensor = None          # the planes of the `with tensor(...)` in force: kept alive here, the library holds their addresses
+
+
+@contextlib.contextmanager
+def tensor(dyy, dxx, dxy):
+    """inside the block every step and run of this module takes the tensor operator with these [H, W] planes in laplace's
+    place (orc_set_tensor, a process-wide switch: one block at a time, no steps from other threads meanwhile)"""
+    global _tensor
+    assert _tensor is None, 'oracle.tensor blocks do not nest'
+    D = tuple(_f32(p) for p in (dyy, dxx, dxy))
+    assert D[0].ndim == 2 and D[1].shape == D[0].shape and D[2].shape == D[0].shape
+    _tensor = D
+    try:
+        lib().orc_set_tensor(*[_p(p) for p in D])
+        yield D
+    finally:
+        lib().orc_set_tensor(None, None, None)
+        _tensor = None
+
+
+def _grid(H, W):
+    """every stepping wrapper passes its grid through here: the planes in force must be that grid's"""
+    if _tensor is not None and _tensor[0].shape != (H, W):
+        raise ValueError('oracle.tensor planes are %r, the grid stepped is %r' % (_tensor[0].shape, (H, W)))
+    return H, W
+
+
 def phase_field(X0, phi):
     X0 = _f32(X0); out = np.empty_like(X0); phi = _phi(phi, *X0.shape)
     lib().orc_phase_field(X0.shape[0], X0.shape[1], _p(X0), _p(phi), _p(out))
@@ -130,14 +169,14 @@ def fenton_diff(U, V, W, S):
 
 
 def fenton_step(slab, dt, diff, phi=None):
-    slab = _f32(slab); _, H, W = slab.shape
+    slab = _f32(slab); _, H, W = slab.shape; _grid(H, W)
     out = np.empty_like(slab); scr = np.empty(2 * H * W, np.float32); phi = _phi(phi, H, W)
     lib().orc_fenton_step(H, W, dt, diff, _p(phi), _p(slab), _p(out), _p(scr))
     return out
 
 
 def br_step(slab, dt, diff, phi=None, cheb=None, nslow=1):
-    slab = _f32(slab); _, H, W = slab.shape
+    slab = _f32(slab); _, H, W = slab.shape; _grid(H, W)
     out = np.empty_like(slab); scr = np.empty(2 * H * W, np.float32); phi = _phi(phi, H, W)
     cheb = None if cheb is None else _f32(cheb)
     lib().orc_br_step(H, W, dt, diff, _p(phi), _p(cheb), nslow, _p(slab), _p(out), _p(scr))
@@ -151,7 +190,7 @@ def court_calc_inter(V):
 
 
 def court_step(slab, dt, diff, phi=None, chronic=True):
-    slab = _f32(slab); _, H, W = slab.shape
+    slab = _f32(slab); _, H, W = slab.shape; _grid(H, W)
     out = np.empty_like(slab); scr = np.empty(2 * H * W, np.float32); phi = _phi(phi, H, W)
     lib().orc_court_step(H, W, dt, diff, _p(phi), int(chronic), _p(slab), _p(out), _p(scr))
     return out
@@ -160,7 +199,7 @@ def court_step(slab, dt, diff, phi=None, chronic=True):
 def fenton_run(slab, dt, diff, phi, nsteps):
     """in place; nsteps sub-steps (10 per tick, fenton.py:135-138)"""
     assert slab.dtype == np.float32 and slab.flags.c_contiguous
-    _, H, W = slab.shape
+    _, H, W = slab.shape; _grid(H, W)
     tmp = np.empty(6 * H * W, np.float32); phi = _phi(phi, H, W)
     lib().orc_fenton_run(H, W, dt, diff, _p(phi), _p(slab), _p(tmp), nsteps)
     return slab
@@ -168,7 +207,7 @@ def fenton_run(slab, dt, diff, phi, nsteps):
 
 def br_run(slab, dt, diff, phi, cheb, skip, nticks):
     assert slab.dtype == np.float32 and slab.flags.c_contiguous
-    _, H, W = slab.shape
+    _, H, W = slab.shape; _grid(H, W)
     tmp = np.empty(10 * H * W, np.float32); phi = _phi(phi, H, W)
     cheb = None if cheb is None else _f32(cheb)
     lib().orc_br_run(H, W, dt, diff, _p(phi), _p(cheb), int(skip), _p(slab), _p(tmp), nticks)
@@ -177,7 +216,7 @@ def br_run(slab, dt, diff, phi, cheb, skip, nticks):
 
 def court_run(slab, dt, diff, phi, chronic, tick0, nticks, slow_every=10):
     assert slab.dtype == np.float32 and slab.flags.c_contiguous
-    _, H, W = slab.shape
+    _, H, W = slab.shape; _grid(H, W)
     tmp = np.empty(23 * H * W, np.float32); phi = _phi(phi, H, W)
     lib().orc_court_run(H, W, dt, diff, _p(phi), int(chronic), _p(slab), _p(tmp), tick0, nticks, slow_every)
     return slab
@@ -186,7 +225,7 @@ def court_run(slab, dt, diff, phi, chronic, tick0, nticks, slow_every=10):
 def court_ultra_run(slab, dt, diff, phi, chronic, nticks):
     """court_ultra.py schedule: every tick assigns all 21 variables with dt"""
     assert slab.dtype == np.float32 and slab.flags.c_contiguous
-    _, H, W = slab.shape
+    _, H, W = slab.shape; _grid(H, W)
     tmp = np.empty(23 * H * W, np.float32); phi = _phi(phi, H, W)
     lib().orc_court_ultra_run(H, W, dt, diff, _p(phi), int(chronic), _p(slab), _p(tmp), nticks)
     return slab
@@ -195,7 +234,7 @@ def court_ultra_run(slab, dt, diff, phi, chronic, nticks):
 def court_ultra_us_run(slab, dt, diff, phi, chronic, nticks):
     """court_ultra.py with ultra_slow=True: 22 arrays (`_us_` last), single rate"""
     assert slab.dtype == np.float32 and slab.flags.c_contiguous and slab.shape[0] == 22
-    _, H, W = slab.shape
+    _, H, W = slab.shape; _grid(H, W)
     tmp = np.empty(24 * H * W, np.float32); phi = _phi(phi, H, W)
     lib().orc_court_ultra_us_run(H, W, dt, diff, _p(phi), int(chronic), _p(slab), _p(tmp), nticks)
     return slab

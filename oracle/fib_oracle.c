@@ -87,6 +87,52 @@ void orc_laplace(int H, int W, const float *X0, const float *phi, float *out)
     }
 }
 
+/* The tensor operator of DESIGN.md 25 (the reference has none): div(phi D grad X) / phi on the 3x3 stencil, D = (dyy, dxx, dxy)
+ * per cell, every plane read through the REFLECT pad.  tests/tensor_ref.py laplace32 restated: every product and sum rounded
+ * once, in that order; the first-order part divided by 4 phi as q = a * rc, r = fma(-q, c, a), fma(r, rc, q) with rc = 1 / c.
+ * phi == NULL: phi = 1 everywhere.                                                     */
+void orc_laplace_tensor(int H, int W, const float *X0, const float *phi, const float *dyy, const float *dxx,
+                        const float *dxy, float *out)
+{
+#pragma omp parallel for schedule(static)
+    for (int r = 0; r < H; ++r) {
+        const int rn = reflecti(r - 1, H), rs = reflecti(r + 1, H);
+        for (int c = 0; c < W; ++c) {
+            const int cw = reflecti(c - 1, W), ce = reflecti(c + 1, W);
+            const int n_ = rn * W + c, s_ = rs * W + c, w_ = r * W + cw, e_ = r * W + ce, c_ = r * W + c;
+            const float N = X0[n_], S = X0[s_], Wv = X0[w_], E = X0[e_], C = X0[c_];
+            const float NW = X0[rn * W + cw], SW = X0[rs * W + cw], NE = X0[rn * W + ce], SE = X0[rs * W + ce];
+            const float yy = dyy[c_], xx = dxx[c_], xy = dxy[c_];
+            const float wd = 0.25f * (yy + xx);
+            const float wy = 1.5f * yy - 0.5f * xx, wx = 1.5f * xx - 0.5f * yy;
+            const float wa = wd + xy, wb = wd - xy, wc = 12.0f * wd;
+            float l = (((wy * N + wy * S) + wx * Wv) + wx * E) + (((wa * NW + wb * SW) + wb * NE) + wa * SE);
+            l = l - wc * C;
+            const float p = phi ? phi[c_] : 1.0f;
+            const float dpy = phi ? phi[s_] - phi[n_] : 0.0f, dpx = phi ? phi[e_] - phi[w_] : 0.0f;
+            const float p2 = 2.0f * p, q4 = 4.0f * p;
+            const float gy = (yy * dpy + xy * dpx) + p2 * ((dyy[s_] - dyy[n_]) + (dxy[e_] - dxy[w_]));
+            const float gx = (xy * dpy + xx * dpx) + p2 * ((dxy[s_] - dxy[n_]) + (dxx[e_] - dxx[w_]));
+            const float num = (S - N) * gy + (E - Wv) * gx;
+            const float rc = 1.0f / q4, q = num * rc;
+            out[c_] = l + fmaf(fmaf(-q, q4, num), rc, q);
+        }
+    }
+}
+
+/* Test switch (all NULL = off): the three sub-steps below take orc_laplace_tensor with these planes in orc_laplace's place, and
+ * so does every *_run driver.  The planes are the caller's, [H][W] of the grid stepped, alive until the switch is cleared. */
+static const float *orc_dyy = NULL, *orc_dxx = NULL, *orc_dxy = NULL;
+void orc_set_tensor(const float *dyy, const float *dxx, const float *dxy)
+{
+    orc_dyy = dyy; orc_dxx = dxx; orc_dxy = dxy;
+}
+static void step_laplace(int H, int W, const float *X0, const float *phi, float *out)
+{
+    if (orc_dyy) orc_laplace_tensor(H, W, X0, phi, orc_dyy, orc_dxx, orc_dxy, out);
+    else orc_laplace(H, W, X0, phi, out);
+}
+
 /* phase_field alone, ionic.py:70-81 (X0 is the un-padded array; pad is REFLECT)      */
 void orc_phase_field(int H, int W, const float *X0, const float *phi, float *out)
 {
@@ -178,7 +224,7 @@ void orc_fenton_step(int H, int W, double dt, double diff, const float *phi,
     float *U0 = scratch, *lap = scratch + n;
     const float dtf = F(dt), ddt = F(diff * dt);          /* self.diff * self.dt in double   */
     orc_enforce_boundary(H, W, in, U0);
-    orc_laplace(H, W, U0, phi, lap);
+    step_laplace(H, W, U0, phi, lap);
 #pragma omp parallel for schedule(static)
     for (long i = 0; i < n; ++i) {
         float dU, dV, dW, dS;
@@ -254,7 +300,7 @@ void orc_br_step(int H, int W, double dt, double diff, const float *phi, const f
     const float mdt = F(-dt), mdtn = F(-(dt * nslow));    /* dt*n is a Python float, br.py:195 */
     const float xmid = F(0.5 * (30.0 + -90.0)), xhalf = F(0.5 * (30.0 - -90.0)); /* br.py:215 */
     orc_enforce_boundary(H, W, in, V0a);
-    orc_laplace(H, W, V0a, phi, lap);
+    step_laplace(H, W, V0a, phi, lap);
 #pragma omp parallel for schedule(static)
     for (long i = 0; i < n; ++i) {
         const float V0 = V0a[i];
@@ -490,7 +536,7 @@ static void court_step_impl(int H, int W, double dt, double diff, const float *p
     const float RTF = F((R * T) / Fd), RT2F = F((R * T) / (2.0 * Fd)), ViF = F(V_i * Fd);
 
     orc_enforce_boundary(H, W, in, Va);
-    orc_laplace(H, W, Va, phi, lap);
+    step_laplace(H, W, Va, phi, lap);
 #pragma omp parallel for schedule(static)
     for (long i = 0; i < n; ++i) {
         float s[COURT_NVAR];

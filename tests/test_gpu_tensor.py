@@ -11,47 +11,14 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import tensor_ref  # noqa: E402
-from test_gpu_variant_table import br_state, br_table, clear_env, court_state, fenton_state  # noqa: E402
+from tensor_cases import (BR, CASES, COURT, COURT_US, DIFF, FENTON, N_FAST, U24, handle, hole_field, run_ticks, same,  # noqa: E402
+                          spd_field, unit_values)
+from test_gpu_variant_table import clear_env, fenton_state  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-FENTON, BR, COURT, COURT_US = 0, 1, 2, 3
-U24 = 2.0 ** -24
-# rounded operations on the longest path of the Fast form, prepared planes included: derived beside the form itself
-# (csrc/stencil.hpp lap9_tensor) — 5 for the second-order part, 3 for its weights, 2 for the first-order term's two FMAs
-N_FAST = 10
-DIFF = {FENTON: 1.2, BR: 0.809, COURT: 0.809, COURT_US: 0.809}
-
-
-def spd_field(H, W, seed):
-    """a random fibre field: angle, ratio <= 3 and scale all varying from cell to cell"""
-    rng = np.random.default_rng(seed)
-    return tensor_ref.fibre_planes(rng.uniform(-np.pi, np.pi, (H, W)), rng.uniform(1.0, 3.0, (H, W)), rng.uniform(0.3, 1.0, (H, W)))
-
-
-def hole_field(H, W):
-    """add_hole_to_phase_field's plane for a hole in the middle, radius a sixth of the shorter side"""
-    rows, cols = np.arange(H)[:, None] - H // 2, np.arange(W)[None, :] - W // 2
-    mask = np.array(0.5 * (np.tanh(np.hypot(cols, rows) - min(H, W) / 6.0) + 1.0), dtype=np.float32)
-    return np.maximum(mask, np.float32(1e-5))
-
-
-def same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
 
 # ---- 4. the unit op -----------------------------------------------------------------------------------------------------------
-def unit_values(H, W):
-    rng = np.random.default_rng(H * 100 + W)
-    X = rng.standard_normal((H, W)).astype(np.float32)
-    flat = X.reshape(-1)
-    n = flat.size
-    flat[rng.choice(n, max(2, n // 10), replace=False)] = 0.0            # exact zeros
-    flat[1], flat[n // 2] = np.float32(1e-20), np.float32(-1e20)          # edge magnitudes, far from the denormals
-    flat[n // 3] = np.inf
-    return X
-
-
 @pytest.mark.parametrize('hole', [False, True], ids=['plain', 'hole'])
 @pytest.mark.parametrize('shape', [(5, 4), (13, 17), (70, 75)], ids=lambda s: '%dx%d' % s)
 def test_unit_op(shape, hole):
@@ -84,40 +51,7 @@ def test_model_laplace_uses_the_tensor():
 
 
 # ---- handles ---------------------------------------------------------------------------------------------------------------------
-CASES = {   # name -> (model, flags without the policy, state maker)
-    'fenton': (FENTON, 0, fenton_state),
-    'br-direct': (BR, 0, br_state),
-    'br-cheby': (BR, 1, br_state),                                       # FIBHIP_CHEBY
-    'court': (COURT, 4, court_state),                                     # FIBHIP_CHRONIC; the fast / slow mix
-    'court-all': (COURT, 4 | 16, court_state),                            # FIBHIP_ALLVARS
-    'court-us': (COURT_US, 4, lambda H, W: court_state(H, W, us=True)),
-}
-
-
-def handle(name, H, W, fast, phi=None, tensor=None, spt=0, diff=None):
-    from fib_tf_amd import _lib
-    model, flags, make = CASES[name]
-    st = _lib.Stepper(model, H, W, 0.1, DIFF[model] if diff is None else diff, flags=flags | (_lib.FAST if fast else 0), steps_per_tick=spt)
-    if flags & 1:
-        st.set_consts(br_table())
-    if phi is not None:
-        st.set_phase(phi)
-    if tensor is not None:
-        st.set_tensor(*tensor)
-    st.set_state(-1, make(H, W)[0])
-    return st
-
-
-def run_ticks(st, name, n):
-    """n ticks; Courtemanche's two-rate handle fires 'slow' once, right behind a tick, as the reference's driver does"""
-    if name == 'court':
-        st.step(n - 2)
-        st.step(1)
-        st.step_slow()
-        st.step(1)
-    else:
-        st.step(n)
-    return st.get_state(-1)
+# (CASES, handle and run_ticks: tests/tensor_cases.py)
 
 
 # ---- 5. the identity tensor is no tensor -----------------------------------------------------------------------------------------
